@@ -40,6 +40,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICRO
 METRIC = "decoded Mpixels/sec at 1920x1080 (MSVideo1 + ScreenPressor), 1/2/4/8 GPUs"
 # what the default line carries beside the headline workload (BASELINE.json configs[2], configs[3])
 ALSO_DEFAULT = ("screenpressor_v4_1080p_iframes", "screenpressor_v4_1080p_pclip300")
+DUMP_BYTES = 64_000_000   # --dump-outputs: every .npy file of one run together
+DUMP_SEED = 1080          # --dump-outputs: the pixel positions sampled (legacy RandomState: the same stream in every numpy)
 
 
 def _oracle_stream(spec, clip, budget_s, max_frames, gate=None):
@@ -146,21 +148,32 @@ def _init_collectives(rank: int, world: int, local_rank: int, want_rccl: bool, w
     if not want_rccl:
         dist.init_process_group("gloo", store=dist.PrefixStore("gloo", store), rank=rank, world_size=world)
         return "cpu", f"gloo ({why_not})"
+    def why(e):
+        return f"{type(e).__name__}: {str(e).splitlines()[0][:160] if str(e) else ''}"
     reason = None
     try:
         forced = os.environ.get("JSP_BENCH_FORCE_RCCL_FAILURE")
         if forced is not None and (forced == "all" or forced == str(rank)):
             raise RuntimeError("forced by JSP_BENCH_FORCE_RCCL_FAILURE")
-        dist.init_process_group("nccl", store=dist.PrefixStore("rccl", store), rank=rank, world_size=world,
-                                device_id=torch.device("cuda", local_rank), timeout=datetime.timedelta(seconds=120))
-        probe = torch.full((2,), float(rank + 1), dtype=torch.float64, device=f"cuda:{local_rank}")
-        dist.all_reduce(probe)
-        torch.cuda.synchronize()
-        want = world * (world + 1) / 2.0
-        if probe.tolist() != [want, want]:
-            raise RuntimeError(f"all-reduce over RCCL returned {probe.tolist()}, not {want}")
-    except Exception as e:                                    # noqa: BLE001 — whatever RCCL / torch raise here, the run goes on over gloo
-        reason = f"{type(e).__name__}: {str(e).splitlines()[0][:160] if str(e) else ''}"
+        if local_rank >= torch.cuda.device_count():
+            raise RuntimeError(f"no device cuda:{local_rank} ({torch.cuda.device_count()} visible)")
+    except Exception as e:                                    # noqa: BLE001
+        reason = why(e)
+    # every rank says whether it can try before any of them enters RCCL: a rank left alone in RCCL's rendezvous waits for the
+    # missing ones without end (more ranks than devices, or one rank forced to fail)
+    store.set(f"rccl_ready_{rank}", reason or "ok")
+    if reason is None and all(store.get(f"rccl_ready_{r}").decode() == "ok" for r in range(world)):
+        try:
+            dist.init_process_group("nccl", store=dist.PrefixStore("rccl", store), rank=rank, world_size=world,
+                                    device_id=torch.device("cuda", local_rank), timeout=datetime.timedelta(seconds=120))
+            probe = torch.full((2,), float(rank + 1), dtype=torch.float64, device=f"cuda:{local_rank}")
+            dist.all_reduce(probe)
+            torch.cuda.synchronize()
+            want = world * (world + 1) / 2.0
+            if probe.tolist() != [want, want]:
+                raise RuntimeError(f"all-reduce over RCCL returned {probe.tolist()}, not {want}")
+        except Exception as e:                                # noqa: BLE001 — whatever RCCL / torch raise here, the run goes on over gloo
+            reason = why(e)
     store.set(f"rccl_verdict_{rank}", reason or "ok")
     verdicts = [store.get(f"rccl_verdict_{r}").decode() for r in range(world)]
     bad = [(r, v) for r, v in enumerate(verdicts) if v != "ok"]
@@ -189,6 +202,48 @@ class Job:
             import torch.distributed as dist
             dist.barrier()
         torch.cuda.synchronize()
+
+
+def dump_outputs(name: str, work, out_dir: str, budget: int) -> int:
+    """--dump-outputs: what the LAST timed step handed its caller, read before anything else touches the frames.  Per frame of every
+    clip, in order: the picture the caller is shown (the destination frame when the decode adopted it, else the picture shown before it:
+    an inter frame without significant changes hands back the previous frame), as its 32-bit pixel values in float64 (exact) at a fixed
+    seeded sample of pixel positions, the same positions in every frame; and the status / adopted / significant_changes the batch
+    reports per frame.  Files `<workload>.<array>.npy`, at most `budget` bytes together.  Returns the bytes written."""
+    import numpy as np
+    import torch
+    from jsplayer_amd import workloads as wl
+    work.sync()
+    shown, status, adopted, sig = [], [], [], []
+    for dsts, first, st in zip(work.dsts, work.firsts, work.staged):
+        s, a, g = st.results()
+        prev = first                          # inter-mode clips: the key frame decoded at staging comes before the step's frames
+        for d, ad in zip(dsts, a):
+            prev = d if (ad or prev is None) else prev
+            shown.append(prev)
+        status += s
+        adopted += a
+        sig += g
+    header = 4096                             # per file, more than np.save writes
+    per_frame = (budget - 4 * header - 3 * 8 * len(shown)) // (8 * len(shown))
+    if per_frame < 1:
+        raise SystemExit(f"bench.py: --dump-outputs: {len(shown)} frames of {name} do not fit in {budget} bytes")
+    per_frame = min(per_frame, wl.W * wl.H)
+    idx = np.sort(np.random.RandomState(DUMP_SEED).choice(wl.W * wl.H, per_frame, replace=False))
+    idx_t = torch.from_numpy(idx).to(shown[0].device)
+    pixels = torch.stack([f[idx_t] for f in shown]).cpu().numpy()
+    arrays = {"frames": pixels.view(np.uint32).astype(np.float64),
+              "status": np.asarray(status, dtype=np.float64),
+              "adopted": np.asarray(adopted, dtype=np.float64),
+              "significant_changes": np.asarray(sig, dtype=np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for key, arr in arrays.items():
+        path = os.path.join(out_dir, f"{name}.{key}.npy")
+        np.save(path, arr)
+        written += os.path.getsize(path)
+    assert written <= budget, (name, written, budget)
+    return written
 
 
 def resident_leg(job: Job, name: str, nfr_override=None, nclips=None):
@@ -225,6 +280,9 @@ def resident_leg(job: Job, name: str, nfr_override=None, nclips=None):
     elapsed = time.perf_counter() - t0
     job.barrier()                             # closing bracket; the job's time is the max over ranks (below)
     gpu_ms = ev0.elapsed_time(ev1)            # HIP events on the launch stream, whole timed region
+    dumped = None
+    if args.dump_outputs and rank == 0:       # before the check below overwrites the frames
+        dumped = dump_outputs(name, work, args.dump_outputs, args.dump_bytes)
     # ---- what a launch of the timed kind writes, against the oracle's digests ---------------------------------
     # Warm-up already left correct frames in HBM, so hashing them would pass even if the timed replays had done nothing.  Every
     # destination frame is therefore overwritten with 0xEE bytes first, ONE more (untimed) step of exactly the launches that were
@@ -329,6 +387,8 @@ def resident_leg(job: Job, name: str, nfr_override=None, nclips=None):
         "total_frames": total_frames,
         "per_rank_frames": per_rank,
     }
+    if dumped is not None:
+        res["dumped_bytes"] = dumped
     work.close()
     return res, clips
 
@@ -538,7 +598,13 @@ def main():
                          "on one device); the line says ranks_share_device and n_gpus 1")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: the launcher, the process group (gloo) and the counter collectives only; value is null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after each timed leg, write what its last timed step returned (rank 0: a fixed seeded sample of every frame's "
+                         "pixels + per-frame status / adopted / significant_changes) as DIR/<workload>.<array>.npy, float64, "
+                         f"at most {DUMP_BYTES} bytes in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_spawn_ranks(args.gpus))
     also = [] if args.no_also else ([w for w in args.also.split(",") if w] if args.also is not None else
@@ -546,6 +612,7 @@ def main():
     for w in also:
         if w not in wl.WORKLOADS:
             raise SystemExit(f"--also: no workload named {w}")
+    args.dump_bytes = DUMP_BYTES // (1 + len(also))     # an equal share per timed leg
 
     import torch
     import torch.distributed as dist
@@ -656,8 +723,10 @@ def main():
 
     # ---- the other configurations the metric names, each to the same bar (same K and W, same bracket, digests, roofline) ----
     entries = []
+    dumped = head.get("dumped_bytes", 0)
     for w in also:
         leg, wclips = resident_leg(job, w)
+        dumped += leg.get("dumped_bytes", 0)
         wspec = leg["spec"]
         many = None if args.no_e2e else e2e_leg(job, w, wclips, one_stream=False, batch_calls=False)
         if rank == 0:
@@ -690,6 +759,8 @@ def main():
             out["ranks"] = args.gpus
         if also:
             out["also"] = entries
+        if args.dump_outputs:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
         out["bench_wall_s"] = round(time.perf_counter() - t_all, 1)
         print(json.dumps(out), flush=True)
     if distributed:

@@ -20,8 +20,12 @@ g++ $FLAGS -c "$T/kernel_stubs.cpp" -o "$OUT/kernel_stubs.o"
 g++ $FLAGS "$T/driver.cpp" "$OUT"/*.o -o "$OUT/tsan_driver" -ldl
 python3 "$T/make_clips.py" "$OUT/clips.bin" > /dev/null
 cd "$OUT"
+# GCC's TSan runtime cannot place its shadow memory under high-entropy mmap ASLR (vm.mmap_rnd_bits > 28: "unexpected memory
+# mapping"); the driver runs without address randomisation for this one process where the system allows it
+NORAND=()
+if setarch "$(uname -m)" -R true 2>/dev/null; then NORAND=(setarch "$(uname -m)" -R); fi
 set +e
-TSAN_OPTIONS="halt_on_error=0 exitcode=66 history_size=4" timeout 900 ./tsan_driver "$OUT/clips.bin" "${1:-3}" > "$OUT/tsan.log" 2>&1
+TSAN_OPTIONS="halt_on_error=0 exitcode=66 history_size=4" timeout 900 "${NORAND[@]}" ./tsan_driver "$OUT/clips.bin" "${1:-3}" > "$OUT/tsan.log" 2>&1
 rc=$?
 set -e
 n=$(grep -c "WARNING: ThreadSanitizer" "$OUT/tsan.log" || true)
