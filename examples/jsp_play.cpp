@@ -12,6 +12,8 @@
 //   ... --pipelined [--prefetch MB]  MSVideo1: the file's bytes go to the device in ranges of about MB megabytes (default 32), one range
 //                                ahead of the one being decoded and every pass over the file anew (jsp_prefetch): the frames then queue
 //                                no upload of their own.  --prefetch 0: a copy, or a read over the bus inside the kernel, per frame
+//   jsp_play clip.avi --seek N   MSVideo1: frame N first, through ONE jsp_seek from the nearest key frame (DataLoader.hx:125-132;
+//                                Manager.hx:216-259), then on frame by frame; the lines from N on carry the CRCs of a plain run
 //   jsp_play a.avi,b.avi --pipelined --devices 0,1,... [--streams T] [--quiet ...]
 //                                streams sharded one per GPU inside this process: stream s plays file s (mod their number) on
 //                                device devices[s mod G], a host thread, a codec instance and a frame pool each; the per-device
@@ -391,6 +393,7 @@ int main(int argc, char** argv) {
     bool pipelined = false, quiet = false;
     int depth = 4, streams = 0, repeat = 1, warmup = 1, batch = 0, device = 0;
     double seconds = 0;
+    long seek_to = -1;                                        // --seek N: frame N first, through jsp_seek
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -404,6 +407,7 @@ int main(int argc, char** argv) {
         else if (o == "--warmup" && a + 1 < argc) warmup = std::atoi(argv[++a]);
         else if (o == "--batch" && a + 1 < argc) batch = std::atoi(argv[++a]);
         else if (o == "--device" && a + 1 < argc) device = std::atoi(argv[++a]);
+        else if (o == "--seek" && a + 1 < argc) seek_to = std::atol(argv[++a]);
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
             for (size_t at = 0; at <= list.size();) {
@@ -415,6 +419,7 @@ int main(int argc, char** argv) {
         }
         else { std::fprintf(stderr, "unknown option %s\n", argv[a]); return 2; }
     }
+    if (seek_to >= 0 && (pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--seek goes with the plain per-frame run\n"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
         if (!quiet) return play_batched(clip, batch, 1, false) < 0 ? 1 : 0;
@@ -532,7 +537,38 @@ int main(int argc, char** argv) {
     size_t prev_key_len = 0;
     bool last_was_key = false;
     int rc = 0;
-    for (size_t i = 0; i < clip.frames.size(); ++i) {
+    size_t begin = 0;
+    if (seek_to >= 0) {   // the seek branch of GetDecompressedFrame: frames [nearest key frame, N] in one call, into slot 0
+        if ((size_t)seek_to >= clip.frames.size()) { std::fprintf(stderr, "--seek %ld: the clip has %zu frames\n", seek_to, clip.frames.size()); return 2; }
+        size_t k = (size_t)seek_to;
+        while (k > 0 && !frame_is_key(clip, dec, k)) --k;
+        std::vector<const uint8_t*> srcs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> keys;
+        for (size_t i = k; i <= (size_t)seek_to; ++i) {
+            srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+            lens.push_back(clip.frames[i].second);
+            keys.push_back(frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        int32_t* dst = jsp_pool_buffer(pool, 0);
+        int32_t* shown_ptr = nullptr;
+        int signif = -1;
+        if (jsp_seek(dec, (int)srcs.size(), srcs.data(), lens.data(), keys.data(), dst, &shown_ptr, &signif) != JSP_ZERO_STATE) {
+            std::fprintf(stderr, "jsp_seek: %s\n", jsp_last_error());
+            jsp_pool_destroy(pool);
+            jsp_codec_destroy(dec);
+            return 1;
+        }
+        const int shown = shown_ptr == dst ? 0 : -1;
+        if (shown == 0) first[0] = last[0] = seek_to;
+        uint32_t crc = 0;
+        if (shown >= 0 && jsp_download(dst, host.data(), npx) == 0) crc = crc32(reinterpret_cast<const uint8_t*>(host.data()), npx * 4);
+        last_was_key = keys.back() != 0;
+        if (last_was_key) { prev_key = srcs.back(); prev_key_len = lens.back(); }
+        std::printf("%ld %s %d %d %08x\n", seek_to, last_was_key ? "key" : "inter", shown, last_was_key ? -1 : signif, crc);
+        begin = (size_t)seek_to + 1;
+    }
+    for (size_t i = begin; i < clip.frames.size(); ++i) {
         const uint8_t* src = clip.bytes.data() + clip.frames[i].first;
         const size_t len = clip.frames[i].second;
         const bool key = frame_is_key(clip, dec, i);

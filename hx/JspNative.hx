@@ -39,6 +39,10 @@ extern class JspNative {
     @:native("jsp_decompress_p_async") static function decompressPAsync(c:RawPointer<JspCodec>, src:RawConstPointer<UInt8>, n:SizeT, dst:RawPointer<cpp.Int32>, ticket:RawPointer<UInt64>):Int;
     @:native("jsp_prefetch")           static function prefetch(c:RawPointer<JspCodec>, host:RawConstPointer<UInt8>, bytes:SizeT):Int;   // a stretch of the file ahead of the frames submitted next: one copy instead of one per frame
     @:native("jsp_wait")               static function wait(c:RawPointer<JspCodec>, ticket:UInt64, dataPnt:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
+    // the seek branch of Manager.GetDecompressedFrame (Manager.hx:216-259), MSVideo1: frames from the nearest key frame up to the target, composed into `dst` in one call
+    @:native("jsp_seek")               static function seek(c:RawPointer<JspCodec>, nframes:Int, srcs:RawPointer<RawConstPointer<UInt8>>, lens:RawPointer<SizeT>,
+                                                            isKey:RawConstPointer<UInt8>, dst:RawPointer<cpp.Int32>,
+                                                            dataPnt:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
     // frame pool in HBM (Manager.hx:114-118) and the two Manager passes that follow the codec
     @:native("jsp_key_frame_differs")  static function keyFrameDiffers(c:RawPointer<JspCodec>):Int;
     @:native("jsp_device_count")       static function deviceCount():Int;

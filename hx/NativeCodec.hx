@@ -98,6 +98,28 @@ class NativeCodec implements IVideoCodec {
         h = null;
     }
 
+    // ---- optional: seek (jsp_seek; MSVideo1 only — ScreenPressor throws, a Manager decodes frame by frame there) ----------
+    /** Frames `srcs` (from where the stream stands, typically the nearest key frame, up to and including the target; `isKey` as the
+     *  index flags them) composed into `dst` in one call: what DecompressI / DecompressP in order would show, each frame's
+     *  destination starting out as the picture before it.  data_pnt = dst, or the unchanged previous frame when nothing changed. */
+    public function Seek(srcs:Array<Bytes>, isKey:Array<Bool>, dst:FrameBuffer):PFrameResult {
+        var n = srcs.length;
+        var ptrs = new Array<RawConstPointer<UInt8>>();
+        var lens = new Array<cpp.SizeT>();
+        var keys = Bytes.alloc(n);
+        for (i in 0...n) {
+            ptrs.push(bytesPtr(srcs[i]));
+            lens.push(srcs[i].length);
+            keys.set(i, isKey[i] ? 1 : 0);
+        }
+        var dataPnt:RawPointer<cpp.Int32> = null;
+        var signif:Int = 0;
+        var rc = JspNative.seek(h, n, cpp.NativeArray.address(ptrs, 0).raw, cpp.NativeArray.address(lens, 0).raw, bytesPtr(keys), dst.ptr,
+                                cpp.RawPointer.addressOf(dataPnt), cpp.RawPointer.addressOf(signif));
+        if (rc != 0) throw "Seek: " + JspNative.lastError().toString();
+        return { data_pnt: pool.find(dataPnt), significant_changes: signif != 0 };
+    }
+
     // ---- optional: decode ahead of display (jsp_decompress_*_async / jsp_wait) ------------------------------------------
     /** Queue a frame; `src` and `dst` must stay untouched until wait(ticket).  Returns the ticket. */
     public function Submit(src:Bytes, dst:FrameBuffer, key:Bool):haxe.Int64 {

@@ -186,6 +186,8 @@ int jsp_set_stream(jsp_codec* c, void* hip_stream);
  *       jsp_key_frame_differs() after a synchronous DecompressI; *significant_changes of jsp_wait for an asynchronous one (a key
  *       frame that decoded and has no previous frame to be compared with counts as a change: Manager.hx:399-411; for a frame that FAILED
  *       *significant_changes stays what the decode reported and jsp_key_frame_differs() says -1).  Staged batches are not compared. */
+/*   "msv1_seek_chunk_frames" = "auto" (default) | "1".."n" : MSVideo1 only, jsp_seek.  Frames staged and composed per chunk of a
+ *       seek's range; auto: as many as keep the chunk's stream bytes and block tables under 1 GiB.  Results do not depend on it. */
 /*   "async_depth" = "1".."16" (default "4") : any codec.  Frames that may be in flight between jsp_decompress_*_async and
  *       jsp_wait. */
 int jsp_set_option(jsp_codec* c, const char* key, const char* value);
@@ -294,6 +296,34 @@ const char* jsp_staged_kernels(const jsp_staged* s);
 /* Per-frame results of a staged batch: status[i] (DecoderState), adopted[i] (1 if dsts[i] became
  * the previous frame), significant[i] (valid after jsp_staged_decode + jsp_sync). */
 int jsp_staged_results(jsp_staged* s, int* status, int* adopted, int* significant);
+
+/* ---- seek: the seek branch of Manager.GetDecompressedFrame (Manager.hx:216-259) ---------------------------------------------
+ * Seek: frames[0..nframes-1] are the frames from where the caller's stream stands (typically the nearest key frame,
+ * DataLoader.hx:125-132) up to and including the target.  is_key as in jsp_stage_batch (NULL = all key frames).
+ *   EQUIVALENCE  The call does what DecompressI / DecompressP do for each frame in order (is_key), WHEN EACH FRAME'S DESTINATION
+ *       STARTS OUT HOLDING THE PICTURE BEFORE IT; nothing but `dst` is written.  For well-formed streams this is plain sequential
+ *       decoding whatever the pool held.  It differs only where the reference leaves a block or pixel unwritten — blocks after an
+ *       8-bit end marker or a truncated stream, the X % 4 / Y % 4 remainder pixels —: those show the previous picture, not stale pool
+ *       content.  Pixels that no block covers are copied from the previous frame when there is one.  MSVideo1 has no motion, so
+ *       block b of the target is block b as coded by the last frame of the range that coded it: the range is staged as one batch
+ *       (either "msv1_parse") and ONE kernel launch writes `dst`.
+ *   RESULTS  JSP_ZERO_STATE.  *data_pnt = dst if any frame of the range would have adopted its destination (jsp_previous_frame()
+ *       is then dst); otherwise the unchanged previous frame (possibly NULL), and dst is not touched.  *significant_changes = what
+ *       DecompressP of the LAST frame would report (stage 1, MSVideo1.hx:187-194 / 372-379, then the pixel compare against the
+ *       picture before it from row insignificant_lines on, :195-205 / 380-390; 0 when the last frame is a key frame).  Host-side
+ *       codec state — the persistent per-row block_changes included — ends as the sequential calls would leave it: the next
+ *       DecompressP behaves exactly as after a sequential decode.
+ *   ERRORS  Where the reference raises (a skip code with no previous picture): JSP_ERROR_OCCURED, jsp_last_error() names the
+ *       frame's index in the range, jsp_previous_frame() becomes NULL, `dst` is unspecified.
+ *   PRECONDITIONS  `dst` is a device buffer (a host pointer is an error); no asynchronous frame may be in flight; `dst` is not the
+ *       current previous frame.  A violation is an error with nothing changed.
+ *   The key-frame compare (option "key_frame_compare") does not run on a seek: jsp_key_frame_differs() answers -1 afterwards.
+ *   ScreenPressor: JSP_ERROR_OCCURED ("seek: MSVideo1 only"), no state changed — its entropy stage is sequential and its inter
+ *       frames carry motion; a caller decodes frame by frame there (jsplayer_amd/player.py Manager.seek).
+ *   Ranges whose stream bytes and tables exceed a staging budget (1 GiB) are composed chunk by chunk (option
+ *   "msv1_seek_chunk_frames"): after one chunk `dst` IS the picture before the next, so the result does not depend on the split. */
+int jsp_seek(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key,
+             int32_t* dst, int32_t** data_pnt, int* significant_changes);
 
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 

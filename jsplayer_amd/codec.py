@@ -177,6 +177,34 @@ class _NativeCodec:
             raise CodecError(N.last_error())
         return PFrameResult(self._bufs.get(out_ptr.value) if out_ptr.value else None, bool(signif.value))
 
+    # -- seek (jsp_seek): the seek branch of Manager.GetDecompressedFrame (Manager.hx:216-259) ------------------------
+    SEEKS = True   # Seek() composes a range in one call (ScreenPressor: no, it decodes frame by frame)
+
+    def Seek(self, srcs: Sequence, dst, is_key: Optional[Sequence[bool]] = None) -> PFrameResult:
+        """The frames `srcs` (from where the stream stands — typically the nearest key frame — up to and including the
+        target) as DecompressI / DecompressP would decode them in order, each destination starting out as the picture
+        before it, composed into `dst` alone (a device buffer; one launch).  `data_pnt` is `dst` when a frame of the range
+        would have adopted its destination, else the unchanged previous frame; `significant_changes` is the last frame's.
+        CodecError where the reference raises (the previous frame is then None) and on ScreenPressor."""
+        n = len(srcs)
+        if n == 0:
+            raise CodecError("seek: empty range")
+        keeps, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
+        for i, s in enumerate(srcs):
+            keep, p, ln = _src_arg(s)
+            keeps.append(keep)
+            ptrs[i] = p.value if p is not None else None
+            lens[i] = ln
+        addr = _frame_ptr(dst, self.X * self.Y)
+        self._bufs[addr] = dst
+        keys = bytes(bytearray(1 if k else 0 for k in is_key)) if is_key is not None else None
+        out_ptr, signif = C.c_void_p(), C.c_int(0)
+        rc = self._lib.jsp_seek(self._h, n, ptrs, lens, keys, C.c_void_p(addr), C.byref(out_ptr), C.byref(signif))
+        self._track_prev()
+        if rc != 0:
+            raise CodecError(N.last_error())
+        return PFrameResult(self._prev if out_ptr.value else None, bool(signif.value))
+
     def NeedsIndex(self) -> bool:
         return bool(self._lib.jsp_needs_index(self._h))
 
@@ -336,6 +364,8 @@ class MSVideo1_8bit(_NativeCodec):
 class ScreenPressor(_NativeCodec):
     """ScreenPressor.hx:19-490 — `new ScreenPressor(width, height, bits_per_pixel)`"""
     _kind = N.JSP_CODEC_SCREENPRESSOR
+
+    SEEKS = False   # jsp_seek refuses it: sequential entropy stage, motion in inter frames
 
     def __init__(self, width: int, height: int, bits_per_pixel: int, device: int = 0):
         super().__init__(width, height, bits_per_pixel, None, device)

@@ -81,6 +81,8 @@ struct jsp_codec {
     jsp::DeviceBuffer compat[2];
 
     std::unique_ptr<jsp_staged> scratch;  // reused by the per-frame entry points
+    std::unique_ptr<jsp_staged> seek_scratch;   // jsp_seek's staged range (kept: its buffers serve the next seek)
+    int seek_chunk_frames = 0;            // option "msv1_seek_chunk_frames": frames staged per chunk of a seek (0 = auto)
 
     // asynchronous path: a ring of jobs, tickets count up from 1, frames complete in submission order
     std::vector<jsp_async_job> jobs;

@@ -37,6 +37,7 @@ jsp_codec::~jsp_codec() {
         if (j.done) (void)hipEventDestroy(j.done);
     }
     scratch.reset();
+    seek_scratch.reset();
     if (side_stream) { (void)hipStreamSynchronize(side_stream); (void)hipStreamDestroy(side_stream); }
     if (own_stream) (void)hipStreamDestroy(own_stream);
 }

@@ -13,6 +13,7 @@
 
 #include "codec.h"
 #include "msv1.h"
+#include "msv1_seek.h"
 #include <msv1_fused_hooks.h>   // (angle brackets: a lab build puts its own in front on the include path, see the Makefile)
 
 namespace jsp {
@@ -574,6 +575,14 @@ struct Msv1Codec : jsp_codec {
         if (std::strcmp(key, "msv1_parse_ahead") == 0) {    // replays of an inter-frame batch: the next replay's table-writing parse beside this replay's launches (on), or in front of them (off)
             if (std::strcmp(value, "on") != 0 && std::strcmp(value, "off") != 0) return JSP_ERROR_OCCURED;
             opt_parse_ahead = std::strcmp(value, "on") == 0;
+            return 0;
+        }
+        if (std::strcmp(key, "msv1_seek_chunk_frames") == 0) {   // jsp_seek: frames staged and composed per chunk ("auto": by a byte budget)
+            if (std::strcmp(value, "auto") == 0) { seek_chunk_frames = 0; return 0; }
+            char* end = nullptr;
+            const long v = std::strtol(value, &end, 10);
+            if (end == value || *end || v < 1 || v > (1 << 24)) return -1;
+            seek_chunk_frames = (int)v;
             return 0;
         }
         if (std::strcmp(key, "msv1_scrub_tables") == 0) {   // tests: a replay must rebuild every block table it reads
@@ -1305,6 +1314,23 @@ struct Msv1Codec : jsp_codec {
 };
 
 }  // namespace
+
+bool msv1_seek_view(jsp_staged* base, Msv1SeekView& out) {
+    auto* st = dynamic_cast<Msv1Staged*>(base);
+    if (!st) return false;
+    out.geo = st->geo;
+    out.d_stream = static_cast<const uint8_t*>(st->d_stream.p);
+    out.d_desc = static_cast<const uint32_t*>(st->d_desc.p);
+    out.desc_pitch = (size_t)std::max(st->geo.nblocks, 1);
+    out.d_frames = static_cast<const Msv1FrameArgs*>(st->d_frames.p);
+    out.h_frames = static_cast<const Msv1FrameArgs*>(st->h_frames.p);
+    out.d_palette = st->d_palette;
+    out.d_signif = static_cast<uint32_t*>(st->d_signif.p);
+    out.h_signif = static_cast<uint32_t*>(st->h_signif.p);
+    out.nframes = st->nframes;
+    return true;
+}
+
 }  // namespace jsp
 
 jsp_codec* jsp_make_msv1(int bits, int w, int h, const uint8_t* palette, int palette_bytes) {

@@ -1,0 +1,184 @@
+// MSVideo1 seek for gfx950 (MI355X): frames K..N of a staged batch composed into ONE picture in one launch.
+//
+// An MSVideo1 inter frame codes a 4x4 block or leaves it as it was (a skip; nothing written after an 8-bit end marker or a
+// truncated stream); there is no motion.  So block b of frame N is block b as coded by the LAST frame <= N whose table codes it,
+// or the picture before the range when none does.  One work-item per block, blocks in raster order as in msv1_kernels.hip:
+//   * the lane walks its table column from the last frame backwards (four entries in flight per step; one coalesced dword per
+//     lane and frame), stopping at the first code offset;
+//   * decodes that code (decode_block, msv1_decode.h) from the 20 bytes it needs, read as aligned dwords and zeroed past the end
+//     of its frame's data — the 16-bit odd last byte and the codes past the end of a truncated frame exactly as the temporal
+//     kernel handles them;
+//   * or copies the block from the picture before the range when nothing in the range coded it;
+//   * for the stage-2 compare (MSVideo1.hx:195-205) of the last frame, a block the last frame coded is also decoded as the
+//     SECOND writer left it (or taken from the picture before) and compared, rows >= cmp_row_lo.
+// Every pixel of `dst` is written at most once, with the same 16-byte row stores as the other block kernels.  Work-items past
+// the last block copy the pixels no block covers (X % 4 / Y % 4 remainders) from the picture before.
+#include "msv1_decode.h"
+#include "msv1_seek.h"
+
+namespace jsp {
+namespace {
+
+constexpr int WG = 256;
+constexpr int SCAN = 4;   // table entries a lane has in flight per step of its backward walk
+
+typedef uint32_t su32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) su32x4 sgu32x4;
+typedef const __attribute__((address_space(1))) su32x4 scgu32x4;
+typedef __attribute__((address_space(1))) uint32_t sgu32;
+typedef const __attribute__((address_space(1))) uint32_t scgu32;
+
+// The last frame <= `from` whose table codes block `blk` (its code offset in `o`), or -1.
+__device__ __forceinline__ int last_writer(const uint32_t* __restrict__ desc, size_t pitch, int blk, int from, uint32_t& o) {
+    for (int g = from; g >= 0; g -= SCAN) {
+        uint32_t e[SCAN];
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k) e[k] = g - k >= 0 ? *(scgu32*)(desc + (size_t)(g - k) * pitch + blk) : MSV1_DESC_SKIP;
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k)
+            if (e[k] < MSV1_DESC_UNTOUCHED) { o = e[k]; return g - k; }
+    }
+    return -1;
+}
+
+// The 16 pixels of the code at `o` of a frame whose data ends at `stream_end` (MSVideo1.hx:135-181 / 319-364; bytes past the end
+// read as missing, which the reference turns into 0).
+template <int BITS>
+__device__ __forceinline__ void decode_at(const uint8_t* __restrict__ stream, uint32_t o, uint32_t stream_end, const uint32_t* s_pal,
+                                          uint32_t (&px)[16]) {
+    // 16-bit: `end` counts whole words and a code word cut in two (only its first byte exists) is painted solid from that byte
+    const uint32_t end = BITS == 16 ? (stream_end & ~1u) : stream_end;
+    const uint32_t avail = end > o ? end - o : 0u;
+    const bool half = BITS == 16 ? ((stream_end & 1u) && o == end) : avail == 1u;
+    if (half) {
+        const uint32_t a = stream[BITS == 16 ? stream_end - 1u : o];
+        const uint32_t v = BITS == 16 ? rgb555(a) : s_pal[a];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) px[k] = v;
+        return;
+    }
+    if (avail == 0u) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) px[k] = 0u;
+        return;
+    }
+    // o is even (codes are whole words from a 16-byte aligned frame start): six aligned dwords from o & ~3 hold the 20 bytes
+    // decode_block may read; every dword lies inside the batch's stream buffer (64 bytes of slack past its last frame)
+    const uint32_t a0 = o & ~3u;
+    uint32_t w[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const uint32_t at = a0 + 4u * (uint32_t)k;
+        const uint32_t v = at < end ? *(scgu32*)(stream + at) : 0u;
+        const uint32_t have = end - at;   // bytes of this dword that are data (when at < end)
+        w[k] = at >= end ? 0u : (have >= 4u ? v : v & ((1u << (8u * have)) - 1u));
+    }
+    const uint32_t sh = (o & 2u) * 8u;
+    uint32_t cw[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) cw[k] = __builtin_amdgcn_alignbit(w[k + 1], w[k], sh);
+    decode_block<BITS>(reinterpret_cast<const uint8_t*>(cw), avail, s_pal, px);
+}
+
+template <bool VEC>
+__device__ __forceinline__ void load_block(const uint32_t* __restrict__ p, int X, uint32_t (&px)[16]) {
+#pragma unroll
+    for (int y = 0; y < 4; ++y) {
+        if (VEC) {
+            const su32x4 r = *(scgu32x4*)(p + (size_t)y * X);
+            px[y * 4] = r.x; px[y * 4 + 1] = r.y; px[y * 4 + 2] = r.z; px[y * 4 + 3] = r.w;
+        } else {
+#pragma unroll
+            for (int x = 0; x < 4; ++x) px[y * 4 + x] = *(scgu32*)(p + (size_t)y * X + x);
+        }
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store_block(uint32_t* __restrict__ p, int X, const uint32_t (&px)[16]) {
+#pragma unroll
+    for (int y = 0; y < 4; ++y) {
+        if (VEC) {
+            __builtin_nontemporal_store(su32x4{px[y * 4], px[y * 4 + 1], px[y * 4 + 2], px[y * 4 + 3]}, (sgu32x4*)(p + (size_t)y * X));
+        } else {
+#pragma unroll
+            for (int x = 0; x < 4; ++x) *(sgu32*)(p + (size_t)y * X + x) = px[y * 4 + x];
+        }
+    }
+}
+
+template <int BITS, bool VEC>
+__global__ __launch_bounds__(WG) void msv1_seek_kernel(const uint8_t* __restrict__ stream, const uint32_t* __restrict__ desc, size_t pitch,
+                                                       const Msv1FrameArgs* __restrict__ frames, int nframes, const int32_t* __restrict__ palette,
+                                                       uint32_t* __restrict__ dst, const uint32_t* __restrict__ base, uint32_t cmp_row_lo,
+                                                       uint32_t* __restrict__ signif, int nblocks, int nbx, int X, int cx, int cy, long nrem) {
+    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
+    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
+    if (BITS == 8) __syncthreads();
+    const long gid = (long)blockIdx.x * WG + threadIdx.x;
+    if (gid >= nblocks) {   // a pixel no block covers: the right strip [0, cy) x [cx, X), then the rows [cy, Y)
+        const long r = gid - nblocks;
+        if (r >= nrem || base == nullptr || base == dst) return;
+        const long rw = (long)(X - cx) * cy;
+        const size_t i = r < rw ? (size_t)(r / (X - cx)) * (size_t)X + (size_t)cx + (size_t)(r % (X - cx)) : (size_t)cy * (size_t)X + (size_t)(r - rw);
+        *(sgu32*)(dst + i) = *(scgu32*)(base + i);
+        return;
+    }
+    const int blk = (int)gid;
+    const int by = blk / nbx;
+    const int bx = blk - by * nbx;
+    const size_t di = (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
+    uint32_t o = 0;
+    const int wf = last_writer(desc, pitch, blk, nframes - 1, o);
+    uint32_t px[16];
+    if (wf < 0) {   // nothing in the range coded the block: it shows the picture before the range
+        if (base != nullptr && base != dst) {
+            load_block<VEC>(base + di, X, px);
+            store_block<VEC>(dst + di, X, px);
+        }
+        return;
+    }
+    decode_at<BITS>(stream, o, frames[wf].stream_end, s_pal, px);
+    bool diff = false;
+    if (cmp_row_lo != 0xFFFFFFFFu && wf == nframes - 1) {
+        // the picture before the last frame at this block: what the frame before it that coded the block made of it, else the
+        // picture before the range (`dst` itself when that is where it lies — read before this lane writes it)
+        uint32_t pv[16];
+        uint32_t o2 = 0;
+        const int wf2 = last_writer(desc, pitch, blk, nframes - 2, o2);
+        if (wf2 >= 0) decode_at<BITS>(stream, o2, frames[wf2].stream_end, s_pal, pv);
+        else load_block<VEC>((base != nullptr ? base : dst) + di, X, pv);
+#pragma unroll
+        for (int y = 0; y < 4; ++y)
+            if ((uint32_t)(by * 4 + y) >= cmp_row_lo)
+                diff |= (pv[y * 4] != px[y * 4]) | (pv[y * 4 + 1] != px[y * 4 + 1]) | (pv[y * 4 + 2] != px[y * 4 + 2]) | (pv[y * 4 + 3] != px[y * 4 + 3]);
+    }
+    store_block<VEC>(dst + di, X, px);
+    // one word per launch: look before setting (see msv1_blocks_kernel)
+    const unsigned long long m = __ballot(diff);
+    if (m != 0ull && (threadIdx.x & 63) == __ffsll((long long)m) - 1 &&
+        __hip_atomic_load(signif, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+        atomicOr(signif, 1u);
+}
+
+}  // namespace
+
+void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, uint32_t cmp_row_lo, hipStream_t stream) {
+    const Msv1Geometry& geo = v.geo;
+    if (v.nframes <= 0 || geo.X <= 0 || geo.Y <= 0) return;
+    const int cx = geo.nbx * 4, cy = geo.nby * 4;
+    const long nrem = (long)(geo.X - cx) * cy + (long)geo.X * (geo.Y - cy);
+    const long work = (long)std::max(geo.nblocks, 0) + nrem;
+    if (work <= 0) return;
+    const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(dst) & 15) && !(reinterpret_cast<uintptr_t>(base) & 15);
+    uint32_t* signif = v.d_signif + (v.nframes - 1);
+    const dim3 grid((unsigned)((work + WG - 1) / WG)), block(WG);
+#define JSP_SEEK(BITS, VEC) hipLaunchKernelGGL((msv1_seek_kernel<BITS, VEC>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, v.d_frames, \
+                                               v.nframes, v.d_palette, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(base),   \
+                                               cmp_row_lo, signif, geo.nblocks, std::max(geo.nbx, 1), geo.X, cx, cy, nrem)
+    if (geo.bits == 16) { if (vec) JSP_SEEK(16, true); else JSP_SEEK(16, false); }
+    else { if (vec) JSP_SEEK(8, true); else JSP_SEEK(8, false); }
+#undef JSP_SEEK
+}
+
+}  // namespace jsp

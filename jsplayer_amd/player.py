@@ -2,8 +2,13 @@
 kept to what touches the codec — construction from VideoInfo (Manager.hx:103-142), the frame-buffer
 pool that never hands out the buffer holding the previous frame (:424-443,470-477), the
 DecompressI / DecompressP protocol with its identity test (:499-524) and
-`frames_differ_significantly` for key frames (:392-421).  Timers, seeking, bitmaps and audio of the
-reference's Manager are not rebuilt.
+`frames_differ_significantly` for key frames (:392-421), and the seek branch of
+`GetDecompressedFrame` (:216-259; `Manager.seek`, `nearest_key_frame` = DataLoader.hx:125-132): a held
+frame is shown as it is, a seek outside the stretch being decoded trashes every buffer and starts again
+at the nearest key frame, and the frames up to the target go to the decoder's `Seek` (MSVideo1 on the
+GPU: one call, one launch) or, for decoders without one (ScreenPressor, the oracle's classes), through
+`worker` frame by frame as the reference does.  Timers, bitmaps and audio of the reference's Manager
+are not rebuilt.
 """
 from __future__ import annotations
 
@@ -37,6 +42,24 @@ def make_decoder(vi: VideoInfo, classes) -> object:
     if vi.codec == CODEC_MSVC8:
         return m8(vi.X, vi.Y, vi.palette or b"")
     raise ValueError(vi.codec)
+
+
+def nearest_key_frame(key_flags, n: int, count: Optional[int] = None) -> int:
+    """DataLoader.GetNearestKeyframe (DataLoader.hx:125-132): `n` clamped to the last frame, then walked back to the
+    nearest frame flagged key (frame 0 when none is).  `key_flags`: a sequence of flags (None or a missing entry = not
+    key), or a callable index -> bool together with `count` frames."""
+    if callable(key_flags):
+        total = int(count or 0)
+        flag = key_flags
+    else:
+        total = len(key_flags) if count is None else int(count)
+        flag = lambda i: i < len(key_flags) and bool(key_flags[i])
+    if total <= 0:
+        return 0
+    n = min(max(int(n), 0), total - 1)
+    while n > 0 and not flag(n):
+        n -= 1
+    return n
 
 
 def _differ(a, b, start: int) -> bool:
@@ -140,6 +163,52 @@ class Manager:
         return self.log
 
     _last_was_key = False
+
+    def _key_at(self, frames: Sequence[bytes], i: int, key_flags) -> bool:
+        if key_flags is not None:
+            return i < len(key_flags) and bool(key_flags[i])
+        return i == 0 or bool(self.decoder.IsKeyFrame(frames[i]))
+
+    def seek(self, frames: Sequence[bytes], index: int, key_flags: Optional[Sequence[bool]] = None) -> DecodedFrame:
+        """Show frame `index` of `frames` — the seek branch of GetDecompressedFrame (Manager.hx:216-259).  A frame some
+        buffer holds is shown without decoding.  Otherwise decoding starts at the nearest key frame (every hold trashed)
+        unless the stretch being decoded already leads to `index`, and the frames up to it go to the decoder's Seek (one
+        call) or, without one, through worker() one by one.  worker / play continue from index + 1 afterwards."""
+        if not 0 <= index < len(frames):
+            raise IndexError(f"frame {index} outside the clip ({len(frames)} frames)")
+        self.frame_of_interest = index
+        for nb, h in enumerate(self.holds):
+            if h is not None and h.start <= index < h.stop:
+                return DecodedFrame(index, self._key_at(frames, index, key_flags), nb, None)
+        key_idx = nearest_key_frame(lambda i: self._key_at(frames, i, key_flags), index, len(frames))
+        if self.next_frame_to_decode < key_idx or self.next_frame_to_decode > index:
+            self.next_frame_to_decode = key_idx
+            self.holds = [None] * len(self.buffers)
+        start = self.next_frame_to_decode
+        keys = [self._key_at(frames, i, key_flags) for i in range(start, index + 1)]
+        dec = self.decoder
+        if getattr(dec, "SEEKS", False) and hasattr(dec, "Seek"):
+            prev = dec.PreviousFrame()
+            prev_idx = self._slot_of(prev) if prev is not None else -1
+            free = self._get_free_buffer(prev_idx)
+            assert free >= 0
+            res = dec.Seek(frames[start:index + 1], self.buffers[free], keys)
+            shown = free
+            if res.data_pnt is not None:
+                if res.data_pnt is prev and prev_idx >= 0:      # nothing in the range changed the picture
+                    h = self.holds[prev_idx]
+                    self.holds[prev_idx] = range(h.start, index + 1) if h else range(index, index + 1)
+                    shown = prev_idx
+                else:
+                    self.holds[free] = range(index, index + 1)
+            out = DecodedFrame(index, keys[-1], shown, None if keys[-1] else res.significant_changes)
+            self.log.append(out)
+        else:
+            for i in range(start, index + 1):
+                out = self.worker(frames[i], i, None, keys[i - start])
+        self._last_was_key = keys[-1]
+        self.next_frame_to_decode = index + 1
+        return out
 
     def play_pipelined(self, frames: Sequence[bytes], depth: int = 4,
                        on_frame: Optional[Callable[[DecodedFrame, object], None]] = None,
