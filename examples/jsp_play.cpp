@@ -12,6 +12,8 @@
 //   ... --pipelined [--prefetch MB]  MSVideo1: the file's bytes go to the device in ranges of about MB megabytes (default 32), one range
 //                                ahead of the one being decoded and every pass over the file anew (jsp_prefetch): the frames then queue
 //                                no upload of their own.  --prefetch 0: a copy, or a read over the bus inside the kernel, per frame
+//   jsp_play clip.avi --skip-stills   MSVideo1: frame 0, then skip to the next significant change until the end (Manager.SkipStills,
+//                                one jsp_find_change per skip); prints "<index> <key|inter> <changed> <crc32>" per landing
 //   jsp_play clip.avi --seek N   MSVideo1: frame N first, through ONE jsp_seek from the nearest key frame (DataLoader.hx:125-132;
 //                                Manager.hx:216-259), then on frame by frame; the lines from N on carry the CRCs of a plain run
 //   jsp_play a.avi,b.avi --pipelined --devices 0,1,... [--streams T] [--quiet ...]
@@ -394,6 +396,7 @@ int main(int argc, char** argv) {
     int depth = 4, streams = 0, repeat = 1, warmup = 1, batch = 0, device = 0;
     double seconds = 0;
     long seek_to = -1;                                        // --seek N: frame N first, through jsp_seek
+    bool skip_stills = false;                                 // --skip-stills: from frame 0, skip to each significant change (jsp_find_change)
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -408,6 +411,7 @@ int main(int argc, char** argv) {
         else if (o == "--batch" && a + 1 < argc) batch = std::atoi(argv[++a]);
         else if (o == "--device" && a + 1 < argc) device = std::atoi(argv[++a]);
         else if (o == "--seek" && a + 1 < argc) seek_to = std::atol(argv[++a]);
+        else if (o == "--skip-stills") skip_stills = true;
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
             for (size_t at = 0; at <= list.size();) {
@@ -420,6 +424,7 @@ int main(int argc, char** argv) {
         else { std::fprintf(stderr, "unknown option %s\n", argv[a]); return 2; }
     }
     if (seek_to >= 0 && (pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--seek goes with the plain per-frame run\n"); return 2; }
+    if (skip_stills && (seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--skip-stills goes alone\n"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
         if (!quiet) return play_batched(clip, batch, 1, false) < 0 ? 1 : 0;
@@ -538,6 +543,40 @@ int main(int argc, char** argv) {
     bool last_was_key = false;
     int rc = 0;
     size_t begin = 0;
+    if (skip_stills) {   // Manager.SkipStills + SeekTo (Manager.hx:289-317), again and again: frame 0, then ONE jsp_find_change per skip
+        const size_t n = clip.frames.size();
+        std::vector<const uint8_t*> srcs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> keys;
+        for (size_t i = 0; i < n; ++i) {
+            srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+            lens.push_back(clip.frames[i].second);
+            keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        if (n && jsp_decompress_i(dec, srcs[0], lens[0], jsp_pool_buffer(pool, 0)) != JSP_ZERO_STATE) {
+            std::fprintf(stderr, "frame 0: %s\n", jsp_last_error());
+            rc = 1;
+        }
+        for (size_t shown = 0; rc == 0 && shown + 1 < n;) {
+            const size_t s = shown + 1;   // the candidates: every frame after the one shown
+            int32_t* dst = jsp_pool_buffer(pool, jsp_previous_frame(dec) == jsp_pool_buffer(pool, 0) ? 1 : 0);
+            int found = -1, changed = 0;
+            int32_t* data = nullptr;
+            if (jsp_find_change(dec, (int)(n - s), srcs.data() + s, lens.data() + s, keys.data() + s, 0, keys[shown] ? srcs[shown] : nullptr,
+                                keys[shown] ? lens[shown] : 0, kInsignificantLines, dst, &found, &changed, nullptr, &data) != JSP_ZERO_STATE) {
+                std::fprintf(stderr, "jsp_find_change: %s\n", jsp_last_error());
+                rc = 1;
+                break;
+            }
+            shown = s + (size_t)found;
+            uint32_t crc = 0;
+            if (data && jsp_download(data, host.data(), npx) == 0) crc = crc32(reinterpret_cast<const uint8_t*>(host.data()), npx * 4);
+            std::printf("%zu %s %d %08x\n", shown, keys[shown] ? "key" : "inter", changed, crc);
+        }
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        return rc;
+    }
     if (seek_to >= 0) {   // the seek branch of GetDecompressedFrame: frames [nearest key frame, N] in one call, into slot 0
         if ((size_t)seek_to >= clip.frames.size()) { std::fprintf(stderr, "--seek %ld: the clip has %zu frames\n", seek_to, clip.frames.size()); return 2; }
         size_t k = (size_t)seek_to;

@@ -43,6 +43,11 @@ extern class JspNative {
     @:native("jsp_seek")               static function seek(c:RawPointer<JspCodec>, nframes:Int, srcs:RawPointer<RawConstPointer<UInt8>>, lens:RawPointer<SizeT>,
                                                             isKey:RawConstPointer<UInt8>, dst:RawPointer<cpp.Int32>,
                                                             dataPnt:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
+    // Manager.SkipStills over DataLoader.FindPossibleChange (Manager.hx:289-317), MSVideo1: the first frame from `first` on that changes the picture, composed into `dst` in one call
+    @:native("jsp_find_change")        static function findChange(c:RawPointer<JspCodec>, nframes:Int, srcs:RawPointer<RawConstPointer<UInt8>>, lens:RawPointer<SizeT>,
+                                                                  isKey:RawConstPointer<UInt8>, first:Int, keyBefore:RawConstPointer<UInt8>, keyBeforeLen:SizeT,
+                                                                  keyRow:Int, dst:RawPointer<cpp.Int32>, found:RawPointer<Int>, changed:RawPointer<Int>,
+                                                                  significance:RawPointer<Int>, dataPnt:RawPointer<RawPointer<cpp.Int32>>):Int;
     // frame pool in HBM (Manager.hx:114-118) and the two Manager passes that follow the codec
     @:native("jsp_key_frame_differs")  static function keyFrameDiffers(c:RawPointer<JspCodec>):Int;
     @:native("jsp_device_count")       static function deviceCount():Int;

@@ -120,6 +120,35 @@ class NativeCodec implements IVideoCodec {
         return { data_pnt: pool.find(dataPnt), significant_changes: signif != 0 };
     }
 
+    // ---- optional: skip stills (jsp_find_change; MSVideo1 only — ScreenPressor throws, a Manager decodes frame by frame there) --
+    /** Frames `srcs` (from next_frame_to_decode to the clip's end; `isKey` as the index flags them), decoded up to the first frame at
+     *  or after `first` whose significant_changes is true — or the last one — and that frame's picture composed into `dst` in one
+     *  call.  Key frames: frames_differ_significantly (`keyBefore` = the key frame in front of the range, or null; pixels from
+     *  `keyRow` on).  significance[k]: 1 / 0 for the frames judged (first .. found), -1 for the others. */
+    public function FindChange(srcs:Array<Bytes>, isKey:Array<Bool>, first:Int, keyBefore:Null<Bytes>, keyRow:Int, dst:FrameBuffer,
+                               significance:Array<Int>):{ found:Int, changed:Bool, data_pnt:FrameBuffer } {
+        var n = srcs.length;
+        var ptrs = new Array<RawConstPointer<UInt8>>();
+        var lens = new Array<cpp.SizeT>();
+        var keys = Bytes.alloc(n);
+        for (i in 0...n) {
+            ptrs.push(bytesPtr(srcs[i]));
+            lens.push(srcs[i].length);
+            keys.set(i, isKey[i] ? 1 : 0);
+        }
+        significance.resize(n);
+        for (i in 0...n) significance[i] = -1;
+        var dataPnt:RawPointer<cpp.Int32> = null;
+        var found:Int = -1;
+        var changed:Int = 0;
+        var rc = JspNative.findChange(h, n, cpp.NativeArray.address(ptrs, 0).raw, cpp.NativeArray.address(lens, 0).raw, bytesPtr(keys), first,
+                                      keyBefore == null ? null : bytesPtr(keyBefore), keyBefore == null ? 0 : keyBefore.length, keyRow, dst.ptr,
+                                      cpp.RawPointer.addressOf(found), cpp.RawPointer.addressOf(changed),
+                                      cpp.NativeArray.address(significance, 0).raw, cpp.RawPointer.addressOf(dataPnt));
+        if (rc != 0) throw "FindChange: " + JspNative.lastError().toString();
+        return { found: found, changed: changed != 0, data_pnt: pool.find(dataPnt) };
+    }
+
     // ---- optional: decode ahead of display (jsp_decompress_*_async / jsp_wait) ------------------------------------------
     /** Queue a frame; `src` and `dst` must stay untouched until wait(ticket).  Returns the ticket. */
     public function Submit(src:Bytes, dst:FrameBuffer, key:Bool):haxe.Int64 {

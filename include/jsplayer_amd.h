@@ -186,7 +186,7 @@ int jsp_set_stream(jsp_codec* c, void* hip_stream);
  *       jsp_key_frame_differs() after a synchronous DecompressI; *significant_changes of jsp_wait for an asynchronous one (a key
  *       frame that decoded and has no previous frame to be compared with counts as a change: Manager.hx:399-411; for a frame that FAILED
  *       *significant_changes stays what the decode reported and jsp_key_frame_differs() says -1).  Staged batches are not compared. */
-/*   "msv1_seek_chunk_frames" = "auto" (default) | "1".."n" : MSVideo1 only, jsp_seek.  Frames staged and composed per chunk of a
+/*   "msv1_seek_chunk_frames" = "auto" (default) | "1".."n" : MSVideo1 only, jsp_seek and jsp_find_change.  Frames staged and composed per chunk of a
  *       seek's range; auto: as many as keep the chunk's stream bytes and block tables under 1 GiB.  Results do not depend on it. */
 /*   "async_depth" = "1".."16" (default "4") : any codec.  Frames that may be in flight between jsp_decompress_*_async and
  *       jsp_wait. */
@@ -324,6 +324,35 @@ int jsp_staged_results(jsp_staged* s, int* status, int* adopted, int* significan
  *   "msv1_seek_chunk_frames"): after one chunk `dst` IS the picture before the next, so the result does not depend on the split. */
 int jsp_seek(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key,
              int32_t* dst, int32_t** data_pnt, int* significant_changes);
+
+/* ---- skip stills: Manager.SkipStills (Manager.hx:289-317) over DataLoader.FindPossibleChange (DataLoader.hx:239-252) -------------
+ * Find change: frames[0..nframes-1] run from where the caller's stream stands, as for jsp_seek (is_key likewise).  Frames before
+ * `first` are decoded but not judged (the stretch from the decode position to the frame after the one shown); the candidates are
+ * frames first..nframes-1.
+ *   SIGNIFICANCE of candidate k = what the sequential Manager would record for it.  Inter frame: what DecompressP reports (stage 1;
+ *       stage 2 from insignificant_lines on; stage 1 alone without a previous picture or, 16-bit, without Preinit; never for an
+ *       8-bit frame that has a previous picture, since the 8-bit Preinit sets no line).  Key frame (frames_differ_significantly,
+ *       Manager.hx:392-421): when the frame before is a key frame (k - 1 in the range; `key_before`, key_before_len bytes, for
+ *       k == 0, NULL = not a key frame) its bytes differ; else when there is no picture before it 1; else the pixels from row
+ *       `key_row` on differ between its picture and the picture before it (the Manager passes INSIGNIFICANT_LINES).  The Manager's
+ *       rule for frame 0 of the clip stays with the caller.
+ *   RESULTS  JSP_ZERO_STATE.  *found = the first significant candidate and *changed = 1; when there is none, *found = nframes - 1
+ *       and *changed = 0 (FindPossibleChange lands on the last frame).  `dst` holds frame *found's picture, and *data_pnt is what
+ *       jsp_seek defines for the range 0..*found.  significance[k] (NULL: not wanted; else nframes ints) = 0 / 1 for
+ *       first <= k <= *found, -1 elsewhere.  Host-side codec state — previous frame, persistent per-row block_changes — ends as
+ *       the sequential calls on frames 0..*found leave it; frames after *found leave no trace.
+ *   EQUIVALENCE, ERRORS, PRECONDITIONS  as jsp_seek, for the frames up to *found (a frame the reference raises on is an error when
+ *       no earlier candidate is significant; the error names its index in the range).  first outside 0..nframes-1, a null
+ *       found / changed or a negative key_row: an error with nothing changed.  jsp_key_frame_differs() answers -1 afterwards.
+ *   ScreenPressor: JSP_ERROR_OCCURED ("find_change: MSVideo1 only"), no state changed (jsplayer_amd/player.py Manager.skip_stills
+ *       decodes frame by frame there).
+ *   Per chunk of the range (option "msv1_seek_chunk_frames", the 1 GiB budget of jsp_seek): the chunk is staged, ONE launch
+ *   compares every block a judged frame codes with what the block's previous writer left (msv1_change_scan_kernel, no picture
+ *   written), then ONE launch composes `dst` up to the hit (a prefix of the chunk is staged again first, so that the host state
+ *   ends at the hit) or the whole chunk; the chunks after a hit are not staged. */
+int jsp_find_change(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key, int first,
+                    const uint8_t* key_before, size_t key_before_len, int key_row, int32_t* dst, int* found, int* changed,
+                    int* significance, int32_t** data_pnt);
 
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 

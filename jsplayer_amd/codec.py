@@ -25,6 +25,7 @@ from typing import Any, Optional, Sequence
 import numpy as np
 
 from . import _native as N
+from .player import INSIGNIFICANT_LINES
 
 
 class DecoderState(enum.IntEnum):
@@ -39,6 +40,16 @@ class PFrameResult:
     """IVideoCodec.hx:11-14"""
     data_pnt: Any
     significant_changes: bool
+
+
+@dataclass
+class ChangeResult:
+    """FindChange: the frame found (range index), whether it is significant (False: the range's last frame, nothing changed),
+    the previous frame afterwards and the significance of each frame of the range (None where it was not judged)."""
+    index: int
+    changed: bool
+    data_pnt: Any
+    significance: list
 
 
 class CodecError(RuntimeError):
@@ -205,6 +216,39 @@ class _NativeCodec:
             raise CodecError(N.last_error())
         return PFrameResult(self._prev if out_ptr.value else None, bool(signif.value))
 
+    # -- skip stills (jsp_find_change): Manager.SkipStills over DataLoader.FindPossibleChange (Manager.hx:289-317) ----------
+    FINDS_CHANGES = True   # FindChange() judges a range in one call (ScreenPressor: no, it decodes frame by frame)
+
+    def FindChange(self, srcs: Sequence, dst, is_key: Optional[Sequence[bool]] = None, first: int = 0,
+                   key_before=None, key_row: int = INSIGNIFICANT_LINES) -> ChangeResult:
+        """The frames `srcs` (from where the stream stands) as DecompressI / DecompressP would decode them in order, up to the
+        first frame at or after `first` that changes the picture significantly — or the last frame when none does —, that
+        frame's picture composed into `dst` alone (a device buffer).  Key frames are judged by the Manager's rule
+        (frames_differ_significantly: `key_before` = the bytes of the key frame before the range, if it is one; the pixel
+        compare from row `key_row` on).  CodecError where the reference raises (the previous frame is then None), on a bad
+        `first` and on ScreenPressor."""
+        n = len(srcs)
+        if n == 0:
+            raise CodecError("find_change: empty range")
+        keeps, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
+        for i, s in enumerate(srcs):
+            keep, p, ln = _src_arg(s)
+            keeps.append(keep)
+            ptrs[i] = p.value if p is not None else None
+            lens[i] = ln
+        addr = _frame_ptr(dst, self.X * self.Y)
+        self._bufs[addr] = dst
+        keys = bytes(bytearray(1 if k else 0 for k in is_key)) if is_key is not None else None
+        kb_keep, kb_ptr, kb_len = _src_arg(key_before) if key_before is not None else (None, None, 0)
+        out_ptr, found, changed, sig = C.c_void_p(), C.c_int(-1), C.c_int(0), (C.c_int * n)()
+        rc = self._lib.jsp_find_change(self._h, n, ptrs, lens, keys, int(first), kb_ptr, kb_len, int(key_row), C.c_void_p(addr),
+                                       C.byref(found), C.byref(changed), sig, C.byref(out_ptr))
+        self._track_prev()
+        if rc != 0:
+            raise CodecError(N.last_error())
+        return ChangeResult(found.value, bool(changed.value), self._prev if out_ptr.value else None,
+                            [None if v < 0 else bool(v) for v in sig])
+
     def NeedsIndex(self) -> bool:
         return bool(self._lib.jsp_needs_index(self._h))
 
@@ -366,6 +410,7 @@ class ScreenPressor(_NativeCodec):
     _kind = N.JSP_CODEC_SCREENPRESSOR
 
     SEEKS = False   # jsp_seek refuses it: sequential entropy stage, motion in inter frames
+    FINDS_CHANGES = False   # jsp_find_change refuses it likewise
 
     def __init__(self, width: int, height: int, bits_per_pixel: int, device: int = 0):
         super().__init__(width, height, bits_per_pixel, None, device)

@@ -1331,6 +1331,29 @@ bool msv1_seek_view(jsp_staged* base, Msv1SeekView& out) {
     return true;
 }
 
+bool msv1_save_state(jsp_codec* base, Msv1HostState& out) {
+    auto* c = dynamic_cast<Msv1Codec*>(base);
+    if (!c) return false;
+    out.prev_dev = c->prev_dev;
+    out.block_changes = c->block_changes;
+    out.block_changes_stale = c->block_changes_stale;
+    out.last_full_frame = c->last_full_frame;
+    out.last_full_dev = c->last_full_dev;
+    out.last_full_dev_bytes = c->last_full_dev_bytes;
+    return true;
+}
+
+void msv1_restore_state(jsp_codec* base, const Msv1HostState& s) {
+    auto* c = dynamic_cast<Msv1Codec*>(base);
+    if (!c) return;
+    c->prev_dev = s.prev_dev;
+    c->block_changes = s.block_changes;
+    c->block_changes_stale = s.block_changes_stale;
+    c->last_full_frame = s.last_full_frame;
+    c->last_full_dev = s.last_full_dev;
+    c->last_full_dev_bytes = s.last_full_dev_bytes;
+}
+
 }  // namespace jsp
 
 jsp_codec* jsp_make_msv1(int bits, int w, int h, const uint8_t* palette, int palette_bytes) {

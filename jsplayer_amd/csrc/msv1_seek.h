@@ -1,8 +1,11 @@
 // jsp_seek for MSVideo1 (msv1_seek.cpp, msv1_seek_kernels.hip): what the seek needs from a staged batch, and its kernel launcher.
 #pragma once
+#include <vector>
+
 #include "msv1.h"
 
 struct jsp_staged;
+struct jsp_codec;
 
 namespace jsp {
 
@@ -26,5 +29,24 @@ bool msv1_seek_view(jsp_staged* st, Msv1SeekView& out);
 // the pixels no block covers from `base` as well.  cmp_row_lo != ~0u: the stage-2 compare of the last frame (its coded blocks against
 // the picture before it, rows >= cmp_row_lo) ORs v.d_signif[v.nframes - 1].
 void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, uint32_t cmp_row_lo, hipStream_t stream);
+
+// jsp_find_change (msv1_find_change.cpp).  ONE launch of msv1_change_scan_kernel: for every frame f of the batch with
+// d_rows[f] != ~0u, whether a block f codes differs, on pixel rows >= d_rows[f], from that block's previous state — what the last
+// earlier frame of the batch that coded it made of it, else `before` (the picture before the batch) — ORs v.d_signif[f] (zeroed by
+// the caller).  d_walk: the batch's frames that code a block, ascending, nwalk of them; frames after the
+// last judged one need not be listed.  *d_first_hit (~0u from the caller) ends at most at the earliest frame found to differ.
+void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, uint32_t* d_first_hit,
+                             const int32_t* before, hipStream_t stream);
+// What MSVideo1 staging advances on the host (Msv1Codec::stage): a copy taken before a batch is staged puts the codec back where
+// it stood, so that a prefix of the batch can be staged again and the state end at the prefix's last frame.  False: not MSVideo1.
+struct Msv1HostState {
+    int32_t* prev_dev = nullptr;
+    std::vector<uint8_t> block_changes, last_full_frame;
+    bool block_changes_stale = false;
+    const void* last_full_dev = nullptr;
+    size_t last_full_dev_bytes = 0;
+};
+bool msv1_save_state(jsp_codec* c, Msv1HostState& out);
+void msv1_restore_state(jsp_codec* c, const Msv1HostState& s);
 
 }  // namespace jsp

@@ -161,6 +161,81 @@ __global__ __launch_bounds__(WG) void msv1_seek_kernel(const uint8_t* __restrict
         atomicOr(signif, 1u);
 }
 
+// ---- skip stills: which frames of a staged range change the picture (msv1_change_scan_kernel) -------------------------------
+// The last entry of walk[0, j) whose frame codes block `blk` (its code offset in `o`), as a frame index, or -1.  walk[] lists the
+// frames that can code anything (no early-outs), ascending; SCAN entries in flight per step as in last_writer.
+__device__ __forceinline__ int last_writer_walk(const uint32_t* __restrict__ desc, size_t pitch, const uint32_t* __restrict__ walk,
+                                                int blk, int j, uint32_t& o) {
+    for (int g = j - 1; g >= 0; g -= SCAN) {
+        uint32_t e[SCAN];
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k) e[k] = g - k >= 0 ? *(scgu32*)(desc + (size_t)walk[g - k] * pitch + blk) : MSV1_DESC_SKIP;
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k)
+            if (e[k] < MSV1_DESC_UNTOUCHED) { o = e[k]; return (int)walk[g - k]; }
+    }
+    return -1;
+}
+
+// One work-item per block (raster order) and per SEGMENT of the walk list (blockIdx.y: entries [y * seg, (y + 1) * seg)).  A lane
+// walks its table column forward through its segment, SCAN entries in flight per step, and remembers only WHERE the block was
+// last coded (frame, code offset).  At a frame that is judged (rows[f] != ~0u) and codes the block in a block row reaching
+// rows[f], it decodes the new code and the block's previous state — the last earlier writer in the range (found by a backward
+// search when the segment has not met one yet), else `before` — and compares the rows >= rows[f]: the rule and the decode of
+// msv1_seek_kernel's stage-2 compare.  A difference ORs signif[f] and lowers *first_hit; lanes stop at frames past *first_hit
+// (an optimisation only: every frame <= the earliest difference is walked by every lane whatever it sees of other lanes' stores).
+// Writes no picture.
+template <int BITS, bool VEC>
+__global__ __launch_bounds__(WG) void msv1_change_scan_kernel(const uint8_t* __restrict__ stream, const uint32_t* __restrict__ desc, size_t pitch,
+                                                              const Msv1FrameArgs* __restrict__ frames, const int32_t* __restrict__ palette,
+                                                              const uint32_t* __restrict__ walk, int nwalk, int seg, const uint32_t* __restrict__ rows,
+                                                              uint32_t* __restrict__ signif, uint32_t* __restrict__ first_hit,
+                                                              const uint32_t* __restrict__ before, int nblocks, int nbx, int X) {
+    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
+    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
+    if (BITS == 8) __syncthreads();
+    const long gid = (long)blockIdx.x * WG + threadIdx.x;
+    if (gid >= nblocks) return;
+    const int blk = (int)gid;
+    const int by = blk / nbx;
+    const int bx = blk - by * nbx;
+    const uint32_t row_top = (uint32_t)by * 4u + 3u;   // the block's last pixel row
+    const int j0 = (int)blockIdx.y * seg;
+    const int j1 = min(nwalk, j0 + seg);
+    int wf = -2;              // frame that last coded the block (-1: none in the range; -2: not looked up yet)
+    uint32_t wo = 0;          // ... and its code offset
+    for (int j = j0; j < j1; j += SCAN) {
+        if (walk[j] > __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        uint32_t e[SCAN];
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k) e[k] = j + k < j1 ? *(scgu32*)(desc + (size_t)walk[j + k] * pitch + blk) : MSV1_DESC_UNTOUCHED;
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k) {
+            if (e[k] >= MSV1_DESC_UNTOUCHED) continue;
+            const int f = (int)walk[j + k];
+            const uint32_t row = rows[f];
+            if (row != 0xFFFFFFFFu && row_top >= row) {
+                if (wf == -2) wf = last_writer_walk(desc, pitch, walk, blk, j + k, wo);
+                uint32_t px[16], pv[16];
+                decode_at<BITS>(stream, e[k], frames[f].stream_end, s_pal, px);
+                if (wf >= 0) decode_at<BITS>(stream, wo, frames[wf].stream_end, s_pal, pv);
+                else load_block<VEC>(before + (size_t)by * 4u * (size_t)X + (size_t)bx * 4u, X, pv);
+                bool diff = false;
+#pragma unroll
+                for (int y = 0; y < 4; ++y)
+                    if ((uint32_t)(by * 4 + y) >= row)
+                        diff |= (pv[y * 4] != px[y * 4]) | (pv[y * 4 + 1] != px[y * 4 + 1]) | (pv[y * 4 + 2] != px[y * 4 + 2]) | (pv[y * 4 + 3] != px[y * 4 + 3]);
+                if (diff) {
+                    if (__hip_atomic_load(signif + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) atomicOr(signif + f, 1u);
+                    if (__hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)f) atomicMin(first_hit, (uint32_t)f);
+                }
+            }
+            wf = f;
+            wo = e[k];
+        }
+    }
+}
+
 }  // namespace
 
 void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, uint32_t cmp_row_lo, hipStream_t stream) {
@@ -179,6 +254,28 @@ void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, 
     if (geo.bits == 16) { if (vec) JSP_SEEK(16, true); else JSP_SEEK(16, false); }
     else { if (vec) JSP_SEEK(8, true); else JSP_SEEK(8, false); }
 #undef JSP_SEEK
+}
+
+
+void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, uint32_t* d_first_hit,
+                             const int32_t* before, hipStream_t stream) {
+    const Msv1Geometry& geo = v.geo;
+    if (nwalk <= 0 || geo.nblocks <= 0) return;
+    // Segments of the walk list: enough work-items for ~8 waves per SIMD (a 1080p frame alone gives ~2), at least 16 entries each
+    const long waves_one = ((long)geo.nblocks + 63) / 64;
+    long nseg = std::max(1L, (8L * 1024L + waves_one - 1) / waves_one);
+    nseg = std::min(nseg, std::max(1L, ((long)nwalk + 15) / 16));
+    nseg = std::min(nseg, 65535L);
+    const int seg = (int)(((long)nwalk + nseg - 1) / nseg);
+    nseg = ((long)nwalk + seg - 1) / seg;
+    const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
+    const dim3 grid((unsigned)((geo.nblocks + WG - 1) / WG), (unsigned)nseg), block(WG);
+#define JSP_SCAN(BITS, VEC) hipLaunchKernelGGL((msv1_change_scan_kernel<BITS, VEC>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, v.d_frames, \
+                                               v.d_palette, d_walk, nwalk, seg, d_rows, v.d_signif, d_first_hit,                                     \
+                                               reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X)
+    if (geo.bits == 16) { if (vec) JSP_SCAN(16, true); else JSP_SCAN(16, false); }
+    else { if (vec) JSP_SCAN(8, true); else JSP_SCAN(8, false); }
+#undef JSP_SCAN
 }
 
 }  // namespace jsp

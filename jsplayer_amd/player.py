@@ -7,13 +7,16 @@ DecompressI / DecompressP protocol with its identity test (:499-524) and
 frame is shown as it is, a seek outside the stretch being decoded trashes every buffer and starts again
 at the nearest key frame, and the frames up to the target go to the decoder's `Seek` (MSVideo1 on the
 GPU: one call, one launch) or, for decoders without one (ScreenPressor, the oracle's classes), through
-`worker` frame by frame as the reference does.  Timers, bitmaps and audio of the reference's Manager
-are not rebuilt.
+`worker` frame by frame as the reference does.  `Manager.skip_stills` is SkipStills (:289-317) over
+DataLoader.FindPossibleChange (DataLoader.hx:239-252) plus the SeekTo that Main.play_timer does with its
+answer: significance already known is used as it is, and the frames nobody has judged go to the
+decoder's `FindChange` (MSVideo1 on the GPU: one call) or through `worker` frame by frame.  Timers,
+bitmaps and audio of the reference's Manager are not rebuilt.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -85,6 +88,7 @@ class Manager:
         self.next_frame_to_decode = 0
         self.frame_of_interest = 0
         self.log: List[DecodedFrame] = []
+        self.judged: Dict[int, bool] = {}   # significance of frames a FindChange call judged (skip_stills)
 
     def _slot_of(self, buf) -> int:
         for i, b in enumerate(self.buffers):
@@ -148,6 +152,7 @@ class Manager:
             out = DecodedFrame(index, False, shown, res.significant_changes)
         self.log.append(out)
         self.next_frame_to_decode = index + 1
+        self._last_was_key = key
         return out
 
     def play(self, frames: Sequence[bytes], on_frame: Optional[Callable[[DecodedFrame, object], None]] = None,
@@ -208,6 +213,83 @@ class Manager:
                 out = self.worker(frames[i], i, None, keys[i - start])
         self._last_was_key = keys[-1]
         self.next_frame_to_decode = index + 1
+        return out
+
+    def _known_significance(self) -> Dict[int, bool]:
+        """frames[i].significant_changes of the reference's loader: what decoding frame i recorded (missing = not known)."""
+        known = dict(self.judged)
+        for d in self.log:
+            if d.significant_changes is not None:
+                known[d.index] = bool(d.significant_changes)
+        return known
+
+    def skip_stills(self, frames: Sequence[bytes], key_flags: Optional[Sequence[bool]] = None) -> DecodedFrame:
+        """Skip to the next frame that changes the picture significantly — SkipStills(first_call = true) (Manager.hx:289-317)
+        over FindPossibleChange (DataLoader.hx:239-252), then the SeekTo that Main.play_timer does with the answer.  The
+        candidates start after the frame shown; significance already known (frames decoded before, frames a FindChange call
+        judged) is used as it is, and a known change is shown through seek().  From the first frame nobody has judged on, a
+        decoder with FindChange gets ONE call from the decode position to the end of the clip; without one, worker() decodes
+        frame by frame up to a significant frame.  When nothing changes up to the end, the last frame is shown.  worker /
+        play continue from the frame shown + 1 afterwards."""
+        n = len(frames)
+        if n == 0:
+            raise IndexError("skip_stills: empty clip")
+        pos = self.frame_of_interest + 1
+        known = self._known_significance()
+        while pos < n:
+            sig = known.get(pos)
+            if sig is None:
+                break
+            if sig:
+                return self.seek(frames, pos, key_flags)
+            pos += 1
+        if pos >= n:
+            return self.seek(frames, n - 1, key_flags)
+        # frame `pos` has not been judged: decode from where decoding stands (or, as seek() does, from the nearest key frame)
+        self.frame_of_interest = pos
+        key_idx = nearest_key_frame(lambda i: self._key_at(frames, i, key_flags), pos, n)
+        chained = True    # decoding goes on from the frame decoded last
+        if self.next_frame_to_decode < key_idx or self.next_frame_to_decode > pos:
+            self.next_frame_to_decode = key_idx
+            self.holds = [None] * len(self.buffers)
+            chained = False
+        start = self.next_frame_to_decode
+        keys = [self._key_at(frames, i, key_flags) for i in range(start, n)]
+        key_before = frames[start - 1] if chained and start > 0 and self._last_was_key else None
+        dec = self.decoder
+        if getattr(dec, "FINDS_CHANGES", False) and hasattr(dec, "FindChange"):
+            prev = dec.PreviousFrame()
+            prev_idx = self._slot_of(prev) if prev is not None else -1
+            free = self._get_free_buffer(prev_idx)
+            assert free >= 0
+            res = dec.FindChange(frames[start:], self.buffers[free], keys, first=pos - start, key_before=key_before,
+                                 key_row=INSIGNIFICANT_LINES)
+            f = start + res.index
+            for j, sg in enumerate(res.significance):
+                if sg is not None:
+                    self.judged[start + j] = sg
+            shown = free
+            if res.data_pnt is not None:
+                if res.data_pnt is prev and prev_idx >= 0:      # nothing up to f changed the picture
+                    h = self.holds[prev_idx]
+                    self.holds[prev_idx] = range(h.start, f + 1) if h else range(f, f + 1)
+                    shown = prev_idx
+                else:
+                    self.holds[free] = range(f, f + 1)
+            out = DecodedFrame(f, keys[f - start], shown, res.significance[f - start])
+            self.log.append(out)
+            self._last_was_key = keys[f - start]
+        else:
+            prev_key = key_before
+            for i in range(start, n):
+                key = keys[i - start]
+                out = self.worker(frames[i], i, prev_key if key else None, key)
+                prev_key = frames[i] if key else None
+                if i >= pos and out.significant_changes:
+                    break
+            f = out.index
+        self.frame_of_interest = f
+        self.next_frame_to_decode = f + 1
         return out
 
     def play_pipelined(self, frames: Sequence[bytes], depth: int = 4,
