@@ -14,6 +14,9 @@
 //                                no upload of their own.  --prefetch 0: a copy, or a read over the bus inside the kernel, per frame
 //   jsp_play clip.avi --skip-stills   MSVideo1: frame 0, then skip to the next significant change until the end (Manager.SkipStills,
 //                                one jsp_find_change per skip); prints "<index> <key|inter> <changed> <crc32>" per landing
+//   jsp_play clip.avi --step-back   MSVideo1: ONE seek index over the clip (jsp_index_build), then the last frame and every frame down
+//                                to 0, one jsp_index_show each (Main.on_prevframe, Manager.hx:191-196); prints "<index> <key|inter>
+//                                <changed> <crc32>" per frame — sorted, the plain run's frames, significance and CRCs
 //   jsp_play clip.avi --seek N   MSVideo1: frame N first, through ONE jsp_seek from the nearest key frame (DataLoader.hx:125-132;
 //                                Manager.hx:216-259), then on frame by frame; the lines from N on carry the CRCs of a plain run
 //   jsp_play a.avi,b.avi --pipelined --devices 0,1,... [--streams T] [--quiet ...]
@@ -397,6 +400,7 @@ int main(int argc, char** argv) {
     double seconds = 0;
     long seek_to = -1;                                        // --seek N: frame N first, through jsp_seek
     bool skip_stills = false;                                 // --skip-stills: from frame 0, skip to each significant change (jsp_find_change)
+    bool step_back = false;                                   // --step-back: a seek index over the clip, shown from the last frame down to 0
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -412,6 +416,7 @@ int main(int argc, char** argv) {
         else if (o == "--device" && a + 1 < argc) device = std::atoi(argv[++a]);
         else if (o == "--seek" && a + 1 < argc) seek_to = std::atol(argv[++a]);
         else if (o == "--skip-stills") skip_stills = true;
+        else if (o == "--step-back") step_back = true;
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
             for (size_t at = 0; at <= list.size();) {
@@ -425,6 +430,7 @@ int main(int argc, char** argv) {
     }
     if (seek_to >= 0 && (pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--seek goes with the plain per-frame run\n"); return 2; }
     if (skip_stills && (seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--skip-stills goes alone\n"); return 2; }
+    if (step_back && (skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--step-back goes alone\n"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
         if (!quiet) return play_batched(clip, batch, 1, false) < 0 ? 1 : 0;
@@ -573,6 +579,38 @@ int main(int argc, char** argv) {
             if (data && jsp_download(data, host.data(), npx) == 0) crc = crc32(reinterpret_cast<const uint8_t*>(host.data()), npx * 4);
             std::printf("%zu %s %d %08x\n", shown, keys[shown] ? "key" : "inter", changed, crc);
         }
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        return rc;
+    }
+    if (step_back) {   // Main.on_prevframe from the last frame down to 0: one index build, then ONE jsp_index_show per step
+        const size_t n = clip.frames.size();
+        std::vector<const uint8_t*> srcs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> keys;
+        for (size_t i = 0; i < n; ++i) {
+            srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+            lens.push_back(clip.frames[i].second);
+            keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        jsp_index* idx = n ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        if (n && !idx) { std::fprintf(stderr, "jsp_index_build: %s\n", jsp_last_error()); rc = 1; }
+        std::vector<int> sig(n, 0);
+        if (idx) jsp_index_significance(idx, sig.data());
+        for (size_t t = n; idx && t-- > 0;) {
+            int32_t* dst = jsp_pool_buffer(pool, (int)(t & 1));
+            int32_t* data = nullptr;
+            int signif = 0;
+            if (jsp_index_show(dec, idx, (int)t, dst, 0, &data, &signif) != JSP_ZERO_STATE) {
+                std::fprintf(stderr, "jsp_index_show: %s\n", jsp_last_error());
+                rc = 1;
+                break;
+            }
+            uint32_t crc = 0;
+            if (data && jsp_download(data, host.data(), npx) == 0) crc = crc32(reinterpret_cast<const uint8_t*>(host.data()), npx * 4);
+            std::printf("%zu %s %d %08x\n", t, keys[t] ? "key" : "inter", sig[t], crc);
+        }
+        jsp_index_destroy(idx);
         jsp_pool_destroy(pool);
         jsp_codec_destroy(dec);
         return rc;

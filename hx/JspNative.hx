@@ -48,6 +48,13 @@ extern class JspNative {
                                                                   isKey:RawConstPointer<UInt8>, first:Int, keyBefore:RawConstPointer<UInt8>, keyBeforeLen:SizeT,
                                                                   keyRow:Int, dst:RawPointer<cpp.Int32>, found:RawPointer<Int>, changed:RawPointer<Int>,
                                                                   significance:RawPointer<Int>, dataPnt:RawPointer<RawPointer<cpp.Int32>>):Int;
+    // seek index (Main.on_prevframe / on_click, Manager.hx:184-208), MSVideo1: a range kept resident in HBM, any frame of it shown by ONE launch
+    @:native("jsp_index_build")        static function indexBuild(c:RawPointer<JspCodec>, nframes:Int, srcs:RawPointer<RawConstPointer<UInt8>>, lens:RawPointer<SizeT>,
+                                                                  isKey:RawConstPointer<UInt8>, keyRow:Int):RawPointer<JspIndex>;
+    @:native("jsp_index_show")         static function indexShow(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, t:Int, dst:RawPointer<cpp.Int32>, adopt:Int,
+                                                                 dataPnt:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
+    @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
+    @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // frame pool in HBM (Manager.hx:114-118) and the two Manager passes that follow the codec
     @:native("jsp_key_frame_differs")  static function keyFrameDiffers(c:RawPointer<JspCodec>):Int;
     @:native("jsp_device_count")       static function deviceCount():Int;
@@ -65,5 +72,6 @@ extern class JspNative {
 }
 
 @:include("jsplayer_amd.h") @:native("jsp_codec") @:structAccess extern class JspCodec {}
+@:include("jsplayer_amd.h") @:native("jsp_index") @:structAccess extern class JspIndex {}
 @:include("jsplayer_amd.h") @:native("jsp_pool") @:structAccess extern class JspPool {}
 #end

@@ -149,6 +149,41 @@ class NativeCodec implements IVideoCodec {
         return { found: found, changed: changed != 0, data_pnt: pool.find(dataPnt) };
     }
 
+    // ---- optional: seek index (jsp_index_*; MSVideo1 only — ScreenPressor throws, a Manager decodes frame by frame there) -----
+    /** Frames `srcs` (from where the stream stands, as for Seek) kept resident in HBM: ShowIndexed(idx, t, ...) then writes what
+     *  Seek(srcs[0..t]) would write on the codec as it stands now, in one launch.  significance[k] (filled here): 1 / 0 for every
+     *  frame, as FindChange judges it.  Free with DestroyIndex (before or after this codec is stopped). */
+    public function BuildIndex(srcs:Array<Bytes>, isKey:Array<Bool>, keyRow:Int, significance:Array<Int>):RawPointer<JspIndex> {
+        var n = srcs.length;
+        var ptrs = new Array<RawConstPointer<UInt8>>();
+        var lens = new Array<cpp.SizeT>();
+        var keys = Bytes.alloc(n);
+        for (i in 0...n) {
+            ptrs.push(bytesPtr(srcs[i]));
+            lens.push(srcs[i].length);
+            keys.set(i, isKey[i] ? 1 : 0);
+        }
+        var idx = JspNative.indexBuild(h, n, cpp.NativeArray.address(ptrs, 0).raw, cpp.NativeArray.address(lens, 0).raw, bytesPtr(keys), keyRow);
+        if (idx == null) throw "BuildIndex: " + JspNative.lastError().toString();
+        for (i in 0...n) significance[i] = 0;
+        JspNative.indexSignificance(idx, cpp.NativeArray.address(significance, 0).raw);
+        return idx;
+    }
+
+    /** Frame t of the index into `dst` (not the previous frame).  adopt: the codec ends as after Seek(srcs[0..t]), so that
+     *  DecompressP(t + 1) follows on; else it is not touched. */
+    public function ShowIndexed(idx:RawPointer<JspIndex>, t:Int, dst:FrameBuffer, adopt:Bool):PFrameResult {
+        var dataPnt:RawPointer<cpp.Int32> = null;
+        var signif:Int = 0;
+        var rc = JspNative.indexShow(h, idx, t, dst.ptr, adopt ? 1 : 0, cpp.RawPointer.addressOf(dataPnt), cpp.RawPointer.addressOf(signif));
+        if (rc != 0) throw "ShowIndexed: " + JspNative.lastError().toString();
+        return { data_pnt: pool.find(dataPnt), significant_changes: signif != 0 };
+    }
+
+    public static function DestroyIndex(idx:RawPointer<JspIndex>):Void {
+        JspNative.indexDestroy(idx);
+    }
+
     // ---- optional: decode ahead of display (jsp_decompress_*_async / jsp_wait) ------------------------------------------
     /** Queue a frame; `src` and `dst` must stay untouched until wait(ticket).  Returns the ticket. */
     public function Submit(src:Bytes, dst:FrameBuffer, key:Bool):haxe.Int64 {

@@ -354,6 +354,42 @@ int jsp_find_change(jsp_codec* c, int nframes, const uint8_t* const* srcs, const
                     const uint8_t* key_before, size_t key_before_len, int key_row, int32_t* dst, int* found, int* changed,
                     int* significance, int32_t** data_pnt);
 
+/* ---- seek index: scrubbing, previous frame, seek-bar clicks (Main.on_prevframe / Manager.PrevFrameTime, Manager.hx:184-208;
+ * Main.on_click, Main.hx:1197-1215) over a range kept resident in HBM ------------------------------------------------------------
+ * Build: frames[0..nframes-1] run from where the caller's stream stands, as for jsp_seek (is_key likewise).  The range is staged
+ *   once (the codec's staging, either "msv1_parse", chunks under jsp_seek's 1 GiB budget / option "msv1_seek_chunk_frames") and its
+ *   stream bytes, block tables and frame records stay in HBM, with a bitmap of which frame codes which block.  The codec's previous
+ *   picture, if any, is COPIED into the index (the caller may reuse that buffer afterwards).  Every frame is judged as
+ *   jsp_find_change judges its candidates (frame 0 with key_before = NULL; the Manager's rule for frame 0 of the clip stays with
+ *   the caller).
+ *   RESULTS  The index (jsp_index_destroy frees it), or NULL and jsp_last_error().  The codec's host state is left exactly as it
+ *       was and no caller buffer is written.
+ *   ERRORS  A frame the reference raises on (a skip code with no previous picture): NULL, the error names the frame's index in the
+ *       range, nothing changed.  ScreenPressor: NULL ("index: MSVideo1 only"), nothing changed.  Otherwise the refusals of
+ *       jsp_seek: an asynchronous frame in flight, a codec in host-pointer mode, a negative key_row.
+ * Show: EQUIVALENCE  jsp_index_show(t) writes into `dst` exactly what jsp_seek(frames[0..t]) writes, called on the codec as it stood
+ *       at the build: pixels, *data_pnt (dst when a frame 0..t adopts its destination, else the previous frame of the build's time)
+ *       and *significant_changes.  ONE kernel launch, no staging, no upload: every block is decoded from the last frame <= t that
+ *       coded it (bitmap words walked down from t / 32), else copied from the index's picture before the range (none: dst keeps
+ *       it, as with jsp_seek).
+ *   adopt = 0: the codec is not touched (thumbnails, a preview while scrubbing).  adopt = 1: the codec ends as that jsp_seek leaves
+ *       it — previous frame, per-row block_changes (recorded per frame at the build: MSVideo1.hx:122,305 reset a row only when a
+ *       frame reaches it), what the on-GPU parse needs — so a following DecompressP(t + 1) behaves as after sequential decoding.
+ *       The codec keeps no pointer into the index.  jsp_key_frame_differs() answers -1 afterwards.
+ *   PRECONDITIONS  `dst` is a device buffer and not the codec's current previous frame; no asynchronous frame in flight.
+ *   ERRORS  t outside 0..nframes-1, an index built by another codec, ScreenPressor, a violated precondition: JSP_ERROR_OCCURED,
+ *       nothing changed.
+ * Significance: out[0..nframes-1] = 1 / 0, what jsp_find_change judges for each frame (inter frames: what DecompressP reports;
+ *   key frames: frames_differ_significantly from key_row on) — loader.GetFrameChanges (Manager.hx:229) for every frame of the range.
+ * Info: frames, and the bytes the index holds in HBM and in host memory (staging memory is released at the end of the build).
+ * Destroy: frees device memory only; safe before or after jsp_codec_destroy of its codec. */
+typedef struct jsp_index jsp_index;
+jsp_index* jsp_index_build(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key, int key_row);
+int jsp_index_show(jsp_codec* c, jsp_index* idx, int t, int32_t* dst, int adopt, int32_t** data_pnt, int* significant_changes);
+int jsp_index_significance(const jsp_index* idx, int* out);
+int jsp_index_info(const jsp_index* idx, int* nframes, uint64_t* device_bytes, uint64_t* host_bytes);
+void jsp_index_destroy(jsp_index* idx);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

@@ -249,6 +249,29 @@ class _NativeCodec:
         return ChangeResult(found.value, bool(changed.value), self._prev if out_ptr.value else None,
                             [None if v < 0 else bool(v) for v in sig])
 
+    # -- seek index (jsp_index_*): a range resident in HBM, any frame of it shown by one launch ---------------------------------
+    INDEXES = True   # BuildIndex() keeps a range resident (ScreenPressor: no, it decodes frame by frame)
+
+    def BuildIndex(self, srcs: Sequence, is_key: Optional[Sequence[bool]] = None, key_row: int = INSIGNIFICANT_LINES) -> "SeekIndex":
+        """The frames `srcs` (from where the stream stands, as for Seek) staged once and kept in HBM: SeekIndex.Show(t) then
+        writes what Seek(srcs[:t + 1]) on the codec as it stands now would write, in one launch.  Every frame is judged as
+        FindChange judges it (`significance`).  The codec is left as it is; CodecError where the reference raises (the error names
+        the frame) and on ScreenPressor."""
+        n = len(srcs)
+        if n == 0:
+            raise CodecError("index: empty range")
+        keeps, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
+        for i, s in enumerate(srcs):
+            keep, p, ln = _src_arg(s)
+            keeps.append(keep)
+            ptrs[i] = p.value if p is not None else None
+            lens[i] = ln
+        keys = bytes(bytearray(1 if k else 0 for k in is_key)) if is_key is not None else None
+        h = self._lib.jsp_index_build(self._h, n, ptrs, lens, keys, int(key_row))
+        if not h:
+            raise CodecError(N.last_error())
+        return SeekIndex(self, h, self._prev)
+
     def NeedsIndex(self) -> bool:
         return bool(self._lib.jsp_needs_index(self._h))
 
@@ -388,6 +411,65 @@ class StagedBatch:
             pass
 
 
+class SeekIndex:
+    """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch.  `significance` = FindChange's verdict
+    for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
+
+    def __init__(self, codec: _NativeCodec, handle: int, prev_at_build):
+        self._codec, self._h = codec, handle
+        self._prev_at_build = prev_at_build   # what data_pnt is for a frame before the first one that adopts its buffer
+        lib = codec._lib
+        n, dev, host = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        lib.jsp_index_info(handle, C.byref(n), C.byref(dev), C.byref(host))
+        self.frames, self.device_bytes, self.host_bytes = n.value, dev.value, host.value
+        sig = (C.c_int * self.frames)()
+        lib.jsp_index_significance(handle, sig)
+        self.significance = [bool(v) for v in sig]
+        self._lib = lib
+
+    def Show(self, t: int, dst, adopt: bool = True) -> PFrameResult:
+        """Frame t's picture into `dst` (a device buffer, not the codec's previous frame), as Seek(srcs[:t + 1]) would write it
+        on the codec as it stood at the build.  adopt: the codec ends as that Seek leaves it (DecompressP(t + 1) follows on);
+        else it is not touched."""
+        if not self._h:
+            raise CodecError("index_show: the index is closed")
+        codec = self._codec
+        if not codec._h:
+            raise CodecError("index_show: the codec is closed")
+        addr = _frame_ptr(dst, codec.X * codec.Y)
+        codec._bufs[addr] = dst
+        out_ptr, signif = C.c_void_p(), C.c_int(0)
+        rc = self._lib.jsp_index_show(codec._h, self._h, int(t), C.c_void_p(addr), 1 if adopt else 0, C.byref(out_ptr), C.byref(signif))
+        if rc != 0:
+            raise CodecError(N.last_error())
+        if adopt:
+            codec._track_prev()
+        if not out_ptr.value:
+            data = None
+        elif out_ptr.value == addr:
+            data = dst
+        else:
+            data = self._prev_at_build
+        return PFrameResult(data, bool(signif.value))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.jsp_index_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MSVideo1_16bit(_NativeCodec):
     """MSVideo1.hx:8-260 — `new MSVideo1_16bit(width, height)`"""
     _kind = N.JSP_CODEC_MSVIDEO1_16
@@ -411,6 +493,7 @@ class ScreenPressor(_NativeCodec):
 
     SEEKS = False   # jsp_seek refuses it: sequential entropy stage, motion in inter frames
     FINDS_CHANGES = False   # jsp_find_change refuses it likewise
+    INDEXES = False   # jsp_index_build refuses it likewise
 
     def __init__(self, width: int, height: int, bits_per_pixel: int, device: int = 0):
         super().__init__(width, height, bits_per_pixel, None, device)

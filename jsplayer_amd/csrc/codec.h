@@ -1,5 +1,6 @@
 // Internal C++ shape of the C ABI objects (include/jsplayer_amd.h).
 #pragma once
+#include <atomic>
 #include <memory>
 #include <string>
 #include <vector>
@@ -64,7 +65,13 @@ struct jsp_async_job {
     bool key_compare_queued = false;     // ... is being worked out by the pass queued behind the frame's kernels
 };
 
+inline uint64_t jsp_next_codec_serial() {
+    static std::atomic<uint64_t> n{0};
+    return ++n;
+}
+
 struct jsp_codec {
+    const uint64_t serial = jsp_next_codec_serial();   // tells codec instances apart (a seek index names the codec it was built by)
     int kind = 0;
     int X = 0, Y = 0;
     int device = 0;

@@ -1354,6 +1354,38 @@ void msv1_restore_state(jsp_codec* base, const Msv1HostState& s) {
     c->last_full_dev_bytes = s.last_full_dev_bytes;
 }
 
+bool msv1_block_changes_now(jsp_codec* base, std::vector<uint8_t>& out) {
+    auto* c = dynamic_cast<Msv1Codec*>(base);
+    if (!c) return false;
+    out = c->block_changes;
+    if (!c->block_changes_stale) return true;
+    std::vector<uint8_t> bytes;   // as host_parse rebuilds them, on a copy
+    if (c->last_full_dev) {
+        JSP_HIP(hipStreamSynchronize(c->stream));
+        bytes.resize(c->last_full_dev_bytes);
+        if (!bytes.empty()) JSP_HIP(hipMemcpy(bytes.data(), c->last_full_dev, bytes.size(), hipMemcpyDeviceToHost));
+    }
+    const std::vector<uint8_t>& src = c->last_full_dev ? bytes : c->last_full_frame;
+    std::vector<uint32_t> scratch((size_t)std::max(c->geo.nblocks, 1));
+    Msv1Parse tmp;
+    msv1_parse(c->geo, src.data(), src.size(), true, 0, c->insignificant_blocks, 0, scratch.data(), out, tmp);
+    return true;
+}
+
+bool msv1_take_batch(jsp_staged* base, DeviceBuffer& stream, DeviceBuffer& desc, DeviceBuffer& frames) {
+    auto* st = dynamic_cast<Msv1Staged*>(base);
+    if (!st) return false;
+    auto take = [](DeviceBuffer& to, DeviceBuffer& from) {
+        to.release();
+        std::swap(to.p, from.p);
+        std::swap(to.cap, from.cap);
+    };
+    take(stream, st->d_stream);
+    take(desc, st->d_desc);
+    take(frames, st->d_frames);
+    return true;
+}
+
 }  // namespace jsp
 
 jsp_codec* jsp_make_msv1(int bits, int w, int h, const uint8_t* palette, int palette_bytes) {

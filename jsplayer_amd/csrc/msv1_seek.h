@@ -2,6 +2,7 @@
 #pragma once
 #include <vector>
 
+#include "common.h"
 #include "msv1.h"
 
 struct jsp_staged;
@@ -48,5 +49,30 @@ struct Msv1HostState {
 };
 bool msv1_save_state(jsp_codec* c, Msv1HostState& out);
 void msv1_restore_state(jsp_codec* c, const Msv1HostState& s);
+
+// ---- jsp_index_* (msv1_index.cpp) ------------------------------------------------------------------------------------------
+// The per-row flags (block_changes) the codec's next host parse would start from — rebuilt from the last fully parsed frame when the
+// codec keeps them stale — without changing the codec.  False: not MSVideo1.
+bool msv1_block_changes_now(jsp_codec* c, std::vector<uint8_t>& out);
+// The batch's stream buffer, block tables and frame records change hands (the batch keeps none of them; its next staging allocates
+// afresh).  False: not a batch of the MSVideo1 staging.
+bool msv1_take_batch(jsp_staged* st, DeviceBuffer& stream, DeviceBuffer& desc, DeviceBuffer& frames);
+// What the show kernel reads of one staged chunk of an index.
+struct Msv1IndexChunk {
+    const uint8_t* stream;
+    const uint32_t* desc;            // the chunk's frame f at f * pitch (pitch = nblocks)
+    const Msv1FrameArgs* frames;
+    uint32_t first;                  // index frame of the chunk's frame 0
+    uint32_t pad;
+};
+// ONE launch of msv1_change_scan_kernel judging EVERY frame with d_rows[f] != ~0u (ORs v.d_signif[f], zeroed by the caller); the rest
+// as msv1_launch_change_scan.
+void msv1_launch_judge_all(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, const int32_t* before, hipStream_t stream);
+// ONE launch of msv1_coded_bitmap_kernel over the chunk `v` = index frames [a, a + v.nframes): bitmap (word-major, nblocks words per
+// 32 frames, zeroed before the first chunk), d_rows (nby words per 32 frames, zeroed) and d_stop (one word per frame, all ones before).
+void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, uint32_t* d_rows, uint32_t* d_stop, hipStream_t stream);
+// ONE launch of msv1_index_show_kernel: frame t of the index into dst.
+void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                            const uint32_t* d_bitmap, int t, int32_t* dst, const int32_t* before, hipStream_t stream);
 
 }  // namespace jsp

@@ -185,7 +185,9 @@ __device__ __forceinline__ int last_writer_walk(const uint32_t* __restrict__ des
 // msv1_seek_kernel's stage-2 compare.  A difference ORs signif[f] and lowers *first_hit; lanes stop at frames past *first_hit
 // (an optimisation only: every frame <= the earliest difference is walked by every lane whatever it sees of other lanes' stores).
 // Writes no picture.
-template <int BITS, bool VEC>
+// ALL (jsp_index_build): every judged frame is judged — no stop at the first hit, first_hit unused.  The jsp_find_change form (ALL = false)
+// is unchanged.
+template <int BITS, bool VEC, bool ALL = false>
 __global__ __launch_bounds__(WG) void msv1_change_scan_kernel(const uint8_t* __restrict__ stream, const uint32_t* __restrict__ desc, size_t pitch,
                                                               const Msv1FrameArgs* __restrict__ frames, const int32_t* __restrict__ palette,
                                                               const uint32_t* __restrict__ walk, int nwalk, int seg, const uint32_t* __restrict__ rows,
@@ -205,7 +207,7 @@ __global__ __launch_bounds__(WG) void msv1_change_scan_kernel(const uint8_t* __r
     int wf = -2;              // frame that last coded the block (-1: none in the range; -2: not looked up yet)
     uint32_t wo = 0;          // ... and its code offset
     for (int j = j0; j < j1; j += SCAN) {
-        if (walk[j] > __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        if (!ALL && walk[j] > __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
         uint32_t e[SCAN];
 #pragma unroll
         for (int k = 0; k < SCAN; ++k) e[k] = j + k < j1 ? *(scgu32*)(desc + (size_t)walk[j + k] * pitch + blk) : MSV1_DESC_UNTOUCHED;
@@ -227,13 +229,121 @@ __global__ __launch_bounds__(WG) void msv1_change_scan_kernel(const uint8_t* __r
                         diff |= (pv[y * 4] != px[y * 4]) | (pv[y * 4 + 1] != px[y * 4 + 1]) | (pv[y * 4 + 2] != px[y * 4 + 2]) | (pv[y * 4 + 3] != px[y * 4 + 3]);
                 if (diff) {
                     if (__hip_atomic_load(signif + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) atomicOr(signif + f, 1u);
-                    if (__hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)f) atomicMin(first_hit, (uint32_t)f);
+                    if (!ALL && __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)f) atomicMin(first_hit, (uint32_t)f);
                 }
             }
             wf = f;
             wo = e[k];
         }
     }
+}
+
+// ---- seek index (jsp_index_build / jsp_index_show) -----------------------------------------------------------------------
+// Build, once per staged chunk: frames [a, b) of the index are frames [0, b - a) of the chunk's tables.  One work-item per block and
+// per bitmap word (blockIdx.y) overlapping the chunk: the lane reads its table column for the word's frames (one coalesced dword per
+// lane and frame, all in flight at once) and writes
+//   * bitmap[w * nblocks + blk] bit k: frame 32 w + k codes the block (entry below MSV1_DESC_UNTOUCHED) — word-major, so that the
+//     show kernel's lanes read consecutive dwords;
+//   * rows[w * nby + by] bit k |= frame 32 w + k codes a block of block row by (what the host parser leaves in block_changes[by]);
+//     a segmented OR over the wave's lanes of one row, then one atomic per row and wave;
+//   * stop[f] = min(stop[f], the first block frame f leaves untouched) — an 8-bit end marker or the end of a host-parsed stream
+//     (the untouched blocks are a suffix, so the wave's lowest lane is its first); one atomic per frame and wave that has any.
+// Words shared with the chunk before keep its bits (nothing else writes the word meanwhile: the chunks follow each other on one stream).
+__global__ __launch_bounds__(WG) void msv1_coded_bitmap_kernel(const uint32_t* __restrict__ desc, size_t pitch, int a, int b, uint32_t* __restrict__ bitmap,
+                                                               uint32_t* __restrict__ rows, uint32_t* __restrict__ stop, int nblocks, int nbx, int nby) {
+    const long gid = (long)blockIdx.x * WG + threadIdx.x;
+    const int w = a / 32 + (int)blockIdx.y;
+    const int f0 = max(a, 32 * w), f1 = min(b, 32 * w + 32);
+    const bool in = gid < nblocks;
+    const int blk = in ? (int)gid : 0;
+    uint32_t coded = 0, untouched = 0;
+    if (in) {
+        uint32_t e[32];   // (MSV1_DESC_SKIP for frames outside the chunk: neither coded nor untouched)
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+            const int f = 32 * w + k;
+            e[k] = f >= f0 && f < f1 ? *(scgu32*)(desc + (size_t)(f - a) * pitch + blk) : MSV1_DESC_SKIP;
+        }
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+            coded |= (e[k] < MSV1_DESC_UNTOUCHED ? 1u : 0u) << k;
+            untouched |= (e[k] == MSV1_DESC_UNTOUCHED ? 1u : 0u) << k;
+        }
+        uint32_t* word = bitmap + (size_t)w * (size_t)nblocks + blk;
+        *word = (32 * w < a ? *word : 0u) | coded;
+    }
+    // rows: lanes of one block row are consecutive; after the shuffles the first lane of each row holds the row's OR
+    const int lane = threadIdx.x & 63;
+    const int row = in ? blk / nbx : -1;
+    uint32_t v = coded;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_down(v, d);
+        const int orow = __shfl_down(row, d);
+        if (lane + d < 64 && orow == row) v |= o;
+    }
+    const int up = __shfl_up(row, 1);
+    if (in && v != 0u && (lane == 0 || up != row)) atomicOr(rows + (size_t)w * (size_t)nby + row, v);
+    if (__ballot(untouched != 0u) != 0ull) {
+        for (int k = 0; k < 32; ++k) {
+            const unsigned long long m = __ballot((untouched >> k) & 1u);
+            if (m != 0ull && lane == __ffsll((long long)m) - 1) atomicMin(stop + 32 * w + k, (uint32_t)blk);
+        }
+    }
+}
+
+// Show frame t: one work-item per block, as msv1_seek_kernel.  The lane masks bitmap word t / 32 to the frames <= t and walks the words
+// downwards (SCAN in flight per step) to the first non-zero one: its highest set bit is the last frame <= t that coded the block.  That
+// frame's chunk (frame_chunk[], chunks[]) gives its table entry and stream, and the code is decoded as the seek kernel decodes it.  No
+// writer: the block comes from `before` (the picture before the index; null: `dst` is left as it is).  Work-items past the last block
+// copy the pixels no block covers from `before`.
+template <int BITS, bool VEC>
+__global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk,
+                                                             const int32_t* __restrict__ palette, const uint32_t* __restrict__ bitmap, size_t pitch, int t,
+                                                             uint32_t* __restrict__ dst, const uint32_t* __restrict__ before, int nblocks, int nbx, int X,
+                                                             int cx, int cy, long nrem) {
+    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
+    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
+    if (BITS == 8) __syncthreads();
+    const long gid = (long)blockIdx.x * WG + threadIdx.x;
+    if (gid >= nblocks) {   // a pixel no block covers, as in msv1_seek_kernel
+        const long r = gid - nblocks;
+        if (r >= nrem || before == nullptr) return;
+        const long rw = (long)(X - cx) * cy;
+        const size_t i = r < rw ? (size_t)(r / (X - cx)) * (size_t)X + (size_t)cx + (size_t)(r % (X - cx)) : (size_t)cy * (size_t)X + (size_t)(r - rw);
+        *(sgu32*)(dst + i) = *(scgu32*)(before + i);
+        return;
+    }
+    const int blk = (int)gid;
+    const int by = blk / nbx;
+    const int bx = blk - by * nbx;
+    const size_t di = (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
+    int w = t >> 5;
+    uint32_t m = *(scgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
+    while (m == 0u && w > 0) {
+        uint32_t e[SCAN];
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(scgu32*)(bitmap + (size_t)(w - 1 - k) * (size_t)nblocks + blk) : 0u;
+        int step = SCAN;
+#pragma unroll
+        for (int k = SCAN - 1; k >= 0; --k)
+            if (e[k] != 0u) { m = e[k]; step = k + 1; }
+        w -= step;
+    }
+    uint32_t px[16];
+    if (m == 0u) {   // nothing up to t coded the block
+        if (before != nullptr) {
+            load_block<VEC>(before + di, X, px);
+            store_block<VEC>(dst + di, X, px);
+        }
+        return;
+    }
+    const int f = 32 * w + 31 - __builtin_clz(m);
+    const Msv1IndexChunk ch = chunks[frame_chunk[f]];
+    const int lf = f - (int)ch.first;
+    const uint32_t o = *(scgu32*)(ch.desc + (size_t)lf * pitch + blk);
+    decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
+    store_block<VEC>(dst + di, X, px);
 }
 
 }  // namespace
@@ -257,25 +367,73 @@ void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, 
 }
 
 
-void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, uint32_t* d_first_hit,
-                             const int32_t* before, hipStream_t stream) {
-    const Msv1Geometry& geo = v.geo;
-    if (nwalk <= 0 || geo.nblocks <= 0) return;
-    // Segments of the walk list: enough work-items for ~8 waves per SIMD (a 1080p frame alone gives ~2), at least 16 entries each
+namespace {
+// Segments of the walk list: enough work-items for ~8 waves per SIMD (a 1080p frame alone gives ~2), at least 16 entries each
+dim3 scan_grid(const Msv1Geometry& geo, int nwalk, int& seg) {
     const long waves_one = ((long)geo.nblocks + 63) / 64;
     long nseg = std::max(1L, (8L * 1024L + waves_one - 1) / waves_one);
     nseg = std::min(nseg, std::max(1L, ((long)nwalk + 15) / 16));
     nseg = std::min(nseg, 65535L);
-    const int seg = (int)(((long)nwalk + nseg - 1) / nseg);
+    seg = (int)(((long)nwalk + nseg - 1) / nseg);
     nseg = ((long)nwalk + seg - 1) / seg;
+    return dim3((unsigned)((geo.nblocks + WG - 1) / WG), (unsigned)nseg);
+}
+}  // namespace
+
+void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, uint32_t* d_first_hit,
+                             const int32_t* before, hipStream_t stream) {
+    const Msv1Geometry& geo = v.geo;
+    if (nwalk <= 0 || geo.nblocks <= 0) return;
+    int seg = 0;
+    const dim3 grid = scan_grid(geo, nwalk, seg), block(WG);
     const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
-    const dim3 grid((unsigned)((geo.nblocks + WG - 1) / WG), (unsigned)nseg), block(WG);
 #define JSP_SCAN(BITS, VEC) hipLaunchKernelGGL((msv1_change_scan_kernel<BITS, VEC>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, v.d_frames, \
                                                v.d_palette, d_walk, nwalk, seg, d_rows, v.d_signif, d_first_hit,                                     \
                                                reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X)
     if (geo.bits == 16) { if (vec) JSP_SCAN(16, true); else JSP_SCAN(16, false); }
     else { if (vec) JSP_SCAN(8, true); else JSP_SCAN(8, false); }
 #undef JSP_SCAN
+}
+
+void msv1_launch_judge_all(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, const int32_t* before, hipStream_t stream) {
+    const Msv1Geometry& geo = v.geo;
+    if (nwalk <= 0 || geo.nblocks <= 0) return;
+    int seg = 0;
+    const dim3 grid = scan_grid(geo, nwalk, seg), block(WG);
+    const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
+#define JSP_JUDGE(BITS, VEC) hipLaunchKernelGGL((msv1_change_scan_kernel<BITS, VEC, true>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, \
+                                                v.d_frames, v.d_palette, d_walk, nwalk, seg, d_rows, v.d_signif, nullptr,                            \
+                                                reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X)
+    if (geo.bits == 16) { if (vec) JSP_JUDGE(16, true); else JSP_JUDGE(16, false); }
+    else { if (vec) JSP_JUDGE(8, true); else JSP_JUDGE(8, false); }
+#undef JSP_JUDGE
+}
+
+void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, uint32_t* d_rows, uint32_t* d_stop, hipStream_t stream) {
+    const Msv1Geometry& geo = v.geo;
+    if (v.nframes <= 0 || geo.nblocks <= 0) return;
+    const int b = a + v.nframes;
+    const dim3 grid((unsigned)((geo.nblocks + WG - 1) / WG), (unsigned)((b - 1) / 32 - a / 32 + 1)), block(WG);
+    hipLaunchKernelGGL(msv1_coded_bitmap_kernel, grid, block, 0, stream, v.d_desc, v.desc_pitch, a, b, d_bitmap, d_rows, d_stop, geo.nblocks,
+                       std::max(geo.nbx, 1), geo.nby);
+}
+
+void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                            const uint32_t* d_bitmap, int t, int32_t* dst, const int32_t* before, hipStream_t stream) {
+    if (geo.X <= 0 || geo.Y <= 0) return;
+    const int cx = geo.nbx * 4, cy = geo.nby * 4;
+    const long nrem = (long)(geo.X - cx) * cy + (long)geo.X * (geo.Y - cy);
+    const long work = (long)std::max(geo.nblocks, 0) + nrem;
+    if (work <= 0) return;
+    const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(dst) & 15) && !(reinterpret_cast<uintptr_t>(before) & 15);
+    const size_t pitch = (size_t)std::max(geo.nblocks, 1);
+    const dim3 grid((unsigned)((work + WG - 1) / WG)), block(WG);
+#define JSP_SHOW(BITS, VEC) hipLaunchKernelGGL((msv1_index_show_kernel<BITS, VEC>), grid, block, 0, stream, d_chunks, d_frame_chunk, d_palette, d_bitmap, \
+                                               pitch, t, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(before), geo.nblocks,     \
+                                               std::max(geo.nbx, 1), geo.X, cx, cy, nrem)
+    if (geo.bits == 16) { if (vec) JSP_SHOW(16, true); else JSP_SHOW(16, false); }
+    else { if (vec) JSP_SHOW(8, true); else JSP_SHOW(8, false); }
+#undef JSP_SHOW
 }
 
 }  // namespace jsp

@@ -10,8 +10,11 @@ GPU: one call, one launch) or, for decoders without one (ScreenPressor, the orac
 `worker` frame by frame as the reference does.  `Manager.skip_stills` is SkipStills (:289-317) over
 DataLoader.FindPossibleChange (DataLoader.hx:239-252) plus the SeekTo that Main.play_timer does with its
 answer: significance already known is used as it is, and the frames nobody has judged go to the
-decoder's `FindChange` (MSVideo1 on the GPU: one call) or through `worker` frame by frame.  Timers,
-bitmaps and audio of the reference's Manager are not rebuilt.
+decoder's `FindChange` (MSVideo1 on the GPU: one call) or through `worker` frame by frame.  With a seek index
+attached (`Manager.attach_index`: a range kept resident by the decoder's `BuildIndex`), a seek inside it is one
+`Show` launch and its frames' significance is known without decoding; `next_frame` / `prev_frame` / `next_key` /
+`prev_key` are the navigation of Manager.hx:184-208 over `seek`.  Timers, bitmaps and audio of the reference's
+Manager are not rebuilt.
 """
 from __future__ import annotations
 
@@ -89,6 +92,17 @@ class Manager:
         self.frame_of_interest = 0
         self.log: List[DecodedFrame] = []
         self.judged: Dict[int, bool] = {}   # significance of frames a FindChange call judged (skip_stills)
+        self.index = None                   # attach_index: a seek index over clip frames index_first .. index_first + index.frames - 1
+        self.index_first = 0
+
+    def attach_index(self, index, first: int = 0) -> None:
+        """Serve seeks to clip frames first .. first + index.frames - 1 from `index` (the decoder's BuildIndex over those frames,
+        built where the decoder's state was that of frame first - 1 — typically from a key frame): one Show launch each, and the
+        index's significance verdicts count as known.  None detaches."""
+        self.index, self.index_first = index, int(first)
+
+    def _in_index(self, i: int) -> bool:
+        return self.index is not None and self.index_first <= i < self.index_first + self.index.frames
 
     def _slot_of(self, buf) -> int:
         for i, b in enumerate(self.buffers):
@@ -192,18 +206,23 @@ class Manager:
         start = self.next_frame_to_decode
         keys = [self._key_at(frames, i, key_flags) for i in range(start, index + 1)]
         dec = self.decoder
-        if getattr(dec, "SEEKS", False) and hasattr(dec, "Seek"):
+        use_index = self._in_index(index)
+        if use_index or (getattr(dec, "SEEKS", False) and hasattr(dec, "Seek")):
             prev = dec.PreviousFrame()
             prev_idx = self._slot_of(prev) if prev is not None else -1
             free = self._get_free_buffer(prev_idx)
             assert free >= 0
-            res = dec.Seek(frames[start:index + 1], self.buffers[free], keys)
+            if use_index:   # one launch; the decoder ends as the Seek from the index's first frame would leave it
+                res = self.index.Show(index - self.index_first, self.buffers[free], adopt=True)
+            else:
+                res = dec.Seek(frames[start:index + 1], self.buffers[free], keys)
             shown = free
             if res.data_pnt is not None:
-                if res.data_pnt is prev and prev_idx >= 0:      # nothing in the range changed the picture
-                    h = self.holds[prev_idx]
-                    self.holds[prev_idx] = range(h.start, index + 1) if h else range(index, index + 1)
-                    shown = prev_idx
+                held = self._slot_of(res.data_pnt)
+                if res.data_pnt is not self.buffers[free] and held >= 0:      # nothing in the range changed the picture
+                    h = self.holds[held]
+                    self.holds[held] = range(h.start, index + 1) if h else range(index, index + 1)
+                    shown = held
                 else:
                     self.holds[free] = range(index, index + 1)
             out = DecodedFrame(index, keys[-1], shown, None if keys[-1] else res.significant_changes)
@@ -217,7 +236,10 @@ class Manager:
 
     def _known_significance(self) -> Dict[int, bool]:
         """frames[i].significant_changes of the reference's loader: what decoding frame i recorded (missing = not known)."""
-        known = dict(self.judged)
+        known = {}
+        if self.index is not None:
+            known.update((self.index_first + i, bool(v)) for i, v in enumerate(self.index.significance))
+        known.update(self.judged)
         for d in self.log:
             if d.significant_changes is not None:
                 known[d.index] = bool(d.significant_changes)
@@ -291,6 +313,29 @@ class Manager:
         self.frame_of_interest = f
         self.next_frame_to_decode = f + 1
         return out
+
+    # -- navigation, Manager.hx:184-208 (last_frame_drawn = the frame shown) over seek() -------------------------------------
+    def next_frame(self, frames: Sequence[bytes], key_flags: Optional[Sequence[bool]] = None) -> DecodedFrame:
+        """NextFrameTime: the frame after the one shown (the last frame stays)."""
+        return self.seek(frames, min(self.frame_of_interest + 1, len(frames) - 1), key_flags)
+
+    def prev_frame(self, frames: Sequence[bytes], key_flags: Optional[Sequence[bool]] = None) -> DecodedFrame:
+        """PrevFrameTime: the frame before the one shown (frame 0 stays)."""
+        return self.seek(frames, max(self.frame_of_interest - 1, 0), key_flags)
+
+    def next_key(self, frames: Sequence[bytes], key_flags: Optional[Sequence[bool]] = None) -> DecodedFrame:
+        """NextKeyTime over DataLoader.GetNextKeyFrame (DataLoader.hx:134-142): the first key frame after the one shown, else the
+        last frame."""
+        n = len(frames)
+        i = min(self.frame_of_interest + 1, n - 1)
+        while i < n - 1 and not self._key_at(frames, i, key_flags):
+            i += 1
+        return self.seek(frames, i, key_flags)
+
+    def prev_key(self, frames: Sequence[bytes], key_flags: Optional[Sequence[bool]] = None) -> DecodedFrame:
+        """PrevKeyTime: the nearest key frame before the one shown (frame 0 at the start)."""
+        i = nearest_key_frame(lambda k: self._key_at(frames, k, key_flags), self.frame_of_interest - 1, len(frames))
+        return self.seek(frames, i, key_flags)
 
     def play_pipelined(self, frames: Sequence[bytes], depth: int = 4,
                        on_frame: Optional[Callable[[DecodedFrame, object], None]] = None,
