@@ -68,6 +68,20 @@ def _src_arg(src):
     return arr, C.c_void_p(arr.ctypes.data), arr.size
 
 
+def _range_args(srcs: Sequence, is_key: Optional[Sequence[bool]]):
+    """A range of frames -> (ctypes pointer array, ctypes length array, is_key bytes or None, objects to keep alive until the
+    native call returns)"""
+    n = len(srcs)
+    keeps, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
+    for i, s in enumerate(srcs):
+        keep, p, ln = _src_arg(s)
+        keeps.append(keep)
+        ptrs[i] = p.value if p is not None else None
+        lens[i] = ln
+    keys = bytes(bytearray(1 if k else 0 for k in is_key)) if is_key is not None else None
+    return ptrs, lens, keys, keeps
+
+
 def _frame_ptr(buf, npixels: int) -> int:
     """Address of a caller-owned frame buffer (torch device tensor or numpy host array)."""
     if isinstance(buf, np.ndarray):
@@ -200,15 +214,9 @@ class _NativeCodec:
         n = len(srcs)
         if n == 0:
             raise CodecError("seek: empty range")
-        keeps, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
-        for i, s in enumerate(srcs):
-            keep, p, ln = _src_arg(s)
-            keeps.append(keep)
-            ptrs[i] = p.value if p is not None else None
-            lens[i] = ln
+        ptrs, lens, keys, keeps = _range_args(srcs, is_key)
         addr = _frame_ptr(dst, self.X * self.Y)
         self._bufs[addr] = dst
-        keys = bytes(bytearray(1 if k else 0 for k in is_key)) if is_key is not None else None
         out_ptr, signif = C.c_void_p(), C.c_int(0)
         rc = self._lib.jsp_seek(self._h, n, ptrs, lens, keys, C.c_void_p(addr), C.byref(out_ptr), C.byref(signif))
         self._track_prev()
@@ -230,15 +238,9 @@ class _NativeCodec:
         n = len(srcs)
         if n == 0:
             raise CodecError("find_change: empty range")
-        keeps, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
-        for i, s in enumerate(srcs):
-            keep, p, ln = _src_arg(s)
-            keeps.append(keep)
-            ptrs[i] = p.value if p is not None else None
-            lens[i] = ln
+        ptrs, lens, keys, keeps = _range_args(srcs, is_key)
         addr = _frame_ptr(dst, self.X * self.Y)
         self._bufs[addr] = dst
-        keys = bytes(bytearray(1 if k else 0 for k in is_key)) if is_key is not None else None
         kb_keep, kb_ptr, kb_len = _src_arg(key_before) if key_before is not None else (None, None, 0)
         out_ptr, found, changed, sig = C.c_void_p(), C.c_int(-1), C.c_int(0), (C.c_int * n)()
         rc = self._lib.jsp_find_change(self._h, n, ptrs, lens, keys, int(first), kb_ptr, kb_len, int(key_row), C.c_void_p(addr),
@@ -260,13 +262,7 @@ class _NativeCodec:
         n = len(srcs)
         if n == 0:
             raise CodecError("index: empty range")
-        keeps, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
-        for i, s in enumerate(srcs):
-            keep, p, ln = _src_arg(s)
-            keeps.append(keep)
-            ptrs[i] = p.value if p is not None else None
-            lens[i] = ln
-        keys = bytes(bytearray(1 if k else 0 for k in is_key)) if is_key is not None else None
+        ptrs, lens, keys, keeps = _range_args(srcs, is_key)
         h = self._lib.jsp_index_build(self._h, n, ptrs, lens, keys, int(key_row))
         if not h:
             raise CodecError(N.last_error())

@@ -1,83 +1,232 @@
-// jsp_seek (include/jsplayer_amd.h): the seek branch of Manager.GetDecompressedFrame (Manager.hx:216-259) for MSVideo1 — frames
-// K..N staged as one batch (host or on-GPU parse, the codec's own staging) and composed into the caller's buffer by ONE launch of
-// msv1_seek_kernel, instead of N - K + 1 decodes each writing a whole frame.
+// The MSVideo1 range calls of include/jsplayer_amd.h — jsp_seek, jsp_find_change and jsp_index_* — and what they share: the chunks a
+// range is staged in (the codec's own staging, host or on-GPU parse), the refusals, the significance rules and the change scan.
 //
 // Kept apart from jsp_api.cpp / msv1_codec.cpp: those are also built against the stub HIP runtime of the host-layer sanitizer
-// build (tools/tsan_cpu.sh), which knows nothing of the seek kernel.
+// build (tools/tsan_cpu.sh), which knows nothing of the seek kernels.
 #include <algorithm>
+#include <cstring>
 
 #include "codec.h"
 #include "msv1_seek.h"
 
 using namespace jsp;
 
+struct jsp_index {
+    uint64_t codec_serial = 0;       // jsp_codec::serial of the codec that built it
+    int device = 0;
+    Msv1Geometry geo{};
+    int nframes = 0;
+    struct Chunk {
+        DeviceBuffer stream, desc, frames;
+        int first = 0, count = 0;
+    };
+    std::vector<std::unique_ptr<Chunk>> chunks;
+    DeviceBuffer d_chunks, d_frame_chunk, d_bitmap, d_palette, d_before;
+    bool has_before = false;
+    std::vector<int> significance;         // per frame: jsp_find_change's verdict (1 / 0)
+    std::vector<uint8_t> reported;         // per frame: what jsp_seek of frames 0..t reports as *significant_changes
+    std::vector<uint8_t> block_changes;    // nframes rows of nby flags: the per-row state after frame t
+    int first_adopted = 0;                 // the first frame that adopts its destination (nframes: none)
+    int32_t* prev_caller = nullptr;        // the codec's previous frame at build time (what a show before first_adopted leaves)
+    int32_t* prev_dev = nullptr;
+    uint64_t device_bytes() const {
+        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap;
+        for (const auto& c : chunks) n += c->stream.cap + c->desc.cap + c->frames.cap;
+        return n;
+    }
+    uint64_t host_bytes() const {
+        return sizeof(*this) + chunks.size() * sizeof(Chunk) + significance.size() * sizeof(int) + reported.size() + block_changes.size();
+    }
+};
+
 namespace {
 
 // Frames per chunk when the caller leaves it to the library: what the staged range holds in HBM (stream bytes in 16 KiB tiles,
 // 4 bytes per block of table) and in pinned host memory stays under this budget.
-constexpr uint64_t kSeekChunkBudget = 1ull << 30;
+constexpr uint64_t kChunkBudget = 1ull << 30;
 
 int fail(const char* fmt, const char* what = "") {
     set_error(fmt, what);
     return JSP_ERROR_OCCURED;
 }
 
+bool same_bytes(const uint8_t* a, size_t na, const uint8_t* b, size_t nb) {
+    return na == nb && (na == 0 || std::memcmp(a, b, na) == 0);
+}
+
+// The caller's range: frame k is srcs[k], lens[k] bytes, a key frame unless is_key[k] == 0 (no is_key: every frame is one).
+// key_before: the bytes of the key frame before the range, if it is one (jsp_find_change; null: there is none).
+struct Range {
+    const uint8_t* const* srcs;
+    const size_t* lens;
+    const uint8_t* is_key;
+    const uint8_t* key_before = nullptr;
+    size_t key_before_len = 0;
+    bool key(int k) const { return is_key ? is_key[k] != 0 : true; }
+};
+
+bool null_frame(int nframes, const uint8_t* const* srcs, const size_t* lens) {
+    for (int i = 0; i < nframes; ++i)
+        if (!srcs[i] && lens[i]) return true;
+    return false;
+}
+
+// ---- refusals: one function each, so that every entry point keeps its order (and so its message for an input refused on several
+// counts).  False: refused, the error "<who>: <what>" is set. ------------------------------------------------------------------
+bool refuse(const char* who, const char* what) {
+    set_error("%s: %s", who, what);
+    return false;
+}
+bool is_msv1(const jsp_codec* c, const char* who) {
+    return c->kind == JSP_CODEC_MSVIDEO1_16 || c->kind == JSP_CODEC_MSVIDEO1_8 || refuse(who, "MSVideo1 only");
+}
+bool nothing_in_flight(const jsp_codec* c, const char* who) {
+    return c->next_ticket == c->oldest_ticket || refuse(who, "an asynchronous frame is in flight (jsp_wait for it first)");
+}
+bool dst_not_previous(const jsp_codec* c, const int32_t* dst, const char* who) {
+    return dst != c->prev_caller || refuse(who, "dst is the current previous frame");
+}
+bool dst_on_device(const int32_t* dst, const char* who) {   // (after c->activate())
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, dst) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged)) return true;
+    (void)hipGetLastError();
+    return refuse(who, "dst must be a device frame buffer");
+}
+bool device_pointers(const jsp_codec* c, const char* who) { return c->ptr_mode != 2 || refuse(who, "codec is in host-pointer mode"); }
+
+// A call that leaves the codec where a sequential decode into `dst` would: the worker's frames finished, device pointers from now
+// on, and no key-frame compare to report (it does not run on these calls).
+void take_over(jsp_codec* c) {
+    c->worker_drain();
+    c->ptr_mode = 1;
+    c->last_key_differs = -1;
+}
+
+// ---- chunks ----------------------------------------------------------------------------------------------------------------
+// The end of the chunk that starts at frame a: option "msv1_seek_chunk_frames" frames, else as many as kChunkBudget holds (one at least).
+int chunk_end(const jsp_codec* c, const size_t* lens, int nframes, int a) {
+    if (c->seek_chunk_frames > 0) return std::min(nframes, a + c->seek_chunk_frames);
+    const uint64_t table_bytes = 4ull * (uint64_t)std::max((int64_t)c->X / 4 * (c->Y / 4), (int64_t)1);
+    int b = a + 1;
+    uint64_t bytes = lens[a] + table_bytes;
+    while (b < nframes && bytes + lens[b] + 16384 + table_bytes <= kChunkBudget) bytes += lens[b++] + 16384 + table_bytes;
+    return b;
+}
+
+// Frames [a, b) of the range staged into `into` (reused, or replaced by the staging object the codec returns), every frame's
+// destination `dst`.  The codec's host state advances to frame b - 1.
+jsp_staged* stage(jsp_codec* c, const Range& r, int a, int b, std::unique_ptr<jsp_staged>& into, int32_t* dst) {
+    std::vector<jsp_frame_in> frames((size_t)(b - a));
+    for (int i = a; i < b; ++i) frames[(size_t)(i - a)] = jsp_frame_in{r.srcs[i], r.lens[i], r.key(i), dst};
+    jsp_staged* st = c->stage(frames, into.get());
+    st->device = c->device;
+    if (st != into.get()) into.reset(st);
+    return st;
+}
+
+// The first frame of a staged chunk of nf frames that the reference raises on (-1: none): nothing at or past it is reached.
+int first_error(const jsp_staged* st, int nf) {
+    for (int i = 0; i < nf; ++i)
+        if (st->status[(size_t)i] != JSP_ZERO_STATE) return i;
+    return -1;
+}
+
+void range_error(const char* who, int k, const jsp_staged* st) {
+    set_error("%s: frame %d of the range: %s", who, k, st->why.empty() ? "the reference raises on this stream" : st->why.c_str());
+}
+
+// jsp_seek / jsp_find_change: the reference raises out of frame k, and what the caller had as its previous frame is gone with the range.
+int raised(jsp_codec* c, const char* who, int k, const jsp_staged* st) {
+    c->prev_dev = nullptr;
+    c->prev_caller = nullptr;
+    range_error(who, k, st);
+    return JSP_ERROR_OCCURED;
+}
+
+bool adopts(const jsp_staged* st) { return std::any_of(st->adopted.begin(), st->adopted.end(), [](int ad) { return ad != 0; }); }
+
+// ---- significance ------------------------------------------------------------------------------------------------------------
+// Frame k of the range (frame i of the staged chunk st / v): 1 / 0 where the host stage settles it, else -1 with `row` set to the
+// pixel row the compare starts from.  Key frames by frames_differ_significantly (Manager.hx:392-421): after a key frame by their
+// bytes, else significant with no picture before them, else the pixel compare from key_row.  Inter frames as DecompressP: stage 1
+// on the host, stage 2 (st->significant == -1) from insign_lines on.
+int settle(const Range& r, int k, int i, const jsp_staged* st, const Msv1SeekView& v, int key_row, uint32_t& row) {
+    if (r.key(k)) {
+        const bool key_prev = k > 0 ? r.key(k - 1) : r.key_before != nullptr;
+        if (key_prev)
+            return k > 0 ? !same_bytes(r.srcs[k - 1], r.lens[k - 1], r.srcs[k], r.lens[k]) : !same_bytes(r.key_before, r.key_before_len, r.srcs[k], r.lens[k]);
+        if (!v.h_frames[i].prev) return 1;
+        row = (uint32_t)key_row;
+        return -1;
+    }
+    const int s = st->significant[(size_t)i];
+    if (s >= 0) return s;
+    row = v.h_frames[i].cmp_row_lo;
+    return -1;
+}
+
+// A chunk's judgement lives in the caller's scratch, host `h` and device `d` alike laid out as [first-hit word, with stop_at_hit]
+// [rows: one per frame of the chunk][walk list].  judge_rows: room for a chunk of nf frames, every row ~0u (not judged); the rows.
+uint32_t* judge_rows(PinnedBuffer& h, int nf, bool stop_at_hit) {
+    h.reserve(sizeof(uint32_t) * ((stop_at_hit ? 1 : 0) + 2 * (size_t)nf));
+    uint32_t* rows = static_cast<uint32_t*>(h.p) + (stop_at_hit ? 1 : 0);
+    std::fill(rows, rows + nf, 0xFFFFFFFFu);
+    return rows;
+}
+
+// ONE launch of msv1_change_scan_kernel judges the chunk's frames that have a row, against `before` (the picture before the chunk),
+// and v.d_signif comes back to v.h_signif — queued on the codec's stream, not waited for.  The walk list: the frames up to judged_last
+// that code a block (early-outs and all-skip frames code none).  stop_at_hit: the scan stops at the first frame found to differ
+// (jsp_find_change); else every frame with a row is judged (jsp_index_build).
+void judge_chunk(jsp_codec* c, const jsp_staged* st, const Msv1SeekView& v, int judged_last, bool stop_at_hit, PinnedBuffer& h,
+                 DeviceBuffer& d, const int32_t* before) {
+    const int nf = v.nframes, head = stop_at_hit ? 1 : 0;
+    uint32_t* h_first = static_cast<uint32_t*>(h.p);
+    uint32_t* h_walk = h_first + head + nf;
+    int nwalk = 0;
+    for (int i = 0; i <= judged_last; ++i)
+        if (st->adopted[(size_t)i]) h_walk[nwalk++] = (uint32_t)i;
+    if (stop_at_hit) *h_first = 0xFFFFFFFFu;
+    const size_t words = (size_t)head + (size_t)nf + (size_t)nwalk;
+    d.reserve(sizeof(uint32_t) * words);
+    uint32_t* d_first = static_cast<uint32_t*>(d.p);
+    JSP_HIP(hipMemcpyAsync(d_first, h_first, sizeof(uint32_t) * words, hipMemcpyHostToDevice, c->stream));
+    JSP_HIP(hipMemsetAsync(v.d_signif, 0, sizeof(uint32_t) * (size_t)nf, c->stream));
+    msv1_launch_change_scan(v, d_first + head + nf, nwalk, d_first + head, stop_at_hit ? d_first : nullptr, before, c->stream);
+    JSP_HIP(hipGetLastError());
+    JSP_HIP(hipMemcpyAsync(v.h_signif, v.d_signif, sizeof(uint32_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+}
+
 }  // namespace
 
+// ---- jsp_seek: the seek branch of Manager.GetDecompressedFrame (Manager.hx:216-259) — frames K..N staged as one batch and composed
+// into the caller's buffer by ONE launch of msv1_seek_kernel, instead of N - K + 1 decodes each writing a whole frame. --------------
 extern "C" int jsp_seek(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key, int32_t* dst,
                         int32_t** data_pnt, int* significant_changes) {
     if (data_pnt) *data_pnt = c ? c->prev_caller : nullptr;
     if (significant_changes) *significant_changes = 0;
     if (!c || nframes <= 0 || !srcs || !lens || !dst) return fail("seek: null argument or empty range");
-    for (int i = 0; i < nframes; ++i)
-        if (!srcs[i] && lens[i]) return fail("seek: null frame bytes");
-    if (c->kind != JSP_CODEC_MSVIDEO1_16 && c->kind != JSP_CODEC_MSVIDEO1_8) return fail("seek: MSVideo1 only");
-    if (c->next_ticket != c->oldest_ticket) return fail("seek: an asynchronous frame is in flight (jsp_wait for it first)");
-    if (dst == c->prev_caller) return fail("seek: dst is the current previous frame");
+    if (null_frame(nframes, srcs, lens)) return fail("seek: null frame bytes");
+    if (!is_msv1(c, "seek") || !nothing_in_flight(c, "seek") || !dst_not_previous(c, dst, "seek")) return JSP_ERROR_OCCURED;
     try {
         c->activate();
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, dst) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
-            (void)hipGetLastError();
-            return fail("seek: dst must be a device frame buffer");
-        }
-        if (c->ptr_mode == 2) return fail("seek: codec is in host-pointer mode");
-        c->worker_drain();
-        c->ptr_mode = 1;
-        c->last_key_differs = -1;   // (the key-frame compare does not run on a seek)
+        if (!dst_on_device(dst, "seek") || !device_pointers(c, "seek")) return JSP_ERROR_OCCURED;
+        take_over(c);
 
+        const Range range{srcs, lens, is_key};
         int sig = 0, last_sig_word = -1;
         bool any_adopted = false;
         uint32_t* h_word = nullptr;
-        const uint64_t table_bytes = 4ull * (uint64_t)std::max((int64_t)c->X / 4 * (c->Y / 4), (int64_t)1);
         for (int a = 0, b = 0; a < nframes; a = b) {
-            b = a + 1;
-            if (c->seek_chunk_frames > 0) {
-                b = std::min(nframes, a + c->seek_chunk_frames);
-            } else {
-                uint64_t bytes = lens[a] + table_bytes;
-                while (b < nframes && bytes + lens[b] + 16384 + table_bytes <= kSeekChunkBudget) bytes += lens[b++] + 16384 + table_bytes;
-            }
+            b = chunk_end(c, lens, nframes, a);
             // (the chunk before may still be composing from the batch buffers that staging refills)
             if (a > 0) JSP_HIP(hipStreamSynchronize(c->stream));
             const int32_t* base = c->prev_dev;   // the picture before this chunk (null: there is none; dst: the chunks before wrote it)
-            std::vector<jsp_frame_in> frames((size_t)(b - a));
-            for (int i = a; i < b; ++i) frames[(size_t)(i - a)] = jsp_frame_in{srcs[i], lens[i], is_key ? is_key[i] != 0 : true, dst};
-            jsp_staged* st = c->stage(frames, c->seek_scratch.get());
-            st->device = c->device;
-            if (st != c->seek_scratch.get()) c->seek_scratch.reset(st);
-            for (int i = 0; i < b - a; ++i)
-                if (st->status[(size_t)i] != JSP_ZERO_STATE) {
-                    // the reference raises out of this frame: what the caller had as its previous frame is gone with the range
-                    c->prev_dev = nullptr;
-                    c->prev_caller = nullptr;
-                    set_error("seek: frame %d of the range: %s", i + a, st->why.empty() ? "the reference raises on this stream" : st->why.c_str());
-                    return JSP_ERROR_OCCURED;
-                }
+            jsp_staged* st = stage(c, range, a, b, c->seek_scratch, dst);
+            if (const int err = first_error(st, b - a); err >= 0) return raised(c, "seek", a + err, st);
             Msv1SeekView v;
             if (!msv1_seek_view(st, v)) throw std::runtime_error("seek: not an MSVideo1 batch");
-            bool chunk_adopted = false;
-            for (int ad : st->adopted) chunk_adopted |= ad != 0;
+            const bool chunk_adopted = adopts(st);
             const bool last = b == nframes;
             const int lf = b - a - 1;
             uint32_t cmp_row_lo = 0xFFFFFFFFu;
@@ -104,4 +253,316 @@ extern "C" int jsp_seek(jsp_codec* c, int nframes, const uint8_t* const* srcs, c
         set_error("%s", e.what());
         return JSP_ERROR_OCCURED;
     }
+}
+
+// ---- jsp_find_change: Manager.SkipStills (Manager.hx:289-317) over DataLoader.FindPossibleChange (DataLoader.hx:239-252) — which
+// frame after the one shown is the first to change the picture significantly, and that frame's picture, without decoding and writing
+// every idle frame in between.  Per chunk: ONE launch of msv1_change_scan_kernel for the frames whose significance needs a pixel
+// compare, then ONE launch of msv1_seek_kernel composing the picture up to the hit (or the whole chunk, which becomes the next
+// chunk's picture before). ---------------------------------------------------------------------------------------------------
+extern "C" int jsp_find_change(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key, int first,
+                               const uint8_t* key_before, size_t key_before_len, int key_row, int32_t* dst, int* found, int* changed,
+                               int* significance, int32_t** data_pnt) {
+    if (data_pnt) *data_pnt = c ? c->prev_caller : nullptr;
+    if (found) *found = -1;
+    if (changed) *changed = 0;
+    if (significance)
+        for (int i = 0; i < nframes; ++i) significance[i] = -1;
+    if (!c || nframes <= 0 || !srcs || !lens || !dst || !found || !changed) return fail("find_change: null argument or empty range");
+    if (null_frame(nframes, srcs, lens)) return fail("find_change: null frame bytes");
+    if (first < 0 || first >= nframes) return fail("find_change: first is outside the range");
+    if (key_row < 0) return fail("find_change: negative key_row");
+    if (!is_msv1(c, "find_change") || !nothing_in_flight(c, "find_change") || !dst_not_previous(c, dst, "find_change")) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        if (!dst_on_device(dst, "find_change") || !device_pointers(c, "find_change")) return JSP_ERROR_OCCURED;
+        take_over(c);
+
+        const Range range{srcs, lens, is_key, key_before, key_before_len};
+        int hit = -1;               // the frame found (range index)
+        bool any_adopted = false;
+        for (int a = 0, b = 0; a < nframes && hit < 0; a = b) {
+            b = chunk_end(c, lens, nframes, a);
+            if (a > 0) JSP_HIP(hipStreamSynchronize(c->stream));   // (the chunk before may still be composing from the batch buffers)
+            const int32_t* base = c->prev_dev;   // the picture before this chunk (null: there is none; dst: the chunks before wrote it)
+            Msv1HostState saved;
+            if (!msv1_save_state(c, saved)) throw std::runtime_error("find_change: not an MSVideo1 codec");
+            jsp_staged* st = stage(c, range, a, b, c->seek_scratch, dst);
+            const int nf = b - a;
+            const int err = first_error(st, nf);
+            Msv1SeekView v;
+            if (!msv1_seek_view(st, v)) throw std::runtime_error("find_change: not an MSVideo1 batch");
+
+            // from `first` on, up to the first frame the host already knows to be significant (nothing after it is judged)
+            const int lo = std::max(first - a, 0), limit = err >= 0 ? err : nf;
+            std::vector<int> sig((size_t)nf, -1);
+            uint32_t* h_rows = judge_rows(c->find_host, nf, true);
+            int judged_last = -1;
+            for (int i = lo; i < limit; ++i) {
+                const int s = sig[(size_t)i] = settle(range, a + i, i, st, v, key_row, h_rows[i]);
+                if (s == 1) break;
+                if (s < 0) judged_last = i;
+            }
+            if (judged_last >= 0) {
+                judge_chunk(c, st, v, judged_last, true, c->find_host, c->find_dev, base ? base : dst);
+                JSP_HIP(hipStreamSynchronize(c->stream));
+            }
+            int local = -1;
+            for (int i = lo; i < limit && local < 0; ++i) {
+                if (sig[(size_t)i] < 0) sig[(size_t)i] = v.h_signif[i] ? 1 : 0;
+                if (significance) significance[a + i] = sig[(size_t)i];
+                if (sig[(size_t)i] == 1) local = i;
+            }
+            if (local < 0 && err >= 0) return raised(c, "find_change", a + err, st);
+            if (local >= 0) {
+                hit = a + local;
+                *changed = 1;
+                if (local < nf - 1) {
+                    // the staging ran on to the chunk's end: back to where the chunk began, and the prefix up to the hit again, so that
+                    // prev_dev and block_changes end at the hit as the per-frame calls would leave them
+                    msv1_restore_state(c, saved);
+                    st = stage(c, range, a, hit + 1, c->seek_scratch, dst);
+                    if (!msv1_seek_view(st, v)) throw std::runtime_error("find_change: not an MSVideo1 batch");
+                }
+            } else if (b == nframes) {
+                hit = nframes - 1;   // nothing changes up to the end: FindPossibleChange lands on the last frame
+            }
+            const bool chunk_adopted = adopts(st);
+            if (chunk_adopted) {
+                msv1_launch_seek(v, dst, base == dst ? nullptr : base, 0xFFFFFFFFu, c->stream);
+                JSP_HIP(hipGetLastError());
+            }
+            any_adopted |= chunk_adopted;
+        }
+        JSP_HIP(hipStreamSynchronize(c->stream));
+        if (any_adopted) c->prev_caller = dst;
+        if (data_pnt) *data_pnt = c->prev_caller;
+        *found = hit;
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- jsp_index_*: a resident MSVideo1 SEEK INDEX — a range's stream bytes, block tables and frame records kept in HBM after one
+// staging, so that showing any frame of it is ONE launch of msv1_index_show_kernel with no host work: the scrubbing, previous-frame
+// and seek-bar navigation of the reference player (Main.on_prevframe / Manager.PrevFrameTime, Manager.hx:184-208; Main.on_click,
+// Main.hx:1197-1215) without restaging the range from its key frame on every step.
+//
+// Build, per chunk of the range:
+//   * the chunk is staged and its device buffers change hands (msv1_take_batch) — the index keeps no staged batch, nothing that
+//     refers to the codec's streams;
+//   * ONE launch of msv1_change_scan_kernel<.., ALL> judges every frame whose significance needs a pixel compare, against a running
+//     picture of the build's own (the picture before the chunk);
+//   * ONE launch of msv1_coded_bitmap_kernel adds the chunk's frames to the global coded-block bitmap, the per-row coded words and the
+//     first untouched block of each frame — from which the host derives, per frame, the per-row block_changes the sequential calls
+//     leave behind (MSVideo1.hx:122,305: a row is reset when a frame reaches it);
+//   * ONE launch of msv1_seek_kernel moves the running picture on to the chunk's end (when a chunk follows).
+// The codec's host state is saved first and put back at the end: the build changes nothing but the index. ---------------------------
+extern "C" jsp_index* jsp_index_build(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key,
+                                      int key_row) {
+    if (!c || nframes <= 0 || !srcs || !lens) { fail("index: null argument or empty range"); return nullptr; }
+    if (null_frame(nframes, srcs, lens)) { fail("index: null frame bytes"); return nullptr; }
+    if (key_row < 0) { fail("index: negative key_row"); return nullptr; }
+    if (!is_msv1(c, "index") || !nothing_in_flight(c, "index") || !device_pointers(c, "index")) return nullptr;
+    Msv1HostState saved;
+    bool restore = false;
+    std::unique_ptr<jsp_staged> stg;   // the build's own staging object (its last chunk's leftovers go with it, before the build returns)
+    try {
+        c->activate();
+        c->worker_drain();
+        if (!msv1_save_state(c, saved)) throw std::runtime_error("index: not an MSVideo1 codec");
+        restore = true;
+        auto idx = std::make_unique<jsp_index>();
+        idx->codec_serial = c->serial;
+        idx->device = c->device;
+        idx->nframes = nframes;
+        idx->prev_caller = c->prev_caller;
+        idx->prev_dev = c->prev_dev;
+        idx->significance.assign((size_t)nframes, 0);
+        idx->reported.assign((size_t)nframes, 0);
+        idx->first_adopted = nframes;
+        std::vector<uint8_t> noop((size_t)nframes, 0);
+        std::vector<uint8_t> rows_now;   // block_changes at build time, as the next host parse would see them
+        if (!msv1_block_changes_now(c, rows_now)) throw std::runtime_error("index: not an MSVideo1 codec");
+
+        const size_t npix = (size_t)c->X * (size_t)c->Y;
+        const size_t pic_bytes = sizeof(int32_t) * std::max<size_t>(npix, 1);
+        // the running picture: the picture before the chunk being judged (and the staging's stand-in destination — nothing writes
+        // it but this build)
+        DeviceBuffer d_run;
+        d_run.reserve(pic_bytes);
+        int32_t* run = static_cast<int32_t*>(d_run.p);
+        if (c->prev_dev) {
+            idx->has_before = true;
+            idx->d_before.reserve(pic_bytes);
+            JSP_HIP(hipMemcpyAsync(idx->d_before.p, c->prev_dev, sizeof(int32_t) * npix, hipMemcpyDeviceToDevice, c->stream));
+            JSP_HIP(hipMemcpyAsync(run, c->prev_dev, sizeof(int32_t) * npix, hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            JSP_HIP(hipMemsetAsync(run, 0, pic_bytes, c->stream));
+        }
+        const int nwords = (nframes + 31) / 32;
+        const int nblocks_all = (c->X / 4) * (c->Y / 4), nby = c->Y / 4;
+        idx->d_bitmap.reserve(sizeof(uint32_t) * std::max<size_t>((size_t)nwords * (size_t)nblocks_all, 1));
+        JSP_HIP(hipMemsetAsync(idx->d_bitmap.p, 0, sizeof(uint32_t) * (size_t)nwords * (size_t)nblocks_all, c->stream));
+        DeviceBuffer d_rows, d_stop, d_work;   // per-row coded words, first untouched block per frame; rows / walk list of a chunk
+        d_rows.reserve(sizeof(uint32_t) * std::max<size_t>((size_t)nwords * (size_t)nby, 1));
+        d_stop.reserve(sizeof(uint32_t) * (size_t)nframes);
+        JSP_HIP(hipMemsetAsync(d_rows.p, 0, sizeof(uint32_t) * (size_t)nwords * (size_t)nby, c->stream));
+        JSP_HIP(hipMemsetAsync(d_stop.p, 0xFF, sizeof(uint32_t) * (size_t)nframes, c->stream));
+        PinnedBuffer h_work;
+
+        const Range range{srcs, lens, is_key};
+        for (int a = 0, b = 0; a < nframes; a = b) {
+            b = chunk_end(c, lens, nframes, a);
+            const int nf = b - a;
+            jsp_staged* st = stage(c, range, a, b, stg, run);
+            if (const int err = first_error(st, nf); err >= 0) {
+                range_error("index", a + err, st);
+                msv1_restore_state(c, saved);
+                return nullptr;
+            }
+            Msv1SeekView v;
+            if (!msv1_seek_view(st, v)) throw std::runtime_error("index: not an MSVideo1 batch");
+            if (a == 0) {   // the codec's palette (8-bit): the index keeps a copy of its own
+                idx->geo = v.geo;
+                idx->d_palette.reserve(sizeof(int32_t) * 256);
+                if (v.d_palette) JSP_HIP(hipMemcpyAsync(idx->d_palette.p, v.d_palette, sizeof(int32_t) * 256, hipMemcpyDeviceToDevice, c->stream));
+                else JSP_HIP(hipMemsetAsync(idx->d_palette.p, 0, sizeof(int32_t) * 256, c->stream));
+            }
+
+            // every frame judged (frame 0 of the range: no key frame before it)
+            uint32_t* h_rows = judge_rows(h_work, nf, false);
+            int judged_last = -1;
+            bool chunk_adopted = false;
+            for (int i = 0; i < nf; ++i) {
+                const int k = a + i;
+                const int s = idx->significance[(size_t)k] = settle(range, k, i, st, v, key_row, h_rows[i]);
+                if (s < 0) judged_last = i;
+                noop[(size_t)k] = (v.h_frames[i].pad & MSV1_FRAME_NOOP) != 0;
+                if (st->adopted[(size_t)i]) {
+                    chunk_adopted = true;
+                    idx->first_adopted = std::min(idx->first_adopted, k);
+                }
+            }
+            if (judged_last >= 0) judge_chunk(c, st, v, judged_last, false, h_work, d_work, run);
+            msv1_launch_coded_bitmap(v, a, static_cast<uint32_t*>(idx->d_bitmap.p), static_cast<uint32_t*>(d_rows.p),
+                                     static_cast<uint32_t*>(d_stop.p), c->stream);
+            JSP_HIP(hipGetLastError());
+            if (b < nframes && chunk_adopted) {   // the running picture moves on to the chunk's end: the picture before the next one
+                msv1_launch_seek(v, run, nullptr, 0xFFFFFFFFu, c->stream);
+                JSP_HIP(hipGetLastError());
+            }
+            JSP_HIP(hipStreamSynchronize(c->stream));   // (the judged words are read now; the pinned work buffer is reused next chunk)
+            for (int i = 0; i < nf; ++i) {
+                const int k = a + i;
+                if (idx->significance[(size_t)k] < 0) idx->significance[(size_t)k] = v.h_signif[i] ? 1 : 0;
+                idx->reported[(size_t)k] = range.key(k) ? 0 : (uint8_t)idx->significance[(size_t)k];   // (DecompressI reports nothing)
+            }
+            auto ch = std::make_unique<jsp_index::Chunk>();
+            ch->first = a;
+            ch->count = nf;
+            if (!msv1_take_batch(st, ch->stream, ch->desc, ch->frames)) throw std::runtime_error("index: not an MSVideo1 batch");
+            idx->chunks.push_back(std::move(ch));
+        }
+        stg.reset();   // (pinned stream copy, host tables, parse buffers: not needed any more)
+        h_work.release();
+        d_work.release();
+
+        // ---- per-row block_changes after every frame: a frame resets and sets the rows its walk reaches (all of them, up to the row
+        // of its first untouched block; none for an early-out), the rows after that keep what was there ----------------------------
+        std::vector<uint32_t> rows((size_t)nwords * (size_t)nby), stop((size_t)nframes);
+        if (!rows.empty()) JSP_HIP(hipMemcpy(rows.data(), d_rows.p, sizeof(uint32_t) * rows.size(), hipMemcpyDeviceToHost));
+        JSP_HIP(hipMemcpy(stop.data(), d_stop.p, sizeof(uint32_t) * stop.size(), hipMemcpyDeviceToHost));
+        const Msv1Geometry& geo = idx->geo;
+        idx->block_changes.resize((size_t)nframes * (size_t)nby);
+        rows_now.resize((size_t)nby, 0);
+        for (int t = 0; t < nframes; ++t) {
+            if (!noop[(size_t)t] && geo.nblocks > 0) {
+                const int reached = std::min((int)(std::min<uint32_t>(stop[(size_t)t], (uint32_t)geo.nblocks) / (uint32_t)geo.nbx), geo.nby - 1);
+                for (int r = 0; r <= reached; ++r) rows_now[(size_t)r] = (uint8_t)((rows[(size_t)(t / 32) * nby + r] >> (t % 32)) & 1u);
+            }
+            std::copy(rows_now.begin(), rows_now.end(), idx->block_changes.begin() + (size_t)t * (size_t)nby);
+        }
+
+        // ---- what the show kernel reads: per-chunk pointers, the chunk of every frame, the palette ---------------------------------
+        std::vector<Msv1IndexChunk> table;
+        std::vector<uint32_t> frame_chunk((size_t)nframes);
+        for (size_t k = 0; k < idx->chunks.size(); ++k) {
+            const auto& ch = *idx->chunks[k];
+            table.push_back(Msv1IndexChunk{static_cast<const uint8_t*>(ch.stream.p), static_cast<const uint32_t*>(ch.desc.p),
+                                           static_cast<const Msv1FrameArgs*>(ch.frames.p), (uint32_t)ch.first, 0});
+            std::fill(frame_chunk.begin() + ch.first, frame_chunk.begin() + ch.first + ch.count, (uint32_t)k);
+        }
+        idx->d_chunks.reserve(sizeof(Msv1IndexChunk) * table.size());
+        idx->d_frame_chunk.reserve(sizeof(uint32_t) * frame_chunk.size());
+        JSP_HIP(hipMemcpy(idx->d_chunks.p, table.data(), sizeof(Msv1IndexChunk) * table.size(), hipMemcpyHostToDevice));
+        JSP_HIP(hipMemcpy(idx->d_frame_chunk.p, frame_chunk.data(), sizeof(uint32_t) * frame_chunk.size(), hipMemcpyHostToDevice));
+        msv1_restore_state(c, saved);
+        return idx.release();
+    } catch (const std::exception& e) {
+        if (restore) msv1_restore_state(c, saved);
+        set_error("%s", e.what());
+        return nullptr;
+    }
+}
+
+extern "C" int jsp_index_show(jsp_codec* c, jsp_index* idx, int t, int32_t* dst, int adopt, int32_t** data_pnt, int* significant_changes) {
+    if (data_pnt) *data_pnt = c ? c->prev_caller : nullptr;
+    if (significant_changes) *significant_changes = 0;
+    if (!c || !idx || !dst) return fail("index_show: null argument");
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_show: the index was built by another codec");
+    if (t < 0 || t >= idx->nframes) return fail("index_show: t is outside the index");
+    if (!nothing_in_flight(c, "index_show") || !dst_not_previous(c, dst, "index_show")) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        if (!dst_on_device(dst, "index_show") || !device_pointers(c, "index_show")) return JSP_ERROR_OCCURED;
+        const bool adopted = t >= idx->first_adopted;   // jsp_seek of frames 0..t writes dst only then
+        if (adopted) {
+            msv1_launch_index_show(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
+                                   static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p), t, dst,
+                                   idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, c->stream);
+            JSP_HIP(hipGetLastError());
+            JSP_HIP(hipStreamSynchronize(c->stream));
+        }
+        int32_t* shown = adopted ? dst : idx->prev_caller;
+        if (adopt) {
+            take_over(c);   // (as on a seek)
+            const int nby = std::max(idx->geo.nby, 0);
+            Msv1HostState s;
+            s.prev_dev = adopted ? dst : idx->prev_dev;
+            s.block_changes.assign(idx->block_changes.begin() + (size_t)t * (size_t)nby, idx->block_changes.begin() + (size_t)(t + 1) * (size_t)nby);
+            msv1_restore_state(c, s);   // (exact per-row flags: nothing stale, nothing that points into the index)
+            c->prev_caller = shown;
+        }
+        if (data_pnt) *data_pnt = shown;
+        if (significant_changes) *significant_changes = idx->reported[(size_t)t];
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+extern "C" int jsp_index_significance(const jsp_index* idx, int* out) {
+    if (!idx || !out) return fail("index_significance: null argument");
+    std::copy(idx->significance.begin(), idx->significance.end(), out);
+    return JSP_ZERO_STATE;
+}
+
+extern "C" int jsp_index_info(const jsp_index* idx, int* nframes, uint64_t* device_bytes, uint64_t* host_bytes) {
+    if (!idx) return fail("index_info: null index");
+    if (nframes) *nframes = idx->nframes;
+    if (device_bytes) *device_bytes = idx->device_bytes();
+    if (host_bytes) *host_bytes = idx->host_bytes();
+    return JSP_ZERO_STATE;
+}
+
+extern "C" void jsp_index_destroy(jsp_index* idx) {
+    if (!idx) return;
+    // device memory only: no stream, event or staged batch of the codec is touched, so the codec may be gone already
+    (void)hipSetDevice(idx->device);
+    delete idx;
 }

@@ -1,4 +1,5 @@
-// jsp_seek for MSVideo1 (msv1_seek.cpp, msv1_seek_kernels.hip): what the seek needs from a staged batch, and its kernel launcher.
+// The MSVideo1 range calls jsp_seek, jsp_find_change and jsp_index_* (msv1_seek.cpp, msv1_seek_kernels.hip): what they need from a
+// staged batch and the codec, and their kernel launchers.
 #pragma once
 #include <vector>
 
@@ -31,11 +32,12 @@ bool msv1_seek_view(jsp_staged* st, Msv1SeekView& out);
 // the picture before it, rows >= cmp_row_lo) ORs v.d_signif[v.nframes - 1].
 void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, uint32_t cmp_row_lo, hipStream_t stream);
 
-// jsp_find_change (msv1_find_change.cpp).  ONE launch of msv1_change_scan_kernel: for every frame f of the batch with
-// d_rows[f] != ~0u, whether a block f codes differs, on pixel rows >= d_rows[f], from that block's previous state — what the last
-// earlier frame of the batch that coded it made of it, else `before` (the picture before the batch) — ORs v.d_signif[f] (zeroed by
-// the caller).  d_walk: the batch's frames that code a block, ascending, nwalk of them; frames after the
-// last judged one need not be listed.  *d_first_hit (~0u from the caller) ends at most at the earliest frame found to differ.
+// ONE launch of msv1_change_scan_kernel: for every frame f of the batch with d_rows[f] != ~0u, whether a block f codes differs, on
+// pixel rows >= d_rows[f], from that block's previous state — what the last earlier frame of the batch that coded it made of it, else
+// `before` (the picture before the batch) — ORs v.d_signif[f] (zeroed by the caller).  d_walk: the batch's frames that code a block,
+// ascending, nwalk of them; frames after the last judged one need not be listed.  *d_first_hit (~0u from the caller) ends at most at
+// the earliest frame found to differ, and the scan may stop there (jsp_find_change); null d_first_hit: every frame with a row is
+// judged (jsp_index_build).
 void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, uint32_t* d_first_hit,
                              const int32_t* before, hipStream_t stream);
 // What MSVideo1 staging advances on the host (Msv1Codec::stage): a copy taken before a batch is staged puts the codec back where
@@ -50,7 +52,7 @@ struct Msv1HostState {
 bool msv1_save_state(jsp_codec* c, Msv1HostState& out);
 void msv1_restore_state(jsp_codec* c, const Msv1HostState& s);
 
-// ---- jsp_index_* (msv1_index.cpp) ------------------------------------------------------------------------------------------
+// ---- jsp_index_* -------------------------------------------------------------------------------------------------------------
 // The per-row flags (block_changes) the codec's next host parse would start from — rebuilt from the last fully parsed frame when the
 // codec keeps them stale — without changing the codec.  False: not MSVideo1.
 bool msv1_block_changes_now(jsp_codec* c, std::vector<uint8_t>& out);
@@ -65,9 +67,6 @@ struct Msv1IndexChunk {
     uint32_t first;                  // index frame of the chunk's frame 0
     uint32_t pad;
 };
-// ONE launch of msv1_change_scan_kernel judging EVERY frame with d_rows[f] != ~0u (ORs v.d_signif[f], zeroed by the caller); the rest
-// as msv1_launch_change_scan.
-void msv1_launch_judge_all(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, const int32_t* before, hipStream_t stream);
 // ONE launch of msv1_coded_bitmap_kernel over the chunk `v` = index frames [a, a + v.nframes): bitmap (word-major, nblocks words per
 // 32 frames, zeroed before the first chunk), d_rows (nby words per 32 frames, zeroed) and d_stop (one word per frame, all ones before).
 void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, uint32_t* d_rows, uint32_t* d_stop, hipStream_t stream);

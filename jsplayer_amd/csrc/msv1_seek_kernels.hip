@@ -346,28 +346,21 @@ __global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexChun
     store_block<VEC>(dst + di, X, px);
 }
 
-}  // namespace
-
-void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, uint32_t cmp_row_lo, hipStream_t stream) {
-    const Msv1Geometry& geo = v.geo;
-    if (v.nframes <= 0 || geo.X <= 0 || geo.Y <= 0) return;
-    const int cx = geo.nbx * 4, cy = geo.nby * 4;
-    const long nrem = (long)(geo.X - cx) * cy + (long)geo.X * (geo.Y - cy);
-    const long work = (long)std::max(geo.nblocks, 0) + nrem;
-    if (work <= 0) return;
-    const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(dst) & 15) && !(reinterpret_cast<uintptr_t>(base) & 15);
-    uint32_t* signif = v.d_signif + (v.nframes - 1);
-    const dim3 grid((unsigned)((work + WG - 1) / WG)), block(WG);
-#define JSP_SEEK(BITS, VEC) hipLaunchKernelGGL((msv1_seek_kernel<BITS, VEC>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, v.d_frames, \
-                                               v.nframes, v.d_palette, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(base),   \
-                                               cmp_row_lo, signif, geo.nblocks, std::max(geo.nbx, 1), geo.X, cx, cy, nrem)
-    if (geo.bits == 16) { if (vec) JSP_SEEK(16, true); else JSP_SEEK(16, false); }
-    else { if (vec) JSP_SEEK(8, true); else JSP_SEEK(8, false); }
-#undef JSP_SEEK
+// The seek and show kernels' work: one work-item per block, then one per pixel no block covers (nrem of them: the columns from cx on
+// in the block rows, the rows from cy on), and whether rows of `dst` and `src` may move 16 bytes at a time.  False: nothing to do.
+struct PictureGrid { int cx, cy; long nrem; dim3 grid; bool vec; };
+bool picture_grid(const Msv1Geometry& geo, const void* dst, const void* src, PictureGrid& g) {
+    if (geo.X <= 0 || geo.Y <= 0) return false;
+    g.cx = geo.nbx * 4;
+    g.cy = geo.nby * 4;
+    g.nrem = (long)(geo.X - g.cx) * g.cy + (long)geo.X * (geo.Y - g.cy);
+    const long work = (long)std::max(geo.nblocks, 0) + g.nrem;
+    if (work <= 0) return false;
+    g.vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(dst) & 15) && !(reinterpret_cast<uintptr_t>(src) & 15);
+    g.grid = dim3((unsigned)((work + WG - 1) / WG));
+    return true;
 }
 
-
-namespace {
 // Segments of the walk list: enough work-items for ~8 waves per SIMD (a 1080p frame alone gives ~2), at least 16 entries each
 dim3 scan_grid(const Msv1Geometry& geo, int nwalk, int& seg) {
     const long waves_one = ((long)geo.nblocks + 63) / 64;
@@ -380,6 +373,19 @@ dim3 scan_grid(const Msv1Geometry& geo, int nwalk, int& seg) {
 }
 }  // namespace
 
+void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, uint32_t cmp_row_lo, hipStream_t stream) {
+    const Msv1Geometry& geo = v.geo;
+    PictureGrid g;
+    if (v.nframes <= 0 || !picture_grid(geo, dst, base, g)) return;
+    uint32_t* signif = v.d_signif + (v.nframes - 1);
+#define JSP_SEEK(BITS, VEC) hipLaunchKernelGGL((msv1_seek_kernel<BITS, VEC>), g.grid, dim3(WG), 0, stream, v.d_stream, v.d_desc, v.desc_pitch, v.d_frames, \
+                                               v.nframes, v.d_palette, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(base),      \
+                                               cmp_row_lo, signif, geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem)
+    if (geo.bits == 16) { if (g.vec) JSP_SEEK(16, true); else JSP_SEEK(16, false); }
+    else { if (g.vec) JSP_SEEK(8, true); else JSP_SEEK(8, false); }
+#undef JSP_SEEK
+}
+
 void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, uint32_t* d_first_hit,
                              const int32_t* before, hipStream_t stream) {
     const Msv1Geometry& geo = v.geo;
@@ -387,26 +393,17 @@ void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int 
     int seg = 0;
     const dim3 grid = scan_grid(geo, nwalk, seg), block(WG);
     const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
-#define JSP_SCAN(BITS, VEC) hipLaunchKernelGGL((msv1_change_scan_kernel<BITS, VEC>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, v.d_frames, \
-                                               v.d_palette, d_walk, nwalk, seg, d_rows, v.d_signif, d_first_hit,                                     \
-                                               reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X)
-    if (geo.bits == 16) { if (vec) JSP_SCAN(16, true); else JSP_SCAN(16, false); }
-    else { if (vec) JSP_SCAN(8, true); else JSP_SCAN(8, false); }
+#define JSP_SCAN(BITS, VEC, ALL) hipLaunchKernelGGL((msv1_change_scan_kernel<BITS, VEC, ALL>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, \
+                                                    v.d_frames, v.d_palette, d_walk, nwalk, seg, d_rows, v.d_signif, d_first_hit,                         \
+                                                    reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X)
+    if (d_first_hit) {
+        if (geo.bits == 16) { if (vec) JSP_SCAN(16, true, false); else JSP_SCAN(16, false, false); }
+        else { if (vec) JSP_SCAN(8, true, false); else JSP_SCAN(8, false, false); }
+    } else {
+        if (geo.bits == 16) { if (vec) JSP_SCAN(16, true, true); else JSP_SCAN(16, false, true); }
+        else { if (vec) JSP_SCAN(8, true, true); else JSP_SCAN(8, false, true); }
+    }
 #undef JSP_SCAN
-}
-
-void msv1_launch_judge_all(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, const int32_t* before, hipStream_t stream) {
-    const Msv1Geometry& geo = v.geo;
-    if (nwalk <= 0 || geo.nblocks <= 0) return;
-    int seg = 0;
-    const dim3 grid = scan_grid(geo, nwalk, seg), block(WG);
-    const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
-#define JSP_JUDGE(BITS, VEC) hipLaunchKernelGGL((msv1_change_scan_kernel<BITS, VEC, true>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, \
-                                                v.d_frames, v.d_palette, d_walk, nwalk, seg, d_rows, v.d_signif, nullptr,                            \
-                                                reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X)
-    if (geo.bits == 16) { if (vec) JSP_JUDGE(16, true); else JSP_JUDGE(16, false); }
-    else { if (vec) JSP_JUDGE(8, true); else JSP_JUDGE(8, false); }
-#undef JSP_JUDGE
 }
 
 void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, uint32_t* d_rows, uint32_t* d_stop, hipStream_t stream) {
@@ -420,19 +417,14 @@ void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, 
 
 void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
                             const uint32_t* d_bitmap, int t, int32_t* dst, const int32_t* before, hipStream_t stream) {
-    if (geo.X <= 0 || geo.Y <= 0) return;
-    const int cx = geo.nbx * 4, cy = geo.nby * 4;
-    const long nrem = (long)(geo.X - cx) * cy + (long)geo.X * (geo.Y - cy);
-    const long work = (long)std::max(geo.nblocks, 0) + nrem;
-    if (work <= 0) return;
-    const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(dst) & 15) && !(reinterpret_cast<uintptr_t>(before) & 15);
+    PictureGrid g;
+    if (!picture_grid(geo, dst, before, g)) return;
     const size_t pitch = (size_t)std::max(geo.nblocks, 1);
-    const dim3 grid((unsigned)((work + WG - 1) / WG)), block(WG);
-#define JSP_SHOW(BITS, VEC) hipLaunchKernelGGL((msv1_index_show_kernel<BITS, VEC>), grid, block, 0, stream, d_chunks, d_frame_chunk, d_palette, d_bitmap, \
-                                               pitch, t, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(before), geo.nblocks,     \
-                                               std::max(geo.nbx, 1), geo.X, cx, cy, nrem)
-    if (geo.bits == 16) { if (vec) JSP_SHOW(16, true); else JSP_SHOW(16, false); }
-    else { if (vec) JSP_SHOW(8, true); else JSP_SHOW(8, false); }
+#define JSP_SHOW(BITS, VEC) hipLaunchKernelGGL((msv1_index_show_kernel<BITS, VEC>), g.grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk, d_palette, \
+                                               d_bitmap, pitch, t, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(before),     \
+                                               geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem)
+    if (geo.bits == 16) { if (g.vec) JSP_SHOW(16, true); else JSP_SHOW(16, false); }
+    else { if (g.vec) JSP_SHOW(8, true); else JSP_SHOW(8, false); }
 #undef JSP_SHOW
 }
 
