@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: decoded Mpixels/s at 1920x1080 (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--also a,b | --no-also]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--also a,b | --no-also]
+                    [--full [--no-e2e] [--no-cpu-baseline]]
+
+A plain run does what the headline needs and nothing else: it stages the workload, runs W untimed and K timed steps, checks
+the frames the timed launches write against the oracle's digests and prints the line.  What else the line can carry takes
+runs of its own and comes with --full only: the end-to-end legs, the CPU baselines, the fill rate measured in the run, and
+the further workloads of `also`.  --dump-outputs writes the arrays of every timed leg, so with it the `also` workloads are
+staged, timed, checked and dumped in a plain run too (without their end-to-end legs and CPU baselines).
 
 Workload at every N (weak scaling): each rank owns its own independent stream(s) — by default
 BASELINE.json configs[1], "MSVideo1 1920x1080 keyframe-only": 512 distinct frames of block mix M1 (25 % solid /
@@ -13,17 +20,18 @@ the counter reduce.
 
 After the timed region every frame the timed kernels left in HBM is compared with the CPU oracle's digest of
 the same frame (tests/golden/bench_digests.json, written by tests/golden/make_bench_digests.py): no value is
-printed on a mismatch.  A second leg times the SAME frames end to end — compressed bytes in host memory -> host
-stage -> H2D -> kernels, one frame per call through the asynchronous entry points — and reports it beside the
+printed on a mismatch.  With --full a second leg times the SAME frames end to end — compressed bytes in host memory
+-> host stage -> H2D -> kernels, one frame per call through the asynchronous entry points — and reports it beside the
 resident-input number ("e2e").
 
-The metric names both codecs, so the default line carries the ScreenPressor configurations as well: `also` = one entry
+The metric names both codecs, so the --full line carries the ScreenPressor configurations as well: `also` = one entry
 per further workload (BASELINE.json configs[2] and [3]: ScreenPressor key frames, ScreenPressor 300-frame clips), each
 timed, digest-verified and priced against the roofline exactly like the headline (same K, W, barriers, HIP events), with
 a bounded CPU baseline and the many-stream end-to-end rate beside it.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`, `cpu_baseline`, `e2e`,
-`verified`, `also`.  The oracle (oracle/) is used ONLY in the cpu_baseline legs.
+Prints ONE JSON line on rank 0 with `roofline` and `verified`, with --full `cpu_baseline`, `e2e` and `also`, and with
+--dump-outputs `also`.
+The oracle (oracle/) is used ONLY in the cpu_baseline legs.
 """
 from __future__ import annotations
 
@@ -38,7 +46,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 METRIC = "decoded Mpixels/sec at 1920x1080 (MSVideo1 + ScreenPressor), 1/2/4/8 GPUs"
-# what the default line carries beside the headline workload (BASELINE.json configs[2], configs[3])
+# what a --full line carries beside the headline workload (BASELINE.json configs[2], configs[3])
 ALSO_DEFAULT = ("screenpressor_v4_1080p_iframes", "screenpressor_v4_1080p_pclip300")
 DUMP_BYTES = 64_000_000   # --dump-outputs: every .npy file of one run together
 DUMP_SEED = 1080          # --dump-outputs: the pixel positions sampled (legacy RandomState: the same stream in every numpy)
@@ -246,10 +254,11 @@ def dump_outputs(name: str, work, out_dir: str, budget: int) -> int:
     return written
 
 
-def resident_leg(job: Job, name: str, nfr_override=None, nclips=None):
+def resident_leg(job: Job, name: str, nfr_override=None, nclips=None, built=None):
     """Workload `name` with its inputs resident in HBM: W untimed steps, EXACTLY K timed steps between barrier +
     synchronize on both sides, HIP events on the launch stream around the same region, then every frame the timed kernels
-    left in HBM against the oracle's digests.  Returns (result dict, clips); raises SystemExit on a mismatch (any rank)."""
+    left in HBM against the oracle's digests.  `built`: (clips, seconds) when the clips were generated beforehand.
+    Returns (result dict, clips); raises SystemExit on a mismatch (any rank)."""
     import torch
     import torch.distributed as dist
     from jsplayer_amd import workloads as wl
@@ -257,10 +266,10 @@ def resident_leg(job: Job, name: str, nfr_override=None, nclips=None):
     args, rank = job.args, job.rank
     spec = dict(wl.WORKLOADS[name])
     t_gen = time.perf_counter()
-    clips = wl.build_clips(name, rank, nfr_override)
+    clips = wl.build_clips(name, rank, nfr_override) if built is None else built[0]
     if nclips:   # experiment knob: the first n clips of the workload only (digests still match: clips are independent)
         clips = clips[:max(1, nclips)]
-    t_gen = time.perf_counter() - t_gen
+    t_gen = time.perf_counter() - t_gen if built is None else built[1]
 
     t_stage = time.perf_counter()
     options = dict(kv.split("=", 1) for kv in os.environ.get("JSP_BENCH_OPTIONS", "").split(",") if "=" in kv)    # experiment knob: codec options, "key=value,key=value"
@@ -534,24 +543,25 @@ def e2e_leg(job: Job, name: str, clips, one_stream=True, batch_calls=True, secon
     return e2e
 
 
-def measured_ceilings(job: Job):
+def measured_ceilings(job: Job, measure: bool = True):
     """What THIS box's memory takes right now, measured in this run: nothing but 16-byte stores, one per lane, workgroups in
     address order (the friendliest shape found, profiles/archive/r03_sp_store_lab.txt) over 2 GiB, HIP events on the bench's stream —
     and the rate on file (tools/hbm_ceiling.hip, profiles/hbm_ceiling.json).  The boxes of the pool differ by up to a fifth
-    here, so the fraction of this number travels better than the fraction of 8 TB/s."""
+    here, so the fraction of this number travels better than the fraction of 8 TB/s.  measure=False: the rate on file only."""
     import torch
     live, recorded = None, None
-    try:
-        import ctypes as C
-        from jsplayer_amd import _native as N
-        scratch = torch.empty(1 << 29, dtype=torch.int32, device=f"cuda:{job.local_rank}")
-        rate = C.c_double(0.0)
-        if N.lib().jsp_measure_fill(C.c_void_p(scratch.data_ptr()), C.c_size_t(scratch.numel() * 4), 10, C.byref(rate), C.c_void_p(job.stream.cuda_stream)) == 0:
-            live = {"value": round(rate.value, 1), "unit": "GB/s", "kind": "fill", "shape": "16-byte stores, one per lane, 256-lane workgroups in address order, 2 GiB",
-                    "source": "measured in this run (jsp_measure_fill: 10 launches, HIP events, best of 3)"}
-        del scratch
-    except Exception as e:   # (the number is a courtesy: the bench line does not depend on it)
-        print(f"[bench] live fill ceiling not measured: {e}", file=sys.stderr)
+    if measure:
+        try:
+            import ctypes as C
+            from jsplayer_amd import _native as N
+            scratch = torch.empty(1 << 29, dtype=torch.int32, device=f"cuda:{job.local_rank}")
+            rate = C.c_double(0.0)
+            if N.lib().jsp_measure_fill(C.c_void_p(scratch.data_ptr()), C.c_size_t(scratch.numel() * 4), 10, C.byref(rate), C.c_void_p(job.stream.cuda_stream)) == 0:
+                live = {"value": round(rate.value, 1), "unit": "GB/s", "kind": "fill", "shape": "16-byte stores, one per lane, 256-lane workgroups in address order, 2 GiB",
+                        "source": "measured in this run (jsp_measure_fill: 10 launches, HIP events, best of 3)"}
+            del scratch
+        except Exception as e:   # (the number is a courtesy: the bench line does not depend on it)
+            print(f"[bench] live fill ceiling not measured: {e}", file=sys.stderr)
     cpath = os.path.join(ROOT, "profiles", "hbm_ceiling.json")
     if os.path.exists(cpath):
         try:
@@ -586,8 +596,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=wl.DEFAULT, choices=sorted(wl.WORKLOADS))
-    ap.add_argument("--also", default=None, help="comma-separated further workloads for the `also` block (default: the ScreenPressor "
-                                                  "configurations, when --workload is the default one)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the end-to-end legs, the CPU baselines, the fill rate measured in "
+                         "the run and the further workloads of `also` (each governed by the options below)")
+    ap.add_argument("--also", default=None, help="with --full or --dump-outputs: comma-separated further workloads for the `also` block "
+                                                  "(default: the ScreenPressor configurations, when --workload is the default one)")
     ap.add_argument("--no-also", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
@@ -605,6 +618,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.also is not None and not (args.full or args.dump_outputs):
+        ap.error("--also: the further workloads run with --full or --dump-outputs only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_spawn_ranks(args.gpus))
     also = [] if args.no_also else ([w for w in args.also.split(",") if w] if args.also is not None else
@@ -613,6 +628,8 @@ def main():
         if w not in wl.WORKLOADS:
             raise SystemExit(f"--also: no workload named {w}")
     args.dump_bytes = DUMP_BYTES // (1 + len(also))     # an equal share per timed leg
+    if not (args.full or args.dump_outputs):            # a plain run writes every timed leg's arrays as well, so the `also`
+        also = []                                       # legs run there for their outputs (no e2e, no CPU baseline)
 
     import torch
     import torch.distributed as dist
@@ -667,10 +684,20 @@ def main():
     name = args.workload
     nfr_override = int(os.environ["JSP_BENCH_FRAMES"]) if os.environ.get("JSP_BENCH_FRAMES") else None   # experiment knob
     nclips = int(os.environ["JSP_BENCH_CLIPS"]) if os.environ.get("JSP_BENCH_CLIPS") else None          # experiment knob
-    head, clips = resident_leg(job, name, nfr_override, nclips)
+    built = [None] * (1 + len(also))
+    if also:
+        # the clips of every timed leg generated side by side (the generators are CPU-bound, a 300-frame clip is one serial chain),
+        # all of it before the first leg is staged: nothing runs beside the timed steps
+        from concurrent.futures import ThreadPoolExecutor
+        t_gen = time.perf_counter()
+        with ThreadPoolExecutor(1 + len(also)) as ex:
+            futs = [ex.submit(wl.build_clips, w, rank, nfr_override if i == 0 else None) for i, w in enumerate([name] + also)]
+            built = [(f.result(), time.perf_counter() - t_gen) for f in futs]
+    head, clips = resident_leg(job, name, nfr_override, nclips, built[0])
+    built[0] = None
     spec = head["spec"]
-    e2e = None if args.no_e2e else e2e_leg(job, name, clips)
-    live, recorded = measured_ceilings(job) if rank == 0 else (None, None)
+    e2e = e2e_leg(job, name, clips) if args.full and not args.no_e2e else None
+    live, recorded = measured_ceilings(job, measure=args.full) if rank == 0 else (None, None)
 
     out = None
     if rank == 0:
@@ -713,7 +740,7 @@ def main():
             "total_frames": head["total_frames"],
             "per_rank_frames": head["per_rank_frames"],
         }
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(spec, clips[0])
             if e2e:
                 out["e2e"]["vs_cpu_one_thread"] = round(e2e["value"] / out["cpu_baseline"]["value"], 2)
@@ -724,11 +751,12 @@ def main():
     # ---- the other configurations the metric names, each to the same bar (same K and W, same bracket, digests, roofline) ----
     entries = []
     dumped = head.get("dumped_bytes", 0)
-    for w in also:
-        leg, wclips = resident_leg(job, w)
+    for i, w in enumerate(also):
+        leg, wclips = resident_leg(job, w, built=built[1 + i])
+        built[1 + i] = None
         dumped += leg.get("dumped_bytes", 0)
         wspec = leg["spec"]
-        many = None if args.no_e2e else e2e_leg(job, w, wclips, one_stream=False, batch_calls=False)
+        many = e2e_leg(job, w, wclips, one_stream=False, batch_calls=False) if args.full and not args.no_e2e else None
         if rank == 0:
             ent = {
                 "workload": w,
@@ -745,7 +773,7 @@ def main():
             ent["roofline"]["reference_fill"] = ent["roofline"]["reference_fill"]["value"] if ent["roofline"]["reference_fill"] else None
             if many:
                 ent["e2e"] = many
-            if args.gpus == 1 and not args.no_cpu_baseline:
+            if args.full and args.gpus == 1 and not args.no_cpu_baseline:
                 base = cpu_baseline(wspec, wclips[0], budget_s=4.0)
                 ent["cpu_baseline"] = {"value": base["value"], "unit": "Mpixels/s", "cores": 1, "kind": "port", "sample": base["sample"],
                                        "all_cores": base["all_cores"]}

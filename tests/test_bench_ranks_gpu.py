@@ -1,6 +1,6 @@
 """BASELINE.json configs[4] rehearsed on the one GPU a test box has: `bench.py --gpus 2 --ranks-share-device` starts two ranks of itself
 (torch.distributed.run as a child process, exactly as `--gpus 2` does on a 2-GPU node) which both decode on device 0 — every rank
-its own streams (the seeds and oracle digests of ITS rank), the full default line per rank (headline leg, the `also` legs, the
+its own streams (the seeds and oracle digests of ITS rank), the whole --full line per rank (headline leg, the `also` legs, the
 end-to-end legs), the counter / verdict / per-rank collectives over gloo on host tensors.  What this cannot show is RCCL between two
 devices; everything else of the N-GPU path has then executed before the driver's multi-GPU run (the caller side of Manager.hx:97-142
 per rank)."""
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_ranks_of_the_default_line_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["JSP_BENCH_E2E_SECONDS"] = "0.5"          # (the end-to-end legs run on every rank; half a second each is enough to have run them)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ranks-share-device", "--steps", "3", "--warmup", "1"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ranks-share-device", "--steps", "3", "--warmup", "1", "--full"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     doc = json.loads([l for l in res.stdout.decode().splitlines() if l.startswith("{")][-1])

@@ -112,6 +112,21 @@ def test_ranks_that_share_a_device_do_not_try_rccl():
     assert _dry_run(extra_args=("--ranks-share-device",))["collectives"] == "gloo (ranks share a device)"
 
 
+def test_a_plain_line_leaves_out_the_further_workloads():
+    """A plain line is the headline workload alone; --full adds the ScreenPressor configurations in `also`, and --also without
+    --full or --dump-outputs is refused rather than ignored."""
+    import subprocess
+    import sys
+    assert _dry_run()["also"] == []
+    full = _dry_run(extra_args=("--full",))
+    assert [a["workload"] for a in full["also"]] == ["screenpressor_v4_1080p_iframes", "screenpressor_v4_1080p_pclip300"]
+    assert all(a["per_rank_frames"][0] == a["per_rank_frames"][1] > 0 for a in full["also"])
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dry-run", "--also", "screenpressor_v4_1080p_iframes"],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert res.returncode == 2 and b"--full" in res.stderr, res.stderr.decode()[-800:]
+
+
 def test_native_stream_assignment_and_counter_reduce_without_a_gpu():
     """The native (one process, several devices) form of the same sharding, jsp_assign_stream / jsp_reduce_counters of the C ABI:
     stream i -> devices[i mod G]; the counters' sums are the host's when no device (hence no RCCL communicator) is there."""

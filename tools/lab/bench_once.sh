@@ -1,8 +1,8 @@
 #!/bin/bash
-# lab: the default bench once, with its wall time; prints the headline fields
+# lab: the --full bench once, with its wall time; prints the headline fields
 R="${GRAFT_REPO_ROOT:-$(pwd)}"; cd $R; O=gpurun_out; T="${TAG:-once}"
 s=$SECONDS
-timeout -k 10 500 python bench.py "$@" > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail -5 $O/${T}_bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full "$@" > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail -5 $O/${T}_bench.err; exit 1; }
 echo "wall $((SECONDS - s)) s"
 python - "$O/${T}_bench.json" <<'PY'
 import json, sys

@@ -20,14 +20,14 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/${T}_smoke.log" 2>&1 || { tail -20 "$O/${T}_smoke.log"; exit 1; }
       tail -1 "$O/${T}_smoke.log" ;;
     bench)
-      timeout -k 10 500 python bench.py > "$O/${T}_bench_default.json" 2> "$O/${T}_bench_default.err" || { tail -20 "$O/${T}_bench_default.err"; exit 1; }
+      timeout -k 10 500 python bench.py --full > "$O/${T}_bench_default.json" 2> "$O/${T}_bench_default.err" || { tail -20 "$O/${T}_bench_default.err"; exit 1; }
       cat "$O/${T}_bench_default.json" ;;
     all-workloads)
       : > "$O/${T}_bench_all.jsonl"
       for w in msvideo1_16_1080p_keyframes_m1_hostdesc msvideo1_8_1080p_keyframes_m1 msvideo1_16_1080p_keyframes_solid \
                msvideo1_16_1080p_keyframes_eight msvideo1_16_1080p_inter70 screenpressor_v4_1080p_iframes \
                screenpressor_v2_1080p_iframes screenpressor_v4_1080p_pclip300; do
-        timeout -k 10 600 python bench.py --workload $w --steps 20 --warmup 5 >> "$O/${T}_bench_all.jsonl" 2>> "$O/${T}_bench_all.err" || { tail -20 "$O/${T}_bench_all.err"; exit 1; }
+        timeout -k 10 600 python bench.py --workload $w --steps 20 --warmup 5 --full >> "$O/${T}_bench_all.jsonl" 2>> "$O/${T}_bench_all.err" || { tail -20 "$O/${T}_bench_all.err"; exit 1; }
         echo "done $w"
       done ;;
     profile:*)
