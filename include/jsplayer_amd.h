@@ -205,6 +205,8 @@ int jsp_key_frame_differs(jsp_codec* c);
  *                        the tiles before it;
  *   "sp_groups_held", "sp_spare_decoders"  (ScreenPressor) groups of pictures the asynchronous path keeps a record of, and
  *                        host decoders on its shelf: both stay bounded however long a stream runs without jsp_sync.
+ *   "msv1_block_changes" (MSVideo1, for tests) not a count: the persistent per-row flags (MSVideo1.hx:122,305) of block
+ *                        rows 0..61, row r in bit r — what the next DecompressP's significance starts from.
  * Unknown names and null arguments answer -1.  Results never depend on either path having been taken. */
 long long jsp_counter(jsp_codec* c, const char* name);
 

@@ -362,6 +362,17 @@ struct Msv1Codec : jsp_codec {
     long long counter(const char* name) override {
         if (std::strcmp(name, "prefetched_frames") == 0) return prefetched_frames;
         if (std::strcmp(name, "paired_frames") == 0) return paired_frames;
+        if (std::strcmp(name, "msv1_block_changes") == 0) {   // (tests) the per-row flags of block rows 0..61 as bits
+            std::vector<uint8_t> rows;
+            try {
+                if (!msv1_block_changes_now(this, rows)) return -1;
+            } catch (const std::exception&) {
+                return -1;
+            }
+            long long m = 0;
+            for (size_t r = 0; r < rows.size() && r < 62; ++r) m |= (long long)(rows[r] != 0) << r;
+            return m;
+        }
         return std::strcmp(name, "lookback_fallbacks") == 0 ? lookback_fallbacks->load() : -1;
     }
     bool opt_async_merged = true, opt_async_dma = true, opt_async_auto = true;

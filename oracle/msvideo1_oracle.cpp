@@ -279,5 +279,12 @@ int orc_msv1_decompress_i(void* c, const uint8_t* src, size_t n, int32_t* dst) {
     return ((Msv1*)c)->decompress_p(src, n, dst, &dp, &sg);
 }
 int orc_msv1_needs_index(void*) { return 1; }
+// block_changes of rows 0..61 as bits (row r in bit r)
+long long orc_msv1_block_changes(void* c) {
+    const Msv1* m = (const Msv1*)c;
+    long long v = 0;
+    for (size_t r = 0; r < m->block_changes.size() && r < 62; ++r) v |= (long long)(m->block_changes[r] != 0) << r;
+    return v;
+}
 
 }  // extern "C"

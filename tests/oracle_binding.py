@@ -31,6 +31,8 @@ def lib():
         L.orc_msv1_decompress_i.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p]
         L.orc_msv1_decompress_p.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p,
                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        L.orc_msv1_block_changes.restype = C.c_longlong
+        L.orc_msv1_block_changes.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -74,6 +76,10 @@ class OracleMSVideo1:
         if rc != 0:
             raise OracleAbort()
         return (self._bufs.get(out.value) if out.value else None), bool(sg.value)
+
+    def BlockChanges(self):
+        """The persistent per-row flags of block rows 0..61 as bits (row r in bit r)."""
+        return int(self.L.orc_msv1_block_changes(self.h))
 
     def close(self):
         if self.h:

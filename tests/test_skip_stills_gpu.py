@@ -14,7 +14,9 @@ import pytest
 
 from jsplayer_amd import CodecError, MSVideo1_16bit, MSVideo1_8bit, ScreenPressor, player
 from jsplayer_amd import streamgen as sg
-from oracle_binding import OracleAbort, OracleMSVideo1, OracleScreenPressor
+from msv1_range_clips import Idle, expected_landing, truth_run
+from msv1_range_clips import walk as _walk
+from oracle_binding import OracleMSVideo1
 
 pytestmark = pytest.mark.gpu
 
@@ -47,99 +49,7 @@ def make_gpu(bits, w, h, pal=None, lines=36, chunk=None):
     return c
 
 
-# ---- clips -------------------------------------------------------------------------------------------------------------------
-class Idle:
-    """MSVideo1 frames built code by code.  The generator keeps the solid colour of every block (None once a block holds a
-    pattern), so that it can recode a block with what it already shows."""
-
-    def __init__(self, bits, w, h, seed):
-        self.bits, self.w, self.h = bits, w, h
-        self.nbx, self.nby = w // 4, h // 4
-        self.nb = self.nbx * self.nby
-        self.rng = np.random.default_rng(seed)
-        self.col = [None] * self.nb
-
-    def colour(self):
-        if self.bits == 8:
-            return int(self.rng.integers(1, 256))
-        while True:   # a solid 16-bit code must not look like a skip code: red == 1 is left out
-            v = int(self.rng.integers(0, 0x8000))
-            if (v >> 10) != 1:
-                return v
-
-    def solid(self, v):
-        return bytes([v, 0x80]) if self.bits == 8 else bytes([v & 0xFF, 0x80 | (v >> 8)])
-
-    def two(self, v0, v1, flags=0x5A5A):
-        if self.bits == 8:
-            return bytes([flags & 0xFF, flags >> 8, v0, v1])
-        return bytes([flags & 0xFF, flags >> 8, v0 & 0xFF, v0 >> 8, v1 & 0xFF, v1 >> 8])
-
-    def eight(self, v):
-        if self.bits == 8:
-            return bytes([0x34, 0x92] + [v] * 8)
-        return bytes([0x34, 0x12, v & 0xFF, (v >> 8) | 0x80] + [v & 0xFF, v >> 8] * 7)
-
-    def encode(self, codes):
-        """codes: one entry per block, None = skip."""
-        out, run = bytearray(), 0
-        for c in codes + [b""]:
-            if c is None:
-                run += 1
-                continue
-            while run:
-                k = min(run, 1023)
-                out += bytes([k & 0xFF, 0x84 + (k >> 8)])
-                run -= k
-            out += c
-        return bytes(out)
-
-    def key(self, same=False, how="solid"):
-        """A key frame of solid blocks; same: the colours the blocks hold (how="two": as 2-colour codes, other bytes)."""
-        if not same:
-            self.col = [self.colour() for _ in range(self.nb)]
-        self.col = [0 if v is None else v for v in self.col]
-        return self.encode([self.solid(v) if how == "solid" else self.two(v, v) for v in self.col])
-
-    def recode(self, blocks, how=None):
-        codes = [None] * self.nb
-        for b in blocks:
-            v = self.col[b]
-            if v is None:
-                continue
-            kind = how or ("solid", "two", "eight")[int(self.rng.integers(0, 3))]
-            codes[b] = self.solid(v) if kind == "solid" else self.two(v, v) if kind == "two" else self.eight(v)
-        return self.encode(codes)
-
-    def change(self, blocks):
-        codes = [None] * self.nb
-        for b in blocks:
-            self.col[b] = self.colour()
-            codes[b] = self.solid(self.col[b])
-        return self.encode(codes)
-
-    def row_of(self, by, n=None):
-        bs = list(range(by * self.nbx, (by + 1) * self.nbx))
-        return bs if n is None else bs[:n]
-
-    def first_line_only(self, by):
-        """The blocks of block row `by` change their first pixel line only (a 2-colour code: new colour where flags are set)."""
-        codes = [None] * self.nb
-        for b in self.row_of(by):
-            if self.col[b] is None:
-                continue
-            codes[b] = self.two(self.colour(), self.col[b], flags=0x000F)
-            self.col[b] = None
-        return self.encode(codes)
-
-    def all_skip(self, kind):
-        if kind == "empty":
-            return b""
-        if kind == "short":
-            return bytes([0x01, 0x84])
-        return self.encode([None] * self.nb)
-
-
+# ---- clips (Idle: msv1_range_clips) -------------------------------------------------------------------------------------
 def idle_clip(bits, w, h, seed=1, lines=36, stretches=(3, 1, 5, 2, 0, 4), with_keys=True):
     """(frames, keys, palette): a key frame, then idle stretches of the given lengths each ending in a real change, mixed
     with key frames that repeat the one before (bytes) or repaint the same picture."""
@@ -178,96 +88,10 @@ def idle_clip(bits, w, h, seed=1, lines=36, stretches=(3, 1, 5, 2, 0, 4), with_k
     return frames, keys, pal
 
 
-# ---- truth -------------------------------------------------------------------------------------------------------------------
-def truth_run(bits, w, h, pal, frames, keys, lines=36, key_row=36, key_before=None):
-    """Per frame: (picture, significance as the Manager records it, adopted) — or OracleAbort at the frame that raises."""
-    o = OracleMSVideo1(bits, w, h, pal)
-    o.Preinit(lines)
-    bufs = [np.full(w * h, POISON, dtype=np.int32) for _ in range(3)]
-    out = []
-    for i, (src, key) in enumerate(zip(frames, keys)):
-        prev = o.PreviousFrame()
-        before = None if prev is None else prev.copy()
-        dst = next(b for b in bufs if b is not prev)
-        if prev is not None:
-            np.copyto(dst, prev)
-        else:
-            dst.fill(POISON)
-        if key:
-            if o.DecompressI(src, dst) != 0:
-                raise OracleAbort()
-            kb = frames[i - 1] if i > 0 and keys[i - 1] else (key_before if i == 0 else None)
-            if kb is not None:
-                sig = bytes(kb) != bytes(src)
-            elif before is None:
-                sig = True
-            else:
-                sig = bool(np.any(dst[key_row * w:] != before[key_row * w:]))
-        else:
-            try:
-                data, sig = o.DecompressP(src, dst)
-            except OracleAbort:
-                out.append(None)
-                return out
-        pic = o.PreviousFrame()
-        out.append((None if pic is None else pic.copy(), bool(sig)))
-    return out
-
-
-def expected_landing(truth, first):
-    for k in range(first, len(truth)):
-        if truth[k] is None:
-            return None
-        if truth[k][1]:
-            return k
-    return len(truth) - 1
-
-
-# ---- the walk ----------------------------------------------------------------------------------------------------------------
+# ---- the walk (truth_run, expected_landing, walk: msv1_range_clips) ------------------------------------------------------------
 def walk(bits, w, h, pal, frames, keys, lines=36, chunk=None, misalign=False, step=True):
-    """Frame 0 by DecompressI, then FindChange from the frame after the one shown to the end, again and again.  step: after
-    each landing the next frame goes through DecompressI / DecompressP (its picture and significance against the oracle: the
-    codec state FindChange left — previous frame, block_changes — is the sequential one) before the next skip."""
-    truth = truth_run(bits, w, h, pal, frames, keys, lines, key_row=lines)
-    gpu = make_gpu(bits, w, h, pal, lines, chunk)
-    n = len(frames)
-    first_buf = dev_buf(w * h, misalign=misalign)
-    assert gpu.DecompressI(frames[0], first_buf) == 0
-    pool = [first_buf] + [dev_buf(w * h, misalign=misalign) for _ in range(2)]
-    shown, landings = 0, []
-    where = f"{bits}-bit {w}x{h} lines={lines} chunk={chunk} ({PARSE} parse)"
-    while shown < n - 1:
-        start = shown + 1
-        want = expected_landing(truth, start)
-        prev = gpu.PreviousFrame()
-        dst = next(b for b in pool if b is not prev)
-        kb = frames[shown] if keys[shown] else None
-        res = gpu.FindChange(frames[start:], dst, keys[start:], 0, kb, lines)
-        f = start + res.index
-        assert f == want, f"{where}: skip from {shown} landed on {f}, the oracle on {want}"
-        assert res.changed == bool(truth[f][1]), where
-        for k in range(start, n):
-            s = res.significance[k - start]
-            assert s == (truth[k][1] if k <= f else None), f"{where}: significance of frame {k}"
-        got = gpu.PreviousFrame()
-        assert res.data_pnt is got, where
-        assert np.array_equal(got.cpu().numpy(), truth[f][0]), f"{where}: picture of frame {f}"
-        landings.append(f)
-        shown = f
-        if step and shown < n - 1:
-            i = shown + 1
-            prev = gpu.PreviousFrame()
-            d = next(b for b in pool if b is not prev)
-            d.copy_(prev)
-            if keys[i]:
-                assert gpu.DecompressI(frames[i], d) == 0
-            else:
-                r = gpu.DecompressP(frames[i], d)
-                assert r.significant_changes == truth[i][1], f"{where}: frame {i} after the landing on {f}: significance"
-            assert np.array_equal(gpu.PreviousFrame().cpu().numpy(), truth[i][0]), f"{where}: frame {i} after the landing on {f}"
-            shown = i
-    gpu.StopAndClean()
-    return landings, truth
+    """msv1_range_clips.walk with this module's parse mode."""
+    return _walk(bits, w, h, pal, frames, keys, lines=lines, chunk=chunk, misalign=misalign, step=step, parse=PARSE)
 
 
 @pytest.mark.parametrize("bits", [16, 8])
