@@ -22,6 +22,67 @@ namespace {
 // Published tile tables carry the launch's epoch; 0 is what freshly zeroed memory reads as, so the counter skips it when it wraps.
 inline uint32_t next_epoch(uint32_t& e) { if (++e == 0) ++e; return e; }
 
+// One tile's record for msv1_fused_kernel (msv1.h): tile k of `ntiles` (the first is number `first_tile` of the launch's published words), `tile_bytes`
+// each, of the frame whose bytes start at `beg` of the stream buffer; `even_end`: the end without an odd last byte, `data_end`: of what may be read.
+inline Msv1TileRec tile_rec(uint32_t beg, uint32_t even_end, uint32_t data_end, uint32_t k, uint32_t tile_bytes, uint32_t first_tile, uint32_t ntiles,
+                            int32_t* dst, const int32_t* prev, uint32_t* signif, uint32_t cmp_row_lo, uint32_t flags) {
+    Msv1TileRec r{};
+    r.byte0 = beg + k * tile_bytes;
+    r.frame_end = even_end;
+    r.data_end = data_end;
+    r.k = k;
+    r.first_tile = first_tile;
+    r.ntiles = ntiles;
+    r.cmp_row_lo = cmp_row_lo;
+    r.flags = flags;
+    r.dst = dst;
+    r.prev = prev;
+    r.signif = signif;
+    r.pad = 0;
+    return r;
+}
+
+// Launch order of the tiles of frames [f0, f1), frame i having ntiles[i] of them: emit(i, k) for every tile, in that order.
+// Tile-major over the frames — tile j of every frame before tile j + 1 of any — so that when a tile starts, its predecessor in the frame is long done
+// and has published where the chain stands (the kernel's one-word look-back).
+// ... and the frames do not march in step: frame i starts ((i - f0) mod stagger) rounds late, so that at any time the batch's write
+// fronts stand at different depths of their frames instead of all at tile j.  What the memory system makes of
+// hundreds of fronts depends on where the frames lie in physical memory; staggered by 64, the same frames
+// take 2 - 6 % less time whichever way they lie (one process, same buffers: profiles/archive/r03_stagger_one_process.txt).  stagger 0: in step.
+template <class Emit>
+inline void staggered_tile_order(int f0, int f1, const std::vector<uint32_t>& ntiles, uint32_t stagger, Emit&& emit) {
+    uint32_t maxt = 0;
+    for (int i = f0; i < f1; ++i) maxt = std::max(maxt, ntiles[i]);
+    for (uint32_t j = 0; j < maxt + stagger; ++j)
+        for (int i = f0; i < f1; ++i) {
+            const uint32_t late = stagger ? (uint32_t)(i - f0) % stagger : 0u;
+            if (j >= late && j - late < ntiles[i]) emit(i, j - late);
+        }
+}
+
+// Significance of a frame, MSVideo1.hx:187-204 / 372-388: 1, 0, or -1 = stage 2 decides (the compare with the previous frame, on the GPU).
+// `s1`: a coded block lies in a significant block row; `compares`: a 16-bit codec whose Preinit set insign_lines.  Key frames report none.
+inline int msv1_significance(bool s1, bool have_prev, bool key, bool compares) {
+    if (!s1 || key) return 0;
+    if (!have_prev) return 1;
+    return compares ? -1 : 0;   // 8-bit: NaN loop bound -> no pixel is compared -> false
+}
+
+// What the phases of Msv1Codec::stage() hand on to each other about the batch being staged.
+struct StagePlan {
+    std::vector<size_t> beg;               // where each frame's bytes start in the batch's stream buffer
+    size_t total_stream = 0;
+    std::vector<uint8_t> in_pinned;        // the frame's bytes are uploaded from where the caller keeps them
+    Msv1ParseFrame* h_pf = nullptr;        // on-GPU parse: the frames' parse records ...
+    const Msv1FrameInfo* h_info = nullptr; // ... and what the parse kernels counted in each
+    struct Attr { bool dependent, noop, special, edge; };
+    std::vector<Attr> attr;
+    std::vector<uint64_t> frame_stream;    // stream bytes each frame's codes occupy
+    bool pframes_dirty = false;            // some frame went to the host parser after the parse records were uploaded
+    bool vec_ok = true;
+    double h2d_ms = 0, gpu_parse_ms = 0;
+};
+
 struct Msv1Staged : jsp_staged {
     Msv1Geometry geo{};
     const int32_t* d_palette = nullptr;
@@ -62,65 +123,40 @@ struct Msv1Staged : jsp_staged {
     hipEvent_t ev_fork = nullptr, ev_tables = nullptr;   // "the stream has reached this replay's reconstruction launches" / "the tables written ahead are complete"
     int cur_set = 0;                   // which set this replay's launches read
     bool ahead_valid = false;          // the tables of cur_set were written ahead (on `side`) and ev_tables says when
-    // What a replay writes and reads (round 6): the COMPACT table where every launch that reads tables is a temporal launch (`compact_ok`, settled at
-    // staging) — 2 bytes per block and a base per 256 blocks instead of 4 bytes per block, msv1.h —, else 4-byte tables as ever.  Set 0 of the 4-byte kind is
-    // d_desc itself (what staging built: the first decode and the look-back fall-back always read that); every other set is made by the first replay that
-    // needs it.  Tables a replay does not rewrite (frames the host parser settled) are put into every set when it is made.
-    bool compact_ok = false;
-    struct TableSet { DeviceBuffer wide, tab16, bases, recs; bool made = false; } sets[2];
-    uint32_t* wide_tables(int i) { return static_cast<uint32_t*>(compact_ok || i == 0 ? d_desc.p : sets[i].wide.p); }
+    // What a replay writes and reads: 4-byte block tables.  Set 0 is d_desc itself (what staging built: the first decode and the look-back fall-back always
+    // read that); set 1 is a copy of it, with table-writing records of its own, made by the first replay that parses ahead.  Tables a replay does not
+    // rewrite (frames the host parser settled) come along in the copy.
+    struct TableSet {
+        DeviceBuffer wide, recs;
+        bool made = false;
+        void drop() { wide.release(); recs.release(); made = false; }
+    } sets[2];
+    uint32_t* wide_tables(int i) { return static_cast<uint32_t*>(i == 0 ? d_desc.p : sets[i].wide.p); }
     void make_set(int i, hipStream_t stream) {
         TableSet& t = sets[i];
         if (t.made) return;
-        const size_t nblk = (size_t)std::max(geo.nblocks, 1);
-        std::vector<Msv1TileRec> recs((size_t)ntiles_emit);
-        std::memcpy(recs.data(), h_recs_emit.p, sizeof(Msv1TileRec) * recs.size());
-        if (compact_ok) {
-            const size_t pitch = (size_t)msv1_tab16_pitch(geo.nblocks), ngr = (size_t)msv1_tab16_groups(geo.nblocks);
-            t.tab16.reserve(sizeof(uint16_t) * pitch * (size_t)nframes);
-            t.bases.reserve(sizeof(uint32_t) * ngr * (size_t)nframes);
-            JSP_HIP(hipMemsetAsync(t.tab16.p, 0xFF, sizeof(uint16_t) * pitch * (size_t)nframes, stream));   // (MSV1_TAB16_UNTOUCHED)
-            JSP_HIP(hipMemsetAsync(t.bases.p, 0, sizeof(uint32_t) * ngr * (size_t)nframes, stream));
-            std::vector<uint32_t> kept;                // frames whose tables the replays leave alone: converted from the 4-byte tables staging uploaded
-            const auto* pf = static_cast<const Msv1ParseFrame*>(h_pframes.p);
-            for (int f = 0; f < nframes; ++f) if (pf[f].host_parsed) kept.push_back((uint32_t)f);
-            if (!kept.empty()) {
-                d_kept.reserve(sizeof(uint32_t) * kept.size());
-                JSP_HIP(hipMemcpy(d_kept.p, kept.data(), sizeof(uint32_t) * kept.size(), hipMemcpyHostToDevice));
-                msv1_launch_tables_compact(geo, static_cast<const uint32_t*>(d_desc.p), static_cast<uint16_t*>(t.tab16.p), static_cast<uint32_t*>(t.bases.p),
-                                           static_cast<const uint32_t*>(d_kept.p), (int)kept.size(), stream);
-            }
-            for (auto& r : recs) {
-                const size_t f = (size_t)(reinterpret_cast<uint32_t*>(r.dst) - static_cast<uint32_t*>(d_desc.p)) / nblk;   // (staging pointed the record at the frame's 4-byte table)
-                r.dst = reinterpret_cast<int32_t*>(static_cast<uint16_t*>(t.tab16.p) + f * pitch);
-                r.prev = reinterpret_cast<const int32_t*>(static_cast<uint32_t*>(t.bases.p) + f * ngr);
-            }
-        } else if (i != 0) {
-            const size_t table_bytes = sizeof(uint32_t) * nblk * (size_t)nframes;
+        if (i != 0) {
+            std::vector<Msv1TileRec> recs((size_t)ntiles_emit);
+            std::memcpy(recs.data(), h_recs_emit.p, sizeof(Msv1TileRec) * recs.size());
+            const size_t table_bytes = sizeof(uint32_t) * (size_t)std::max(geo.nblocks, 1) * (size_t)nframes;
             t.wide.reserve(table_bytes);
             JSP_HIP(hipMemcpyAsync(t.wide.p, d_desc.p, table_bytes, hipMemcpyDeviceToDevice, stream));
             for (auto& r : recs) r.dst = reinterpret_cast<int32_t*>(static_cast<uint32_t*>(t.wide.p) + (reinterpret_cast<uint32_t*>(r.dst) - static_cast<uint32_t*>(d_desc.p)));
-        }
-        if (compact_ok || i != 0) {
             t.recs.reserve(sizeof(Msv1TileRec) * std::max<size_t>(recs.size(), 1));
             JSP_HIP(hipMemcpy(t.recs.p, recs.data(), sizeof(Msv1TileRec) * recs.size(), hipMemcpyHostToDevice));
         }
         t.made = true;
     }
-    DeviceBuffer d_kept;
     void launch_table_parse(int set, hipStream_t on) {
         make_set(set, on);
         const TableSet& t = sets[set];
-        const size_t pitch = (size_t)msv1_tab16_pitch(geo.nblocks);
-        for (uint32_t i : scrub) {
-            if (compact_ok) JSP_HIP(hipMemsetAsync(static_cast<uint16_t*>(t.tab16.p) + (size_t)i * pitch, 0xEE, sizeof(uint16_t) * (size_t)geo.nblocks, on));
-            else JSP_HIP(hipMemsetAsync(wide_tables(set) + (size_t)i * (size_t)std::max(geo.nblocks, 1), 0xEE, sizeof(uint32_t) * (size_t)geo.nblocks, on));
-        }
+        for (uint32_t i : scrub)
+            JSP_HIP(hipMemsetAsync(wide_tables(set) + (size_t)i * (size_t)std::max(geo.nblocks, 1), 0xEE, sizeof(uint32_t) * (size_t)geo.nblocks, on));
         msv1_launch_fused(geo, static_cast<const uint8_t*>(d_stream.p), static_cast<const Msv1TileRec*>(t.recs.p ? t.recs.p : d_recs_emit.p), d_palette,
                           static_cast<unsigned long long*>(d_agg_emit.p), next_epoch(epoch), 0, ntiles_emit, static_cast<uint32_t*>(d_sync.p), on,
-                          nullptr, 0, compact_ok ? 5 : 4, 0, nullptr, nullptr, nullptr, (uint32_t)ntiles_emit, nullptr, /*small_tiles=*/true);   // (`want`: where a lab build's phase clocks go)
+                          nullptr, 0, 4, 0, nullptr, nullptr, nullptr, (uint32_t)ntiles_emit, nullptr, /*small_tiles=*/true);   // (`want`: where a lab build's phase clocks go)
     }
-    void drop_sets() { for (auto& t : sets) { t.wide.release(); t.tab16.release(); t.bases.release(); t.recs.release(); t.made = false; } }
+    void drop_sets() { for (auto& t : sets) t.drop(); }
     void quiesce_side() {              // nothing of this batch is left running beside the stream (before its buffers are reused or freed)
         if (side) (void)hipStreamSynchronize(side);
         ahead_valid = false;
@@ -152,10 +188,7 @@ struct Msv1Staged : jsp_staged {
             if (run_ahead && ahead_valid) JSP_HIP(hipStreamWaitEvent(stream, ev_tables, 0));   // written beside the replay before this one
             else launch_table_parse(cur_set, stream);
         }
-        const bool compact = replay && compact_ok;                 // this decode's temporal launches read the compact tables of cur_set
         const uint32_t* tables = replay ? wide_tables(cur_set) : static_cast<const uint32_t*>(d_desc.p);
-        const uint16_t* tab16 = compact ? static_cast<const uint16_t*>(sets[cur_set].tab16.p) : nullptr;
-        const uint32_t* bases = compact ? static_cast<const uint32_t*>(sets[cur_set].bases.p) : nullptr;
         if (run_ahead && decoded) {
             // the next replay's tables, into the other set, beside the launches below: the other set's last readers (the replay before this one) and the
             // last table-writing launch (it shares the published tile words and the fault word) are all in front of `ev_fork` on the stream
@@ -163,7 +196,7 @@ struct Msv1Staged : jsp_staged {
                 make_set(cur_set ^ 1, stream);
             } catch (const std::exception&) {          // no room for a second table set: this batch's replays parse in line from now on
                 (void)hipGetLastError();
-                { TableSet& t = sets[cur_set ^ 1]; t.wide.release(); t.tab16.release(); t.bases.release(); t.recs.release(); t.made = false; }
+                sets[cur_set ^ 1].drop();
                 side = nullptr;
             }
         }
@@ -175,10 +208,205 @@ struct Msv1Staged : jsp_staged {
             launch_table_parse(cur_set ^ 1, side);
             JSP_HIP(hipEventRecord(ev_tables, side));
         }
+        launch_groups(tables, /*fused=*/true, stream);
+        if (any_fused || needs_desc)
+            JSP_HIP(hipMemcpyAsync(h_fault.p, d_sync.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        ++clock_launches;
+        if (run_ahead && decoded && side) { cur_set ^= 1; ahead_valid = true; }   // the next replay reads what was just started beside this one
+        decoded = true;
+    }
+    // ---- stage(), phase 5: the launch plan ----
+    // "special" frames (abort, partially written) run alone with the per-frame kernel.  Between
+    // them: a run of frames none of which reads its predecessor is one launch with grid.y = frame;
+    // a run containing inter frames is one launch of the temporal kernel (tile per workgroup,
+    // frames walked in registers) when the buffers allow 16-byte rows, else one launch per frame.
+    void plan_launches(const std::vector<jsp_frame_in>& frames, const StagePlan& plan) {
+        const auto& attr = plan.attr;
+        const int nf = nframes;
+        int i = 0;
+        while (i < nf) {
+            if (attr[i].special) { groups.push_back({i, 1, attr[i].edge, false, false}); ++i; continue; }
+            int j = i;
+            bool any_dep = false;
+            while (j < nf && !attr[j].special) { any_dep |= attr[j].dependent; ++j; }
+            std::unordered_set<const void*> seen;
+            if (any_dep && vec_ok) {
+                // every access to a tile, in whichever buffer, comes from the same workgroup in
+                // program order, so buffers may even repeat inside the group
+                bool edge = false;
+                for (int k = i; k < j; ++k) edge |= attr[k].edge;
+                groups.push_back({i, j - i, edge, true, false});
+            } else {
+                // frames that do not read their predecessor: one launch per run of them with grid.y = frame —
+                // or, straight from the stream bytes, one fused launch per run of GPU-parsed frames
+                bool closed = true;
+                for (int k = i; k < j; ++k) {
+                    const bool writes = !attr[k].noop;
+                    const bool fusable = gpu_parse && vec_ok && !attr[k].dependent && !attr[k].noop && !plan.h_pf[k].host_parsed;
+                    if (attr[k].dependent || closed || (writes && seen.count(frames[k].dst)) || groups.back().fused != fusable) {
+                        groups.push_back({k, 1, attr[k].edge, false, fusable});
+                        seen.clear();
+                        closed = attr[k].dependent;
+                    } else {
+                        groups.back().count++;
+                    }
+                    if (writes) seen.insert(frames[k].dst);
+                }
+            }
+            i = j;
+        }
+    }
+
+    // ---- stage(), phase 6: what the plan launches and moves (info.*, kernels, needs_desc, any_fused) ----
+    void account(const StagePlan& plan) {
+        const int nf = nframes;
+        const auto* h_frames = static_cast<const Msv1FrameArgs*>(this->h_frames.p);
+        need_signif = false;
+        for (int v : significant) need_signif |= v < 0;
+        info.frames = nf;
+        info.pixels = (uint64_t)geo.X * geo.Y * nf;
+        info.descriptor_bytes = sizeof(uint32_t) * (uint64_t)geo.nblocks * nf + sizeof(Msv1FrameArgs) * nf;
+        // SURVEY.md 8(d): A = S + 64*N_coded + 128*N_skipped
+        info.algorithmic_bytes = info.stream_bytes + 64 * info.units_coded + 128 * info.units_copied;
+        // Fused launches read their frames' stream bytes once and write every block
+        // once.  Descriptor launches read stream + table, write the blocks, and read a previous frame per skipped /
+        // compared block (per-frame kernel) or once per tile (temporal launch); when the table of any of them comes from
+        // the parse kernels, every replay also runs tiles + chain + emit over the whole batch (two more reads of the
+        // stream, one write of the table).
+        needs_desc = false;
+        any_fused = false;
+        kernels.clear();
+        const uint64_t table_bytes_per_frame = sizeof(uint32_t) * (uint64_t)geo.nblocks;
+        uint64_t moved = 0;
+        for (const auto& g : groups) {
+            uint64_t written = 0, prev_reads = 0, sbytes = 0;
+            bool uses_prev = false, gpu_table = false;
+            for (int k = g.first; k < g.first + g.count; ++k) {
+                if (!plan.attr[k].noop) written += (uint64_t)geo.nblocks;
+                uses_prev |= (h_frames[k].pad & MSV1_FRAME_USES_PREV) != 0;
+                if (h_frames[k].pad & MSV1_FRAME_USES_PREV) prev_reads += (uint64_t)geo.nblocks;
+                sbytes += plan.frame_stream[k];
+                gpu_table |= gpu_parse && !plan.h_pf[k].host_parsed;
+            }
+            moved += sbytes + 64 * written;
+            if (g.fused) {
+                any_fused = true;
+                note_kernel("msv1_fused_kernel");
+            } else {
+                needs_desc |= gpu_table;
+                moved += table_bytes_per_frame * g.count +
+                         64 * (g.temporal ? (uses_prev ? (uint64_t)geo.nblocks : 0) : prev_reads);
+                note_kernel(g.temporal ? "msv1_blocks_temporal_kernel" : "msv1_blocks_kernel");
+            }
+            if (g.edge_compare) note_kernel("msv1_edge_compare_kernel");
+        }
+        if (needs_desc) {   // (a replay: msv1_fused_kernel in its descriptor form reads the stream once and writes the tables)
+            moved += info.stream_bytes + table_bytes_per_frame * nf;
+            if (!any_fused) kernels = "msv1_fused_kernel" + (kernels.empty() ? std::string() : " + " + kernels);
+        }
+        info.moved_bytes = moved;
+        info.kernel_launches = groups.size() + (needs_desc ? 1 : 0);
+    }
+
+    // ---- stage(), phase 7: what msv1_fused_kernel needs to know about every tile, for the launches that write pixels and the one that writes tables ----
+    void build_tile_records(const std::vector<jsp_frame_in>& frames, const StagePlan& plan, bool scrub_tables, hipStream_t stream) {
+        if (!any_fused && !needs_desc) return;
+        d_agg.reserve(sizeof(unsigned long long) * (9 + 8) * (size_t)std::max(ntiles, 1));   // (+ 8 per tile: the lab build's phase clocks)
+        d_sync.reserve(2 * sizeof(uint32_t) + 64);   // (+ room for the lab build's phase clocks)
+        h_fault.reserve(sizeof(uint32_t));
+        *static_cast<uint32_t*>(h_fault.p) = 0;
+        epoch = 0;
+        build_pixel_records(plan, stream);
+        if (needs_desc) build_table_records(frames, plan, scrub_tables, stream);
+        // published tile tables carry the launch epoch (first launch: 1), so stale words must read as epoch 0
+        JSP_HIP(hipMemsetAsync(d_agg.p, 0, sizeof(unsigned long long) * (9 + 8) * (size_t)std::max(ntiles, 1), stream));
+        JSP_HIP(hipMemsetAsync(d_sync.p, 0, 2 * sizeof(uint32_t) + 64, stream));   // the fault word
+    }
+    // one record per 16 KiB tile, in stream order; then in launch order inside every fused launch
+    void build_pixel_records(const StagePlan& plan, hipStream_t stream) {
+        const int nf = nframes;
+        const Msv1ParseFrame* h_pf = plan.h_pf;
+        const auto* h_frames = static_cast<const Msv1FrameArgs*>(this->h_frames.p);
+        h_recs.reserve(sizeof(Msv1TileRec) * (size_t)std::max(ntiles, 1));
+        d_recs.reserve(sizeof(Msv1TileRec) * (size_t)std::max(ntiles, 1));
+        auto* recs = static_cast<Msv1TileRec*>(h_recs.p);
+        std::vector<uint32_t> nt16((size_t)nf);
+        for (int i = 0; i < nf; ++i) {
+            nt16[i] = h_pf[i].ntiles;
+            for (uint32_t k = 0; k < h_pf[i].ntiles; ++k)   // (byte0 == (first_tile + k) * tile: frames start on tile boundaries)
+                recs[h_pf[i].first_tile + k] = tile_rec(h_pf[i].beg, h_pf[i].end, geo.bits == 16 ? h_pf[i].end : h_frames[i].stream_end, k, msv1_parse_tile_bytes(),
+                                                        h_pf[i].first_tile, h_pf[i].ntiles, h_frames[i].dst, h_frames[i].prev, h_frames[i].signif,
+                                                        h_frames[i].cmp_row_lo, h_pf[i].host_parsed ? MSV1_TILE_SKIP : 0u);
+        }
+        // Launch order (staggered_tile_order): a launch covers the contiguous record range of its frames; the records are
+        // permuted inside that range (a record carries its own byte offset and its number in stream order).
+        const uint32_t stagger = [] { const char* e = std::getenv("JSP_MSV1_STAGGER"); return e ? (uint32_t)std::atoi(e) : 64u; }();   // (lab: read at every staging)
+        auto tile_major = [&](int f0, int f1) {   // frames [f0, f1)
+            if (f1 - f0 < 2) return;
+            const uint32_t t0 = h_pf[f0].first_tile, t1 = h_pf[f1 - 1].first_tile + h_pf[f1 - 1].ntiles;
+            const std::vector<Msv1TileRec> tmp(recs + t0, recs + t1);
+            uint32_t o = t0;
+            staggered_tile_order(f0, f1, nt16, stagger, [&](int i, uint32_t k) { recs[o++] = tmp[h_pf[i].first_tile - t0 + k]; });
+        };
+        static const int major_frames = [] { const char* e = std::getenv("JSP_MSV1_TILE_MAJOR_FRAMES"); return e ? std::atoi(e) : 0; }();   // lab: permute within runs of this many frames
+        for (const auto& g : groups)
+            if (g.fused) {
+                if (major_frames > 0)
+                    for (int f = g.first; f < g.first + g.count; f += major_frames) tile_major(f, std::min(f + major_frames, g.first + g.count));
+                else
+                    tile_major(g.first, g.first + g.count);
+            }
+        JSP_HIP(hipMemcpyAsync(d_recs.p, recs, sizeof(Msv1TileRec) * (size_t)ntiles, hipMemcpyHostToDevice, stream));
+    }
+    // The same for the descriptor form: `dst` = the frame's block table; frames whose table nobody reads (fused groups) or that came from the
+    // host parser are skipped.
+    // The table-writing form has no pixel stores to hide its parse behind: it runs in 8 KiB tiles (msv1_fused_kernel<BITS, 4, 16>: 64 VGPRs and
+    // 19 KB of LDS, eight workgroups per CU instead of four, half the serial work per tile).  Frames start on 16 KiB boundaries of the
+    // stream buffer, so a frame's 8 KiB tiles are numbered from twice its first 16 KiB tile... minus the halves that are all padding: the
+    // tiles are counted per frame, records and published words (d_agg_emit) are this form's own.
+    void build_table_records(const std::vector<jsp_frame_in>& frames, const StagePlan& plan, bool scrub_tables, hipStream_t stream) {
+        const int nf = nframes;
+        const Msv1ParseFrame* h_pf = plan.h_pf;
+        const auto* h_frames = static_cast<const Msv1FrameArgs*>(this->h_frames.p);
+        const size_t nblk = (size_t)std::max(geo.nblocks, 1);
+        const uint32_t tile8 = msv1_small_tile_bytes();
+        std::vector<uint32_t> first8((size_t)nf), n8((size_t)nf);
+        uint32_t nt8 = 0;
+        for (int i = 0; i < nf; ++i) {
+            first8[i] = nt8;
+            n8[i] = h_pf[i].ntiles ? (uint32_t)((frames[i].n + tile8 - 1) / tile8) : 0u;
+            nt8 += n8[i];
+        }
+        ntiles_emit = (int)nt8;
+        h_recs_emit.reserve(sizeof(Msv1TileRec) * (size_t)std::max<uint32_t>(nt8, 1));
+        d_recs_emit.reserve(sizeof(Msv1TileRec) * (size_t)std::max<uint32_t>(nt8, 1));
+        d_agg_emit.reserve(sizeof(unsigned long long) * (9 + 8) * (size_t)std::max<uint32_t>(nt8, 1));
+        auto* er = static_cast<Msv1TileRec*>(h_recs_emit.p);
+        std::vector<uint8_t> in_fused(nf, 0);
+        for (const auto& g : groups)
+            if (g.fused) std::fill(in_fused.begin() + g.first, in_fused.begin() + g.first + g.count, 1);
+        // written straight in launch order: over the whole batch, staggered by 64 whatever the lab's setting for the pixel-writing form
+        uint32_t o = 0;
+        staggered_tile_order(0, nf, n8, 64u, [&](int i, uint32_t k) {
+            er[o++] = tile_rec(h_pf[i].beg, h_pf[i].end, geo.bits == 16 ? h_pf[i].end : h_frames[i].stream_end, k, tile8, first8[i], n8[i],
+                               reinterpret_cast<int32_t*>(static_cast<uint32_t*>(d_desc.p) + (size_t)i * nblk), nullptr, h_frames[i].signif, 0xFFFFFFFFu,
+                               (h_pf[i].host_parsed || in_fused[i]) ? MSV1_TILE_SKIP : 0u);
+        });
+        JSP_HIP(hipMemcpyAsync(d_recs_emit.p, er, sizeof(Msv1TileRec) * (size_t)nt8, hipMemcpyHostToDevice, stream));
+        JSP_HIP(hipMemsetAsync(d_agg_emit.p, 0, sizeof(unsigned long long) * (9 + 8) * (size_t)std::max<uint32_t>(nt8, 1), stream));
+        scrub.clear();
+        if (scrub_tables)
+            for (int i = 0; i < nf; ++i)
+                if (!h_pf[i].host_parsed && !in_fused[i]) scrub.push_back((uint32_t)i);
+    }
+
+    // The batch's reconstruction launches in plan order, reading the block tables at `tables`, and the significance words' way back.  `fused`: groups
+    // planned as fused launches go straight from the stream bytes; else (the look-back fall-back) they paint from the tables like the others.
+    void launch_groups(const uint32_t* tables, bool fused, hipStream_t stream) {
         if (need_signif) JSP_HIP(hipMemsetAsync(d_signif.p, 0, sizeof(uint32_t) * nframes, stream));
         const auto* frames = static_cast<const Msv1FrameArgs*>(d_frames.p);
         for (const Group& g : groups) {
-            if (g.fused) {
+            if (g.fused && fused) {
                 const auto* pf = static_cast<const Msv1ParseFrame*>(h_pframes.p);
                 const uint32_t tile0 = pf[g.first].first_tile;
                 const Msv1ParseFrame& last = pf[g.first + g.count - 1];
@@ -186,21 +414,14 @@ struct Msv1Staged : jsp_staged {
                                   static_cast<unsigned long long*>(d_agg.p), next_epoch(epoch), tile0, (int)(last.first_tile + last.ntiles - tile0),
                                   static_cast<uint32_t*>(d_sync.p), stream, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, (uint32_t)ntiles);
             } else if (g.temporal) {
-                msv1_launch_blocks_temporal(geo, static_cast<const uint8_t*>(d_stream.p), tables, frames + g.first, g.count, d_palette, stream, tab16, bases);
+                msv1_launch_blocks_temporal(geo, static_cast<const uint8_t*>(d_stream.p), tables, frames + g.first, g.count, d_palette, stream);
             } else {
                 msv1_launch_blocks(geo, static_cast<const uint8_t*>(d_stream.p), tables, frames + g.first, g.count, d_palette, vec_ok, stream);
             }
             if (g.edge_compare) msv1_launch_edge_compare(geo, frames + g.first, g.count, stream);
         }
         JSP_HIP(hipGetLastError());
-        if (need_signif)
-            JSP_HIP(hipMemcpyAsync(h_signif.p, d_signif.p, sizeof(uint32_t) * nframes, hipMemcpyDeviceToHost,
-                                   stream));
-        if (any_fused || needs_desc)
-            JSP_HIP(hipMemcpyAsync(h_fault.p, d_sync.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        ++clock_launches;
-        if (run_ahead && decoded && side) { cur_set ^= 1; ahead_valid = true; }   // the next replay reads what was just started beside this one
-        decoded = true;
+        if (need_signif) JSP_HIP(hipMemcpyAsync(h_signif.p, d_signif.p, sizeof(uint32_t) * nframes, hipMemcpyDeviceToHost, stream));
     }
     int clock_launches = 0;                                    // (read by the lab build's phase clocks only: msv1_fused_hooks.h)
     void after_sync() override {
@@ -230,19 +451,7 @@ struct Msv1Staged : jsp_staged {
             quiesce_side();                            // (a table-writing launch may be running beside the stream: it shares the fault word, and its tables are not to be trusted either)
             JSP_HIP(hipMemsetAsync(d_sync.p, 0, 2 * sizeof(uint32_t) + 64, stream));
             launch_parse(stream);
-            if (need_signif) JSP_HIP(hipMemsetAsync(d_signif.p, 0, sizeof(uint32_t) * nframes, stream));
-            const auto* frames = static_cast<const Msv1FrameArgs*>(d_frames.p);
-            for (const Group& g : groups) {
-                if (g.temporal)
-                    msv1_launch_blocks_temporal(geo, static_cast<const uint8_t*>(d_stream.p), static_cast<const uint32_t*>(d_desc.p), frames + g.first,
-                                                g.count, d_palette, stream);
-                else
-                    msv1_launch_blocks(geo, static_cast<const uint8_t*>(d_stream.p), static_cast<const uint32_t*>(d_desc.p), frames + g.first, g.count,
-                                       d_palette, vec_ok, stream);
-                if (g.edge_compare) msv1_launch_edge_compare(geo, frames + g.first, g.count, stream);
-            }
-            JSP_HIP(hipGetLastError());
-            if (need_signif) JSP_HIP(hipMemcpyAsync(h_signif.p, d_signif.p, sizeof(uint32_t) * nframes, hipMemcpyDeviceToHost, stream));
+            launch_groups(static_cast<const uint32_t*>(d_desc.p), /*fused=*/false, stream);
             JSP_HIP(hipStreamSynchronize(stream));
         }
     }
@@ -318,18 +527,9 @@ struct Msv1AsyncStaged : jsp_staged {
         for (Msv1AsyncStaged* next : behind) next->decoded = true;
     }
     void decode(hipStream_t stream) override {
+        if (merged) { decode_with({}, stream); return; }
         auto* info_dev = d_info();
         const uint32_t bad = bad_mask();
-        if (merged) {
-            want += (uint32_t)ntiles;
-            if (dma) JSP_HIP(hipStreamWaitEvent(stream, uploaded, 0));
-            msv1_launch_fused(geo, src_dev, nullptr, d_palette, static_cast<unsigned long long*>(d_agg.p),
-                              next_epoch(epoch), 0, ntiles, &info_dev->fault, stream, info_dev, insignificant_blocks, 3, bad, d_poison, &rec,
-                              static_cast<Msv1AsyncInfo*>(h_info.p), want, dma ? nullptr : static_cast<uint8_t*>(d_stream.p), small_tiles);
-            JSP_HIP(hipGetLastError());
-            decoded = true;
-            return;
-        }
         for (int mode = 1; mode <= 2; ++mode)   // scout, then the decode it may veto
             msv1_launch_fused(geo, static_cast<const uint8_t*>(d_stream.p), static_cast<const Msv1TileRec*>(d_meta.p), d_palette,
                               static_cast<unsigned long long*>(d_agg.p), next_epoch(epoch), 0, ntiles, &info_dev->fault, stream, info_dev,
@@ -466,10 +666,7 @@ struct Msv1Codec : jsp_codec {
         held.clear();            // (frames held for their successors are among those about to be re-run: they are never launched)
         if (d_poison.p) JSP_HIP(hipMemsetAsync(d_poison.p, 0, sizeof(uint32_t), stream));
     }
-    // Replays of staged inter-frame batches (Msv1Staged::decode): "msv1_parse_ahead" (default on) and "msv1_compact_tables" (default OFF: measured, round 6 — the
-    // compact tables take 265 MB off a 5.15 GB step's traffic and nothing off its time: the temporal launch takes 868 us with either table, the table-writing
-    // launch 168 us instead of 154; profiles/r06_msv1_inter70_compact_tables_*.  Kept as an option: half the table memory.)
-    bool opt_compact_tables = [] { const char* e = std::getenv("JSP_MSV1_COMPACT_TABLES"); return e && e[0] == '1'; }();
+    // Replays of staged inter-frame batches (Msv1Staged::decode): "msv1_parse_ahead" (default on).
     bool opt_parse_ahead = [] { const char* e = std::getenv("JSP_MSV1_PARSE_AHEAD"); return !(e && e[0] == '0'); }();
     // Several frames per launch (option "msv1_async_pairs", default on): a one-launch frame is HELD until enough frames are submitted behind it
     // — half of what may be in flight ("async_depth"), at most 1 + MSV1_MAX_RIDERS — and they go out together (Msv1AsyncStaged::decode_with);
@@ -578,11 +775,6 @@ struct Msv1Codec : jsp_codec {
             opt_async_pairs = std::strcmp(value, "on") == 0;
             return 0;
         }
-        if (std::strcmp(key, "msv1_compact_tables") == 0) { // replays of an inter-frame batch write and read 2-byte block tables (on) or the 4-byte ones staging builds (off)
-            if (std::strcmp(value, "on") != 0 && std::strcmp(value, "off") != 0) return JSP_ERROR_OCCURED;
-            opt_compact_tables = std::strcmp(value, "on") == 0;
-            return 0;
-        }
         if (std::strcmp(key, "msv1_parse_ahead") == 0) {    // replays of an inter-frame batch: the next replay's table-writing parse beside this replay's launches (on), or in front of them (off)
             if (std::strcmp(value, "on") != 0 && std::strcmp(value, "off") != 0) return JSP_ERROR_OCCURED;
             opt_parse_ahead = std::strcmp(value, "on") == 0;
@@ -655,6 +847,51 @@ struct Msv1Codec : jsp_codec {
     bool async_settle_first(const jsp_frame_in& f) override { return sync_staging(f, prescan(f.src, f.n)); }
     bool sync_through_async() const override { return opt_gpu_parse; }
 
+    // the buffers of an asynchronous frame of `nt` tiles: kept from frame to frame, grown (and zeroed where the kernel counts on it) when a frame needs more
+    void reserve_async_buffers(Msv1AsyncStaged& st, int nt, size_t tile_bytes) {
+        st.d_stream.reserve((size_t)nt * tile_bytes + 64);
+        st.h_info.reserve(sizeof(Msv1AsyncInfo));
+        if ((size_t)nt > st.agg_tiles) {   // published tile tables carry the launch epoch: fresh memory must read as epoch 0
+            st.d_agg.reserve(sizeof(unsigned long long) * 9 * (size_t)nt);
+            st.agg_tiles = st.d_agg.cap / (sizeof(unsigned long long) * 9);
+            JSP_HIP(hipMemsetAsync(st.d_agg.p, 0, st.d_agg.cap, stream));
+        }
+        if (st.merged && !st.d_report.p) {
+            st.d_report.reserve(sizeof(Msv1AsyncInfo));
+            JSP_HIP(hipMemsetAsync(st.d_report.p, 0, sizeof(Msv1AsyncInfo), stream));
+            st.want = 0;
+        }
+        if (!st.merged) {
+            const size_t meta_bytes = sizeof(Msv1TileRec) * (size_t)nt + sizeof(Msv1AsyncInfo);
+            st.d_meta.reserve(meta_bytes);
+            st.h_meta.reserve(meta_bytes);
+        }
+    }
+
+    // An asynchronous frame's bytes: on the device already when the caller had the range prefetched (jsp_prefetch); else from where they are
+    // when the caller keeps them in pinned memory, else through our own.  `up`: where a copy reads them, `up_dev`: where a kernel does.
+    struct FrameBytes { const void* up; const uint8_t* up_dev; UpRange* range; };
+    FrameBytes frame_bytes(const jsp_frame_in& f, Msv1AsyncStaged& st) {
+        hipPointerAttribute_t attr{};
+        UpRange* range = range_of(f.src, f.n);
+        if (range) {
+            if (!range->waited || range->waited_on != stream) {   // the first frame out of the range: the frames' stream waits for the range's copy once
+                JSP_HIP(hipStreamWaitEvent(stream, range->up, 0));
+                range->waited = true;
+                range->waited_on = stream;
+            }
+            range->used = true;
+            ++prefetched_frames;
+            return {f.src, static_cast<const uint8_t*>(range->dev.p) + range->skew + (f.src - range->host), range};
+        }
+        if (hipPointerGetAttributes(&attr, f.src) == hipSuccess && attr.type == hipMemoryTypeHost)
+            return {f.src, static_cast<const uint8_t*>(attr.devicePointer ? attr.devicePointer : f.src), nullptr};
+        (void)hipGetLastError();
+        st.h_stream.reserve(f.n + 16);
+        std::memcpy(st.h_stream.p, f.src, f.n);
+        return {st.h_stream.p, static_cast<const uint8_t*>(st.h_stream.p), nullptr};
+    }
+
     jsp_staged* stage_async(const jsp_frame_in& f, jsp_staged* reuse) override {
         activate();
         static const size_t small_limit = [] { const char* e = std::getenv("JSP_MSV1_SMALL_TILE_BYTES"); return e ? (size_t)std::atoll(e) : MSV1_SMALL_TILE_FRAME_BYTES; }();   // (lab)
@@ -701,85 +938,37 @@ struct Msv1Codec : jsp_codec {
         st->small_tiles = small_tiles;
         st->deaf = st->merged && opt_inject_deaf;
         if (st->deaf) opt_inject_deaf = false;
-        const size_t slot = (size_t)nt * tile_bytes;
-        st->d_stream.reserve(slot + 64);
-        st->h_info.reserve(sizeof(Msv1AsyncInfo));
-        if ((size_t)nt > st->agg_tiles) {   // published tile tables carry the launch epoch: fresh memory must read as epoch 0
-            st->d_agg.reserve(sizeof(unsigned long long) * 9 * (size_t)nt);
-            st->agg_tiles = st->d_agg.cap / (sizeof(unsigned long long) * 9);
-            JSP_HIP(hipMemsetAsync(st->d_agg.p, 0, st->d_agg.cap, stream));
-        }
-        if (st->merged && !st->d_report.p) {
-            st->d_report.reserve(sizeof(Msv1AsyncInfo));
-            JSP_HIP(hipMemsetAsync(st->d_report.p, 0, sizeof(Msv1AsyncInfo), stream));
-            st->want = 0;
-        }
+        reserve_async_buffers(*st, nt, tile_bytes);
         const size_t meta_bytes = sizeof(Msv1TileRec) * (size_t)nt + sizeof(Msv1AsyncInfo);
-        if (!st->merged) {
-            st->d_meta.reserve(meta_bytes);
-            st->h_meta.reserve(meta_bytes);
-        }
         auto* info_dev = st->d_info();
-        auto fill = [&](Msv1TileRec& r, int k) {
-            r.byte0 = (uint32_t)(k * tile_bytes);
-            r.frame_end = (uint32_t)n_even;
-            r.data_end = geo.bits == 16 ? (uint32_t)n_even : (uint32_t)f.n;
-            r.k = (uint32_t)k;
-            r.first_tile = 0;
-            r.ntiles = (uint32_t)nt;
-            r.cmp_row_lo = st->key_compare ? (uint32_t)key_compare_row : st->compare ? (uint32_t)std::max(insign_lines, 0) : 0xFFFFFFFFu;
-            r.flags = 0;
-            r.dst = f.dst;
-            r.prev = prev_dev;
-            r.signif = &info_dev->signif;
-            r.pad = 0;
+        const uint32_t cmp_row_lo = st->key_compare ? (uint32_t)key_compare_row : st->compare ? (uint32_t)std::max(insign_lines, 0) : 0xFFFFFFFFu;
+        auto rec = [&](int k) {
+            return tile_rec(0, (uint32_t)n_even, geo.bits == 16 ? (uint32_t)n_even : (uint32_t)f.n, (uint32_t)k, (uint32_t)tile_bytes, 0, (uint32_t)nt, f.dst, prev_dev,
+                            &info_dev->signif, cmp_row_lo, 0);
         };
-        // the frame's bytes: on the device already when the caller had the range prefetched (jsp_prefetch); else from where they are
-        // when the caller keeps them in pinned memory, else through our own
-        const void* up = f.src;
-        const uint8_t* up_dev = nullptr;
-        hipPointerAttribute_t attr{};
-        UpRange* range = range_of(f.src, f.n);
-        if (range) {
-            up_dev = static_cast<const uint8_t*>(range->dev.p) + range->skew + (f.src - range->host);
-            if (!range->waited || range->waited_on != stream) {   // the first frame out of the range: the frames' stream waits for the range's copy once
-                JSP_HIP(hipStreamWaitEvent(stream, range->up, 0));
-                range->waited = true;
-                range->waited_on = stream;
-            }
-            range->used = true;
-            ++prefetched_frames;
-        } else if (hipPointerGetAttributes(&attr, f.src) == hipSuccess && attr.type == hipMemoryTypeHost) {
-            up_dev = static_cast<const uint8_t*>(attr.devicePointer ? attr.devicePointer : f.src);
-        } else {
-            (void)hipGetLastError();
-            st->h_stream.reserve(f.n + 16);
-            std::memcpy(st->h_stream.p, f.src, f.n);
-            up = st->h_stream.p;
-            up_dev = static_cast<const uint8_t*>(st->h_stream.p);
-        }
+        const FrameBytes fb = frame_bytes(f, *st);
         if (st->merged) {
-            fill(st->rec, 0);
-            st->src_dev = up_dev;
+            st->rec = rec(0);
+            st->src_dev = fb.up_dev;
             if (!counted_async) { counted_async = true; g_async_streams.fetch_add(1); }
             // a few streams: the copy engine works next to the kernels; many: its queues become the bottleneck (16 streams on one
             // GPU: 57 against 68 Gpixels/s), the kernels then fetch the bytes themselves
             st->dma = opt_async_auto ? g_async_streams.load() <= kDmaStreams : opt_async_dma;
-            if (range) st->dma = false;      // (the kernel reads the device copy of the range and leaves the frame's own copy in d_stream, as when it reads pinned memory)
+            if (fb.range) st->dma = false;      // (the kernel reads the device copy of the range and leaves the frame's own copy in d_stream, as when it reads pinned memory)
             if (st->dma) {   // the copy engine brings the bytes up on a stream of its own, next to the previous frame's kernel
                 hipStream_t& up_stream = up_streams[up_next++ % (unsigned)up_count];
                 if (!up_stream) JSP_HIP(hipStreamCreateWithFlags(&up_stream, hipStreamNonBlocking));
                 if (!st->uploaded) JSP_HIP(hipEventCreateWithFlags(&st->uploaded, hipEventDisableTiming));
-                JSP_HIP(hipMemcpyAsync(st->d_stream.p, up, f.n, hipMemcpyHostToDevice, up_stream));
+                JSP_HIP(hipMemcpyAsync(st->d_stream.p, fb.up, f.n, hipMemcpyHostToDevice, up_stream));
                 JSP_HIP(hipEventRecord(st->uploaded, up_stream));
                 st->src_dev = static_cast<const uint8_t*>(st->d_stream.p);
             }
         } else {
             auto* recs = static_cast<Msv1TileRec*>(st->h_meta.p);
-            for (int k = 0; k < nt; ++k) fill(recs[k], k);
+            for (int k = 0; k < nt; ++k) recs[k] = rec(k);
             std::memset(recs + nt, 0, sizeof(Msv1AsyncInfo));
-            if (range) JSP_HIP(hipMemcpyAsync(st->d_stream.p, up_dev, f.n, hipMemcpyDeviceToDevice, stream));   // (larger frames: from the range's copy to the frame's own)
-            else JSP_HIP(hipMemcpyAsync(st->d_stream.p, up, f.n, hipMemcpyHostToDevice, stream));
+            if (fb.range) JSP_HIP(hipMemcpyAsync(st->d_stream.p, fb.up_dev, f.n, hipMemcpyDeviceToDevice, stream));   // (larger frames: from the range's copy to the frame's own)
+            else JSP_HIP(hipMemcpyAsync(st->d_stream.p, fb.up, f.n, hipMemcpyHostToDevice, stream));
             JSP_HIP(hipMemcpyAsync(st->d_meta.p, recs, meta_bytes, hipMemcpyHostToDevice, stream));
         }
         // codec state, as the synchronous path leaves it
@@ -805,522 +994,316 @@ struct Msv1Codec : jsp_codec {
         if (in.fault) return false;                              // a tile gave up waiting (timing, not the stream): the host path settles the frame
         if ((in.flags & (MSV1_ASYNC_SHORT | MSV1_ASYNC_END | MSV1_ASYNC_STUCK)) || ((in.flags & MSV1_ASYNC_SKIPCODE) && !st->have_prev))
             return false;                                        // the host parser has to settle this stream
-        // significance, MSVideo1.hx:187-204 / 372-388 (key frames report none)
-        const bool s1 = st->adopted[0] && (in.flags & MSV1_ASYNC_S1);
-        int sg = 0;
-        if (s1 && !st->key) {
-            if (!st->have_prev) sg = 1;
-            else if (st->compare) sg = in.signif ? 1 : 0;
-            // 8-bit: NaN loop bound -> no pixel is compared -> false
-        }
-        st->significant[0] = sg;
+        const int sg = msv1_significance(st->adopted[0] && (in.flags & MSV1_ASYNC_S1), st->have_prev, st->key, st->compare);
+        st->significant[0] = sg < 0 ? (in.signif ? 1 : 0) : sg;   // (stage 2 ran with the frame: its word is in the report)
         if (st->key_compare) st->key_differs[0] = in.signif ? 1 : 0;
         return true;
     }
 
+    // The synchronous staging of a batch, phase by phase; what the phases hand on to each other is in StagePlan.
     jsp_staged* stage(const std::vector<jsp_frame_in>& frames, jsp_staged* reuse) override {
         activate();
         const double t0 = now_ms();
         auto* st = dynamic_cast<Msv1Staged*>(reuse);
         if (!st) st = new Msv1Staged();
         std::unique_ptr<Msv1Staged> guard(reuse ? nullptr : st);
-        const int nf = (int)frames.size();
-        const size_t nblk = (size_t)std::max(geo.nblocks, 1);
-        st->quiesce_side();                            // (a reused batch: nothing of its last replay still runs beside the stream)
-        st->drop_sets();
-        st->side = nullptr;
+        StagePlan plan;
+        reset_batch(*st, (int)frames.size());
+        lay_out_and_gather(frames, *st, plan);
+        if (st->gpu_parse && !frames.empty()) parse_on_gpu(frames, *st, plan);
+        decide_frames(frames, *st, plan);
+        st->plan_launches(frames, plan);
+        st->account(plan);
+        st->build_tile_records(frames, plan, opt_scrub_tables, stream);
+        st->info.host_stage_ms = now_ms() - t0 - plan.gpu_parse_ms;
+        final_uploads(*st, plan);
+        st->info.h2d_ms = plan.h2d_ms;
+        st->info.device_parse_ms = plan.gpu_parse_ms;
+        guard.release();
+        return st;
+    }
+
+    void upload(void* d, const void* h, size_t bytes) {   // queued on the codec's stream and waited for once, where the host needs them
+        if (bytes) JSP_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, stream));
+    }
+
+    // ---- phase 1: the batch object as a fresh one would be, its side stream, the palette ----
+    void reset_batch(Msv1Staged& st, int nf) {
+        st.quiesce_side();                             // (a reused batch: nothing of its last replay still runs beside the stream)
+        st.drop_sets();
+        st.side = nullptr;
         if (opt_parse_ahead) {
             if (!side_stream) JSP_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
-            st->side = side_stream;
+            st.side = side_stream;
         }
-        st->geo = geo;
-        st->nframes = nf;
-        st->decoded = false;
-        st->groups.clear();
-        st->status.assign(nf, JSP_ZERO_STATE);
-        st->adopted.assign(nf, 0);
-        st->significant.assign(nf, 0);
-        st->info = jsp_staged_info{};
-        st->why.clear();
-        st->insignificant_blocks = insignificant_blocks;
-        st->inject_fault = opt_inject_fault;
-        st->fallback_total = lookback_fallbacks;
+        st.geo = geo;
+        st.nframes = nf;
+        st.decoded = false;
+        st.groups.clear();
+        st.status.assign(nf, JSP_ZERO_STATE);
+        st.adopted.assign(nf, 0);
+        st.significant.assign(nf, 0);
+        st.info = jsp_staged_info{};
+        st.why.clear();
+        st.insignificant_blocks = insignificant_blocks;
+        st.inject_fault = opt_inject_fault;
+        st.fallback_total = lookback_fallbacks;
         // the on-GPU parse packs block counts in 20 bits
-        st->gpu_parse = opt_gpu_parse && geo.nblocks > 0 && geo.nblocks < (1 << 20);
+        st.gpu_parse = opt_gpu_parse && geo.nblocks > 0 && geo.nblocks < (1 << 20);
         if (geo.bits == 8 && !d_palette.p) {  // Preinit not called: all-zero palette
             d_palette.reserve(sizeof palette);
             JSP_HIP(hipMemcpy(d_palette.p, palette, sizeof palette, hipMemcpyHostToDevice));
         }
-        st->d_palette = static_cast<const int32_t*>(d_palette.p);
+        st.d_palette = static_cast<const int32_t*>(d_palette.p);
+    }
 
-        // ---- lay the frames out in one stream buffer (16-byte aligned starts) ----------------
-        // With the on-GPU parse every frame starts on a tile boundary of the stream buffer, so tile t of the batch is the
-        // bytes [t * tile, (t + 1) * tile): a workgroup of the fused kernel knows where its bytes are from its index alone.
-        std::vector<size_t> beg(nf);
-        size_t total_stream = 0;
-        const size_t frame_align = st->gpu_parse ? (size_t)msv1_parse_tile_bytes() : 16;
+    // ---- phase 2: lay the frames out in one stream buffer (16-byte aligned starts) and gather those that are not in pinned memory ----
+    // With the on-GPU parse every frame starts on a tile boundary of the stream buffer, so tile t of the batch is the
+    // bytes [t * tile, (t + 1) * tile): a workgroup of the fused kernel knows where its bytes are from its index alone.
+    void lay_out_and_gather(const std::vector<jsp_frame_in>& frames, Msv1Staged& st, StagePlan& plan) {
+        const int nf = (int)frames.size();
+        const size_t nblk = (size_t)std::max(geo.nblocks, 1);
+        plan.beg.resize(nf);
+        const size_t frame_align = st.gpu_parse ? (size_t)msv1_parse_tile_bytes() : 16;
         static const size_t lab_gap = [] { const char* e = std::getenv("JSP_MSV1_FRAME_GAP"); return e ? (size_t)std::atoll(e) & ~size_t(15) : size_t(0); }();   // lab: bytes left free after every frame's slot
         for (int i = 0; i < nf; ++i) {
-            beg[i] = total_stream;
-            total_stream += (frames[i].n + frame_align - 1) / frame_align * frame_align + (st->gpu_parse ? lab_gap : 0);
+            plan.beg[i] = plan.total_stream;
+            plan.total_stream += (frames[i].n + frame_align - 1) / frame_align * frame_align + (st.gpu_parse ? lab_gap : 0);
         }
-        if (total_stream + 64 > 0xFFFFFFF0u) throw std::runtime_error("batch stream exceeds 4 GiB");
+        if (plan.total_stream + 64 > 0xFFFFFFF0u) throw std::runtime_error("batch stream exceeds 4 GiB");
         // Where the frames' bytes are: a frame in pinned host memory (jsp_host_alloc, or memory the caller registered) is uploaded
         // from where it is; the others are first gathered in the batch's own pinned buffer.
-        std::vector<uint8_t> in_pinned(nf, 0);
+        plan.in_pinned.assign(nf, 0);
         size_t gather_bytes = 0;
         for (int i = 0; i < nf; ++i) {
-            if (st->gpu_parse && frames[i].n >= 4096) {
+            if (st.gpu_parse && frames[i].n >= 4096) {
                 hipPointerAttribute_t attr{};
-                if (hipPointerGetAttributes(&attr, frames[i].src) == hipSuccess && attr.type == hipMemoryTypeHost) in_pinned[i] = 1;
+                if (hipPointerGetAttributes(&attr, frames[i].src) == hipSuccess && attr.type == hipMemoryTypeHost) plan.in_pinned[i] = 1;
                 else (void)hipGetLastError();      // plain malloc'd memory: not known to HIP
             }
-            if (!in_pinned[i]) gather_bytes += frames[i].n;
+            if (!plan.in_pinned[i]) gather_bytes += frames[i].n;
         }
-        if (gather_bytes || !st->gpu_parse) st->h_stream.reserve(total_stream + 64);
+        if (gather_bytes || !st.gpu_parse) st.h_stream.reserve(plan.total_stream + 64);
         // (host-built block tables: every frame's with the host parser, else only those of the frames the GPU cannot settle —
         // allocated when the first such frame turns up: a quarter of a gigabyte of pinned memory for 512 frames)
-        if (!st->gpu_parse) st->h_desc.reserve(sizeof(uint32_t) * nblk * std::max(nf, 1));
-        st->h_frames.reserve(sizeof(Msv1FrameArgs) * std::max(nf, 1));
-        st->d_signif.reserve(sizeof(uint32_t) * std::max(nf, 1));
-        st->h_signif.reserve(sizeof(uint32_t) * std::max(nf, 1));
-        st->d_stream.reserve(total_stream + 64);
-        st->d_desc.reserve(sizeof(uint32_t) * nblk * std::max(nf, 1));
-        st->d_frames.reserve(sizeof(Msv1FrameArgs) * std::max(nf, 1));
-        auto* h_stream = static_cast<uint8_t*>(st->h_stream.p);
-        auto* h_frames = static_cast<Msv1FrameArgs*>(st->h_frames.p);
-        auto* d_signif = static_cast<uint32_t*>(st->d_signif.p);
-        {
-            // gathered on several threads when there is much to gather: one thread copies ~6 GB/s, a batch of 512 1080p frames
-            // is half a gigabyte
-            auto gather = [&](int lo, int hi) {
-                for (int i = lo; i < hi; ++i) {
-                    if (in_pinned[i]) continue;
-                    if (frames[i].n) std::memcpy(h_stream + beg[i], frames[i].src, frames[i].n);
-                    const size_t padded = (frames[i].n + 15) & ~size_t(15);   // (the rest of the frame's slot is never read)
-                    std::memset(h_stream + beg[i] + frames[i].n, 0, padded - frames[i].n);
-                }
-            };
-            const int nthreads = gather_bytes > (32u << 20) ? (int)std::min<size_t>(8, (size_t)std::max(1, usable_cpus() / 2)) : 1;
-            if (nthreads > 1) {
-                std::vector<std::thread> pool;
-                std::exception_ptr failed;
-                try {
-                    for (int t = 1; t < nthreads; ++t) pool.emplace_back(gather, (int)((long)nf * t / nthreads), (int)((long)nf * (t + 1) / nthreads));
-                    gather(0, nf / nthreads);
-                } catch (...) {
-                    failed = std::current_exception();
-                }
-                for (auto& th : pool) th.join();
-                if (failed) std::rethrow_exception(failed);
-            } else {
-                gather(0, nf);
+        if (!st.gpu_parse) st.h_desc.reserve(sizeof(uint32_t) * nblk * std::max(nf, 1));
+        st.h_frames.reserve(sizeof(Msv1FrameArgs) * std::max(nf, 1));
+        st.d_signif.reserve(sizeof(uint32_t) * std::max(nf, 1));
+        st.h_signif.reserve(sizeof(uint32_t) * std::max(nf, 1));
+        st.d_stream.reserve(plan.total_stream + 64);
+        st.d_desc.reserve(sizeof(uint32_t) * nblk * std::max(nf, 1));
+        st.d_frames.reserve(sizeof(Msv1FrameArgs) * std::max(nf, 1));
+        // gathered on several threads when there is much to gather: one thread copies ~6 GB/s, a batch of 512 1080p frames
+        // is half a gigabyte
+        auto* h_stream = static_cast<uint8_t*>(st.h_stream.p);
+        auto gather = [&](int lo, int hi) {
+            for (int i = lo; i < hi; ++i) {
+                if (plan.in_pinned[i]) continue;
+                if (frames[i].n) std::memcpy(h_stream + plan.beg[i], frames[i].src, frames[i].n);
+                const size_t padded = (frames[i].n + 15) & ~size_t(15);   // (the rest of the frame's slot is never read)
+                std::memset(h_stream + plan.beg[i] + frames[i].n, 0, padded - frames[i].n);
+            }
+        };
+        const int nthreads = gather_bytes > (32u << 20) ? (int)std::min<size_t>(8, (size_t)std::max(1, usable_cpus() / 2)) : 1;
+        if (nthreads > 1) {
+            std::vector<std::thread> pool;
+            std::exception_ptr failed;
+            try {
+                for (int t = 1; t < nthreads; ++t) pool.emplace_back(gather, (int)((long)nf * t / nthreads), (int)((long)nf * (t + 1) / nthreads));
+                gather(0, nf / nthreads);
+            } catch (...) {
+                failed = std::current_exception();
+            }
+            for (auto& th : pool) th.join();
+            if (failed) std::rethrow_exception(failed);
+        } else {
+            gather(0, nf);
+        }
+    }
+
+    // the batch's stream buffer in HBM: runs of gathered frames go up in one copy each, pinned frames one by one
+    void upload_stream(const std::vector<jsp_frame_in>& frames, Msv1Staged& st, const StagePlan& plan) {
+        const int nf = (int)frames.size();
+        const auto* h_stream = static_cast<const uint8_t*>(st.h_stream.p);
+        auto* d_stream = static_cast<uint8_t*>(st.d_stream.p);
+        int i = 0;
+        while (i < nf) {
+            if (plan.in_pinned[i]) {
+                upload(d_stream + plan.beg[i], frames[i].src, frames[i].n);
+                ++i;
+                continue;
+            }
+            int j = i;
+            while (j < nf && !plan.in_pinned[j]) ++j;
+            const size_t lo = plan.beg[i], hi = j < nf ? plan.beg[j] : plan.total_stream;
+            if (hi > lo) upload(d_stream + lo, h_stream + lo, hi - lo);
+            i = j;
+        }
+    }
+
+    // ---- phase 3, on-GPU parse: upload the raw bytes, parse, read the per-frame counters back ----
+    void parse_on_gpu(const std::vector<jsp_frame_in>& frames, Msv1Staged& st, StagePlan& plan) {
+        const int nf = (int)frames.size();
+        const size_t nblk = (size_t)std::max(geo.nblocks, 1);
+        const uint32_t tile_bytes = msv1_parse_tile_bytes();
+        st.h_pframes.reserve(sizeof(Msv1ParseFrame) * nf);
+        Msv1ParseFrame* h_pf = plan.h_pf = static_cast<Msv1ParseFrame*>(st.h_pframes.p);
+        int ntiles = 0, max_tiles = 1;
+        for (int i = 0; i < nf; ++i) {
+            // an odd trailing byte is left to the host parser (it only matters when the chain reaches it,
+            // and then the stream counts as too short)
+            const size_t n_even = frames[i].n & ~size_t(1);
+            // the frame's slot in the stream buffer, in tiles (the last one is all padding when an odd trailing
+            // byte is the only thing in it: it parses as "covers nothing")
+            const int t = (int)((frames[i].n + tile_bytes - 1) / tile_bytes);
+            // 16-bit early-outs (MSVideo1.hx:109-110) are settled by the host parser
+            const bool pre_host = geo.bits == 16 && frames[i].n < size_of_just_skips;
+            h_pf[i] = Msv1ParseFrame{(uint32_t)plan.beg[i], (uint32_t)(plan.beg[i] + n_even), (uint32_t)(i * nblk), (uint32_t)ntiles,
+                                     (uint32_t)t, pre_host || t == 0 ? 1u : 0u, 0, 0};
+            ntiles += t;
+            max_tiles = std::max(max_tiles, t);
+        }
+        st.ntiles = ntiles;
+        st.max_tiles = max_tiles;
+        st.h_tile_frame.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
+        auto* h_tf = static_cast<uint32_t*>(st.h_tile_frame.p);
+        for (int i = 0; i < nf; ++i)
+            for (uint32_t k = 0; k < h_pf[i].ntiles; ++k) h_tf[h_pf[i].first_tile + k] = (uint32_t)i;
+        st.d_pframes.reserve(sizeof(Msv1ParseFrame) * nf);
+        st.d_tile_frame.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
+        st.d_tile_tab.reserve(sizeof(uint32_t) * 9 * std::max(ntiles, 1));
+        st.d_tile_entry.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
+        st.d_tile_block0.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
+        st.d_info.reserve(sizeof(Msv1FrameInfo) * nf);
+        st.h_info.reserve(sizeof(Msv1FrameInfo) * nf);
+        const double tu = now_ms();
+        upload_stream(frames, st, plan);
+        upload(st.d_pframes.p, h_pf, sizeof(Msv1ParseFrame) * nf);
+        upload(st.d_tile_frame.p, h_tf, sizeof(uint32_t) * ntiles);
+        st.launch_parse(stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipMemcpyAsync(st.h_info.p, st.d_info.p, sizeof(Msv1FrameInfo) * nf, hipMemcpyDeviceToHost, stream));
+        JSP_HIP(hipStreamSynchronize(stream));   // the one wait of the staging pass: counters are needed now
+        plan.gpu_parse_ms = now_ms() - tu;        // uploads + parse, not separable without more waits
+        plan.h_info = static_cast<const Msv1FrameInfo*>(st.h_info.p);
+    }
+
+    // block_changes is rebuilt on demand from the bytes of the last frame parsed on the GPU: they are kept before the host parser needs them, and
+    // before the caller's memory goes away
+    void keep_last_gpu_frame(const std::vector<jsp_frame_in>& frames, int last_gpu_frame) {
+        if (last_gpu_frame < 0 || !block_changes_stale) return;
+        const jsp_frame_in& g = frames[last_gpu_frame];
+        last_full_frame.assign(g.src, g.src + g.n);
+        last_full_dev = nullptr;
+    }
+
+    // What frame i's parse found: the GPU's counters where they settle the frame (then `last_gpu_frame` = i), else the host parser's, whose block
+    // table goes up in place of the GPU's.
+    Msv1Parse frame_parse(const std::vector<jsp_frame_in>& frames, int i, Msv1Staged& st, StagePlan& plan, int& last_gpu_frame) {
+        const jsp_frame_in& f = frames[i];
+        const size_t nblk = (size_t)std::max(geo.nblocks, 1);
+        Msv1Parse pr;
+        if (st.gpu_parse && !plan.h_pf[i].host_parsed) {
+            const Msv1FrameInfo& fi = plan.h_info[i];
+            const bool needs_host = fi.total_blocks < (uint32_t)geo.nblocks ||      // stream too short
+                                    (fi.flags & MSV1_INFO_END_MARKER) ||             // 8-bit end marker
+                                    (fi.n_skip_codes && !prev_dev);                   // the reference raises
+            if (!needs_host) {
+                pr.changes = fi.n_coded != 0;
+                pr.s1 = pr.changes && (fi.flags & MSV1_INFO_S1);
+                pr.n_coded = fi.n_coded;
+                pr.n_skipped = (uint64_t)geo.nblocks - fi.n_coded;
+                pr.consumed = std::min<uint64_t>(fi.consumed, f.n);
+                last_gpu_frame = i;
+                block_changes_stale = true;
+                return pr;
             }
         }
-        // the batch's stream buffer in HBM: runs of gathered frames go up in one copy each, pinned frames one by one
-        auto upload_stream = [&] {
-            int i = 0;
-            while (i < nf) {
-                if (in_pinned[i]) {
-                    if (frames[i].n) JSP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(st->d_stream.p) + beg[i], frames[i].src, frames[i].n, hipMemcpyHostToDevice, stream));
-                    ++i;
-                    continue;
-                }
-                int j = i;
-                while (j < nf && !in_pinned[j]) ++j;
-                const size_t lo = beg[i], hi = j < nf ? beg[j] : total_stream;
-                if (hi > lo) JSP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(st->d_stream.p) + lo, h_stream + lo, hi - lo, hipMemcpyHostToDevice, stream));
-                i = j;
-            }
-        };
-        uint32_t* h_desc = static_cast<uint32_t*>(st->h_desc.p);
-        auto host_table = [&](int i) -> uint32_t* {              // frame i's block table on the host (host parser)
-            if (!h_desc) {
-                st->h_desc.reserve(sizeof(uint32_t) * nblk * std::max(nf, 1));
-                h_desc = static_cast<uint32_t*>(st->h_desc.p);
-            }
-            return h_desc + (size_t)i * nblk;
-        };
-        // uploads are queued on the codec's stream and waited for once, where the host needs them
-        double h2d_ms = 0;
-        auto upload = [&](void* d, const void* h, size_t bytes) {
-            if (bytes) JSP_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, stream));
-        };
-        auto wait_uploads = [&](double since) {
-            JSP_HIP(hipStreamSynchronize(stream));
-            h2d_ms += now_ms() - since;
-        };
-
-        // ---- on-GPU parse: upload the raw bytes, parse, read the per-frame counters back --------
-        Msv1ParseFrame* h_pf = nullptr;
-        const Msv1FrameInfo* h_info = nullptr;
-        double gpu_parse_ms = 0;
-        if (st->gpu_parse && nf) {
-            const uint32_t tile_bytes = msv1_parse_tile_bytes();
-            st->h_pframes.reserve(sizeof(Msv1ParseFrame) * nf);
-            h_pf = static_cast<Msv1ParseFrame*>(st->h_pframes.p);
-            int ntiles = 0, max_tiles = 1;
-            for (int i = 0; i < nf; ++i) {
-                // an odd trailing byte is left to the host parser (it only matters when the chain reaches it,
-                // and then the stream counts as too short)
-                const size_t n_even = frames[i].n & ~size_t(1);
-                // the frame's slot in the stream buffer, in tiles (the last one is all padding when an odd trailing
-                // byte is the only thing in it: it parses as "covers nothing")
-                const int t = (int)((frames[i].n + tile_bytes - 1) / tile_bytes);
-                // 16-bit early-outs (MSVideo1.hx:109-110) are settled by the host parser
-                const bool pre_host = geo.bits == 16 && frames[i].n < size_of_just_skips;
-                h_pf[i] = Msv1ParseFrame{(uint32_t)beg[i], (uint32_t)(beg[i] + n_even), (uint32_t)(i * nblk), (uint32_t)ntiles,
-                                         (uint32_t)t, pre_host || t == 0 ? 1u : 0u, 0, 0};
-                ntiles += t;
-                max_tiles = std::max(max_tiles, t);
-            }
-            st->ntiles = ntiles;
-            st->max_tiles = max_tiles;
-            st->h_tile_frame.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
-            auto* h_tf = static_cast<uint32_t*>(st->h_tile_frame.p);
-            for (int i = 0; i < nf; ++i)
-                for (uint32_t k = 0; k < h_pf[i].ntiles; ++k) h_tf[h_pf[i].first_tile + k] = (uint32_t)i;
-            st->d_pframes.reserve(sizeof(Msv1ParseFrame) * nf);
-            st->d_tile_frame.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
-            st->d_tile_tab.reserve(sizeof(uint32_t) * 9 * std::max(ntiles, 1));
-            st->d_tile_entry.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
-            st->d_tile_block0.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
-            st->d_info.reserve(sizeof(Msv1FrameInfo) * nf);
-            st->h_info.reserve(sizeof(Msv1FrameInfo) * nf);
-            const double tu = now_ms();
-            upload_stream();
-            upload(st->d_pframes.p, h_pf, sizeof(Msv1ParseFrame) * nf);
-            upload(st->d_tile_frame.p, h_tf, sizeof(uint32_t) * ntiles);
-            st->launch_parse(stream);
-            JSP_HIP(hipGetLastError());
-            JSP_HIP(hipMemcpyAsync(st->h_info.p, st->d_info.p, sizeof(Msv1FrameInfo) * nf, hipMemcpyDeviceToHost, stream));
-            JSP_HIP(hipStreamSynchronize(stream));   // the one wait of the staging pass: counters are needed now
-            gpu_parse_ms = now_ms() - tu;             // uploads + parse, not separable without more waits
-            h_info = static_cast<const Msv1FrameInfo*>(st->h_info.p);
+        keep_last_gpu_frame(frames, last_gpu_frame);
+        st.h_desc.reserve(sizeof(uint32_t) * nblk * std::max(st.nframes, 1));   // (on-GPU parse: allocated when the first such frame turns up)
+        uint32_t* desc = static_cast<uint32_t*>(st.h_desc.p) + (size_t)i * nblk;
+        host_parse(f.src, f.n, (uint32_t)plan.beg[i], desc, pr);
+        if (pr.early_out) std::fill(desc, desc + geo.nblocks, MSV1_DESC_UNTOUCHED);
+        if (st.gpu_parse) {  // this frame's table comes from the host from now on
+            plan.h_pf[i].host_parsed = 1;
+            plan.pframes_dirty = true;
+            upload(static_cast<uint32_t*>(st.d_desc.p) + (size_t)i * nblk, desc, sizeof(uint32_t) * geo.nblocks);
         }
+        return pr;
+    }
 
-        // ---- per-frame protocol decisions, in stream order ------------------------------------
-        bool vec_ok = (X & 3) == 0;
-        struct Attr { bool dependent, noop, special, edge; };
-        std::vector<Attr> attr(nf, Attr{false, false, false, false});
-        std::vector<uint64_t> frame_stream(nf, 0);   // stream bytes each frame's codes occupy
+    // ---- phase 4: per-frame protocol decisions, in stream order ----
+    void decide_frames(const std::vector<jsp_frame_in>& frames, Msv1Staged& st, StagePlan& plan) {
+        const int nf = (int)frames.size();
+        const size_t nblk = (size_t)std::max(geo.nblocks, 1);
+        auto* h_frames = static_cast<Msv1FrameArgs*>(st.h_frames.p);
+        auto* d_signif = static_cast<uint32_t*>(st.d_signif.p);
+        plan.vec_ok = (X & 3) == 0;
+        plan.attr.assign(nf, StagePlan::Attr{false, false, false, false});
+        plan.frame_stream.assign(nf, 0);
         int last_gpu_frame = -1;
-        bool pframes_dirty = false;
         for (int i = 0; i < nf; ++i) {
             const jsp_frame_in& f = frames[i];
-            uint32_t* desc = nullptr;
-            Msv1Parse pr;
-            bool from_gpu = false;
-            if (st->gpu_parse && !h_pf[i].host_parsed) {
-                const Msv1FrameInfo& fi = h_info[i];
-                const bool needs_host = fi.total_blocks < (uint32_t)geo.nblocks ||      // stream too short
-                                        (fi.flags & MSV1_INFO_END_MARKER) ||             // 8-bit end marker
-                                        (fi.n_skip_codes && !prev_dev);                   // the reference raises
-                if (!needs_host) {
-                    pr.changes = fi.n_coded != 0;
-                    pr.s1 = pr.changes && (fi.flags & MSV1_INFO_S1);
-                    pr.n_coded = fi.n_coded;
-                    pr.n_skipped = (uint64_t)geo.nblocks - fi.n_coded;
-                    pr.consumed = std::min<uint64_t>(fi.consumed, f.n);
-                    from_gpu = true;
-                    last_gpu_frame = i;
-                    block_changes_stale = true;
-                }
-            }
-            if (!from_gpu) {
-                if (st->gpu_parse && last_gpu_frame >= 0 && block_changes_stale) {
-                    const jsp_frame_in& g = frames[last_gpu_frame];
-                    last_full_frame.assign(g.src, g.src + g.n);
-                    last_full_dev = nullptr;
-                }
-                desc = host_table(i);
-                host_parse(f.src, f.n, (uint32_t)beg[i], desc, pr);
-                if (pr.early_out) std::fill(desc, desc + geo.nblocks, MSV1_DESC_UNTOUCHED);
-                if (st->gpu_parse) {  // this frame's table comes from the host from now on
-                    h_pf[i].host_parsed = 1;
-                    pframes_dirty = true;
-                    upload(static_cast<uint32_t*>(st->d_desc.p) + (size_t)i * nblk, desc, sizeof(uint32_t) * geo.nblocks);
-                }
-            }
+            const Msv1Parse pr = frame_parse(frames, i, st, plan, last_gpu_frame);
             Msv1FrameArgs& fa = h_frames[i];
             fa.dst = f.dst;
             fa.prev = prev_dev;
             fa.signif = d_signif + i;
-            fa.stream_end = (uint32_t)(beg[i] + f.n);
+            fa.stream_end = (uint32_t)(plan.beg[i] + f.n);
             fa.desc_base = (uint32_t)((size_t)i * nblk);
             fa.cmp_row_lo = 0xFFFFFFFFu;
             fa.pad = 0;
             if ((reinterpret_cast<uintptr_t>(f.dst) & 15) || (reinterpret_cast<uintptr_t>(prev_dev) & 15))
-                vec_ok = false;
+                plan.vec_ok = false;
             bool dependent = pr.n_skipped != 0;  // reads its predecessor
             if (pr.early_out) {
                 // nothing to paint: every block untouched, the frame rides along as a no-op
             } else if (pr.aborted) {
-                st->status[i] = JSP_ERROR_OCCURED;  // the reference raises out of DecompressP here
-                st->why = "skip code before any frame was decoded: the reference raises here";
+                st.status[i] = JSP_ERROR_OCCURED;  // the reference raises out of DecompressP here
+                st.why = "skip code before any frame was decoded: the reference raises here";
             } else {
-                // significance, MSVideo1.hx:187-204 / 372-388
-                int sg = 0;
-                if (pr.s1) {
-                    if (!prev_dev) sg = 1;
-                    else if (geo.bits == 16 && insign_lines_set && !f.key) {
-                        // stage 2 on the GPU; result lands in the frame's signif word
-                        fa.cmp_row_lo = (uint32_t)std::max(insign_lines, 0);
-                        sg = -1;
-                        dependent = true;
-                    }
-                    // 8-bit: NaN loop bound -> no pixel is compared -> false
+                const int sg = msv1_significance(pr.s1, prev_dev != nullptr, f.key, geo.bits == 16 && insign_lines_set);
+                if (sg < 0) {   // stage 2 on the GPU; result lands in the frame's signif word
+                    fa.cmp_row_lo = (uint32_t)std::max(insign_lines, 0);
+                    dependent = true;
                 }
-                st->significant[i] = f.key ? 0 : sg;
-                if (pr.changes) st->adopted[i] = 1;
+                st.significant[i] = sg;
+                if (pr.changes) st.adopted[i] = 1;
             }
             if (dependent && prev_dev) fa.pad |= MSV1_FRAME_USES_PREV;
-            st->info.units_coded += pr.n_coded;
-            st->info.units_copied += pr.n_skipped;
-            st->info.stream_bytes += pr.consumed;
-            frame_stream[i] = pr.consumed;
+            st.info.units_coded += pr.n_coded;
+            st.info.units_copied += pr.n_skipped;
+            st.info.stream_bytes += pr.consumed;
+            plan.frame_stream[i] = pr.consumed;
 
-            attr[i].dependent = dependent;
-            attr[i].noop = pr.early_out;
-            attr[i].special = pr.aborted || (pr.n_untouched > 0 && !pr.early_out);
-            attr[i].edge = fa.cmp_row_lo != 0xFFFFFFFFu && ((X & 3) || (Y & 3));
+            plan.attr[i].dependent = dependent;
+            plan.attr[i].noop = pr.early_out;
+            plan.attr[i].special = pr.aborted || (pr.n_untouched > 0 && !pr.early_out);
+            plan.attr[i].edge = fa.cmp_row_lo != 0xFFFFFFFFu && ((X & 3) || (Y & 3));
             if (pr.early_out) fa.pad |= MSV1_FRAME_NOOP;
-            if (st->adopted[i]) prev_dev = f.dst;
+            if (st.adopted[i]) prev_dev = f.dst;
         }
-        if (st->gpu_parse && last_gpu_frame >= 0 && block_changes_stale) {
-            const jsp_frame_in& g = frames[last_gpu_frame];
-            last_full_frame.assign(g.src, g.src + g.n);
-                    last_full_dev = nullptr;
-        }
-        st->vec_ok = vec_ok;
-        // ---- launch plan ---------------------------------------------------------------------
-        // "special" frames (abort, partially written) run alone with the per-frame kernel.  Between
-        // them: a run of frames none of which reads its predecessor is one launch with grid.y = frame;
-        // a run containing inter frames is one launch of the temporal kernel (tile per workgroup,
-        // frames walked in registers) when the buffers allow 16-byte rows, else one launch per frame.
-        {
-            int i = 0;
-            while (i < nf) {
-                if (attr[i].special) { st->groups.push_back({i, 1, attr[i].edge, false, false}); ++i; continue; }
-                int j = i;
-                bool any_dep = false;
-                while (j < nf && !attr[j].special) { any_dep |= attr[j].dependent; ++j; }
-                std::unordered_set<const void*> seen;
-                if (any_dep && vec_ok) {
-                    // every access to a tile, in whichever buffer, comes from the same workgroup in
-                    // program order, so buffers may even repeat inside the group
-                    bool edge = false;
-                    for (int k = i; k < j; ++k) edge |= attr[k].edge;
-                    st->groups.push_back({i, j - i, edge, true, false});
-                } else {
-                    // frames that do not read their predecessor: one launch per run of them with grid.y = frame —
-                    // or, straight from the stream bytes, one fused launch per run of GPU-parsed frames
-                    bool closed = true;
-                    for (int k = i; k < j; ++k) {
-                        const bool writes = !attr[k].noop;
-                        const bool fusable = st->gpu_parse && vec_ok && !attr[k].dependent && !attr[k].noop && !h_pf[k].host_parsed;
-                        if (attr[k].dependent || closed || (writes && seen.count(frames[k].dst)) || st->groups.back().fused != fusable) {
-                            st->groups.push_back({k, 1, attr[k].edge, false, fusable});
-                            seen.clear();
-                            closed = attr[k].dependent;
-                        } else {
-                            st->groups.back().count++;
-                        }
-                        if (writes) seen.insert(frames[k].dst);
-                    }
-                }
-                i = j;
-            }
-        }
-        st->need_signif = false;
-        for (int v : st->significant) st->need_signif |= v < 0;
-        st->info.frames = nf;
-        st->info.pixels = (uint64_t)X * Y * nf;
-        st->info.descriptor_bytes = sizeof(uint32_t) * (uint64_t)geo.nblocks * nf + sizeof(Msv1FrameArgs) * nf;
-        // SURVEY.md 8(d): A = S + 64*N_coded + 128*N_skipped
-        st->info.algorithmic_bytes = st->info.stream_bytes + 64 * st->info.units_coded + 128 * st->info.units_copied;
-        // What the plan launches and moves.  Fused launches read their frames' stream bytes once and write every block
-        // once.  Descriptor launches read stream + table, write the blocks, and read a previous frame per skipped /
-        // compared block (per-frame kernel) or once per tile (temporal launch); when the table of any of them comes from
-        // the parse kernels, every replay also runs tiles + chain + emit over the whole batch (two more reads of the
-        // stream, one write of the table).
-        {
-            st->needs_desc = false;
-            st->any_fused = false;
-            st->kernels.clear();
-            // replays write and read the compact block table (2 bytes per block + a base per 256 blocks, msv1.h) when every launch that reads tables is a
-            // temporal launch of the loader-wave kernel: the per-frame block kernel and the frame-at-a-time temporal kernel read 4-byte tables
-            static const bool temporal_old = std::getenv("JSP_MSV1_TEMPORAL_OLD") != nullptr;
-            bool compact = st->gpu_parse && opt_compact_tables && !temporal_old;
-            for (const auto& g : st->groups) compact = compact && (g.fused || g.temporal);
-            st->compact_ok = compact;
-            const uint64_t table_bytes_per_frame = compact ? sizeof(uint16_t) * (uint64_t)geo.nblocks + sizeof(uint32_t) * (uint64_t)msv1_tab16_groups(geo.nblocks)
-                                                           : sizeof(uint32_t) * (uint64_t)geo.nblocks;
-            uint64_t moved = 0;
-            for (const auto& g : st->groups) {
-                uint64_t written = 0, prev_reads = 0, sbytes = 0;
-                bool uses_prev = false, gpu_table = false;
-                for (int k = g.first; k < g.first + g.count; ++k) {
-                    if (!attr[k].noop) written += (uint64_t)geo.nblocks;
-                    uses_prev |= (h_frames[k].pad & MSV1_FRAME_USES_PREV) != 0;
-                    if (h_frames[k].pad & MSV1_FRAME_USES_PREV) prev_reads += (uint64_t)geo.nblocks;
-                    sbytes += frame_stream[k];
-                    gpu_table |= st->gpu_parse && !h_pf[k].host_parsed;
-                }
-                moved += sbytes + 64 * written;
-                if (g.fused) {
-                    st->any_fused = true;
-                    st->note_kernel("msv1_fused_kernel");
-                } else {
-                    st->needs_desc |= gpu_table;
-                    moved += table_bytes_per_frame * g.count +
-                             64 * (g.temporal ? (uses_prev ? (uint64_t)geo.nblocks : 0) : prev_reads);
-                    st->note_kernel(g.temporal ? "msv1_blocks_temporal_kernel" : "msv1_blocks_kernel");
-                }
-                if (g.edge_compare) st->note_kernel("msv1_edge_compare_kernel");
-            }
-            if (st->needs_desc) {   // (a replay: msv1_fused_kernel in its descriptor form reads the stream once and writes the tables)
-                moved += st->info.stream_bytes + table_bytes_per_frame * nf;
-                if (!st->any_fused) st->kernels = "msv1_fused_kernel" + (st->kernels.empty() ? std::string() : " + " + st->kernels);
-            }
-            st->info.moved_bytes = moved;
-            st->info.kernel_launches = st->groups.size() + (st->needs_desc ? 1 : 0);
-            if (st->any_fused || st->needs_desc) {
-                st->d_agg.reserve(sizeof(unsigned long long) * (9 + 8) * (size_t)std::max(st->ntiles, 1));   // (+ 8 per tile: the lab build's phase clocks)
-                st->d_sync.reserve(2 * sizeof(uint32_t) + 64);   // (+ room for the lab build's phase clocks)
-                st->h_fault.reserve(sizeof(uint32_t));
-                *static_cast<uint32_t*>(st->h_fault.p) = 0;
-                st->epoch = 0;
-                // one record per tile: what msv1_fused_kernel needs to know about it
-                st->h_recs.reserve(sizeof(Msv1TileRec) * (size_t)std::max(st->ntiles, 1));
-                st->d_recs.reserve(sizeof(Msv1TileRec) * (size_t)std::max(st->ntiles, 1));
-                auto* recs = static_cast<Msv1TileRec*>(st->h_recs.p);
-                const uint32_t tile_bytes = msv1_parse_tile_bytes();
-                for (int i = 0; i < nf; ++i)
-                    for (uint32_t k = 0; k < h_pf[i].ntiles; ++k) {
-                        Msv1TileRec& r = recs[h_pf[i].first_tile + k];
-                        r.byte0 = h_pf[i].beg + k * tile_bytes;   // == (first_tile + k) * tile_bytes: frames start on tile boundaries
-                        r.frame_end = h_pf[i].end;
-                        r.data_end = geo.bits == 16 ? h_pf[i].end : h_frames[i].stream_end;
-                        r.k = k;
-                        r.first_tile = h_pf[i].first_tile;
-                        r.ntiles = h_pf[i].ntiles;
-                        r.cmp_row_lo = h_frames[i].cmp_row_lo;
-                        r.flags = h_pf[i].host_parsed ? MSV1_TILE_SKIP : 0u;
-                        r.dst = h_frames[i].dst;
-                        r.prev = h_frames[i].prev;
-                        r.signif = h_frames[i].signif;
-                        r.pad = 0;
-                    }
-                // Launch order: tile-major over the frames of a launch — tile j of every frame before tile j + 1 of any — so that
-                // when a tile starts, its predecessor in the frame is long done and has published where the chain stands (the
-                // kernel's one-word look-back).  A launch covers the contiguous record range of its frames; the records are
-                // permuted inside that range (a record carries its own byte offset and its number in stream order).
-                auto tile_major = [&](Msv1TileRec* rr, int f0, int f1) {   // frames [f0, f1)
-                    if (f1 - f0 < 2) return;
-                    const uint32_t t0 = h_pf[f0].first_tile, t1 = h_pf[f1 - 1].first_tile + h_pf[f1 - 1].ntiles;
-                    std::vector<Msv1TileRec> tmp(rr + t0, rr + t1);
-                    uint32_t maxt = 0, o = t0;
-                    for (int i = f0; i < f1; ++i) maxt = std::max(maxt, h_pf[i].ntiles);
-                    // ... and the frames do not march in step: frame i starts (i mod 64) rounds late, so that at any time the batch's write
-                    // fronts stand at different depths of their frames instead of all at tile j.  What the memory system makes of
-                    // hundreds of fronts depends on where the frames lie in physical memory; staggered, the same frames
-                    // take 2 - 6 % less time whichever way they lie (one process, same buffers: profiles/archive/r03_stagger_one_process.txt).
-                    const uint32_t stagger = [] { const char* e = std::getenv("JSP_MSV1_STAGGER"); return e ? (uint32_t)std::atoi(e) : 64u; }();   // (lab: read at every staging)
-                    for (uint32_t j = 0; j < maxt + stagger; ++j)
-                        for (int i = f0; i < f1; ++i) {
-                            const uint32_t late = stagger ? (uint32_t)(i - f0) % stagger : 0u;
-                            if (j >= late && j - late < h_pf[i].ntiles) rr[o++] = tmp[h_pf[i].first_tile - t0 + (j - late)];
-                        }
-                };
-                static const int major_frames = [] { const char* e = std::getenv("JSP_MSV1_TILE_MAJOR_FRAMES"); return e ? std::atoi(e) : 0; }();   // lab: permute within runs of this many frames
-                for (const auto& g : st->groups)
-                    if (g.fused) {
-                        if (major_frames > 0)
-                            for (int f = g.first; f < g.first + g.count; f += major_frames) tile_major(recs, f, std::min(f + major_frames, g.first + g.count));
-                        else
-                            tile_major(recs, g.first, g.first + g.count);
-                    }
-                JSP_HIP(hipMemcpyAsync(st->d_recs.p, recs, sizeof(Msv1TileRec) * (size_t)st->ntiles, hipMemcpyHostToDevice, stream));
-                if (st->needs_desc) {   // the same records for the descriptor form: `dst` = the frame's block table; frames whose
-                                        // table nobody reads (fused groups) or that came from the host parser are skipped
-                    // The table-writing form has no pixel stores to hide its parse behind: it runs in 8 KiB tiles (msv1_fused_kernel<BITS, 4, 16>: 64 VGPRs and
-                    // 19 KB of LDS, eight workgroups per CU instead of four, half the serial work per tile).  Frames start on 16 KiB boundaries of the
-                    // stream buffer, so a frame's 8 KiB tiles are numbered from twice its first 16 KiB tile... minus the halves that are all padding: the
-                    // tiles are counted per frame, records and published words (d_agg_emit) are this form's own.
-                    const uint32_t tile8 = msv1_small_tile_bytes();
-                    std::vector<uint32_t> first8((size_t)nf), n8((size_t)nf);
-                    uint32_t nt8 = 0;
-                    for (int i = 0; i < nf; ++i) {
-                        first8[i] = nt8;
-                        n8[i] = h_pf[i].ntiles ? (uint32_t)((frames[i].n + tile8 - 1) / tile8) : 0u;
-                        nt8 += n8[i];
-                    }
-                    st->ntiles_emit = (int)nt8;
-                    st->h_recs_emit.reserve(sizeof(Msv1TileRec) * (size_t)std::max<uint32_t>(nt8, 1));
-                    st->d_recs_emit.reserve(sizeof(Msv1TileRec) * (size_t)std::max<uint32_t>(nt8, 1));
-                    st->d_agg_emit.reserve(sizeof(unsigned long long) * (9 + 8) * (size_t)std::max<uint32_t>(nt8, 1));
-                    auto* er = static_cast<Msv1TileRec*>(st->h_recs_emit.p);
-                    std::vector<uint8_t> in_fused(nf, 0);
-                    for (const auto& g : st->groups)
-                        if (g.fused) std::fill(in_fused.begin() + g.first, in_fused.begin() + g.first + g.count, 1);
-                    // launch order: tile-major over the frames, frame i (i mod 64) rounds late — as for the pixel-writing form above
-                    {
-                        uint32_t maxt = 0, o = 0;
-                        for (int i = 0; i < nf; ++i) maxt = std::max(maxt, n8[i]);
-                        const uint32_t stagger = 64u;
-                        for (uint32_t j = 0; j < maxt + stagger; ++j)
-                            for (int i = 0; i < nf; ++i) {
-                                const uint32_t late = nf > 1 ? (uint32_t)i % stagger : 0u;
-                                if (j < late || j - late >= n8[i]) continue;
-                                const uint32_t k = j - late;
-                                Msv1TileRec& r = er[o++];
-                                r = Msv1TileRec{};
-                                r.byte0 = h_pf[i].beg + k * tile8;
-                                r.frame_end = h_pf[i].end;
-                                r.data_end = geo.bits == 16 ? h_pf[i].end : h_frames[i].stream_end;
-                                r.k = k;
-                                r.first_tile = first8[i];
-                                r.ntiles = n8[i];
-                                r.signif = h_frames[i].signif;
-                                r.pad = 0;
-                                r.dst = reinterpret_cast<int32_t*>(static_cast<uint32_t*>(st->d_desc.p) + (size_t)i * nblk);
-                                r.prev = nullptr;
-                                r.cmp_row_lo = 0xFFFFFFFFu;
-                                r.flags = (h_pf[i].host_parsed || in_fused[i]) ? MSV1_TILE_SKIP : 0u;
-                            }
-                    }
-                    JSP_HIP(hipMemcpyAsync(st->d_recs_emit.p, er, sizeof(Msv1TileRec) * (size_t)nt8, hipMemcpyHostToDevice, stream));
-                    JSP_HIP(hipMemsetAsync(st->d_agg_emit.p, 0, sizeof(unsigned long long) * (9 + 8) * (size_t)std::max<uint32_t>(nt8, 1), stream));
-                    st->scrub.clear();
-                    if (opt_scrub_tables)
-                        for (int i = 0; i < nf; ++i)
-                            if (!h_pf[i].host_parsed && !in_fused[i]) st->scrub.push_back((uint32_t)i);
-                }
-                // published tile tables carry the launch epoch (first launch: 1), so stale words must read as epoch 0
-                JSP_HIP(hipMemsetAsync(st->d_agg.p, 0, sizeof(unsigned long long) * (9 + 8) * (size_t)std::max(st->ntiles, 1), stream));
-                JSP_HIP(hipMemsetAsync(st->d_sync.p, 0, 2 * sizeof(uint32_t) + 64, stream));   // the fault word
-            }
-        }
-        st->info.host_stage_ms = now_ms() - t0 - gpu_parse_ms;
+        keep_last_gpu_frame(frames, last_gpu_frame);
+        st.vec_ok = plan.vec_ok;
+    }
 
-        if (nf) {
-            // queued behind whatever is on the stream; jsp_staged_decode queues behind them in turn.
-            // (The pinned staging buffers belong to the staged batch and outlive the copies.)
-            const double tu = now_ms();
-            if (!st->gpu_parse) {
-                upload(st->d_stream.p, h_stream, total_stream);
-                upload(st->d_desc.p, h_desc, sizeof(uint32_t) * nblk * nf);
-            } else if (pframes_dirty) {
-                upload(st->d_pframes.p, h_pf, sizeof(Msv1ParseFrame) * nf);
-            }
-            upload(st->d_frames.p, h_frames, sizeof(Msv1FrameArgs) * nf);
-            if (nf > 1) wait_uploads(tu);   // batches: report the upload time; single frames skip the wait
+    // ---- phase 8: what the launches still need, queued behind whatever is on the stream; jsp_staged_decode queues behind them in turn ----
+    // (The pinned staging buffers belong to the staged batch and outlive the copies.)
+    void final_uploads(Msv1Staged& st, StagePlan& plan) {
+        const int nf = st.nframes;
+        if (!nf) return;
+        const double tu = now_ms();
+        if (!st.gpu_parse) {
+            upload(st.d_stream.p, st.h_stream.p, plan.total_stream);
+            upload(st.d_desc.p, st.h_desc.p, sizeof(uint32_t) * (size_t)std::max(geo.nblocks, 1) * nf);
+        } else if (plan.pframes_dirty) {
+            upload(st.d_pframes.p, plan.h_pf, sizeof(Msv1ParseFrame) * nf);
         }
-        st->info.h2d_ms = h2d_ms;
-        st->info.device_parse_ms = gpu_parse_ms;
-        guard.release();
-        return st;
+        upload(st.d_frames.p, st.h_frames.p, sizeof(Msv1FrameArgs) * nf);
+        if (nf > 1) {   // batches: report the upload time; single frames skip the wait
+            JSP_HIP(hipStreamSynchronize(stream));
+            plan.h2d_ms += now_ms() - tu;
+        }
     }
 };
 

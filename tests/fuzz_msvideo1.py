@@ -80,7 +80,7 @@ def main():
                 A.drive(gpu, OracleMSVideo1(bits, w, h, pal), w, h, frames, keys, depth=depth, pinned=bool(ranges) or bool(rng.random() < 0.5), lines=lines,
                         prefetch=ranges, drop_ranges_at=(n // 2 if ranges and rng.random() < 0.5 else None))
             elif mode == "staged":
-                opts = dict(msv1_parse_ahead=str(rng.choice(["on", "off"])), msv1_compact_tables=str(rng.choice(["on", "off"])), msv1_scrub_tables="1")
+                opts = dict(msv1_parse_ahead=str(rng.choice(["on", "off"])), msv1_scrub_tables="1")
                 tag += " " + " ".join(f"{k}={v}" for k, v in opts.items())
                 drive_staged(T, bits, w, h, frames, keys, pal, lines, int(rng.integers(2, 6)), int(rng.integers(1, 4)), opts)
             else:
@@ -106,7 +106,7 @@ def drive(T, bits, w, h, frames, keys, pal, lines, mode, host_buffers, misalign)
 
 def drive_staged(T, bits, w, h, frames, keys, pal, lines, nbuf, replays, opts):
     """The clip as ONE staged batch into `nbuf` rotating buffers, decoded and replayed `replays` times back to back (round 6: the next replay's
-    parse beside this one, compact block tables, tables poisoned before every parse) — mutated, truncated and random frames included, so that
+    parse beside this one, tables poisoned before every parse) — mutated, truncated and random frames included, so that
     frames the host parser has to settle sit between the GPU-parsed ones.  Statuses, adoption, significance and every buffer against the oracle."""
     from jsplayer_amd import MSVideo1_16bit, MSVideo1_8bit
     from oracle_binding import OracleAbort, OracleMSVideo1
