@@ -17,6 +17,11 @@
 //   jsp_play clip.avi --step-back   MSVideo1: ONE seek index over the clip (jsp_index_build), then the last frame and every frame down
 //                                to 0, one jsp_index_show each (Main.on_prevframe, Manager.hx:191-196); prints "<index> <key|inter>
 //                                <changed> <crc32>" per frame — sorted, the plain run's frames, significance and CRCs
+//   jsp_play clip.avi --filmstrip N[:scale]
+//                                MSVideo1: ONE seek index over the clip, then ONE jsp_index_thumbs call for N frames spread evenly over
+//                                it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
+//                                8) — the seek bar's hover preview / a contact sheet (Main.on_mouse_move, Main.hx:1147-1215); prints
+//                                "<frame> <crc32 of the thumbnail's words>" per thumbnail
 //   jsp_play clip.avi --seek N   MSVideo1: frame N first, through ONE jsp_seek from the nearest key frame (DataLoader.hx:125-132;
 //                                Manager.hx:216-259), then on frame by frame; the lines from N on carry the CRCs of a plain run
 //   jsp_play a.avi,b.avi --pipelined --devices 0,1,... [--streams T] [--quiet ...]
@@ -379,7 +384,7 @@ long play_batched(const Clip& clip, int batch, int repeat, bool quiet, int warmu
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale]\n", argv[0]); return 2; }
     // (throughput runs: several files, separated by commas — stream s plays file s modulo their number, so that the streams of a
     // multi-stream run are independent inputs)
     std::deque<Clip> clips;                                   // (a deque: elements never move)
@@ -401,6 +406,7 @@ int main(int argc, char** argv) {
     long seek_to = -1;                                        // --seek N: frame N first, through jsp_seek
     bool skip_stills = false;                                 // --skip-stills: from frame 0, skip to each significant change (jsp_find_change)
     bool step_back = false;                                   // --step-back: a seek index over the clip, shown from the last frame down to 0
+    int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -417,6 +423,13 @@ int main(int argc, char** argv) {
         else if (o == "--seek" && a + 1 < argc) seek_to = std::atol(argv[++a]);
         else if (o == "--skip-stills") skip_stills = true;
         else if (o == "--step-back") step_back = true;
+        else if (o == "--filmstrip" && a + 1 < argc) {
+            const std::string v = argv[++a];
+            const size_t colon = v.find(':');
+            strip = std::atoi(v.substr(0, colon).c_str());
+            if (colon != std::string::npos) strip_scale = std::atoi(v.substr(colon + 1).c_str());
+            if (strip < 1 || strip > 4096) { std::fprintf(stderr, "--filmstrip: N is 1..4096\n"); return 2; }
+        }
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
             for (size_t at = 0; at <= list.size();) {
@@ -431,6 +444,7 @@ int main(int argc, char** argv) {
     if (seek_to >= 0 && (pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--seek goes with the plain per-frame run\n"); return 2; }
     if (skip_stills && (seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--skip-stills goes alone\n"); return 2; }
     if (step_back && (skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--step-back goes alone\n"); return 2; }
+    if (strip > 0 && (step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--filmstrip goes alone\n"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
         if (!quiet) return play_batched(clip, batch, 1, false) < 0 ? 1 : 0;
@@ -610,6 +624,41 @@ int main(int argc, char** argv) {
             if (data && jsp_download(data, host.data(), npx) == 0) crc = crc32(reinterpret_cast<const uint8_t*>(host.data()), npx * 4);
             std::printf("%zu %s %d %08x\n", t, keys[t] ? "key" : "inter", sig[t], crc);
         }
+        jsp_index_destroy(idx);
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        return rc;
+    }
+    if (strip > 0) {   // the seek bar's preview pictures: one index build, then ONE jsp_index_thumbs for all of them
+        const size_t n = clip.frames.size();
+        std::vector<const uint8_t*> srcs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> keys;
+        for (size_t i = 0; i < n; ++i) {
+            srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+            lens.push_back(clip.frames[i].second);
+            keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        jsp_index* idx = n ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        if (!idx) { std::fprintf(stderr, "jsp_index_build: %s\n", n ? jsp_last_error() : "no frames"); rc = 1; }
+        int tw = 0, th = 0;
+        if (idx && jsp_index_thumb_size(idx, strip_scale, &tw, &th) != JSP_ZERO_STATE) { std::fprintf(stderr, "jsp_index_thumb_size: %s\n", jsp_last_error()); rc = 1; }
+        jsp_pool* sheet = nullptr;   // cols = 1: a plain [N][th][tw] array, one "frame" of tw x N th pixels
+        if (rc == 0 && !(sheet = jsp_pool_create(0, tw, strip * th, 1))) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
+        if (rc == 0) {
+            std::vector<int> picks;
+            for (int k = 0; k < strip; ++k) picks.push_back((int)(((long long)k * (long long)n) / strip));
+            const size_t cell = (size_t)tw * th;
+            std::vector<int32_t> thumbs(cell * (size_t)strip);
+            if (jsp_index_thumbs(dec, idx, strip, picks.data(), strip_scale, 1, jsp_pool_buffer(sheet, 0), thumbs.size()) != JSP_ZERO_STATE ||
+                jsp_download(jsp_pool_buffer(sheet, 0), thumbs.data(), thumbs.size()) != 0) {
+                std::fprintf(stderr, "jsp_index_thumbs: %s\n", jsp_last_error());
+                rc = 1;
+            }
+            for (int k = 0; rc == 0 && k < strip; ++k)
+                std::printf("%d %08x\n", picks[k], crc32(reinterpret_cast<const uint8_t*>(thumbs.data() + cell * (size_t)k), cell * 4));
+        }
+        if (sheet) jsp_pool_destroy(sheet);
         jsp_index_destroy(idx);
         jsp_pool_destroy(pool);
         jsp_codec_destroy(dec);

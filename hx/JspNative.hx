@@ -53,6 +53,9 @@ extern class JspNative {
                                                                   isKey:RawConstPointer<UInt8>, keyRow:Int):RawPointer<JspIndex>;
     @:native("jsp_index_show")         static function indexShow(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, t:Int, dst:RawPointer<cpp.Int32>, adopt:Int,
                                                                  dataPnt:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
+    @:native("jsp_index_thumb_size")   static function indexThumbSize(idx:RawPointer<JspIndex>, scale:Int, width:RawPointer<Int>, height:RawPointer<Int>):Int;
+    @:native("jsp_index_thumbs")       static function indexThumbs(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, n:Int, frames:RawConstPointer<Int>, scale:Int, cols:Int,
+                                                                   out:RawPointer<cpp.Int32>, outPixels:SizeT):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // frame pool in HBM (Manager.hx:114-118) and the two Manager passes that follow the codec

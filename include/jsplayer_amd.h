@@ -379,13 +379,39 @@ int jsp_find_change(jsp_codec* c, int nframes, const uint8_t* const* srcs, const
  * Significance: out[0..nframes-1] = 1 / 0, what jsp_find_change judges for each frame (inter frames: what DecompressP reports;
  *   key frames: frames_differ_significantly from key_row on) — loader.GetFrameChanges (Manager.hx:229) for every frame of the range.
  * Info: frames, and the bytes the index holds in HBM and in host memory (staging memory is released at the end of the build).
- * Destroy: frees device memory only; safe before or after jsp_codec_destroy of its codec. */
+ * Destroy: frees the index's device (and pinned) memory only; safe before or after jsp_codec_destroy of its codec. */
 typedef struct jsp_index jsp_index;
 jsp_index* jsp_index_build(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key, int key_row);
 int jsp_index_show(jsp_codec* c, jsp_index* idx, int t, int32_t* dst, int adopt, int32_t** data_pnt, int* significant_changes);
 int jsp_index_significance(const jsp_index* idx, int* out);
 int jsp_index_info(const jsp_index* idx, int* nframes, uint64_t* device_bytes, uint64_t* host_bytes);
 void jsp_index_destroy(jsp_index* idx);
+
+/* ---- thumbnails of an index: the preview that follows the pointer along the seek bar (Main.on_mouse_move / the seek bar,
+ * Main.hx:1147-1215), a filmstrip or contact sheet of a key interval, the landing candidates of "skip idle" ----------------------
+ * Thumb size: for scale s = 4, 8 or 16, *width = (4 * (W / 4)) / s and *height = (4 * (H / 4)) / s: whole s x s squares of the
+ *   picture's whole 4x4 blocks.  The W % 4 / H % 4 remainder pixels and, for s > 4, a trailing odd block column / row are left out.
+ * Thumbs: EQUIVALENCE  thumbnail k is the picture of frame frames[k], reduced: pixel (x, y), per channel c of the 0x00RRGGBB words,
+ *       = (sum of c over the s x s source pixels at (x s .. x s + s - 1, y s .. y s + s - 1) + s s / 2) >> log2(s s); top byte 0.
+ *       The PICTURE of frame t is what jsp_index_show(t) writes into a destination that held zeros: every block from the last frame
+ *       <= t that coded it, else from the index's copy of the picture before the range, else 0 (so a frame before the first one that
+ *       adopts its destination, where Show writes nothing, shows the picture before the range).  Rows keep the frame's bottom-up
+ *       order (thumbnail row 0 is frame rows 0 .. s - 1): jsp_display_convert with flip_rows applies to a thumbnail, or to a whole
+ *       sheet, as it does to a frame.
+ *   SHEET  `out` is one image of cols * width by ceil(n / cols) * height pixels, pitch cols * width; thumbnail k has its pixel
+ *       (0, 0) at (k / cols) * height * pitch + (k % cols) * width.  cols = 1: a plain [n][height][width] array; cols = n: a
+ *       horizontal strip.  The cells of the last sheet row past n are not written.  frames[] is any list of frames of the index:
+ *       unordered, repeats allowed.
+ *   ONE kernel launch whatever n (msv1_index_thumbs_kernel): per block and thumbnail a bitmap walk, a table entry and one code
+ *       decoded and summed; no full-size picture is written anywhere.  Runs on the codec's stream and returns synchronised.  The
+ *       codec's state, its previous frame and every frame buffer are untouched.  The frame list travels through pinned memory and a
+ *       device array the index owns (grown on demand, counted in jsp_index_info).
+ *   PRECONDITIONS  `out` is a device buffer of at least out_pixels ints; no asynchronous frame in flight.
+ *   ERRORS  A null argument, n outside 1..4096, a frame number outside the index, a scale other than 4 / 8 / 16, a zero-sized
+ *       thumbnail, cols < 1, out_pixels smaller than the sheet, an index built by another codec, ScreenPressor, a violated
+ *       precondition: JSP_ERROR_OCCURED, jsp_last_error(), nothing written. */
+int jsp_index_thumb_size(const jsp_index* idx, int scale, int* width, int* height);
+int jsp_index_thumbs(jsp_codec* c, jsp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels);
 
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 

@@ -105,6 +105,7 @@ class _NativeCodec:
     def __init__(self, width: int, height: int, bpp: int = 0, palette: Optional[bytes] = None,
                  device: int = 0):
         self.X, self.Y = int(width), int(height)
+        self._device = int(device)
         self._lib = N.lib()
         pal = bytes(palette) if palette is not None else None
         self._h = self._lib.jsp_codec_create(self._kind, self.X, self.Y, int(bpp), pal,
@@ -427,11 +428,7 @@ class SeekIndex:
         """Frame t's picture into `dst` (a device buffer, not the codec's previous frame), as Seek(srcs[:t + 1]) would write it
         on the codec as it stood at the build.  adopt: the codec ends as that Seek leaves it (DecompressP(t + 1) follows on);
         else it is not touched."""
-        if not self._h:
-            raise CodecError("index_show: the index is closed")
-        codec = self._codec
-        if not codec._h:
-            raise CodecError("index_show: the codec is closed")
+        codec = self._open("index_show")
         addr = _frame_ptr(dst, codec.X * codec.Y)
         codec._bufs[addr] = dst
         out_ptr, signif = C.c_void_p(), C.c_int(0)
@@ -447,6 +444,42 @@ class SeekIndex:
         else:
             data = self._prev_at_build
         return PFrameResult(data, bool(signif.value))
+
+    def _open(self, who: str) -> _NativeCodec:
+        if not self._h:
+            raise CodecError(f"{who}: the index is closed")
+        if not self._codec._h:
+            raise CodecError(f"{who}: the codec is closed")
+        return self._codec
+
+    def ThumbSize(self, scale: int) -> tuple:
+        """(width, height) of a thumbnail at `scale` (4, 8 or 16): whole scale x scale squares of the picture's whole 4x4 blocks."""
+        self._open("index_thumb_size")
+        tw, th = C.c_int(0), C.c_int(0)
+        if self._lib.jsp_index_thumb_size(self._h, int(scale), C.byref(tw), C.byref(th)) != 0:
+            raise CodecError(N.last_error())
+        return tw.value, th.value
+
+    def Thumbs(self, frames, scale: int = 8, cols: int = 1, out=None):
+        """The pictures of `frames` (any frame numbers of the index: unordered, repeats allowed, 1..4096 of them), each reduced
+        scale x scale pixels to one (box mean, rounded half up), `cols` to a sheet row: ONE launch, the codec is not touched.
+        Returns the sheet, an int32 device tensor of shape (ceil(n / cols) * TH, cols * TW) — `out` (contiguous, at least that
+        many elements; cells of the last row past n keep what they held) or a new zero-filled one.  Rows are bottom-up as in a
+        frame."""
+        codec = self._open("index_thumbs")
+        frames = [int(t) for t in frames]
+        n, scale, cols = len(frames), int(scale), int(cols)
+        tw, th = C.c_int(0), C.c_int(0)
+        self._lib.jsp_index_thumb_size(self._h, scale, C.byref(tw), C.byref(th))   # (refused: 0 x 0, and jsp_index_thumbs says why)
+        rows, width = -(-n // max(cols, 1)) * th.value, max(cols, 1) * tw.value
+        if out is None:
+            import torch
+            out = torch.zeros(max(rows * width, 1), dtype=torch.int32, device=f"cuda:{codec._device}")
+        arr = (C.c_int * max(n, 1))(*frames)
+        rc = self._lib.jsp_index_thumbs(codec._h, self._h, n, arr, scale, cols, C.c_void_p(_frame_ptr(out, 0)), int(np.prod(out.shape)))
+        if rc != 0:
+            raise CodecError(N.last_error())
+        return out.reshape(-1)[:rows * width].reshape(rows, width)
 
     def close(self) -> None:
         if self._h:

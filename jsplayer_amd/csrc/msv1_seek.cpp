@@ -29,13 +29,16 @@ struct jsp_index {
     int first_adopted = 0;                 // the first frame that adopts its destination (nframes: none)
     int32_t* prev_caller = nullptr;        // the codec's previous frame at build time (what a show before first_adopted leaves)
     int32_t* prev_dev = nullptr;
+    PinnedBuffer h_thumb_frames;           // jsp_index_thumbs: the call's frame list on its way to ...
+    DeviceBuffer d_thumb_frames;           // ... the array the kernel reads (both grown on demand)
     uint64_t device_bytes() const {
-        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap;
+        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_thumb_frames.cap;
         for (const auto& c : chunks) n += c->stream.cap + c->desc.cap + c->frames.cap;
         return n;
     }
     uint64_t host_bytes() const {
-        return sizeof(*this) + chunks.size() * sizeof(Chunk) + significance.size() * sizeof(int) + reported.size() + block_changes.size();
+        return sizeof(*this) + chunks.size() * sizeof(Chunk) + significance.size() * sizeof(int) + reported.size() + block_changes.size() +
+               h_thumb_frames.cap;
     }
 };
 
@@ -546,6 +549,65 @@ extern "C" int jsp_index_show(jsp_codec* c, jsp_index* idx, int t, int32_t* dst,
     }
 }
 
+// ---- thumbnails: the preview that follows the pointer along the seek bar (Main.on_mouse_move, Main.hx:1147-1215), a filmstrip of a
+// key interval — n frames of the index, each reduced scale x scale pixels to one, in ONE launch of msv1_index_thumbs_kernel.  The
+// full-size pictures never exist, and the codec is only lent: its stream carries the launch, nothing of its state is read or written.
+namespace {
+// The thumbnail of an index at `scale`: false (error set) for a scale other than 4 / 8 / 16 or a picture too small for one pixel.
+bool thumb_size(const jsp_index* idx, int scale, const char* who, int& tw, int& th) {
+    if (scale != 4 && scale != 8 && scale != 16) return refuse(who, "scale must be 4, 8 or 16");
+    tw = std::max(idx->geo.nbx, 0) * 4 / scale;
+    th = std::max(idx->geo.nby, 0) * 4 / scale;
+    return (tw > 0 && th > 0) || refuse(who, "the picture is too small for a thumbnail at this scale");
+}
+}  // namespace
+
+extern "C" int jsp_index_thumb_size(const jsp_index* idx, int scale, int* width, int* height) {
+    if (!idx || !width || !height) return fail("index_thumb_size: null argument");
+    int tw = 0, th = 0;
+    if (!thumb_size(idx, scale, "index_thumb_size", tw, th)) return JSP_ERROR_OCCURED;
+    *width = tw;
+    *height = th;
+    return JSP_ZERO_STATE;
+}
+
+extern "C" int jsp_index_thumbs(jsp_codec* c, jsp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels) {
+    if (!c || !idx || !frames || !out) return fail("index_thumbs: null argument");
+    if (!is_msv1(c, "index_thumbs")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_thumbs: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("index_thumbs: n is outside 1..4096");
+    for (int k = 0; k < n; ++k)
+        if (frames[k] < 0 || frames[k] >= idx->nframes) return fail("index_thumbs: a frame number is outside the index");
+    int tw = 0, th = 0;
+    if (!thumb_size(idx, scale, "index_thumbs", tw, th)) return JSP_ERROR_OCCURED;
+    if (cols < 1) return fail("index_thumbs: cols must be at least 1");
+    const uint64_t sheet = (uint64_t)cols * (uint64_t)tw * (uint64_t)((n + (int64_t)cols - 1) / cols) * (uint64_t)th;
+    if ((uint64_t)out_pixels < sheet) return fail("index_thumbs: out_pixels is smaller than the sheet");
+    if (!nothing_in_flight(c, "index_thumbs")) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, out) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
+            (void)hipGetLastError();
+            return fail("index_thumbs: out must be a device buffer");
+        }
+        idx->h_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
+        idx->d_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
+        std::copy(frames, frames + n, static_cast<int32_t*>(idx->h_thumb_frames.p));
+        JSP_HIP(hipMemcpyAsync(idx->d_thumb_frames.p, idx->h_thumb_frames.p, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        msv1_launch_index_thumbs(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
+                                 static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p),
+                                 static_cast<const int32_t*>(idx->d_thumb_frames.p), n, scale, cols, out,
+                                 idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, c->stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned list is free for the next call)
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
 extern "C" int jsp_index_significance(const jsp_index* idx, int* out) {
     if (!idx || !out) return fail("index_significance: null argument");
     std::copy(idx->significance.begin(), idx->significance.end(), out);
@@ -562,7 +624,8 @@ extern "C" int jsp_index_info(const jsp_index* idx, int* nframes, uint64_t* devi
 
 extern "C" void jsp_index_destroy(jsp_index* idx) {
     if (!idx) return;
-    // device memory only: no stream, event or staged batch of the codec is touched, so the codec may be gone already
+    // device memory (and the pinned frame list of jsp_index_thumbs) only: no stream, event or staged batch of the codec is touched,
+    // so the codec may be gone already
     (void)hipSetDevice(idx->device);
     delete idx;
 }

@@ -73,5 +73,11 @@ void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, 
 // ONE launch of msv1_index_show_kernel: frame t of the index into dst.
 void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
                             const uint32_t* d_bitmap, int t, int32_t* dst, const int32_t* before, hipStream_t stream);
+// ONE launch of msv1_index_thumbs_kernel: the pictures of index frames d_frames[0..n) (a device array), each reduced scale x scale
+// pixels to one (scale 4, 8 or 16; box mean, rounded half up), into the sheet `out`: thumbnails of (4 nbx / scale) x (4 nby / scale)
+// pixels, `cols` to a sheet row, row pitch cols thumbnail widths.  A block nothing up to its frame coded comes from `before`, else is 0.
+void msv1_launch_index_thumbs(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                              const uint32_t* d_bitmap, const int32_t* d_frames, int n, int scale, int cols, int32_t* out, const int32_t* before,
+                              hipStream_t stream);
 
 }  // namespace jsp

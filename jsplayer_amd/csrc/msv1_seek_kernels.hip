@@ -292,6 +292,25 @@ __global__ __launch_bounds__(WG) void msv1_coded_bitmap_kernel(const uint32_t* _
     }
 }
 
+// The bitmap word of block `blk` that holds the last frame <= t coding it, masked to the frames <= t (its highest set bit is that
+// frame: 32 * w + 31 - clz; w is set), or 0 when nothing up to t coded the block.  Word t / 32 first, then the words below it, SCAN in flight
+// per step.  Shared by the show and the thumbnail kernel.
+__device__ __forceinline__ uint32_t index_last_writer(const uint32_t* __restrict__ bitmap, int nblocks, int blk, int t, int& w) {
+    w = t >> 5;
+    uint32_t m = *(scgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
+    while (m == 0u && w > 0) {
+        uint32_t e[SCAN];
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(scgu32*)(bitmap + (size_t)(w - 1 - k) * (size_t)nblocks + blk) : 0u;
+        int step = SCAN;
+#pragma unroll
+        for (int k = SCAN - 1; k >= 0; --k)
+            if (e[k] != 0u) { m = e[k]; step = k + 1; }
+        w -= step;
+    }
+    return m;
+}
+
 // Show frame t: one work-item per block, as msv1_seek_kernel.  The lane masks bitmap word t / 32 to the frames <= t and walks the words
 // downwards (SCAN in flight per step) to the first non-zero one: its highest set bit is the last frame <= t that coded the block.  That
 // frame's chunk (frame_chunk[], chunks[]) gives its table entry and stream, and the code is decoded as the seek kernel decodes it.  No
@@ -318,18 +337,8 @@ __global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexChun
     const int by = blk / nbx;
     const int bx = blk - by * nbx;
     const size_t di = (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
-    int w = t >> 5;
-    uint32_t m = *(scgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
-    while (m == 0u && w > 0) {
-        uint32_t e[SCAN];
-#pragma unroll
-        for (int k = 0; k < SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(scgu32*)(bitmap + (size_t)(w - 1 - k) * (size_t)nblocks + blk) : 0u;
-        int step = SCAN;
-#pragma unroll
-        for (int k = SCAN - 1; k >= 0; --k)
-            if (e[k] != 0u) { m = e[k]; step = k + 1; }
-        w -= step;
-    }
+    int w;
+    const uint32_t m = index_last_writer(bitmap, nblocks, blk, t, w);
     uint32_t px[16];
     if (m == 0u) {   // nothing up to t coded the block
         if (before != nullptr) {
@@ -344,6 +353,78 @@ __global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexChun
     const uint32_t o = *(scgu32*)(ch.desc + (size_t)lf * pitch + blk);
     decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
     store_block<VEC>(dst + di, X, px);
+}
+
+// Thumbnails (jsp_index_thumbs): the pictures of n frames of the index, each reduced S x S pixels to one (box mean, rounded half up),
+// into one sheet — ONE launch, no full-size picture anywhere.  blockIdx.y is the thumbnail, frames[blockIdx.y] its frame; a lane per
+// 4x4 block and thumbnail finds the block's last writer <= t as the show kernel does (index_last_writer), decodes that one code (or
+// loads the block from `before`; neither: zeros) and sums its 16 pixels, R and B together under 0x00FF00FF, G apart: at S = 16 a field
+// ends at most at 256 * 255 + 128 < 2^16, so the 16-bit fields never carry into each other.
+//   S = 4:  the lane's block is the output pixel; lanes in block raster order, one dword store each (a wave writes 256 contiguous bytes
+//           of a thumbnail row, or the end of one row and the start of the next).
+//   S = 8 / 16: G = S / 4; the G x G blocks of one output pixel are G * G consecutive lanes (lane & (G - 1) the block column, the next
+//           bits the block row), output pixels in raster order.  A wave covers 16 / 4 output pixels of a thumbnail row, so per block
+//           row it reads 32 / 16 consecutive bitmap and table dwords.  The partial sums are added with __shfl_xor inside the group
+//           (no LDS memory, no barrier) and the group's first lane stores.
+// Only whole output pixels are enumerated (tw = 4 nbx / S, th = 4 nby / S), so every lane of a live group has a block inside the
+// picture; the trailing block column / row that fills no output pixel and the X % 4, Y % 4 remainders are never read.  A group is
+// aligned to G * G lanes and lives or returns as one, so the shuffles only meet live lanes.
+template <int BITS, int S>
+__global__ __launch_bounds__(WG) void msv1_index_thumbs_kernel(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk,
+                                                               const int32_t* __restrict__ palette, const uint32_t* __restrict__ bitmap, size_t pitch,
+                                                               const int32_t* __restrict__ frames, uint32_t* __restrict__ out,
+                                                               const uint32_t* __restrict__ before, int nblocks, int nbx, int X, int tw, int th,
+                                                               int cols, int before_vec) {
+    constexpr int G = S / 4, GG = G * G;                            // blocks per output pixel: a side, all
+    constexpr int LG = S == 4 ? 0 : S == 8 ? 1 : 2;                 // log2(G)
+    constexpr uint32_t SH = 4 + 2 * LG, HALF = (uint32_t)(S * S) / 2u;   // log2(S * S), the rounding term
+    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
+    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
+    if (BITS == 8) __syncthreads();
+    const long gid = (long)blockIdx.x * WG + threadIdx.x;
+    const long q = gid >> (2 * LG);                                 // output pixel of the thumbnail, raster order
+    if (q >= (long)tw * th) return;
+    const int sub = (int)(gid & (GG - 1));
+    const int py = (int)(q / tw);
+    const int px_ = (int)(q - (long)py * tw);
+    const int by = py * G + (sub >> LG);
+    const int bx = px_ * G + (sub & (G - 1));
+    const int blk = by * nbx + bx;
+    const int k = (int)blockIdx.y;
+    const int t = frames[k];
+    int w;
+    const uint32_t m = index_last_writer(bitmap, nblocks, blk, t, w);
+    uint32_t px[16];
+    if (m != 0u) {
+        const int f = 32 * w + 31 - __builtin_clz(m);
+        const Msv1IndexChunk ch = chunks[frame_chunk[f]];
+        const int lf = f - (int)ch.first;
+        const uint32_t o = *(scgu32*)(ch.desc + (size_t)lf * pitch + blk);
+        decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
+    } else if (before != nullptr) {   // nothing up to t coded the block: the picture before the index
+        const uint32_t* p = before + (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
+        if (before_vec) load_block<true>(p, X, px);
+        else load_block<false>(p, X, px);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) px[i] = 0u;
+    }
+    uint32_t rb = 0, g = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        rb += px[i] & 0x00FF00FFu;
+        g += (px[i] >> 8) & 0xFFu;
+    }
+#pragma unroll
+    for (int d = 1; d < GG; d <<= 1) {
+        rb += (uint32_t)__shfl_xor((int)rb, d);
+        g += (uint32_t)__shfl_xor((int)g, d);
+    }
+    if (sub != 0) return;
+    const uint32_t r = ((rb >> 16) + HALF) >> SH, b = ((rb & 0xFFFFu) + HALF) >> SH;
+    const size_t sheet_pitch = (size_t)cols * (size_t)tw;
+    const size_t at = (size_t)(k / cols) * (size_t)th * sheet_pitch + (size_t)(k % cols) * (size_t)tw + (size_t)py * sheet_pitch + (size_t)px_;
+    *(sgu32*)(out + at) = (r << 16) | (((g + HALF) >> SH) << 8) | b;
 }
 
 // The seek and show kernels' work: one work-item per block, then one per pixel no block covers (nrem of them: the columns from cx on
@@ -426,6 +507,23 @@ void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chu
     if (geo.bits == 16) { if (g.vec) JSP_SHOW(16, true); else JSP_SHOW(16, false); }
     else { if (g.vec) JSP_SHOW(8, true); else JSP_SHOW(8, false); }
 #undef JSP_SHOW
+}
+
+void msv1_launch_index_thumbs(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                              const uint32_t* d_bitmap, const int32_t* d_frames, int n, int scale, int cols, int32_t* out, const int32_t* before,
+                              hipStream_t stream) {
+    const int tw = geo.nbx * 4 / scale, th = geo.nby * 4 / scale;
+    if (n <= 0 || cols <= 0 || tw <= 0 || th <= 0) return;
+    const long lanes = (long)tw * th * (scale / 4) * (scale / 4);
+    const dim3 grid((unsigned)((lanes + WG - 1) / WG), (unsigned)n);
+    const size_t pitch = (size_t)std::max(geo.nblocks, 1);
+    const int before_vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
+#define JSP_THUMBS(BITS, S) hipLaunchKernelGGL((msv1_index_thumbs_kernel<BITS, S>), grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk, d_palette, d_bitmap, \
+                                               pitch, d_frames, reinterpret_cast<uint32_t*>(out), reinterpret_cast<const uint32_t*>(before),            \
+                                               geo.nblocks, geo.nbx, geo.X, tw, th, cols, before_vec)
+    if (geo.bits == 16) { if (scale == 4) JSP_THUMBS(16, 4); else if (scale == 8) JSP_THUMBS(16, 8); else if (scale == 16) JSP_THUMBS(16, 16); }
+    else { if (scale == 4) JSP_THUMBS(8, 4); else if (scale == 8) JSP_THUMBS(8, 8); else if (scale == 16) JSP_THUMBS(8, 16); }
+#undef JSP_THUMBS
 }
 
 }  // namespace jsp

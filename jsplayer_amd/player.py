@@ -104,6 +104,27 @@ class Manager:
     def _in_index(self, i: int) -> bool:
         return self.index is not None and self.index_first <= i < self.index_first + self.index.frames
 
+    def preview(self, i: int, scale: int = 8):
+        """The thumbnail of clip frame `i` from the attached index (the picture that follows the pointer along the seek bar,
+        Main.on_mouse_move): one `Thumbs` launch, a pure read — no buffer, hold, log entry or decoder state changes.  No index
+        attached, or `i` outside it: ValueError (a hover preview is not worth a decode)."""
+        if not self._in_index(i):
+            raise ValueError(f"frame {i} is not in an attached seek index")
+        return self.index.Thumbs([i - self.index_first], scale=scale, cols=1)
+
+    def filmstrip(self, n: int, scale: int = 8, cols: Optional[int] = None):
+        """`n` frames spread evenly over the attached index — clip frame index_first + (k * index.frames) // n for k < n — as one
+        sheet of thumbnails, `cols` to a row (None: one row): (clip frame numbers, sheet).  One `Thumbs` launch, a pure read as
+        `preview`.  No index attached: ValueError."""
+        if self.index is None:
+            raise ValueError("no seek index attached")
+        n = int(n)
+        if n < 1:
+            raise ValueError("a filmstrip needs at least one frame")
+        picks = [(k * self.index.frames) // n for k in range(n)]
+        sheet = self.index.Thumbs(picks, scale=scale, cols=n if cols is None else int(cols))
+        return [self.index_first + t for t in picks], sheet
+
     def _slot_of(self, buf) -> int:
         for i, b in enumerate(self.buffers):
             if b is buf:
