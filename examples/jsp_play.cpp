@@ -14,7 +14,8 @@
 //                                no upload of their own.  --prefetch 0: a copy, or a read over the bus inside the kernel, per frame
 //   jsp_play clip.avi --skip-stills   MSVideo1: frame 0, then skip to the next significant change until the end (Manager.SkipStills,
 //                                one jsp_find_change per skip); prints "<index> <key|inter> <changed> <crc32>" per landing
-//   jsp_play clip.avi --step-back   MSVideo1: ONE seek index over the clip (jsp_index_build), then the last frame and every frame down
+//   jsp_play clip.avi --step-back   ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build and
+//                                jsp_sp_index_show), then the last frame and every frame down
 //                                to 0, one jsp_index_show each (Main.on_prevframe, Manager.hx:191-196); prints "<index> <key|inter>
 //                                <changed> <crc32>" per frame — sorted, the plain run's frames, significance and CRCs
 //   jsp_play clip.avi --filmstrip N[:scale]
@@ -606,6 +607,26 @@ int main(int argc, char** argv) {
             srcs.push_back(clip.bytes.data() + clip.frames[i].first);
             lens.push_back(clip.frames[i].second);
             keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        if (clip.kind == JSP_CODEC_SCREENPRESSOR) {   // the host entropy stage once (jsp_sp_index_build), then ONE jsp_sp_index_show per step
+            jsp_sp_index* sidx = n ? jsp_sp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+            if (n && !sidx) { std::fprintf(stderr, "jsp_sp_index_build: %s\n", jsp_last_error()); rc = 1; }
+            for (size_t t = n; sidx && t-- > 0;) {
+                int32_t* dst = jsp_pool_buffer(pool, (int)(t & 1));
+                int signif = 0;
+                if (jsp_sp_index_show(dec, sidx, (int)t, dst, &signif) != JSP_ZERO_STATE) {
+                    std::fprintf(stderr, "jsp_sp_index_show: %s\n", jsp_last_error());
+                    rc = 1;
+                    break;
+                }
+                uint32_t crc = 0;
+                if (jsp_download(dst, host.data(), npx) == 0) crc = crc32(reinterpret_cast<const uint8_t*>(host.data()), npx * 4);
+                std::printf("%zu %s %d %08x\n", t, keys[t] ? "key" : "inter", signif, crc);
+            }
+            jsp_sp_index_destroy(sidx);
+            jsp_pool_destroy(pool);
+            jsp_codec_destroy(dec);
+            return rc;
         }
         jsp_index* idx = n ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
         if (n && !idx) { std::fprintf(stderr, "jsp_index_build: %s\n", jsp_last_error()); rc = 1; }

@@ -58,6 +58,15 @@ extern class JspNative {
                                                                    out:RawPointer<cpp.Int32>, outPixels:SizeT):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
+    // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)
+    @:native("jsp_sp_index_build")        static function spIndexBuild(c:RawPointer<JspCodec>, nframes:Int, srcs:RawPointer<RawConstPointer<UInt8>>, lens:RawPointer<SizeT>,
+                                                                       isKey:RawConstPointer<UInt8>, keyRow:Int):RawPointer<JspSpIndex>;
+    @:native("jsp_sp_index_show")         static function spIndexShow(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, t:Int, dst:RawPointer<cpp.Int32>,
+                                                                      significant:RawPointer<Int>):Int;
+    @:native("jsp_sp_index_significance") static function spIndexSignificance(idx:RawPointer<JspSpIndex>, out:RawPointer<Int>):Int;
+    @:native("jsp_sp_index_info")         static function spIndexInfo(idx:RawPointer<JspSpIndex>, nframes:RawPointer<Int>, deviceBytes:RawPointer<cpp.UInt64>,
+                                                                      hostBytes:RawPointer<cpp.UInt64>):Int;
+    @:native("jsp_sp_index_destroy")      static function spIndexDestroy(idx:RawPointer<JspSpIndex>):Void;
     // frame pool in HBM (Manager.hx:114-118) and the two Manager passes that follow the codec
     @:native("jsp_key_frame_differs")  static function keyFrameDiffers(c:RawPointer<JspCodec>):Int;
     @:native("jsp_device_count")       static function deviceCount():Int;
@@ -76,5 +85,6 @@ extern class JspNative {
 
 @:include("jsplayer_amd.h") @:native("jsp_codec") @:structAccess extern class JspCodec {}
 @:include("jsplayer_amd.h") @:native("jsp_index") @:structAccess extern class JspIndex {}
+@:include("jsplayer_amd.h") @:native("jsp_sp_index") @:structAccess extern class JspSpIndex {}
 @:include("jsplayer_amd.h") @:native("jsp_pool") @:structAccess extern class JspPool {}
 #end

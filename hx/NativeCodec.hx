@@ -184,6 +184,41 @@ class NativeCodec implements IVideoCodec {
         JspNative.indexDestroy(idx);
     }
 
+    // ---- optional: ScreenPressor seek index (jsp_sp_index_*; ScreenPressor only — MSVideo1 throws, it has BuildIndex above) -----------
+    /** The host entropy stage over `srcs` ONCE (srcs[0] a coded key frame), its records kept resident in HBM: ShowSpIndexed(idx, t,
+     *  dst) then writes frame t's picture in one launch with no host decode work.  The codec is only lent: its stream position,
+     *  previous frame and entropy state stay as they are.  significance[k] (filled here): 1 / 0 for every frame, what the sequential
+     *  run records.  Free with DestroySpIndex (before or after this codec is stopped). */
+    public function BuildSpIndex(srcs:Array<Bytes>, isKey:Array<Bool>, keyRow:Int, significance:Array<Int>):RawPointer<JspSpIndex> {
+        var n = srcs.length;
+        var ptrs = new Array<RawConstPointer<UInt8>>();
+        var lens = new Array<cpp.SizeT>();
+        var keys = Bytes.alloc(n);
+        for (i in 0...n) {
+            ptrs.push(bytesPtr(srcs[i]));
+            lens.push(srcs[i].length);
+            keys.set(i, isKey[i] ? 1 : 0);
+        }
+        var idx = JspNative.spIndexBuild(h, n, cpp.NativeArray.address(ptrs, 0).raw, cpp.NativeArray.address(lens, 0).raw, bytesPtr(keys), keyRow);
+        if (idx == null) throw "BuildSpIndex: " + JspNative.lastError().toString();
+        for (i in 0...n) significance[i] = 0;
+        JspNative.spIndexSignificance(idx, cpp.NativeArray.address(significance, 0).raw);
+        return idx;
+    }
+
+    /** Frame t of the index into `dst` (a free buffer, never the previous frame): every pixel is written, the codec is not
+     *  touched — decoding continues from where the decoder stands.  Returns the frame's significance. */
+    public function ShowSpIndexed(idx:RawPointer<JspSpIndex>, t:Int, dst:FrameBuffer):Bool {
+        var signif:Int = 0;
+        var rc = JspNative.spIndexShow(h, idx, t, dst.ptr, cpp.RawPointer.addressOf(signif));
+        if (rc != 0) throw "ShowSpIndexed: " + JspNative.lastError().toString();
+        return signif != 0;
+    }
+
+    public static function DestroySpIndex(idx:RawPointer<JspSpIndex>):Void {
+        JspNative.spIndexDestroy(idx);
+    }
+
     // ---- optional: decode ahead of display (jsp_decompress_*_async / jsp_wait) ------------------------------------------
     /** Queue a frame; `src` and `dst` must stay untouched until wait(ticket).  Returns the ticket. */
     public function Submit(src:Bytes, dst:FrameBuffer, key:Bool):haxe.Int64 {

@@ -413,6 +413,51 @@ void jsp_index_destroy(jsp_index* idx);
 int jsp_index_thumb_size(const jsp_index* idx, int scale, int* width, int* height);
 int jsp_index_thumbs(jsp_codec* c, jsp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels);
 
+/* ---- ScreenPressor seek index: previous frame, seek-bar clicks and skip idle over a range whose host-stage records stay resident in
+ * HBM (the calls above refuse ScreenPressor: its entropy stage is sequential host work, and the Manager's fallback decodes again from
+ * the nearest key frame for every step back) -------------------------------------------------------------------------------------
+ * Build: the host entropy stage runs over frames[0..nframes-1] ONCE (is_key as in jsp_stage_batch), in waves of at most 64 frames,
+ *   groups of pictures side by side on host threads, with host decoders of the build's own.  Every inter frame's motion rectangles are
+ *   rewritten as literal ones, so no block of an inter frame reads the picture before it anywhere but at its own position.  Kept in
+ *   HBM: per key frame (coded or flat) its PICTURE, materialised by the key-frame kernels; per inter frame one 16-byte record per
+ *   16x16 block and the literal pixels of its changed rectangles; a bitmap of which frame changes which block.  Everything goes up
+ *   from pinned memory that the build owns and releases; the index keeps no pointer to `srcs`.
+ *   RANGE  frames[0] must be a CODED key frame (it renews every bit of decoder state: the index depends on nothing before it).  Key
+ *       frames (coded or flat), unchanged frames and inter frames of any mix may follow.
+ *   RESULTS  The index (jsp_sp_index_destroy frees it), or NULL and jsp_last_error().
+ *   ERRORS, each with nothing changed and nothing written: an MSVideo1 codec ("sp_index: ScreenPressor only"); a range that does not
+ *       start at a coded key frame; a frame that does not end in JSP_ZERO_STATE or clears the previous frame (a truncated or invalid
+ *       stream: the error names the frame's index in the range); nframes < 1, a null argument, a negative key_row; an asynchronous
+ *       frame in flight; literal pixels beyond what the records' 32-bit offsets (in 16-byte units) reach.
+ * Show: EQUIVALENCE  jsp_sp_index_show(t) writes into `dst` exactly the picture that a FRESH ScreenPressor codec of the same geometry
+ *       and Preinit leaves as its previous frame after DecompressI / DecompressP of frames[0..t] in order, WHEN EACH FRAME'S
+ *       DESTINATION STARTS OUT HOLDING THE PICTURE BEFORE IT (the rule of jsp_seek; it settles the one read an inter frame makes of
+ *       its destination, "left of column 0": the build answers it with the last column of the picture before the frame).  Every pixel
+ *       of `dst` is written, whatever it held.  *significant_changes (may be NULL) = what that sequential run records for frame t:
+ *       an inter frame's DecompressP verdict; a key frame's frames_differ_significantly (Manager.hx:392-421) as jsp_find_change words
+ *       it — the frame before is a key frame: their bytes differ; else the pixels from row `key_row` on differ from the picture
+ *       before (judged once, at the build, on the GPU); frame 0: 1.
+ *   ONE kernel launch (sp_index_show_kernel): no entropy decoding, no staging, no upload, no host pass over pictures.  Per 16x16 block
+ *       the bitmap words are walked down from t / 32 to the frame after t's key picture; every pixel takes the literal of the last
+ *       frame whose changed rectangle covers it, else the key picture's.  Runs on the codec's stream and returns synchronised.
+ *   THE CODEC IS ONLY LENT  Build and Show use the codec's device, stream, Preinit value and key-frame options ("sp_band_rows",
+ *       "sp_host_threads") and nothing else: its stream position, previous frame, entropy state and worker groups are exactly as
+ *       before, and a sequential decode can go on across any number of builds and shows.  There is no `adopt`: the entropy state
+ *       after frame t exists only at the end of a host decode.  One thing Show does to the codec: it has written a caller buffer
+ *       behind the codec's back, so the codec forgets what it remembers of that buffer's last column (what option
+ *       "sp_forget_buffers" does, for `dst` alone).
+ *   ERRORS, each with nothing changed and nothing written: a null argument, an MSVideo1 codec, an index built by another codec, t
+ *       outside 0..nframes-1, an asynchronous frame in flight, `dst` = the codec's current previous frame, a host-pointer `dst`.
+ * Significance: out[0..nframes-1] = 1 / 0, the verdict Show reports for each frame.
+ * Info: frames, and the bytes the index holds in HBM and in host memory (the build's staging memory is released when it returns).
+ * Destroy: frees the index's device memory only; safe before or after jsp_codec_destroy of its codec. */
+typedef struct jsp_sp_index jsp_sp_index;
+jsp_sp_index* jsp_sp_index_build(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key, int key_row);
+int jsp_sp_index_show(jsp_codec* c, jsp_sp_index* idx, int t, int32_t* dst, int* significant_changes);
+int jsp_sp_index_significance(const jsp_sp_index* idx, int* out);
+int jsp_sp_index_info(const jsp_sp_index* idx, int* nframes, uint64_t* device_bytes, uint64_t* host_bytes);
+void jsp_sp_index_destroy(jsp_sp_index* idx);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

@@ -6,7 +6,7 @@ through the C ABI of include/jsplayer_amd.h.  This package is the Python mirror 
 plugin interface over that ABI.
 """
 from .codec import (CodecError, DecoderState, FramePool, HostBuffer, MSVideo1_16bit, MSVideo1_8bit, PFrameResult, ScreenPressor,
-                    SeekIndex, StagedBatch)
+                    SeekIndex, SpScrubIndex, StagedBatch)
 
 __all__ = ["CodecError", "DecoderState", "FramePool", "HostBuffer", "MSVideo1_16bit", "MSVideo1_8bit", "PFrameResult", "ScreenPressor",
-           "SeekIndex", "StagedBatch"]
+           "SeekIndex", "SpScrubIndex", "StagedBatch"]

@@ -412,6 +412,8 @@ class SeekIndex:
     """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch.  `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
+    ADOPTS = True   # Show(adopt=True) leaves the decoder at frame t: a Manager moves its decode position with it
+
     def __init__(self, codec: _NativeCodec, handle: int, prev_at_build):
         self._codec, self._h = codec, handle
         self._prev_at_build = prev_at_build   # what data_pnt is for a frame before the first one that adopts its buffer
@@ -526,6 +528,74 @@ class ScreenPressor(_NativeCodec):
 
     def __init__(self, width: int, height: int, bits_per_pixel: int, device: int = 0):
         super().__init__(width, height, bits_per_pixel, None, device)
+
+    def BuildScrubIndex(self, srcs: Sequence, is_key: Optional[Sequence[bool]] = None, key_row: int = INSIGNIFICANT_LINES) -> "SpScrubIndex":
+        """The host entropy stage over the frames `srcs` ONCE (srcs[0] a coded key frame), its records kept in HBM
+        (jsp_sp_index_build): SpScrubIndex.Show(t) then writes frame t's picture in one launch, with no host decode work.  The
+        codec is only lent — its stream position, previous frame and entropy state stay as they are — and the index keeps no
+        reference to `srcs`.  CodecError for a range that does not start at a coded key frame or holds a frame that does not
+        decode (the error names it)."""
+        n = len(srcs)
+        if n == 0:
+            raise CodecError("sp_index: empty range")
+        ptrs, lens, keys, keeps = _range_args(srcs, is_key)
+        h = self._lib.jsp_sp_index_build(self._h, n, ptrs, lens, keys, int(key_row))
+        del keeps
+        if not h:
+            raise CodecError(N.last_error())
+        return SpScrubIndex(self, h)
+
+
+class SpScrubIndex:
+    """A ScreenPressor range resident in HBM (jsp_sp_index_build, via ScreenPressor.BuildScrubIndex): Show(t) is one launch.
+    `significance` = the verdict the sequential run records for every frame, `frames`, `device_bytes`, `host_bytes`.  close() (or
+    the context manager) frees it; safe after the codec is gone."""
+
+    ADOPTS = False   # Show never moves the decoder: a Manager serves the frame and leaves its decode position where it is
+
+    def __init__(self, codec: _NativeCodec, handle: int):
+        self._codec, self._h = codec, handle
+        lib = self._lib = codec._lib
+        n, dev, host = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        lib.jsp_sp_index_info(handle, C.byref(n), C.byref(dev), C.byref(host))
+        self.frames, self.device_bytes, self.host_bytes = n.value, dev.value, host.value
+        sig = (C.c_int * self.frames)()
+        lib.jsp_sp_index_significance(handle, sig)
+        self.significance = [bool(v) for v in sig]
+
+    def Show(self, t: int, dst, adopt: bool = False) -> PFrameResult:
+        """Frame t's picture into `dst` (a device buffer, not the codec's previous frame): what a fresh codec leaves as its
+        previous frame after decoding srcs[:t + 1] in order.  Every pixel is written.  PFrameResult(dst, the frame's verdict).
+        The codec is not touched (`adopt` must stay False: the entropy state after frame t is not in the index)."""
+        if adopt:
+            raise CodecError("sp_index_show: a ScreenPressor index cannot adopt")
+        if not self._h:
+            raise CodecError("sp_index_show: the index is closed")
+        codec = self._codec
+        if not codec._h:
+            raise CodecError("sp_index_show: the codec is closed")
+        addr = _frame_ptr(dst, codec.X * codec.Y)
+        signif = C.c_int(0)
+        if self._lib.jsp_sp_index_show(codec._h, self._h, int(t), C.c_void_p(addr), C.byref(signif)) != 0:
+            raise CodecError(N.last_error())
+        return PFrameResult(dst, bool(signif.value))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.jsp_sp_index_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class _DeviceView:

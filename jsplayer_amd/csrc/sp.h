@@ -196,7 +196,8 @@ private:
 // `stream_decoder` would have produced for frames[i] decoding them one after the other, and `stream_decoder` ends in the
 // state that run would leave it in (the decoder that took the last group takes its place).  A group whose key frame does
 // not decode (its failure leaves older state showing through) is re-run in order.  `literalise`: inter frames that move at
-// most a quarter of their pixels get literalise_motion() applied (what the staged batch's group launches need).
+// most a quarter of their pixels get literalise_motion() applied (what the staged batch's group launches need);
+// `literalise_all`: every inter frame with motion does, whatever it moves (the seek index keeps no motion block).
 struct HostFrame { const uint8_t* src; size_t n; bool key; const void* dst = nullptr; const int32_t* dst_host = nullptr; };
 // What the caller's destination buffers hold in their last column (see HostDecoder::set_destination_column): asked before a frame is
 // decoded into `dst`, told after.  Implemented by the codec (which knows the buffers); may be called from several host threads.
@@ -206,9 +207,23 @@ struct DstColumns {
     virtual void after(const HostFrame& f, const HostDecoder& d, const FrameOut& out) = 0;
 };
 bool starts_group(const HostFrame& f);   // a coded key frame
-void decode_single(HostDecoder& d, const HostFrame& f, FrameOut& out, bool literalise, DstColumns* cols = nullptr);   // one frame through decoder `d` (what decode_frames does per frame)
+void decode_single(HostDecoder& d, const HostFrame& f, FrameOut& out, bool literalise, DstColumns* cols = nullptr,
+                   bool literalise_all = false);   // one frame through decoder `d` (what decode_frames does per frame)
 void decode_frames(HostDecoder& stream_decoder, std::vector<std::unique_ptr<HostDecoder>>& spare, const HostFrame* frames,
-                   int count, FrameOut* outs, int threads, bool literalise, DstColumns* cols = nullptr);
+                   int count, FrameOut* outs, int threads, bool literalise, DstColumns* cols = nullptr, bool literalise_all = false);
+
+// What the ScreenPressor seek index (sp_index.cpp: jsp_sp_index_*) borrows from a ScreenPressor codec: it decodes with host
+// decoders of its own, so it takes the codec's Preinit and key-frame options, never its decoder.  Implemented by the codec.
+struct IndexLender {
+    virtual ~IndexLender() = default;
+    virtual Geometry lend_geometry() const = 0;
+    virtual HostDecoder::Settings lend_settings() const = 0;   // Preinit (the layout fields are the build's own choice)
+    virtual int lend_band_rows() const = 0;                    // option "sp_band_rows" (-1: auto)
+    virtual int lend_host_threads() const = 0;                 // option "sp_host_threads" (0: auto)
+    // the caller's buffer `dst` has been written behind the codec's back: what the codec remembers of its last column is dropped
+    // (option "sp_forget_buffers", for one buffer)
+    virtual void forget_buffer(const void* dst) = 0;
+};
 
 // ---- kernels (sp_kernels.hip), asynchronous on `stream` -------------------------------------
 struct IFrameArgs {    // one per frame of an intra launch (grid.x = frame, grid.y = band)
@@ -250,6 +265,11 @@ struct PGroupFrame {   // one per frame of the group, in decode order
 };
 void launch_pframe_group(const Geometry& g, const PGroupFrame* d_frames, int nframes, const int32_t* prev,
                          const PBlock* d_blocks, const uint32_t* d_payload, bool aligned16, hipStream_t stream);
+// Seek index (sp_index_kernels.hip): frame t of a resident range — the key picture `key` of frame k <= t under the literal rectangles of the
+// LAST frame in (k, t] that covers each pixel.  Frame f's block table is d_blocks + (f + slot_base) * nblocks; PBlock::payload counts in
+// 16-byte units of d_payload there; d_bitmap[w * nblocks + b] bit j: frame 32 w + j changes block b.  Every pixel of dst is written.
+void launch_index_show(const Geometry& g, int32_t* dst, const int32_t* key, const PBlock* d_blocks, const uint32_t* d_payload,
+                       const uint32_t* d_bitmap, int t, int k, long slot_base, hipStream_t stream);
 constexpr int kGroupMaxFrames = 65535;        // frames one group launch may walk
 size_t iframe_lds_bytes(const Geometry& g, int band_rows = 0);
 constexpr int kMaxIntraWidth = 8192;  // LDS plan of the row-wavefront kernel

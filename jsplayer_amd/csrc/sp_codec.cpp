@@ -62,8 +62,17 @@ struct SpStaged : jsp_staged {
 
 std::atomic<int> g_sp_async_streams{0};   // ScreenPressor codec instances of this process whose asynchronous calls run on worker threads
 
-struct SpCodec : jsp_codec, DstColumns {
+struct SpCodec : jsp_codec, DstColumns, IndexLender {
     HostDecoder host;
+    // ---- IndexLender (called with no asynchronous frame in flight: no worker is inside `host`) ---------------------------------
+    Geometry lend_geometry() const override { return host.geo(); }
+    HostDecoder::Settings lend_settings() const override { return groups.empty() ? host.settings() : settings_at_submit; }
+    int lend_band_rows() const override { return opt_band_rows; }
+    int lend_host_threads() const override { return opt_host_threads; }
+    void forget_buffer(const void* dst) override {
+        std::lock_guard<std::mutex> lk(col_mu);
+        last_col.erase(dst);
+    }
     // ---- what the caller's frame buffers hold in their last column (DstColumns) ------------------------------------------------
     // The reference's inter frames read ONE kind of pixel from their destination before writing it (HostDecoder::
     // set_destination_column); to hand back what the reference hands back whatever the caller's buffer rotation, the codec remembers

@@ -527,7 +527,7 @@ void HostDecoder::literalise_motion(FrameOut& out) const {
 
 // ---- groups of pictures side by side ---------------------------------------------------------------------------------
 namespace {
-void decode_one(HostDecoder& d, const HostFrame& f, FrameOut& out, bool literalise, DstColumns* cols) {
+void decode_one(HostDecoder& d, const HostFrame& f, FrameOut& out, bool literalise, DstColumns* cols, bool literalise_all) {
     if (cols && !f.key && (f.dst || f.dst_host)) d.set_destination_column([cols, &f] { return cols->before(f); });
     else d.set_destination_column(nullptr);
     if (f.key) d.decode_i(f.src, f.n, out);
@@ -535,17 +535,17 @@ void decode_one(HostDecoder& d, const HostFrame& f, FrameOut& out, bool literali
     d.set_destination_column(nullptr);
     if (cols && (f.dst || f.dst_host)) cols->after(f, d, out);
     const Geometry& g = d.geo();
-    if (literalise && out.kind == FrameKind::Inter && out.motion_pixels * 4 <= (uint64_t)g.X * g.Y) {
+    if (out.kind == FrameKind::Inter && (literalise_all || (literalise && out.motion_pixels * 4 <= (uint64_t)g.X * g.Y))) {
         d.literalise_motion(out);
         out.literalised = true;
     }
 }
 }  // namespace
-void decode_single(HostDecoder& d, const HostFrame& f, FrameOut& out, bool literalise, DstColumns* cols) { decode_one(d, f, out, literalise, cols); }
+void decode_single(HostDecoder& d, const HostFrame& f, FrameOut& out, bool literalise, DstColumns* cols, bool literalise_all) { decode_one(d, f, out, literalise, cols, literalise_all); }
 bool starts_group(const HostFrame& f) { return f.key && f.n > 0 && (f.src[0] & 0xF) == 2; }   // a CODED key frame (flat ones renew nothing)
 
 void decode_frames(HostDecoder& stream_decoder, std::vector<std::unique_ptr<HostDecoder>>& spare, const HostFrame* frames,
-                   int count, FrameOut* outs, int threads, bool literalise, DstColumns* cols) {
+                   int count, FrameOut* outs, int threads, bool literalise, DstColumns* cols, bool literalise_all) {
     // groups: [0, first coded key frame) continues whatever the stream decoder holds; then one group per coded key frame
     std::vector<int> begin;
     begin.push_back(0);
@@ -559,7 +559,7 @@ void decode_frames(HostDecoder& stream_decoder, std::vector<std::unique_ptr<Host
         if (starts_group(frames[i])) version = (frames[i].src[0] >> 4) + 1;
     const bool side_by_side = threads > 1 && ngroups > 1 && version >= 2 && version <= 4;
     if (!side_by_side) {
-        for (int i = 0; i < count; ++i) decode_one(stream_decoder, frames[i], outs[i], literalise, cols);
+        for (int i = 0; i < count; ++i) decode_one(stream_decoder, frames[i], outs[i], literalise, cols, literalise_all);
         return;
     }
     const Geometry g = stream_decoder.geo();
@@ -577,7 +577,7 @@ void decode_frames(HostDecoder& stream_decoder, std::vector<std::unique_ptr<Host
         if (!usable[grp]) return;
         HostDecoder& d = decoder_of(grp);
         try {
-            for (int i = begin[grp]; i < begin[grp + 1]; ++i) decode_one(d, frames[i], outs[i], literalise, cols);
+            for (int i = begin[grp]; i < begin[grp + 1]; ++i) decode_one(d, frames[i], outs[i], literalise, cols, literalise_all);
         } catch (...) {            // (out of memory on a thread of its own must not end the process: the group is decoded again, in order)
             if (grp > 0) usable[grp] = 0;
             else throw;
@@ -613,7 +613,7 @@ void decode_frames(HostDecoder& stream_decoder, std::vector<std::unique_ptr<Host
         last_good = grp;
     }
     if (last_good > 0) std::swap(stream_decoder, *spare[last_good - 1]);   // the stream goes on from the last group that stands
-    for (int i = begin[last_good + 1]; i < count; ++i) decode_one(stream_decoder, frames[i], outs[i], literalise, cols);
+    for (int i = begin[last_good + 1]; i < count; ++i) decode_one(stream_decoder, frames[i], outs[i], literalise, cols, literalise_all);
 }
 
 }  // namespace jsp::sp

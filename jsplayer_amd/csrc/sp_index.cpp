@@ -1,0 +1,358 @@
+// The ScreenPressor seek index of include/jsplayer_amd.h — jsp_sp_index_* —: the host entropy stage runs over a range ONCE, its
+// records stay resident in HBM, and any frame of the range is then one launch of sp_index_show_kernel (sp_index_kernels.hip).
+//
+// Kept apart from sp_codec.cpp / jsp_api.cpp: those are also built against the stub kernels of the host-layer sanitizer build
+// (tools/tsan_cpu.sh), which knows nothing of the index kernel.  What the build needs of the codec comes through sp::IndexLender.
+#include <algorithm>
+#include <cstring>
+
+#include "codec.h"
+#include "sp.h"
+
+using namespace jsp;
+using namespace jsp::sp;
+
+namespace jsp {
+void launch_frames_differ(const int32_t* a, const int32_t* b, size_t first_pixel, size_t npixels, uint32_t* d_flag, hipStream_t stream);
+}
+
+struct jsp_sp_index {
+    uint64_t codec_serial = 0;       // jsp_codec::serial of the codec that built it
+    int device = 0;
+    Geometry geo{};
+    int nframes = 0;
+    size_t pic_stride = 0;           // ints from one key picture to the next (a multiple of 4: every picture 16-byte aligned)
+    DeviceBuffer d_keys, d_blocks, d_payload, d_bitmap;
+    uint64_t table_bytes = 0, payload_bytes = 0, bitmap_bytes = 0, key_bytes = 0;
+    std::vector<int32_t> key_of;     // per frame: the frame number of its key picture (a key frame: its own)
+    std::vector<int32_t> key_slot;   // per frame: which picture of d_keys that is
+    std::vector<int64_t> slot_base;  // per frame: its block table is d_blocks + (frame + slot_base) * nblocks (key frames: unused)
+    std::vector<int> significance;   // per frame: the verdict of the sequential run (1 / 0)
+    uint64_t device_bytes() const { return d_keys.cap + d_blocks.cap + d_payload.cap + d_bitmap.cap; }
+    uint64_t host_bytes() const {
+        return sizeof(*this) + key_of.size() * sizeof(int32_t) + key_slot.size() * sizeof(int32_t) + slot_base.size() * sizeof(int64_t) +
+               significance.size() * sizeof(int);
+    }
+    const int32_t* key_picture(int t) const { return static_cast<const int32_t*>(d_keys.p) + (size_t)key_slot[(size_t)t] * pic_stride; }
+    void show(int t, int32_t* dst, hipStream_t stream) const {
+        launch_index_show(geo, dst, key_picture(t), static_cast<const PBlock*>(d_blocks.p), static_cast<const uint32_t*>(d_payload.p),
+                          static_cast<const uint32_t*>(d_bitmap.p), t, key_of[(size_t)t], (long)slot_base[(size_t)t], stream);
+    }
+};
+
+namespace {
+
+int fail(const char* fmt, const char* what = "") {
+    set_error(fmt, what);
+    return JSP_ERROR_OCCURED;
+}
+
+bool on_device(const void* p) {   // (after c->activate())
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged)) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// exactly `bytes` of device memory (DeviceBuffer::reserve keeps a quarter spare for growth: an index never grows)
+void exact(DeviceBuffer& d, size_t bytes) {
+    d.release();
+    bytes = std::max<size_t>(bytes, 16);
+    JSP_HIP(hipMalloc(&d.p, bytes));
+    d.cap = bytes;
+}
+
+// Host memory to the device through pinned memory owned by the build, slice by slice.
+struct Uploader {
+    PinnedBuffer pin;
+    hipStream_t stream;
+    static constexpr size_t kSlice = 8u << 20;
+    explicit Uploader(hipStream_t s) : stream(s) { pin.reserve(kSlice); }
+    void operator()(void* d, const void* h, size_t bytes) {
+        for (size_t at = 0; at < bytes; at += kSlice) {
+            const size_t n = std::min(kSlice, bytes - at);
+            std::memcpy(pin.p, static_cast<const uint8_t*>(h) + at, n);
+            JSP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(d) + at, pin.p, n, hipMemcpyHostToDevice, stream));
+            JSP_HIP(hipStreamSynchronize(stream));   // (the slice is free for the next one)
+        }
+    }
+};
+
+// What the destination of frame i holds in its last column: the last column of the picture before it (the rule of jsp_seek — each
+// frame's destination starts out holding the picture before it).  `after` notes the column every frame leaves; groups of pictures run
+// on threads of their own, each writing its own frames' rows and reading the row of the frame before, which its own thread wrote (a
+// group opens with a key frame, and key frames do not ask).
+struct PictureColumns : DstColumns {
+    const HostFrame* base = nullptr;
+    int Y = 0;
+    std::vector<int32_t> cols;   // nframes rows of Y
+    const int32_t* before(const HostFrame& f) override {
+        const size_t i = (size_t)(&f - base);
+        return i > 0 ? cols.data() + (i - 1) * (size_t)Y : nullptr;
+    }
+    void after(const HostFrame& f, const HostDecoder& d, const FrameOut& out) override {
+        const size_t i = (size_t)(&f - base);
+        int32_t* mine = cols.data() + i * (size_t)Y;
+        if (out.adopted) d.last_column(mine);
+        else if (i > 0) std::copy(mine - Y, mine, mine);   // an unchanged frame: the picture before it stays
+    }
+};
+
+// The key frames of one wave of the build, materialised by the codec's key-frame kernels into pictures the index owns.
+struct KeyWave {
+    std::vector<IRun> runs;
+    std::vector<uint32_t> rows, seeds, tileidx, left;
+    std::vector<IFrameArgs> iargs;
+    std::vector<size_t> run_off, row_off, seed_off, tile_off, left_off;
+    DeviceBuffer d_runs, d_rows, d_seeds, d_tileidx, d_left, d_iargs;
+    void clear() {
+        runs.clear(); rows.clear(); seeds.clear(); tileidx.clear(); left.clear(); iargs.clear();
+        run_off.clear(); row_off.clear(); seed_off.clear(); tile_off.clear(); left_off.clear();
+    }
+    void add(const FrameOut& fo, int32_t* dst, bool tiles) {
+        IFrameArgs a{};
+        a.dst = dst;
+        a.flat = fo.kind == FrameKind::Flat;
+        a.colour = fo.flat_colour;
+        a.nruns = (uint32_t)fo.runs.size();
+        run_off.push_back(runs.size()); row_off.push_back(rows.size()); seed_off.push_back(seeds.size());
+        tile_off.push_back(tileidx.size()); left_off.push_back(left.size());
+        runs.insert(runs.end(), fo.runs.begin(), fo.runs.end());
+        if (!tiles) rows.insert(rows.end(), fo.row_run.begin(), fo.row_run.end());
+        seeds.insert(seeds.end(), fo.seeds.begin(), fo.seeds.end());
+        tileidx.insert(tileidx.end(), fo.tile_idx.begin(), fo.tile_idx.end());
+        left.insert(left.end(), fo.left.begin(), fo.left.end());
+        iargs.push_back(a);
+    }
+    void launch(const Geometry& g, int band_rows, bool tiles, Uploader& up, hipStream_t stream) {
+        if (iargs.empty()) return;
+        d_runs.reserve(std::max<size_t>(runs.size(), 1) * sizeof(IRun));
+        d_rows.reserve(std::max<size_t>(rows.size(), 1) * 4);
+        d_seeds.reserve(std::max<size_t>(seeds.size(), 1) * 4);
+        d_tileidx.reserve(std::max<size_t>(tileidx.size(), 1) * 4);
+        d_left.reserve(std::max<size_t>(left.size(), 1) * 4);
+        d_iargs.reserve(iargs.size() * sizeof(IFrameArgs));
+        for (size_t k = 0; k < iargs.size(); ++k) {
+            iargs[k].runs = static_cast<const IRun*>(d_runs.p) + run_off[k];
+            iargs[k].row_run = static_cast<const uint32_t*>(d_rows.p) + row_off[k];
+            iargs[k].seeds = static_cast<const uint32_t*>(d_seeds.p) + seed_off[k];
+            iargs[k].tile_idx = static_cast<const uint32_t*>(d_tileidx.p) + tile_off[k];
+            iargs[k].left = static_cast<const uint32_t*>(d_left.p) + left_off[k];
+        }
+        up(d_runs.p, runs.data(), runs.size() * sizeof(IRun));
+        up(d_rows.p, rows.data(), rows.size() * 4);
+        up(d_seeds.p, seeds.data(), seeds.size() * 4);
+        up(d_tileidx.p, tileidx.data(), tileidx.size() * 4);
+        up(d_left.p, left.data(), left.size() * 4);
+        up(d_iargs.p, iargs.data(), iargs.size() * sizeof(IFrameArgs));
+        if (tiles) launch_iframe_tiles(g, static_cast<const IFrameArgs*>(d_iargs.p), (int)iargs.size(), band_rows, stream);
+        else launch_iframes(g, static_cast<const IFrameArgs*>(d_iargs.p), (int)iargs.size(), band_rows, stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(stream));   // (the wave's tables are reused by the next wave)
+    }
+};
+
+}  // namespace
+
+extern "C" jsp_sp_index* jsp_sp_index_build(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key,
+                                            int key_row) {
+    if (!c || !srcs || !lens) { set_error("sp_index: null argument"); return nullptr; }
+    if (nframes < 1) { set_error("sp_index: empty range"); return nullptr; }
+    if (key_row < 0) { set_error("sp_index: negative key_row"); return nullptr; }
+    auto* lender = c->kind == JSP_CODEC_SCREENPRESSOR ? dynamic_cast<IndexLender*>(c) : nullptr;
+    if (!lender) { set_error("sp_index: ScreenPressor only"); return nullptr; }
+    for (int i = 0; i < nframes; ++i)
+        if (!srcs[i] && lens[i]) { set_error("sp_index: null frame bytes"); return nullptr; }
+    if (c->next_ticket != c->oldest_ticket) { set_error("sp_index: an asynchronous frame is in flight (jsp_wait for it first)"); return nullptr; }
+    std::vector<HostFrame> hf((size_t)nframes);
+    static const int32_t kSomewhere = 0;   // (a destination that is never written: it makes the host stage ask for its last column)
+    for (int i = 0; i < nframes; ++i) hf[(size_t)i] = HostFrame{srcs[i], lens[i], is_key ? is_key[i] != 0 : true, &kSomewhere};
+    if (!starts_group(hf[0])) { set_error("sp_index: the range must start at a coded key frame"); return nullptr; }
+    try {
+        c->activate();
+        hipStream_t stream = c->stream;
+        const Geometry g = lender->lend_geometry();
+        auto idx = std::make_unique<jsp_sp_index>();
+        idx->codec_serial = c->serial;
+        idx->device = c->device;
+        idx->geo = g;
+        idx->geo.aligned16 = true;
+        idx->nframes = nframes;
+        idx->key_of.assign((size_t)nframes, 0);
+        idx->key_slot.assign((size_t)nframes, 0);
+        idx->slot_base.assign((size_t)nframes, 0);
+        idx->significance.assign((size_t)nframes, 0);
+        const size_t npix = (size_t)g.X * (size_t)g.Y, nblocks = (size_t)g.nbx * (size_t)g.nby;
+        idx->pic_stride = (npix + 3) & ~size_t(3);
+
+        // ---- layout of what stays: a picture per key frame, a table slot per other frame --------------------------------------
+        int nkeys = 0;
+        int64_t nslots = 0;
+        for (int i = 0; i < nframes; ++i) {
+            if (hf[(size_t)i].key) {
+                idx->key_of[(size_t)i] = i;
+                idx->key_slot[(size_t)i] = nkeys++;
+            } else {
+                idx->key_of[(size_t)i] = idx->key_of[(size_t)i - 1];
+                idx->key_slot[(size_t)i] = idx->key_slot[(size_t)i - 1];
+                idx->slot_base[(size_t)i] = nslots++ - i;
+            }
+        }
+        const int nwords = (nframes + 31) / 32;
+        idx->key_bytes = (uint64_t)nkeys * idx->pic_stride * sizeof(int32_t);
+        idx->table_bytes = (uint64_t)nslots * nblocks * sizeof(PBlock);
+        idx->bitmap_bytes = (uint64_t)nwords * nblocks * sizeof(uint32_t);
+        exact(idx->d_keys, idx->key_bytes);
+        exact(idx->d_blocks, idx->table_bytes);
+        exact(idx->d_bitmap, idx->bitmap_bytes);
+        std::vector<uint32_t> bitmap((size_t)nwords * nblocks, 0u);
+        std::vector<uint32_t> payload;               // every literal of the range (the frames' sizes are known only once they are decoded)
+
+        // ---- host decoders of the build's own, with the codec's Preinit and key-frame options -----------------------------------
+        const bool tiles = iframe_tiles_ok(idx->geo);
+        int band_rows = lender->lend_band_rows() >= 0 ? lender->lend_band_rows() : choose_band_rows(g, std::min(nkeys, 64));
+        if (tiles && g.Y > iframe_tile_max_band_rows() && (band_rows <= 0 || band_rows > iframe_tile_max_band_rows())) band_rows = iframe_tile_max_band_rows();
+        HostDecoder host(g.X, g.Y, g.bpp);
+        host.adopt_settings(lender->lend_settings());
+        host.set_iframe_layout(band_rows, tiles ? iframe_tile_span(idx->geo) : 0);
+        host.set_key_compare_row(-1);
+        std::vector<std::unique_ptr<HostDecoder>> spare;
+        int threads = lender->lend_host_threads();
+        if (threads <= 0) { threads = usable_cpus(); threads = threads < 1 ? 1 : (threads > 8 ? 8 : threads); }
+        PictureColumns cols;
+        cols.base = hf.data();
+        cols.Y = g.Y;
+        cols.cols.assign((size_t)nframes * (size_t)g.Y, 0);
+
+        Uploader up(stream);
+        KeyWave keys;
+        std::vector<FrameOut> outs;
+        std::vector<PBlock> table;
+        for (int w0 = 0; w0 < nframes;) {   // waves as the codec's staging cuts them: up to `threads` groups of pictures, at most 64 frames
+            int w1 = w0 + 1, groups = 1;
+            while (w1 < nframes && w1 - w0 < 64) {
+                if (starts_group(hf[(size_t)w1])) { if (groups == threads) break; ++groups; }
+                ++w1;
+            }
+            if ((int)outs.size() < w1 - w0) outs.resize((size_t)(w1 - w0));
+            decode_frames(host, spare, hf.data() + w0, w1 - w0, outs.data(), threads, false, &cols, true);
+            keys.clear();
+            for (int i = w0; i < w1; ++i) {
+                FrameOut& fo = outs[(size_t)(i - w0)];
+                if (fo.status != JSP_ZERO_STATE || fo.prev_cleared) {
+                    set_error("sp_index: frame %d of the range: %s", i, fo.error ? fo.error : "the frame does not decode");
+                    return nullptr;
+                }
+                if (hf[(size_t)i].key) {
+                    if (fo.kind != FrameKind::Flat && fo.kind != FrameKind::Intra) {
+                        set_error("sp_index: frame %d of the range: the key frame leaves no picture", i);
+                        return nullptr;
+                    }
+                    keys.add(fo, static_cast<int32_t*>(idx->d_keys.p) + (size_t)idx->key_slot[(size_t)i] * idx->pic_stride, tiles);
+                    continue;
+                }
+                idx->significance[(size_t)i] = fo.significant ? 1 : 0;
+                if (fo.kind != FrameKind::Inter) continue;   // an unchanged frame: no bit of the bitmap is set, its slot is never read
+                if (fo.blocks.size() != nblocks) throw std::runtime_error("sp_index: block table of unexpected size");
+                const uint64_t base16 = payload.size() / 4;
+                if (base16 + (fo.payload.size() + 3) / 4 > 0xFFFFFFFFull) {
+                    set_error("sp_index: the range's literal pixels do not fit the records' 32-bit offsets (frame %d)", i);
+                    return nullptr;
+                }
+                table.assign(fo.blocks.begin(), fo.blocks.end());
+                uint32_t* word = bitmap.data() + (size_t)(i >> 5) * nblocks;
+                for (size_t b = 0; b < nblocks; ++b) {
+                    PBlock& pb = table[b];
+                    if (!pb.flags) continue;
+                    if ((pb.flags & PB_MOTION) || !(pb.flags & PB_DATA) || (pb.payload & 3u)) throw std::runtime_error("sp_index: a block that is not a literal rectangle");
+                    pb.payload = (uint32_t)(base16 + pb.payload / 4);   // in 16-byte units of the index's payload
+                    word[b] |= 1u << (i & 31);
+                }
+                up(static_cast<PBlock*>(idx->d_blocks.p) + (size_t)((int64_t)i + idx->slot_base[(size_t)i]) * nblocks, table.data(), nblocks * sizeof(PBlock));
+                payload.insert(payload.end(), fo.payload.begin(), fo.payload.end());
+                payload.resize((payload.size() + 3) & ~size_t(3), 0u);   // every frame's literals start on a 16-byte boundary (so does every rectangle)
+            }
+            keys.launch(idx->geo, band_rows, tiles, up, stream);
+            w0 = w1;
+        }
+        idx->payload_bytes = payload.size() * sizeof(uint32_t);
+        exact(idx->d_payload, idx->payload_bytes);
+        up(idx->d_payload.p, payload.data(), idx->payload_bytes);
+        up(idx->d_bitmap.p, bitmap.data(), idx->bitmap_bytes);
+
+        // ---- key frames: frames_differ_significantly (Manager.hx:392-421), once -----------------------------------------------------
+        std::vector<int> judged;   // key frames behind an inter frame: the picture before them against their own, from key_row on
+        for (int i = 0; i < nframes; ++i) {
+            if (!hf[(size_t)i].key) continue;
+            if (i == 0) idx->significance[0] = 1;
+            else if (hf[(size_t)i - 1].key)
+                idx->significance[(size_t)i] = !(lens[i] == lens[i - 1] && (lens[i] == 0 || std::memcmp(srcs[i], srcs[i - 1], lens[i]) == 0));
+            else judged.push_back(i);
+        }
+        if (!judged.empty()) {
+            DeviceBuffer d_before, d_flags;
+            d_before.reserve(idx->pic_stride * sizeof(int32_t));
+            d_flags.reserve(judged.size() * sizeof(uint32_t));
+            std::vector<uint32_t> flags(judged.size(), 0u);
+            for (size_t j = 0; j < judged.size(); ++j) {
+                const int i = judged[j];
+                idx->show(i - 1, static_cast<int32_t*>(d_before.p), stream);
+                JSP_HIP(hipGetLastError());
+                launch_frames_differ(idx->key_picture(i), static_cast<const int32_t*>(d_before.p), (size_t)key_row * (size_t)g.X, npix,
+                                     static_cast<uint32_t*>(d_flags.p) + j, stream);
+                JSP_HIP(hipGetLastError());
+            }
+            JSP_HIP(hipMemcpyAsync(flags.data(), d_flags.p, flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            JSP_HIP(hipStreamSynchronize(stream));
+            for (size_t j = 0; j < judged.size(); ++j) idx->significance[(size_t)judged[j]] = flags[j] ? 1 : 0;
+        }
+        return idx.release();
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return nullptr;
+    }
+}
+
+extern "C" int jsp_sp_index_show(jsp_codec* c, jsp_sp_index* idx, int t, int32_t* dst, int* significant_changes) {
+    if (!c || !idx || !dst) return fail("sp_index_show: null argument");
+    auto* lender = c->kind == JSP_CODEC_SCREENPRESSOR ? dynamic_cast<IndexLender*>(c) : nullptr;
+    if (!lender) return fail("sp_index: ScreenPressor only");
+    if (idx->codec_serial != c->serial) return fail("sp_index_show: the index was built by another codec");
+    if (t < 0 || t >= idx->nframes) return fail("sp_index_show: t is outside the index");
+    if (c->next_ticket != c->oldest_ticket) return fail("sp_index_show: an asynchronous frame is in flight (jsp_wait for it first)");
+    if (dst == c->prev_caller || dst == c->prev_dev) return fail("sp_index_show: dst is the current previous frame");
+    try {
+        c->activate();
+        if (!on_device(dst)) return fail("sp_index_show: dst must be a device frame buffer");
+        idx->show(t, dst, c->stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(c->stream));
+        lender->forget_buffer(dst);   // (written behind the codec's back: its last column is asked for again)
+        if (significant_changes) *significant_changes = idx->significance[(size_t)t];
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+extern "C" int jsp_sp_index_significance(const jsp_sp_index* idx, int* out) {
+    if (!idx || !out) return fail("sp_index_significance: null argument");
+    std::copy(idx->significance.begin(), idx->significance.end(), out);
+    return JSP_ZERO_STATE;
+}
+
+extern "C" int jsp_sp_index_info(const jsp_sp_index* idx, int* nframes, uint64_t* device_bytes, uint64_t* host_bytes) {
+    if (!idx) return fail("sp_index_info: null index");
+    if (nframes) *nframes = idx->nframes;
+    if (device_bytes) *device_bytes = idx->device_bytes();
+    if (host_bytes) *host_bytes = idx->host_bytes();
+    return JSP_ZERO_STATE;
+}
+
+extern "C" void jsp_sp_index_destroy(jsp_sp_index* idx) {
+    if (!idx) return;
+    // device memory only: no stream, event or decoder of the codec is touched, so the codec may be gone already
+    (void)hipSetDevice(idx->device);
+    delete idx;
+}

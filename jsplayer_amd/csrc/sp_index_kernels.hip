@@ -1,0 +1,131 @@
+// ScreenPressor seek index: frame t of a resident range in ONE launch (jsp_sp_index_show; host side in sp_index.cpp).
+//
+// Every inter frame of the index is literalised (HostDecoder::literalise_motion): no block reads the picture before it anywhere but at
+// its own position.  Pixel p of frame t is therefore the literal of the LAST frame in (k, t] whose changed rectangle covers p, else
+// pixel p of the key picture k.  The index keeps, in HBM: the key pictures, one 16-byte PBlock per inter frame and 16x16 block, the
+// literal pixels, and a changed-block bitmap (bitmap[w * nblocks + b], bit j: frame 32 w + j changes block b).
+//
+// One WAVE per 16x16 block, lane = (row, 4-pixel chunk); a workgroup is four neighbouring blocks, so its four waves together store
+// 256 contiguous bytes per row.  The lane loads its 4 pixels of the key picture first (most blocks of a desktop clip need nothing
+// else), then the wave walks the block's bitmap words DOWN from t / 32 to the word of frame k + 1, most recent frame first.  The
+// block number is wave-uniform, so bitmap words and PBlocks come through the scalar path; the records of up to four set bits are
+// fetched together before the first is applied.  A lane keeps a 4-bit mask of the pixels no rectangle has covered yet and takes
+// literals only for those; the wave stops when a ballot says nothing is left uncovered.  No LDS, no barrier.
+#include <hip/hip_runtime.h>
+
+#include "sp.h"
+
+namespace jsp::sp {
+namespace {
+
+constexpr int SHOW_WG = 256;   // four waves = four neighbouring blocks
+constexpr int SHOW_AHEAD = 4;  // records fetched per step of the walk
+
+struct Rect {   // a PBlock as the walk needs it
+    uint32_t x1, y1, x2, y2, payload16;   // payload16: first literal, in 16-byte units of the index's payload
+};
+__device__ __forceinline__ Rect unpack(const uint4 raw) {
+    return Rect{(raw.x >> 8) & 0xFFu, (raw.x >> 16) & 0xFFu, raw.x >> 24, raw.y & 0xFFu, raw.w};
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(SHOW_WG) void sp_index_show_kernel(uint32_t* __restrict__ dst, const uint32_t* __restrict__ key,
+                                                                const uint4* __restrict__ blocks, const uint32_t* __restrict__ payload,
+                                                                const uint32_t* __restrict__ bitmap, int t, int k, long slot_base,
+                                                                int X, int Y, int nbx, int nblocks) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int bx = (int)blockIdx.x * 4 + wave, by = (int)blockIdx.y;
+    if (bx >= nbx) return;
+    const int b = by * nbx + bx;
+    const int ly = lane >> 2, cx0 = (lane & 3) * 4;   // row and first column inside the block
+    const int y = by * 16 + ly, x0 = bx * 16 + cx0;
+    const bool mine = y < Y && x0 < X;
+    const size_t i0 = (size_t)y * (size_t)X + (size_t)x0;
+    uint32_t px[4] = {0, 0, 0, 0};
+    uint32_t need = 0;                                // bit j: pixel j of the chunk is inside the picture and not covered yet
+    if (mine) {
+        if (VEC) {                                    // (X % 4 == 0: the chunk is whole)
+            const uint4 q = *reinterpret_cast<const uint4*>(key + i0);
+            px[0] = q.x; px[1] = q.y; px[2] = q.z; px[3] = q.w;
+            need = 0xFu;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < X) { px[j] = key[i0 + j]; need |= 1u << j; }
+        }
+    }
+    if (t > k) {
+        const int wlo = (k + 1) >> 5;
+        int w = t >> 5;
+        uint32_t m = bitmap[(size_t)w * (size_t)nblocks + b] & (0xFFFFFFFFu >> (31 - (t & 31)));
+        bool open = true;
+        while (open) {
+            if (w == wlo) m &= 0xFFFFFFFFu << ((k + 1) & 31);   // frames up to k belong to the pictures before the key frame
+            while (m != 0u && open) {
+                // the most recent SHOW_AHEAD writers of this word: their records are fetched together, applied newest first
+                int f[SHOW_AHEAD];
+                uint4 raw[SHOW_AHEAD];
+                int n = 0;
+#pragma unroll
+                for (int a = 0; a < SHOW_AHEAD; ++a) {
+                    f[a] = -1;
+                    if (m != 0u) {
+                        const int bit = 31 - __builtin_clz(m);
+                        m &= ~(1u << bit);
+                        f[a] = 32 * w + bit;
+                        raw[a] = blocks[((size_t)((long)f[a] + slot_base)) * (size_t)nblocks + b];
+                        ++n;
+                    }
+                }
+#pragma unroll
+                for (int a = 0; a < SHOW_AHEAD; ++a) {
+                    if (a < n && open) {
+                        const Rect r = unpack(raw[a]);
+                        if (need != 0u && (uint32_t)ly >= r.y1 && (uint32_t)ly < r.y2) {
+                            const uint32_t* lit = payload + (size_t)r.payload16 * 4 + (size_t)(((uint32_t)ly - r.y1) * (r.x2 - r.x1));
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                const uint32_t rx = (uint32_t)(cx0 + j);
+                                if (((need >> j) & 1u) && rx >= r.x1 && rx < r.x2) {
+                                    px[j] = lit[rx - r.x1];
+                                    need &= ~(1u << j);
+                                }
+                            }
+                        }
+                        open = __ballot(need != 0u) != 0ull;   // every pixel of the block has its last writer: done
+                    }
+                }
+            }
+            if (w == wlo) break;
+            --w;
+            m = bitmap[(size_t)w * (size_t)nblocks + b];
+        }
+    }
+    if (!mine) return;
+    if (VEC) *reinterpret_cast<uint4*>(dst + i0) = make_uint4(px[0], px[1], px[2], px[3]);
+    else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (x0 + j < X) dst[i0 + j] = px[j];
+    }
+}
+
+}  // namespace
+
+void launch_index_show(const Geometry& g, int32_t* dst, const int32_t* key, const PBlock* d_blocks, const uint32_t* d_payload,
+                       const uint32_t* d_bitmap, int t, int k, long slot_base, hipStream_t stream) {
+    const bool vec = (g.X & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (reinterpret_cast<uintptr_t>(key) & 15) == 0;
+    const dim3 grid((g.nbx + 3) / 4, g.nby);
+    const int nblocks = g.nbx * g.nby;
+    if (vec)
+        hipLaunchKernelGGL(sp_index_show_kernel<true>, grid, dim3(SHOW_WG), 0, stream, reinterpret_cast<uint32_t*>(dst),
+                           reinterpret_cast<const uint32_t*>(key), reinterpret_cast<const uint4*>(d_blocks), d_payload, d_bitmap, t, k,
+                           slot_base, g.X, g.Y, g.nbx, nblocks);
+    else
+        hipLaunchKernelGGL(sp_index_show_kernel<false>, grid, dim3(SHOW_WG), 0, stream, reinterpret_cast<uint32_t*>(dst),
+                           reinterpret_cast<const uint32_t*>(key), reinterpret_cast<const uint4*>(d_blocks), d_payload, d_bitmap, t, k,
+                           slot_base, g.X, g.Y, g.nbx, nblocks);
+}
+
+}  // namespace jsp::sp

@@ -12,7 +12,8 @@ DataLoader.FindPossibleChange (DataLoader.hx:239-252) plus the SeekTo that Main.
 answer: significance already known is used as it is, and the frames nobody has judged go to the
 decoder's `FindChange` (MSVideo1 on the GPU: one call) or through `worker` frame by frame.  With a seek index
 attached (`Manager.attach_index`: a range kept resident by the decoder's `BuildIndex`), a seek inside it is one
-`Show` launch and its frames' significance is known without decoding; `next_frame` / `prev_frame` / `next_key` /
+`Show` launch and its frames' significance is known without decoding (an index that cannot leave the decoder at the frame
+shown — ScreenPressor's, `ADOPTS` false — serves the frame and leaves the decode position where it is); `next_frame` / `prev_frame` / `next_key` /
 `prev_key` are the navigation of Manager.hx:184-208 over `seek`.  Timers, bitmaps and audio of the reference's
 Manager are not rebuilt.
 """
@@ -98,8 +99,13 @@ class Manager:
     def attach_index(self, index, first: int = 0) -> None:
         """Serve seeks to clip frames first .. first + index.frames - 1 from `index` (the decoder's BuildIndex over those frames,
         built where the decoder's state was that of frame first - 1 — typically from a key frame): one Show launch each, and the
-        index's significance verdicts count as known.  None detaches."""
+        index's significance verdicts count as known.  None detaches.  An index whose `ADOPTS` is false (ScreenPressor's
+        BuildScrubIndex) shows pictures without moving the decoder: a frame inside it is served before the decode position is
+        touched, and decoding continues later from where the decoder really stands."""
         self.index, self.index_first = index, int(first)
+
+    def _index_adopts(self) -> bool:
+        return bool(getattr(self.index, "ADOPTS", True))
 
     def _in_index(self, i: int) -> bool:
         return self.index is not None and self.index_first <= i < self.index_first + self.index.frames
@@ -110,6 +116,8 @@ class Manager:
         attached, or `i` outside it: ValueError (a hover preview is not worth a decode)."""
         if not self._in_index(i):
             raise ValueError(f"frame {i} is not in an attached seek index")
+        if not hasattr(self.index, "Thumbs"):
+            raise ValueError("the attached seek index has no thumbnails")
         return self.index.Thumbs([i - self.index_first], scale=scale, cols=1)
 
     def filmstrip(self, n: int, scale: int = 8, cols: Optional[int] = None):
@@ -118,6 +126,8 @@ class Manager:
         `preview`.  No index attached: ValueError."""
         if self.index is None:
             raise ValueError("no seek index attached")
+        if not hasattr(self.index, "Thumbs"):
+            raise ValueError("the attached seek index has no thumbnails")
         n = int(n)
         if n < 1:
             raise ValueError("a filmstrip needs at least one frame")
@@ -220,6 +230,19 @@ class Manager:
         for nb, h in enumerate(self.holds):
             if h is not None and h.start <= index < h.stop:
                 return DecodedFrame(index, self._key_at(frames, index, key_flags), nb, None)
+        if self._in_index(index) and not self._index_adopts():
+            # one launch into a free buffer, never the decoder's previous frame; the decoder, the decode position and the other
+            # holds stay as they are: a later seek outside the index, or play, goes on from where the decoder really stands
+            prev = self.decoder.PreviousFrame()
+            prev_idx = self._slot_of(prev) if prev is not None else -1
+            free = self._get_free_buffer(prev_idx)
+            if free < 0:   # (a walk backwards: every hold lies after the frame of interest — the one farthest from it goes)
+                free = max((nb for nb in range(len(self.holds)) if nb != prev_idx), key=lambda nb: abs(self.holds[nb].start - index))
+            res = self.index.Show(index - self.index_first, self.buffers[free])
+            self.holds[free] = range(index, index + 1)
+            out = DecodedFrame(index, self._key_at(frames, index, key_flags), free, res.significant_changes)
+            self.log.append(out)
+            return out
         key_idx = nearest_key_frame(lambda i: self._key_at(frames, i, key_flags), index, len(frames))
         if self.next_frame_to_decode < key_idx or self.next_frame_to_decode > index:
             self.next_frame_to_decode = key_idx
