@@ -19,8 +19,8 @@
 //                                to 0, one jsp_index_show each (Main.on_prevframe, Manager.hx:191-196); prints "<index> <key|inter>
 //                                <changed> <crc32>" per frame — sorted, the plain run's frames, significance and CRCs
 //   jsp_play clip.avi --filmstrip N[:scale]
-//                                MSVideo1: ONE seek index over the clip, then ONE jsp_index_thumbs call for N frames spread evenly over
-//                                it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
+//                                ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build), then ONE
+//                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
 //                                8) — the seek bar's hover preview / a contact sheet (Main.on_mouse_move, Main.hx:1147-1215); prints
 //                                "<frame> <crc32 of the thumbnail's words>" per thumbnail
 //   jsp_play clip.avi --seek N   MSVideo1: frame N first, through ONE jsp_seek from the nearest key frame (DataLoader.hx:125-132;
@@ -650,7 +650,7 @@ int main(int argc, char** argv) {
         jsp_codec_destroy(dec);
         return rc;
     }
-    if (strip > 0) {   // the seek bar's preview pictures: one index build, then ONE jsp_index_thumbs for all of them
+    if (strip > 0) {   // the seek bar's preview pictures: one index build, then ONE jsp_index_thumbs / jsp_sp_index_thumbs for all of them
         const size_t n = clip.frames.size();
         std::vector<const uint8_t*> srcs;
         std::vector<size_t> lens;
@@ -660,10 +660,18 @@ int main(int argc, char** argv) {
             lens.push_back(clip.frames[i].second);
             keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
         }
-        jsp_index* idx = n ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
-        if (!idx) { std::fprintf(stderr, "jsp_index_build: %s\n", n ? jsp_last_error() : "no frames"); rc = 1; }
+        const bool sp = clip.kind == JSP_CODEC_SCREENPRESSOR;   // the same two calls on the index of either codec
+        jsp_index* idx = n && !sp ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        jsp_sp_index* sidx = n && sp ? jsp_sp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        const char* const build_call = sp ? "jsp_sp_index_build" : "jsp_index_build";
+        const char* const size_call = sp ? "jsp_sp_index_thumb_size" : "jsp_index_thumb_size";
+        const char* const thumbs_call = sp ? "jsp_sp_index_thumbs" : "jsp_index_thumbs";
+        if (!idx && !sidx) { std::fprintf(stderr, "%s: %s\n", build_call, n ? jsp_last_error() : "no frames"); rc = 1; }
         int tw = 0, th = 0;
-        if (idx && jsp_index_thumb_size(idx, strip_scale, &tw, &th) != JSP_ZERO_STATE) { std::fprintf(stderr, "jsp_index_thumb_size: %s\n", jsp_last_error()); rc = 1; }
+        if (rc == 0 && (sp ? jsp_sp_index_thumb_size(sidx, strip_scale, &tw, &th) : jsp_index_thumb_size(idx, strip_scale, &tw, &th)) != JSP_ZERO_STATE) {
+            std::fprintf(stderr, "%s: %s\n", size_call, jsp_last_error());
+            rc = 1;
+        }
         jsp_pool* sheet = nullptr;   // cols = 1: a plain [N][th][tw] array, one "frame" of tw x N th pixels
         if (rc == 0 && !(sheet = jsp_pool_create(0, tw, strip * th, 1))) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
         if (rc == 0) {
@@ -671,15 +679,18 @@ int main(int argc, char** argv) {
             for (int k = 0; k < strip; ++k) picks.push_back((int)(((long long)k * (long long)n) / strip));
             const size_t cell = (size_t)tw * th;
             std::vector<int32_t> thumbs(cell * (size_t)strip);
-            if (jsp_index_thumbs(dec, idx, strip, picks.data(), strip_scale, 1, jsp_pool_buffer(sheet, 0), thumbs.size()) != JSP_ZERO_STATE ||
-                jsp_download(jsp_pool_buffer(sheet, 0), thumbs.data(), thumbs.size()) != 0) {
-                std::fprintf(stderr, "jsp_index_thumbs: %s\n", jsp_last_error());
+            int32_t* out = jsp_pool_buffer(sheet, 0);
+            if ((sp ? jsp_sp_index_thumbs(dec, sidx, strip, picks.data(), strip_scale, 1, out, thumbs.size())
+                    : jsp_index_thumbs(dec, idx, strip, picks.data(), strip_scale, 1, out, thumbs.size())) != JSP_ZERO_STATE ||
+                jsp_download(out, thumbs.data(), thumbs.size()) != 0) {
+                std::fprintf(stderr, "%s: %s\n", thumbs_call, jsp_last_error());
                 rc = 1;
             }
             for (int k = 0; rc == 0 && k < strip; ++k)
                 std::printf("%d %08x\n", picks[k], crc32(reinterpret_cast<const uint8_t*>(thumbs.data() + cell * (size_t)k), cell * 4));
         }
         if (sheet) jsp_pool_destroy(sheet);
+        jsp_sp_index_destroy(sidx);
         jsp_index_destroy(idx);
         jsp_pool_destroy(pool);
         jsp_codec_destroy(dec);

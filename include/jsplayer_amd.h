@@ -450,13 +450,42 @@ int jsp_index_thumbs(jsp_codec* c, jsp_index* idx, int n, const int* frames, int
  *       outside 0..nframes-1, an asynchronous frame in flight, `dst` = the codec's current previous frame, a host-pointer `dst`.
  * Significance: out[0..nframes-1] = 1 / 0, the verdict Show reports for each frame.
  * Info: frames, and the bytes the index holds in HBM and in host memory (the build's staging memory is released when it returns).
- * Destroy: frees the index's device memory only; safe before or after jsp_codec_destroy of its codec. */
+ * Destroy: frees the index's device (and pinned) memory only; safe before or after jsp_codec_destroy of its codec. */
 typedef struct jsp_sp_index jsp_sp_index;
 jsp_sp_index* jsp_sp_index_build(jsp_codec* c, int nframes, const uint8_t* const* srcs, const size_t* lens, const uint8_t* is_key, int key_row);
 int jsp_sp_index_show(jsp_codec* c, jsp_sp_index* idx, int t, int32_t* dst, int* significant_changes);
 int jsp_sp_index_significance(const jsp_sp_index* idx, int* out);
 int jsp_sp_index_info(const jsp_sp_index* idx, int* nframes, uint64_t* device_bytes, uint64_t* host_bytes);
 void jsp_sp_index_destroy(jsp_sp_index* idx);
+
+/* ---- thumbnails of a ScreenPressor index: jsp_index_thumb_size / jsp_index_thumbs for a jsp_sp_index, the same contract wherever it
+ * can be, so that a caller treats both kinds of index alike --------------------------------------------------------------------------
+ * Thumb size: for scale s = 4, 8 or 16, *width = X / s and *height = Y / s: whole s x s squares of the picture.  For these three
+ *   scales that equals the MSVideo1 formula (4 * (W / 4)) / s, so one rule (tests/thumbs_ref.thumb_size) serves both.  The X % s /
+ *   Y % s remainder pixels are left out.  A refused call writes neither, as jsp_index_thumb_size.
+ * Thumbs: EQUIVALENCE  thumbnail k is the picture that jsp_sp_index_show(frames[k]) writes, reduced: pixel (x, y), per byte channel of
+ *       the words, = (sum over the s x s source pixels at (x s .. x s + s - 1, y s .. y s + s - 1) + s s / 2) >> log2(s s); top byte
+ *       0.  Rows keep the frame's bottom-up order.  There is no "picture before the range": a ScreenPressor index starts at a coded
+ *       key frame and every pixel of every frame is defined.
+ *   16 BPP  frames carry one 5-bit component per byte (Manager.hx:362-370), so the per-byte mean is the per-component mean and stays
+ *       at most 31 per byte: jsp_display_convert with JSP_DISPLAY_CANVAS_RGB15 applies to a thumbnail, or to a whole sheet, as it
+ *       does to a frame.  (A FLAT 16-bpp key frame is the reference's exception, in frames and so in thumbnails: it fills the picture
+ *       with components already shifted left by 3, ScreenPressor.hx:134-139.  A mean never exceeds what it is the mean of.)
+ *   SHEET  as jsp_index_thumbs: `out` is one image of cols * width by ceil(n / cols) * height pixels, pitch cols * width; thumbnail k
+ *       has its pixel (0, 0) at (k / cols) * height * pitch + (k % cols) * width.  The cells of the last sheet row past n are not
+ *       written.  frames[] is any list of frames of the index: unordered, repeats allowed.
+ *   ONE kernel launch whatever n (sp_index_thumbs_kernel): per 16x16 block and thumbnail the walk of sp_index_show_kernel, the block
+ *       kept in the wave's registers and summed across lanes; no full-size picture is written anywhere.  Runs on the codec's stream
+ *       and returns synchronised.  THE CODEC IS ONLY LENT, as for Show; and since no frame buffer is written, the codec forgets
+ *       nothing either.  One 24-byte record per thumbnail travels through pinned memory into a device array the index owns (both
+ *       grown on demand, counted in jsp_sp_index_info; an index never asked for thumbnails holds neither).
+ *   PRECONDITIONS  `out` is a device buffer of at least out_pixels ints; no asynchronous frame in flight.
+ *   ERRORS  A null argument, an MSVideo1 codec ("sp_index: ScreenPressor only"), an index built by another codec, n outside 1..4096,
+ *       a frame number outside the index, a scale other than 4 / 8 / 16, a picture too small for one thumbnail pixel at this scale,
+ *       cols < 1, out_pixels smaller than the sheet, a violated precondition: JSP_ERROR_OCCURED, jsp_last_error() ("sp_index_thumbs:"
+ *       / "sp_index_thumb_size:" ...), nothing written. */
+int jsp_sp_index_thumb_size(const jsp_sp_index* idx, int scale, int* width, int* height);
+int jsp_sp_index_thumbs(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels);
 
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 

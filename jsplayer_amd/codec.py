@@ -408,11 +408,51 @@ class StagedBatch:
             pass
 
 
-class SeekIndex:
+class _IndexThumbs:
+    """ThumbSize / Thumbs of a seek index, MSVideo1 or ScreenPressor: the two C calls have one contract, so the sheet arithmetic is
+    here once.  A subclass names its pair of C functions in `_THUMB_CALLS` and has `_open(who)` (the codec, or CodecError)."""
+
+    _THUMB_CALLS = ("", "")   # (thumb_size, thumbs): exports of the library, without the "jsp_" in front
+
+    def ThumbSize(self, scale: int) -> tuple:
+        """(width, height) of a thumbnail at `scale` (4, 8 or 16): whole scale x scale squares of the picture (of its whole 4x4
+        blocks for MSVideo1, which is the same number at these scales)."""
+        size_call, _ = self._THUMB_CALLS
+        self._open(size_call)
+        tw, th = C.c_int(0), C.c_int(0)
+        if getattr(self._lib, "jsp_" + size_call)(self._h, int(scale), C.byref(tw), C.byref(th)) != 0:
+            raise CodecError(N.last_error())
+        return tw.value, th.value
+
+    def Thumbs(self, frames, scale: int = 8, cols: int = 1, out=None):
+        """The pictures of `frames` (any frame numbers of the index: unordered, repeats allowed, 1..4096 of them), each reduced
+        scale x scale pixels to one (box mean, rounded half up), `cols` to a sheet row: ONE launch, the codec is not touched.
+        Returns the sheet, an int32 device tensor of shape (ceil(n / cols) * TH, cols * TW) — `out` (contiguous, at least that
+        many elements; cells of the last row past n keep what they held) or a new zero-filled one.  Rows are bottom-up as in a
+        frame."""
+        size_call, thumbs_call = self._THUMB_CALLS
+        codec = self._open(thumbs_call)
+        frames = [int(t) for t in frames]
+        n, scale, cols = len(frames), int(scale), int(cols)
+        tw, th = C.c_int(0), C.c_int(0)
+        getattr(self._lib, "jsp_" + size_call)(self._h, scale, C.byref(tw), C.byref(th))   # (refused: 0 x 0, and the thumbs call says why)
+        rows, width = -(-n // max(cols, 1)) * th.value, max(cols, 1) * tw.value
+        if out is None:
+            import torch
+            out = torch.zeros(max(rows * width, 1), dtype=torch.int32, device=f"cuda:{codec._device}")
+        arr = (C.c_int * max(n, 1))(*frames)
+        rc = getattr(self._lib, "jsp_" + thumbs_call)(codec._h, self._h, n, arr, scale, cols, C.c_void_p(_frame_ptr(out, 0)), int(np.prod(out.shape)))
+        if rc != 0:
+            raise CodecError(N.last_error())
+        return out.reshape(-1)[:rows * width].reshape(rows, width)
+
+
+class SeekIndex(_IndexThumbs):
     """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch.  `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
     ADOPTS = True   # Show(adopt=True) leaves the decoder at frame t: a Manager moves its decode position with it
+    _THUMB_CALLS = ("index_thumb_size", "index_thumbs")
 
     def __init__(self, codec: _NativeCodec, handle: int, prev_at_build):
         self._codec, self._h = codec, handle
@@ -453,35 +493,6 @@ class SeekIndex:
         if not self._codec._h:
             raise CodecError(f"{who}: the codec is closed")
         return self._codec
-
-    def ThumbSize(self, scale: int) -> tuple:
-        """(width, height) of a thumbnail at `scale` (4, 8 or 16): whole scale x scale squares of the picture's whole 4x4 blocks."""
-        self._open("index_thumb_size")
-        tw, th = C.c_int(0), C.c_int(0)
-        if self._lib.jsp_index_thumb_size(self._h, int(scale), C.byref(tw), C.byref(th)) != 0:
-            raise CodecError(N.last_error())
-        return tw.value, th.value
-
-    def Thumbs(self, frames, scale: int = 8, cols: int = 1, out=None):
-        """The pictures of `frames` (any frame numbers of the index: unordered, repeats allowed, 1..4096 of them), each reduced
-        scale x scale pixels to one (box mean, rounded half up), `cols` to a sheet row: ONE launch, the codec is not touched.
-        Returns the sheet, an int32 device tensor of shape (ceil(n / cols) * TH, cols * TW) — `out` (contiguous, at least that
-        many elements; cells of the last row past n keep what they held) or a new zero-filled one.  Rows are bottom-up as in a
-        frame."""
-        codec = self._open("index_thumbs")
-        frames = [int(t) for t in frames]
-        n, scale, cols = len(frames), int(scale), int(cols)
-        tw, th = C.c_int(0), C.c_int(0)
-        self._lib.jsp_index_thumb_size(self._h, scale, C.byref(tw), C.byref(th))   # (refused: 0 x 0, and jsp_index_thumbs says why)
-        rows, width = -(-n // max(cols, 1)) * th.value, max(cols, 1) * tw.value
-        if out is None:
-            import torch
-            out = torch.zeros(max(rows * width, 1), dtype=torch.int32, device=f"cuda:{codec._device}")
-        arr = (C.c_int * max(n, 1))(*frames)
-        rc = self._lib.jsp_index_thumbs(codec._h, self._h, n, arr, scale, cols, C.c_void_p(_frame_ptr(out, 0)), int(np.prod(out.shape)))
-        if rc != 0:
-            raise CodecError(N.last_error())
-        return out.reshape(-1)[:rows * width].reshape(rows, width)
 
     def close(self) -> None:
         if self._h:
@@ -546,12 +557,14 @@ class ScreenPressor(_NativeCodec):
         return SpScrubIndex(self, h)
 
 
-class SpScrubIndex:
-    """A ScreenPressor range resident in HBM (jsp_sp_index_build, via ScreenPressor.BuildScrubIndex): Show(t) is one launch.
+class SpScrubIndex(_IndexThumbs):
+    """A ScreenPressor range resident in HBM (jsp_sp_index_build, via ScreenPressor.BuildScrubIndex): Show(t) is one launch,
+    Thumbs(frames) one launch for any number of downscaled frames (jsp_sp_index_thumbs; _IndexThumbs has the two methods).
     `significance` = the verdict the sequential run records for every frame, `frames`, `device_bytes`, `host_bytes`.  close() (or
     the context manager) frees it; safe after the codec is gone."""
 
     ADOPTS = False   # Show never moves the decoder: a Manager serves the frame and leaves its decode position where it is
+    _THUMB_CALLS = ("sp_index_thumb_size", "sp_index_thumbs")
 
     def __init__(self, codec: _NativeCodec, handle: int):
         self._codec, self._h = codec, handle
@@ -579,6 +592,13 @@ class SpScrubIndex:
         if self._lib.jsp_sp_index_show(codec._h, self._h, int(t), C.c_void_p(addr), C.byref(signif)) != 0:
             raise CodecError(N.last_error())
         return PFrameResult(dst, bool(signif.value))
+
+    def _open(self, who: str) -> _NativeCodec:
+        if not self._h:
+            raise CodecError(f"{who}: the index is closed")
+        if not self._codec._h:
+            raise CodecError(f"{who}: the codec is closed")
+        return self._codec
 
     def close(self) -> None:
         if self._h:

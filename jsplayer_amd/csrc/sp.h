@@ -270,6 +270,18 @@ void launch_pframe_group(const Geometry& g, const PGroupFrame* d_frames, int nfr
 // 16-byte units of d_payload there; d_bitmap[w * nblocks + b] bit j: frame 32 w + j changes block b.  Every pixel of dst is written.
 void launch_index_show(const Geometry& g, int32_t* dst, const int32_t* key, const PBlock* d_blocks, const uint32_t* d_payload,
                        const uint32_t* d_bitmap, int t, int k, long slot_base, hipStream_t stream);
+// Thumbnails of the seek index (sp_index_thumbs_kernel): the pictures launch_index_show would write for d_recs[0..n), each reduced
+// scale x scale pixels to one (scale 4, 8 or 16; box mean per byte, rounded half up), into the sheet `out`: thumbnails of (X / scale) x
+// (Y / scale) pixels, `cols` to a sheet row, row pitch cols thumbnail widths.  ONE launch; no full-size picture is written.
+struct IndexThumbRec {   // one per thumbnail: what launch_index_show takes as arguments
+    int32_t t, k;            // the frame and its key frame
+    uint32_t key_slot, pad;  // the key picture is d_keys + key_slot * pic_stride
+    int64_t slot_base;
+};
+static_assert(sizeof(IndexThumbRec) == 24, "IndexThumbRec is 24 bytes");
+void launch_index_thumbs(const Geometry& g, int32_t* out, const int32_t* d_keys, size_t pic_stride, const IndexThumbRec* d_recs, int n,
+                         const PBlock* d_blocks, const uint32_t* d_payload, const uint32_t* d_bitmap, int scale, int cols,
+                         hipStream_t stream);
 constexpr int kGroupMaxFrames = 65535;        // frames one group launch may walk
 size_t iframe_lds_bytes(const Geometry& g, int band_rows = 0);
 constexpr int kMaxIntraWidth = 8192;  // LDS plan of the row-wavefront kernel

@@ -1,5 +1,6 @@
 // The ScreenPressor seek index of include/jsplayer_amd.h — jsp_sp_index_* —: the host entropy stage runs over a range ONCE, its
-// records stay resident in HBM, and any frame of the range is then one launch of sp_index_show_kernel (sp_index_kernels.hip).
+// records stay resident in HBM, and any frame of the range is then one launch of sp_index_show_kernel, the thumbnails of any n frames
+// of it one launch of sp_index_thumbs_kernel (sp_index_kernels.hip).
 //
 // Kept apart from sp_codec.cpp / jsp_api.cpp: those are also built against the stub kernels of the host-layer sanitizer build
 // (tools/tsan_cpu.sh), which knows nothing of the index kernel.  What the build needs of the codec comes through sp::IndexLender.
@@ -28,10 +29,12 @@ struct jsp_sp_index {
     std::vector<int32_t> key_slot;   // per frame: which picture of d_keys that is
     std::vector<int64_t> slot_base;  // per frame: its block table is d_blocks + (frame + slot_base) * nblocks (key frames: unused)
     std::vector<int> significance;   // per frame: the verdict of the sequential run (1 / 0)
-    uint64_t device_bytes() const { return d_keys.cap + d_blocks.cap + d_payload.cap + d_bitmap.cap; }
+    PinnedBuffer h_thumb_recs;       // jsp_sp_index_thumbs: the call's per-thumbnail records on their way to ...
+    DeviceBuffer d_thumb_recs;       // ... the array the kernel reads (both grown on demand: nothing until the first call)
+    uint64_t device_bytes() const { return d_keys.cap + d_blocks.cap + d_payload.cap + d_bitmap.cap + d_thumb_recs.cap; }
     uint64_t host_bytes() const {
         return sizeof(*this) + key_of.size() * sizeof(int32_t) + key_slot.size() * sizeof(int32_t) + slot_base.size() * sizeof(int64_t) +
-               significance.size() * sizeof(int);
+               significance.size() * sizeof(int) + h_thumb_recs.cap;
     }
     const int32_t* key_picture(int t) const { return static_cast<const int32_t*>(d_keys.p) + (size_t)key_slot[(size_t)t] * pic_stride; }
     void show(int t, int32_t* dst, hipStream_t stream) const {
@@ -336,6 +339,67 @@ extern "C" int jsp_sp_index_show(jsp_codec* c, jsp_sp_index* idx, int t, int32_t
     }
 }
 
+// ---- thumbnails: the preview that follows the pointer along the seek bar, a filmstrip or contact sheet of a screen recording — n
+// frames of the index, each reduced scale x scale pixels to one, in ONE launch of sp_index_thumbs_kernel.  The full-size pictures never
+// exist and no frame buffer is written, so the codec is lent its stream and nothing else (no forget_buffer either).
+namespace {
+// The thumbnail of an index at `scale`: false (error set) for a scale other than 4 / 8 / 16 or a picture too small for one pixel.
+bool thumb_size(const jsp_sp_index* idx, int scale, const char* who, int& tw, int& th) {
+    if (scale != 4 && scale != 8 && scale != 16) { set_error("%s: scale must be 4, 8 or 16", who); return false; }
+    tw = idx->geo.X / scale;
+    th = idx->geo.Y / scale;
+    if (tw > 0 && th > 0) return true;
+    set_error("%s: the picture is too small for a thumbnail at this scale", who);
+    return false;
+}
+}  // namespace
+
+extern "C" int jsp_sp_index_thumb_size(const jsp_sp_index* idx, int scale, int* width, int* height) {
+    if (!idx || !width || !height) return fail("sp_index_thumb_size: null argument");
+    int tw = 0, th = 0;
+    if (!thumb_size(idx, scale, "sp_index_thumb_size", tw, th)) return JSP_ERROR_OCCURED;
+    *width = tw;
+    *height = th;
+    return JSP_ZERO_STATE;
+}
+
+extern "C" int jsp_sp_index_thumbs(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out,
+                                   size_t out_pixels) {
+    if (!c || !idx || !frames || !out) return fail("sp_index_thumbs: null argument");
+    if (c->kind != JSP_CODEC_SCREENPRESSOR || !dynamic_cast<IndexLender*>(c)) return fail("sp_index: ScreenPressor only");
+    if (idx->codec_serial != c->serial) return fail("sp_index_thumbs: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("sp_index_thumbs: n is outside 1..4096");
+    for (int k = 0; k < n; ++k)
+        if (frames[k] < 0 || frames[k] >= idx->nframes) return fail("sp_index_thumbs: a frame number is outside the index");
+    int tw = 0, th = 0;
+    if (!thumb_size(idx, scale, "sp_index_thumbs", tw, th)) return JSP_ERROR_OCCURED;
+    if (cols < 1) return fail("sp_index_thumbs: cols must be at least 1");
+    const uint64_t sheet = (uint64_t)cols * (uint64_t)tw * (uint64_t)((n + (int64_t)cols - 1) / cols) * (uint64_t)th;
+    if ((uint64_t)out_pixels < sheet) return fail("sp_index_thumbs: out_pixels is smaller than the sheet");
+    if (c->next_ticket != c->oldest_ticket) return fail("sp_index_thumbs: an asynchronous frame is in flight (jsp_wait for it first)");
+    try {
+        c->activate();
+        if (!on_device(out)) return fail("sp_index_thumbs: out must be a device buffer");
+        idx->h_thumb_recs.reserve(sizeof(IndexThumbRec) * (size_t)n);
+        idx->d_thumb_recs.reserve(sizeof(IndexThumbRec) * (size_t)n);
+        auto* recs = static_cast<IndexThumbRec*>(idx->h_thumb_recs.p);
+        for (int k = 0; k < n; ++k) {
+            const size_t t = (size_t)frames[k];
+            recs[k] = IndexThumbRec{frames[k], idx->key_of[t], (uint32_t)idx->key_slot[t], 0u, idx->slot_base[t]};
+        }
+        JSP_HIP(hipMemcpyAsync(idx->d_thumb_recs.p, recs, sizeof(IndexThumbRec) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        launch_index_thumbs(idx->geo, out, static_cast<const int32_t*>(idx->d_keys.p), idx->pic_stride,
+                            static_cast<const IndexThumbRec*>(idx->d_thumb_recs.p), n, static_cast<const PBlock*>(idx->d_blocks.p),
+                            static_cast<const uint32_t*>(idx->d_payload.p), static_cast<const uint32_t*>(idx->d_bitmap.p), scale, cols, c->stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned records are free for the next call)
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
 extern "C" int jsp_sp_index_significance(const jsp_sp_index* idx, int* out) {
     if (!idx || !out) return fail("sp_index_significance: null argument");
     std::copy(idx->significance.begin(), idx->significance.end(), out);
@@ -352,7 +416,8 @@ extern "C" int jsp_sp_index_info(const jsp_sp_index* idx, int* nframes, uint64_t
 
 extern "C" void jsp_sp_index_destroy(jsp_sp_index* idx) {
     if (!idx) return;
-    // device memory only: no stream, event or decoder of the codec is touched, so the codec may be gone already
+    // device memory (and the pinned records of jsp_sp_index_thumbs) only: no stream, event or decoder of the codec is touched, so the
+    // codec may be gone already
     (void)hipSetDevice(idx->device);
     delete idx;
 }

@@ -1,4 +1,5 @@
-// ScreenPressor seek index: frame t of a resident range in ONE launch (jsp_sp_index_show; host side in sp_index.cpp).
+// ScreenPressor seek index: frame t of a resident range in ONE launch (jsp_sp_index_show), and the thumbnails of any n frames of it in
+// ONE launch (jsp_sp_index_thumbs, at the end of the file); host side in sp_index.cpp.
 //
 // Every inter frame of the index is literalised (HostDecoder::literalise_motion): no block reads the picture before it anywhere but at
 // its own position.  Pixel p of frame t is therefore the literal of the LAST frame in (k, t] whose changed rectangle covers p, else
@@ -28,6 +29,74 @@ __device__ __forceinline__ Rect unpack(const uint4 raw) {
     return Rect{(raw.x >> 8) & 0xFFu, (raw.x >> 16) & 0xFFu, raw.x >> 24, raw.y & 0xFFu, raw.w};
 }
 
+// The walk, shared by the show and the thumbnail kernel: the lane's 4 pixels of frame t of block b — row ly, columns cx0 .. cx0 + 3 of
+// the block, pixel i0 of the picture — into px[].  Pixels outside the picture (`mine` false, or past column X - 1) come out as 0.
+// EVERY lane of the wave must call it (the walk ends on a ballot), with wave-uniform b, t, k and slot_base.
+template <bool VEC>
+__device__ __forceinline__ void index_compose(uint32_t (&px)[4], const uint32_t* __restrict__ key, const uint4* __restrict__ blocks,
+                                              const uint32_t* __restrict__ payload, const uint32_t* __restrict__ bitmap, int t, int k,
+                                              long slot_base, int X, int nblocks, int b, int ly, int cx0, int x0, size_t i0, bool mine) {
+    px[0] = px[1] = px[2] = px[3] = 0u;
+    uint32_t need = 0;                                // bit j: pixel j of the chunk is inside the picture and not covered yet
+    if (mine) {
+        if (VEC) {                                    // (X % 4 == 0: the chunk is whole)
+            const uint4 q = *reinterpret_cast<const uint4*>(key + i0);
+            px[0] = q.x; px[1] = q.y; px[2] = q.z; px[3] = q.w;
+            need = 0xFu;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < X) { px[j] = key[i0 + j]; need |= 1u << j; }
+        }
+    }
+    if (t <= k) return;
+    const int wlo = (k + 1) >> 5;
+    int w = t >> 5;
+    uint32_t m = bitmap[(size_t)w * (size_t)nblocks + b] & (0xFFFFFFFFu >> (31 - (t & 31)));
+    bool open = true;
+    while (open) {
+        if (w == wlo) m &= 0xFFFFFFFFu << ((k + 1) & 31);   // frames up to k belong to the pictures before the key frame
+        while (m != 0u && open) {
+            // the most recent SHOW_AHEAD writers of this word: their records are fetched together, applied newest first
+            int f[SHOW_AHEAD];
+            uint4 raw[SHOW_AHEAD];
+            int n = 0;
+#pragma unroll
+            for (int a = 0; a < SHOW_AHEAD; ++a) {
+                f[a] = -1;
+                if (m != 0u) {
+                    const int bit = 31 - __builtin_clz(m);
+                    m &= ~(1u << bit);
+                    f[a] = 32 * w + bit;
+                    raw[a] = blocks[((size_t)((long)f[a] + slot_base)) * (size_t)nblocks + b];
+                    ++n;
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < SHOW_AHEAD; ++a) {
+                if (a < n && open) {
+                    const Rect r = unpack(raw[a]);
+                    if (need != 0u && (uint32_t)ly >= r.y1 && (uint32_t)ly < r.y2) {
+                        const uint32_t* lit = payload + (size_t)r.payload16 * 4 + (size_t)(((uint32_t)ly - r.y1) * (r.x2 - r.x1));
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const uint32_t rx = (uint32_t)(cx0 + j);
+                            if (((need >> j) & 1u) && rx >= r.x1 && rx < r.x2) {
+                                px[j] = lit[rx - r.x1];
+                                need &= ~(1u << j);
+                            }
+                        }
+                    }
+                    open = __ballot(need != 0u) != 0ull;   // every pixel of the block has its last writer: done
+                }
+            }
+        }
+        if (w == wlo) break;
+        --w;
+        m = bitmap[(size_t)w * (size_t)nblocks + b];
+    }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(SHOW_WG) void sp_index_show_kernel(uint32_t* __restrict__ dst, const uint32_t* __restrict__ key,
                                                                 const uint4* __restrict__ blocks, const uint32_t* __restrict__ payload,
@@ -42,66 +111,8 @@ __global__ __launch_bounds__(SHOW_WG) void sp_index_show_kernel(uint32_t* __rest
     const int y = by * 16 + ly, x0 = bx * 16 + cx0;
     const bool mine = y < Y && x0 < X;
     const size_t i0 = (size_t)y * (size_t)X + (size_t)x0;
-    uint32_t px[4] = {0, 0, 0, 0};
-    uint32_t need = 0;                                // bit j: pixel j of the chunk is inside the picture and not covered yet
-    if (mine) {
-        if (VEC) {                                    // (X % 4 == 0: the chunk is whole)
-            const uint4 q = *reinterpret_cast<const uint4*>(key + i0);
-            px[0] = q.x; px[1] = q.y; px[2] = q.z; px[3] = q.w;
-            need = 0xFu;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (x0 + j < X) { px[j] = key[i0 + j]; need |= 1u << j; }
-        }
-    }
-    if (t > k) {
-        const int wlo = (k + 1) >> 5;
-        int w = t >> 5;
-        uint32_t m = bitmap[(size_t)w * (size_t)nblocks + b] & (0xFFFFFFFFu >> (31 - (t & 31)));
-        bool open = true;
-        while (open) {
-            if (w == wlo) m &= 0xFFFFFFFFu << ((k + 1) & 31);   // frames up to k belong to the pictures before the key frame
-            while (m != 0u && open) {
-                // the most recent SHOW_AHEAD writers of this word: their records are fetched together, applied newest first
-                int f[SHOW_AHEAD];
-                uint4 raw[SHOW_AHEAD];
-                int n = 0;
-#pragma unroll
-                for (int a = 0; a < SHOW_AHEAD; ++a) {
-                    f[a] = -1;
-                    if (m != 0u) {
-                        const int bit = 31 - __builtin_clz(m);
-                        m &= ~(1u << bit);
-                        f[a] = 32 * w + bit;
-                        raw[a] = blocks[((size_t)((long)f[a] + slot_base)) * (size_t)nblocks + b];
-                        ++n;
-                    }
-                }
-#pragma unroll
-                for (int a = 0; a < SHOW_AHEAD; ++a) {
-                    if (a < n && open) {
-                        const Rect r = unpack(raw[a]);
-                        if (need != 0u && (uint32_t)ly >= r.y1 && (uint32_t)ly < r.y2) {
-                            const uint32_t* lit = payload + (size_t)r.payload16 * 4 + (size_t)(((uint32_t)ly - r.y1) * (r.x2 - r.x1));
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                const uint32_t rx = (uint32_t)(cx0 + j);
-                                if (((need >> j) & 1u) && rx >= r.x1 && rx < r.x2) {
-                                    px[j] = lit[rx - r.x1];
-                                    need &= ~(1u << j);
-                                }
-                            }
-                        }
-                        open = __ballot(need != 0u) != 0ull;   // every pixel of the block has its last writer: done
-                    }
-                }
-            }
-            if (w == wlo) break;
-            --w;
-            m = bitmap[(size_t)w * (size_t)nblocks + b];
-        }
-    }
+    uint32_t px[4];
+    index_compose<VEC>(px, key, blocks, payload, bitmap, t, k, slot_base, X, nblocks, b, ly, cx0, x0, i0, mine);
     if (!mine) return;
     if (VEC) *reinterpret_cast<uint4*>(dst + i0) = make_uint4(px[0], px[1], px[2], px[3]);
     else {
@@ -109,6 +120,60 @@ __global__ __launch_bounds__(SHOW_WG) void sp_index_show_kernel(uint32_t* __rest
         for (int j = 0; j < 4; ++j)
             if (x0 + j < X) dst[i0 + j] = px[j];
     }
+}
+
+// Thumbnails (jsp_sp_index_thumbs): the pictures of n frames of the index, each reduced S x S pixels to one (box mean per byte, rounded
+// half up), into one sheet — ONE launch, no full-size picture anywhere.  blockIdx.z is the thumbnail, recs[blockIdx.z] its frame; a
+// wave composes one 16x16 block of it exactly as the show kernel does (index_compose) and then holds the block in registers, four
+// pixels per lane.  A lane adds its four pixels — R and B together under 0x00FF00FF, G apart: at S = 16 a field ends at
+// 256 * 255 + 128 < 2^16, so the fields never carry into each other — which is one S = 4 cell's row; lanes are (row << 2 | chunk), so
+// __shfl_xor by 4 and 8 adds the cell's four rows (16 cells a block), by 1 and 16 on top makes 8 x 8 cells (4), by 2 and 32 the one
+// 16 x 16 cell.  The first lane of each group stores one word.  S divides 16: a cell never straddles two blocks.  Lanes outside the
+// picture contribute zeros and a cell is stored only when it lies inside tw x th, so a cell that is not whole is never written.  No
+// LDS allocated, no barrier; every lane of a wave reaches the shuffles (a wave past the last block column leaves as a whole).
+template <int S, bool VEC>
+__global__ __launch_bounds__(SHOW_WG) void sp_index_thumbs_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ keys,
+                                                                  const IndexThumbRec* __restrict__ recs, const uint4* __restrict__ blocks,
+                                                                  const uint32_t* __restrict__ payload, const uint32_t* __restrict__ bitmap,
+                                                                  long pic_stride, int X, int Y, int nbx, int nblocks, int tw, int th,
+                                                                  int cols) {
+    static_assert(S == 4 || S == 8 || S == 16, "scale");
+    constexpr int SH = S == 4 ? 4 : (S == 8 ? 6 : 8);   // log2(S * S)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int bx = (int)blockIdx.x * 4 + wave, by = (int)blockIdx.y;
+    if (bx >= nbx) return;   // (wave-uniform)
+    const IndexThumbRec rec = recs[blockIdx.z];
+    const int b = by * nbx + bx;
+    const int ly = lane >> 2, cx0 = (lane & 3) * 4;
+    const int y = by * 16 + ly, x0 = bx * 16 + cx0;
+    const bool mine = y < Y && x0 < X;
+    const size_t i0 = (size_t)y * (size_t)X + (size_t)x0;
+    uint32_t px[4];
+    index_compose<VEC>(px, keys + (size_t)rec.key_slot * (size_t)pic_stride, blocks, payload, bitmap, rec.t, rec.k, (long)rec.slot_base, X,
+                       nblocks, b, ly, cx0, x0, i0, mine);
+    uint32_t rb = 0, g = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        rb += px[j] & 0x00FF00FFu;
+        g += (px[j] >> 8) & 0xFFu;
+    }
+#pragma unroll
+    for (int step : {4, 8, 1, 16, 2, 32}) {
+        if ((step == 1 || step == 16) && S < 8) continue;
+        if ((step == 2 || step == 32) && S < 16) continue;
+        rb += (uint32_t)__shfl_xor((int)rb, step);
+        g += (uint32_t)__shfl_xor((int)g, step);
+    }
+    constexpr int GROUP = S == 4 ? 12 : (S == 8 ? 29 : 63);   // the lane bits a cell is summed over: its first lane has none set
+    const int tx = x0 / S, ty = y / S;
+    if ((lane & GROUP) != 0 || tx >= tw || ty >= th) return;
+    rb += (uint32_t)(S * S / 2) * 0x00010001u;
+    g += (uint32_t)(S * S / 2);
+    const uint32_t word = (((rb >> (16 + SH)) & 0xFFu) << 16) | (((g >> SH) & 0xFFu) << 8) | (((rb & 0xFFFFu) >> SH) & 0xFFu);
+    const size_t pitch = (size_t)cols * (size_t)tw;
+    const size_t cell = (size_t)(blockIdx.z / (unsigned)cols) * (size_t)th * pitch + (size_t)(blockIdx.z % (unsigned)cols) * (size_t)tw;
+    out[cell + (size_t)ty * pitch + (size_t)tx] = word;
 }
 
 }  // namespace
@@ -126,6 +191,21 @@ void launch_index_show(const Geometry& g, int32_t* dst, const int32_t* key, cons
         hipLaunchKernelGGL(sp_index_show_kernel<false>, grid, dim3(SHOW_WG), 0, stream, reinterpret_cast<uint32_t*>(dst),
                            reinterpret_cast<const uint32_t*>(key), reinterpret_cast<const uint4*>(d_blocks), d_payload, d_bitmap, t, k,
                            slot_base, g.X, g.Y, g.nbx, nblocks);
+}
+
+void launch_index_thumbs(const Geometry& g, int32_t* out, const int32_t* d_keys, size_t pic_stride, const IndexThumbRec* d_recs, int n,
+                         const PBlock* d_blocks, const uint32_t* d_payload, const uint32_t* d_bitmap, int scale, int cols,
+                         hipStream_t stream) {
+    const bool vec = (g.X & 3) == 0 && (reinterpret_cast<uintptr_t>(d_keys) & 15) == 0 && (pic_stride & 3) == 0;
+    const dim3 grid((g.nbx + 3) / 4, g.nby, n);
+    const int nblocks = g.nbx * g.nby;
+#define JSP_SP_THUMBS(S, VEC)                                                                                                            \
+    hipLaunchKernelGGL((sp_index_thumbs_kernel<S, VEC>), grid, dim3(SHOW_WG), 0, stream, reinterpret_cast<uint32_t*>(out),                 \
+                       reinterpret_cast<const uint32_t*>(d_keys), d_recs, reinterpret_cast<const uint4*>(d_blocks), d_payload, d_bitmap, \
+                       (long)pic_stride, g.X, g.Y, g.nbx, nblocks, g.X / S, g.Y / S, cols)
+    if (vec) { if (scale == 4) JSP_SP_THUMBS(4, true); else if (scale == 8) JSP_SP_THUMBS(8, true); else if (scale == 16) JSP_SP_THUMBS(16, true); }
+    else { if (scale == 4) JSP_SP_THUMBS(4, false); else if (scale == 8) JSP_SP_THUMBS(8, false); else if (scale == 16) JSP_SP_THUMBS(16, false); }
+#undef JSP_SP_THUMBS
 }
 
 }  // namespace jsp::sp

@@ -14,7 +14,8 @@ decoder's `FindChange` (MSVideo1 on the GPU: one call) or through `worker` frame
 attached (`Manager.attach_index`: a range kept resident by the decoder's `BuildIndex`), a seek inside it is one
 `Show` launch and its frames' significance is known without decoding (an index that cannot leave the decoder at the frame
 shown — ScreenPressor's, `ADOPTS` false — serves the frame and leaves the decode position where it is); `next_frame` / `prev_frame` / `next_key` /
-`prev_key` are the navigation of Manager.hx:184-208 over `seek`.  Timers, bitmaps and audio of the reference's
+`prev_key` are the navigation of Manager.hx:184-208 over `seek`; `preview` / `filmstrip` are the seek bar's small pictures, one
+`Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex).  Timers, bitmaps and audio of the reference's
 Manager are not rebuilt.
 """
 from __future__ import annotations
@@ -112,8 +113,9 @@ class Manager:
 
     def preview(self, i: int, scale: int = 8):
         """The thumbnail of clip frame `i` from the attached index (the picture that follows the pointer along the seek bar,
-        Main.on_mouse_move): one `Thumbs` launch, a pure read — no buffer, hold, log entry or decoder state changes.  No index
-        attached, or `i` outside it: ValueError (a hover preview is not worth a decode)."""
+        Main.on_mouse_move): one `Thumbs` launch, a pure read — no buffer, hold, log entry or decoder state changes.  The index is
+        MSVideo1's SeekIndex or ScreenPressor's SpScrubIndex alike.  No index attached, `i` outside it, or an index object without
+        `Thumbs`: ValueError (a hover preview is not worth a decode)."""
         if not self._in_index(i):
             raise ValueError(f"frame {i} is not in an attached seek index")
         if not hasattr(self.index, "Thumbs"):
@@ -123,7 +125,7 @@ class Manager:
     def filmstrip(self, n: int, scale: int = 8, cols: Optional[int] = None):
         """`n` frames spread evenly over the attached index — clip frame index_first + (k * index.frames) // n for k < n — as one
         sheet of thumbnails, `cols` to a row (None: one row): (clip frame numbers, sheet).  One `Thumbs` launch, a pure read as
-        `preview`.  No index attached: ValueError."""
+        `preview`, from the index of either codec.  No index attached, or an index object without `Thumbs`: ValueError."""
         if self.index is None:
             raise ValueError("no seek index attached")
         if not hasattr(self.index, "Thumbs"):
