@@ -66,6 +66,8 @@ extern class JspNative {
     @:native("jsp_sp_index_thumb_size")   static function spIndexThumbSize(idx:RawPointer<JspSpIndex>, scale:Int, width:RawPointer<Int>, height:RawPointer<Int>):Int;
     @:native("jsp_sp_index_thumbs")       static function spIndexThumbs(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, n:Int, frames:RawConstPointer<Int>, scale:Int, cols:Int,
                                                                         out:RawPointer<cpp.Int32>, outPixels:SizeT):Int;
+    @:native("jsp_sp_index_play")         static function spIndexPlay(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, first:Int, n:Int, stride:Int,
+                                                                      dsts:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
     @:native("jsp_sp_index_significance") static function spIndexSignificance(idx:RawPointer<JspSpIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_sp_index_info")         static function spIndexInfo(idx:RawPointer<JspSpIndex>, nframes:RawPointer<Int>, deviceBytes:RawPointer<cpp.UInt64>,
                                                                       hostBytes:RawPointer<cpp.UInt64>):Int;

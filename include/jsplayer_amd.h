@@ -487,6 +487,30 @@ void jsp_sp_index_destroy(jsp_sp_index* idx);
 int jsp_sp_index_thumb_size(const jsp_sp_index* idx, int scale, int* width, int* height);
 int jsp_sp_index_thumbs(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels);
 
+/* ---- playback from a ScreenPressor index: play on from a shown frame, reverse play, fast-forward by `stride`, filling the free frame
+ * buffers around the frame of interest in one go — a run of frames of the index, each into a buffer of its own ---------------------------
+ * Play: EQUIVALENCE  for k = 0 .. n-1, dsts[k] receives exactly the picture that jsp_sp_index_show(first + k * stride) writes, and
+ *       significant_changes[k] (n ints, may be NULL) the verdict Show reports for that frame.  Every pixel of every buffer is written,
+ *       whatever it held.  The frames between the strided ones are walked, not written.  The caller orders `dsts` as it likes: reverse
+ *       playback is the same call with the buffers shown in reverse.
+ *   ONE kernel launch whatever n and stride (sp_index_play_kernel): per 16x16 block frame `first` is composed by the walk of
+ *       sp_index_show_kernel, once; the pixels then stay in registers and the frames are walked forward — one bitmap word per 32 frames, a
+ *       record and its literals for a frame that changes the block, a reload from the key picture at a key frame (coded or flat) inside
+ *       the run, nothing for a frame that leaves the block alone — and stored at every stride-th frame.  Runs on the codec's stream and
+ *       returns synchronised.  Per frame of the index a 16-byte record and a key-frame bit go to a device array the index owns at the
+ *       first Play; the destination list of a call travels through pinned memory into a device array (both grown on demand).  All of it
+ *       is counted in jsp_sp_index_info; an index never asked to play holds none of it.
+ *   THE CODEC IS ONLY LENT, as for Show: device, stream, Preinit and options are used, nothing else is touched, and a sequential decode
+ *       goes on across any number of Plays.  One thing Play does to the codec: it forgets what it remembers of the last column of EVERY
+ *       buffer in `dsts`.  There is no `adopt`; a player that plays from the index to the end of a key interval hands over to the
+ *       ordinary decoder at the next coded key frame, which renews every bit of decoder state.
+ *   ERRORS, each before anything is queued, with nothing changed and nothing written (jsp_last_error() starts with "sp_index_play:",
+ *       but for the MSVideo1 codec's "sp_index: ScreenPressor only"): a null argument or a null entry of `dsts`, an MSVideo1 codec, an
+ *       index built by another codec, n outside 1..4096, stride < 1, first < 0 or first + (n - 1) * stride (computed in 64 bits) outside
+ *       the index, an asynchronous frame in flight, a host-pointer buffer, a buffer that is the codec's current previous frame, the same
+ *       pointer twice in `dsts`. */
+int jsp_sp_index_play(jsp_codec* c, jsp_sp_index* idx, int first, int n, int stride, int32_t* const* dsts, int* significant_changes);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

@@ -559,6 +559,7 @@ class ScreenPressor(_NativeCodec):
 
 class SpScrubIndex(_IndexThumbs):
     """A ScreenPressor range resident in HBM (jsp_sp_index_build, via ScreenPressor.BuildScrubIndex): Show(t) is one launch,
+    Play(first, dsts, stride) one launch for a run of frames played forward from any frame (jsp_sp_index_play),
     Thumbs(frames) one launch for any number of downscaled frames (jsp_sp_index_thumbs; _IndexThumbs has the two methods).
     `significance` = the verdict the sequential run records for every frame, `frames`, `device_bytes`, `host_bytes`.  close() (or
     the context manager) frees it; safe after the codec is gone."""
@@ -569,12 +570,15 @@ class SpScrubIndex(_IndexThumbs):
     def __init__(self, codec: _NativeCodec, handle: int):
         self._codec, self._h = codec, handle
         lib = self._lib = codec._lib
-        n, dev, host = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
-        lib.jsp_sp_index_info(handle, C.byref(n), C.byref(dev), C.byref(host))
-        self.frames, self.device_bytes, self.host_bytes = n.value, dev.value, host.value
+        self._info()
         sig = (C.c_int * self.frames)()
         lib.jsp_sp_index_significance(handle, sig)
         self.significance = [bool(v) for v in sig]
+
+    def _info(self) -> None:
+        n, dev, host = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        self._lib.jsp_sp_index_info(self._h, C.byref(n), C.byref(dev), C.byref(host))
+        self.frames, self.device_bytes, self.host_bytes = n.value, dev.value, host.value
 
     def Show(self, t: int, dst, adopt: bool = False) -> PFrameResult:
         """Frame t's picture into `dst` (a device buffer, not the codec's previous frame): what a fresh codec leaves as its
@@ -592,6 +596,22 @@ class SpScrubIndex(_IndexThumbs):
         if self._lib.jsp_sp_index_show(codec._h, self._h, int(t), C.c_void_p(addr), C.byref(signif)) != 0:
             raise CodecError(N.last_error())
         return PFrameResult(dst, bool(signif.value))
+
+    def Play(self, first: int, dsts, stride: int = 1) -> list:
+        """Frames first, first + stride, ... of the index, one per buffer of `dsts` (device buffers, all different, none the
+        codec's previous frame): dsts[k] receives exactly what Show(first + k * stride) writes — ONE launch whatever len(dsts) and
+        stride (jsp_sp_index_play): frame `first` is composed once and the pixels are carried forward in registers.  Returns a
+        PFrameResult(dsts[k], the frame's verdict) per buffer.  The codec is not touched (it forgets the buffers' last columns, as
+        after Show).  Reverse playback: the same call, the buffers shown in reverse."""
+        codec = self._open("sp_index_play")
+        dsts = list(dsts)
+        n = len(dsts)
+        ptrs = (C.c_void_p * max(n, 1))(*[_frame_ptr(d, codec.X * codec.Y) for d in dsts])
+        signif = (C.c_int * max(n, 1))()
+        if self._lib.jsp_sp_index_play(codec._h, self._h, int(first), n, int(stride), ptrs, signif) != 0:
+            raise CodecError(N.last_error())
+        self._info()   # (the first Play adds the per-frame table, a longer run a longer destination list)
+        return [PFrameResult(d, bool(signif[k])) for k, d in enumerate(dsts)]
 
     def _open(self, who: str) -> _NativeCodec:
         if not self._h:

@@ -282,6 +282,19 @@ static_assert(sizeof(IndexThumbRec) == 24, "IndexThumbRec is 24 bytes");
 void launch_index_thumbs(const Geometry& g, int32_t* out, const int32_t* d_keys, size_t pic_stride, const IndexThumbRec* d_recs, int n,
                          const PBlock* d_blocks, const uint32_t* d_payload, const uint32_t* d_bitmap, int scale, int cols,
                          hipStream_t stream);
+// Playback from the seek index (sp_index_play_kernel): the pictures launch_index_show would write for frames first, first + stride, ...,
+// first + (n - 1) * stride, into d_dsts[0..n) — ONE launch.  A wave composes frame `first` of its block as the show kernel does, then
+// carries the pixels forward in registers: a set bitmap bit is a literal rectangle laid over them, a key frame (d_keymask, bit j of word w:
+// frame 32 w + j) a reload from its key picture, anything else nothing.  d_frames[f] is what launch_index_show takes as arguments for f.
+struct IndexPlayFrame {   // one per frame of the index
+    int32_t k;               // its key frame (a key frame: itself)
+    uint32_t key_slot;       // the key picture is d_keys + key_slot * pic_stride
+    int64_t slot_base;
+};
+static_assert(sizeof(IndexPlayFrame) == 16, "IndexPlayFrame is 16 bytes");
+void launch_index_play(const Geometry& g, int32_t* const* d_dsts, bool dsts_aligned16, int first, int n, int stride, const int32_t* d_keys,
+                       size_t pic_stride, const IndexPlayFrame* d_frames, const uint32_t* d_keymask, const PBlock* d_blocks,
+                       const uint32_t* d_payload, const uint32_t* d_bitmap, hipStream_t stream);
 constexpr int kGroupMaxFrames = 65535;        // frames one group launch may walk
 size_t iframe_lds_bytes(const Geometry& g, int band_rows = 0);
 constexpr int kMaxIntraWidth = 8192;  // LDS plan of the row-wavefront kernel

@@ -1,6 +1,7 @@
 // The ScreenPressor seek index of include/jsplayer_amd.h — jsp_sp_index_* —: the host entropy stage runs over a range ONCE, its
 // records stay resident in HBM, and any frame of the range is then one launch of sp_index_show_kernel, the thumbnails of any n frames
-// of it one launch of sp_index_thumbs_kernel (sp_index_kernels.hip).
+// of it one launch of sp_index_thumbs_kernel, a run of frames played forward from any frame of it one launch of sp_index_play_kernel
+// (sp_index_kernels.hip).
 //
 // Kept apart from sp_codec.cpp / jsp_api.cpp: those are also built against the stub kernels of the host-layer sanitizer build
 // (tools/tsan_cpu.sh), which knows nothing of the index kernel.  What the build needs of the codec comes through sp::IndexLender.
@@ -31,11 +32,17 @@ struct jsp_sp_index {
     std::vector<int> significance;   // per frame: the verdict of the sequential run (1 / 0)
     PinnedBuffer h_thumb_recs;       // jsp_sp_index_thumbs: the call's per-thumbnail records on their way to ...
     DeviceBuffer d_thumb_recs;       // ... the array the kernel reads (both grown on demand: nothing until the first call)
-    uint64_t device_bytes() const { return d_keys.cap + d_blocks.cap + d_payload.cap + d_bitmap.cap + d_thumb_recs.cap; }
+    DeviceBuffer d_play_frames;      // jsp_sp_index_play: an IndexPlayFrame per frame, then the key-frame mask (nothing until the first call)
+    PinnedBuffer h_play_dsts;        // jsp_sp_index_play: the call's destinations on their way to ...
+    DeviceBuffer d_play_dsts;        // ... the array the kernel reads (both grown on demand)
+    uint64_t device_bytes() const {
+        return d_keys.cap + d_blocks.cap + d_payload.cap + d_bitmap.cap + d_thumb_recs.cap + d_play_frames.cap + d_play_dsts.cap;
+    }
     uint64_t host_bytes() const {
         return sizeof(*this) + key_of.size() * sizeof(int32_t) + key_slot.size() * sizeof(int32_t) + slot_base.size() * sizeof(int64_t) +
-               significance.size() * sizeof(int) + h_thumb_recs.cap;
+               significance.size() * sizeof(int) + h_thumb_recs.cap + h_play_dsts.cap;
     }
+    size_t play_mask_offset() const { return (size_t)nframes * sizeof(IndexPlayFrame); }   // (a multiple of 16)
     const int32_t* key_picture(int t) const { return static_cast<const int32_t*>(d_keys.p) + (size_t)key_slot[(size_t)t] * pic_stride; }
     void show(int t, int32_t* dst, hipStream_t stream) const {
         launch_index_show(geo, dst, key_picture(t), static_cast<const PBlock*>(d_blocks.p), static_cast<const uint32_t*>(d_payload.p),
@@ -393,6 +400,75 @@ extern "C" int jsp_sp_index_thumbs(jsp_codec* c, jsp_sp_index* idx, int n, const
                             static_cast<const uint32_t*>(idx->d_payload.p), static_cast<const uint32_t*>(idx->d_bitmap.p), scale, cols, c->stream);
         JSP_HIP(hipGetLastError());
         JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned records are free for the next call)
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- playback: a run of frames of the index, carried forward in registers from the first one, in ONE launch of sp_index_play_kernel.
+// Everything Show does to the codec, per destination: the buffers are written behind its back, so it forgets their last columns.
+extern "C" int jsp_sp_index_play(jsp_codec* c, jsp_sp_index* idx, int first, int n, int stride, int32_t* const* dsts, int* significant_changes) {
+    if (!c || !idx || !dsts) return fail("sp_index_play: null argument");
+    auto* lender = c->kind == JSP_CODEC_SCREENPRESSOR ? dynamic_cast<IndexLender*>(c) : nullptr;
+    if (!lender) return fail("sp_index: ScreenPressor only");
+    if (idx->codec_serial != c->serial) return fail("sp_index_play: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("sp_index_play: n is outside 1..4096");
+    if (stride < 1) return fail("sp_index_play: stride must be at least 1");
+    if (first < 0 || (int64_t)first + (int64_t)(n - 1) * (int64_t)stride >= (int64_t)idx->nframes) return fail("sp_index_play: the run is outside the index");
+    for (int k = 0; k < n; ++k)
+        if (!dsts[k]) return fail("sp_index_play: null argument (an entry of dsts)");
+    if (c->next_ticket != c->oldest_ticket) return fail("sp_index_play: an asynchronous frame is in flight (jsp_wait for it first)");
+    bool aligned16 = true;
+    {
+        std::vector<const int32_t*> sorted(dsts, dsts + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail("sp_index_play: the same buffer twice in dsts");
+        for (int k = 0; k < n; ++k) {
+            if (dsts[k] == c->prev_caller || dsts[k] == c->prev_dev) return fail("sp_index_play: a buffer of dsts is the current previous frame");
+            aligned16 = aligned16 && (reinterpret_cast<uintptr_t>(dsts[k]) & 15) == 0;
+        }
+    }
+    try {
+        c->activate();
+        for (int k = 0; k < n; ++k)
+            if (!on_device(dsts[k])) return fail("sp_index_play: every buffer of dsts must be a device frame buffer");
+        hipStream_t stream = c->stream;
+        const size_t nwords = ((size_t)idx->nframes + 31) / 32;
+        if (!idx->d_play_frames.p) {   // the first Play of this index: the per-frame table, once
+            const size_t bytes = idx->play_mask_offset() + nwords * sizeof(uint32_t);
+            PinnedBuffer pin;
+            pin.reserve(bytes);
+            auto* recs = static_cast<IndexPlayFrame*>(pin.p);
+            auto* mask = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(pin.p) + idx->play_mask_offset());
+            std::fill(mask, mask + nwords, 0u);
+            for (int f = 0; f < idx->nframes; ++f) {
+                recs[f] = IndexPlayFrame{idx->key_of[(size_t)f], (uint32_t)idx->key_slot[(size_t)f], idx->slot_base[(size_t)f]};
+                if (idx->key_of[(size_t)f] == f) mask[f >> 5] |= 1u << (f & 31);
+            }
+            DeviceBuffer d;
+            exact(d, bytes);
+            JSP_HIP(hipMemcpyAsync(d.p, pin.p, bytes, hipMemcpyHostToDevice, stream));
+            JSP_HIP(hipStreamSynchronize(stream));   // (the pinned copy goes away here)
+            std::swap(idx->d_play_frames.p, d.p);
+            std::swap(idx->d_play_frames.cap, d.cap);
+        }
+        idx->h_play_dsts.reserve(sizeof(int32_t*) * (size_t)n);
+        idx->d_play_dsts.reserve(sizeof(int32_t*) * (size_t)n);
+        std::copy(dsts, dsts + n, static_cast<int32_t**>(idx->h_play_dsts.p));
+        JSP_HIP(hipMemcpyAsync(idx->d_play_dsts.p, idx->h_play_dsts.p, sizeof(int32_t*) * (size_t)n, hipMemcpyHostToDevice, stream));
+        launch_index_play(idx->geo, static_cast<int32_t* const*>(idx->d_play_dsts.p), aligned16, first, n, n == 1 ? 1 : stride,
+                          static_cast<const int32_t*>(idx->d_keys.p), idx->pic_stride, static_cast<const IndexPlayFrame*>(idx->d_play_frames.p),
+                          reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(idx->d_play_frames.p) + idx->play_mask_offset()),
+                          static_cast<const PBlock*>(idx->d_blocks.p), static_cast<const uint32_t*>(idx->d_payload.p),
+                          static_cast<const uint32_t*>(idx->d_bitmap.p), stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(stream));   // (the pinned destination list is free for the next call)
+        for (int k = 0; k < n; ++k) {
+            lender->forget_buffer(dsts[k]);       // (written behind the codec's back: their last columns are asked for again)
+            if (significant_changes) significant_changes[k] = idx->significance[(size_t)first + (size_t)k * (size_t)stride];
+        }
         return JSP_ZERO_STATE;
     } catch (const std::exception& e) {
         set_error("%s", e.what());

@@ -14,7 +14,8 @@ decoder's `FindChange` (MSVideo1 on the GPU: one call) or through `worker` frame
 attached (`Manager.attach_index`: a range kept resident by the decoder's `BuildIndex`), a seek inside it is one
 `Show` launch and its frames' significance is known without decoding (an index that cannot leave the decoder at the frame
 shown — ScreenPressor's, `ADOPTS` false — serves the frame and leaves the decode position where it is); `next_frame` / `prev_frame` / `next_key` /
-`prev_key` are the navigation of Manager.hx:184-208 over `seek`; `preview` / `filmstrip` are the seek bar's small pictures, one
+`prev_key` are the navigation of Manager.hx:184-208 over `seek`; `play_from_index` plays a run of frames out of such a non-adopting
+index, one `Play` launch per batch of free buffers; `preview` / `filmstrip` are the seek bar's small pictures, one
 `Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex).  Timers, bitmaps and audio of the reference's
 Manager are not rebuilt.
 """
@@ -278,6 +279,55 @@ class Manager:
                 out = self.worker(frames[i], i, None, keys[i - start])
         self._last_was_key = keys[-1]
         self.next_frame_to_decode = index + 1
+        return out
+
+    def play_from_index(self, start: int, count: Optional[int] = None, stride: int = 1,
+                        on_frame: Optional[Callable[[DecodedFrame, object], None]] = None,
+                        key_flags: Optional[Sequence[bool]] = None) -> List[DecodedFrame]:
+        """Clip frames start, start + stride, ... (`count` of them; None: to the end of the index) served from an attached index
+        that does not adopt (ScreenPressor's SpScrubIndex) — play on from a shown frame, fast-forward, filling the free buffers
+        around the frame of interest.  The frames go out in batches of the buffers that are not the decoder's previous frame, ONE
+        `Play` launch per batch; holds, `frame_of_interest` and `log` (a DecodedFrame with the index's verdict) follow each frame,
+        and `on_frame(frame, buffer)` is called per frame in order, before the next batch overwrites its buffer.  The decoder, its
+        previous buffer and `next_frame_to_decode` are untouched.  `key_flags` (the clip's, as for seek(); optional) only fills
+        DecodedFrame.key.  Past the end of the index play goes on with `seek()` to the
+        next clip frame: one decode when that frame is a coded key frame (which renews every bit of decoder state), else the
+        decodes from the nearest key frame.  ValueError: no index attached, a frame outside it, an index that adopts (MSVideo1's
+        SeekIndex needs none of this: its Show leaves the decoder at the frame), an index object without `Play`."""
+        if self.index is None:
+            raise ValueError("no seek index attached")
+        if self._index_adopts():
+            raise ValueError("the attached seek index adopts: seek() moves the decoder with it")
+        if not hasattr(self.index, "Play"):
+            raise ValueError("the attached seek index cannot play")
+        start, stride = int(start), int(stride)
+        if stride < 1:
+            raise ValueError("stride must be at least 1")
+        end = self.index_first + self.index.frames
+        if count is None:
+            count = (end - start + stride - 1) // stride if self._in_index(start) else 0
+        count = int(count)
+        if count < 1 or not self._in_index(start) or not self._in_index(start + (count - 1) * stride):
+            raise ValueError(f"frames {start} .. {start + (max(count, 1) - 1) * stride} are not all in the attached seek index")
+        prev = self.decoder.PreviousFrame()
+        prev_idx = self._slot_of(prev) if prev is not None else -1
+        slots = [nb for nb in range(len(self.buffers)) if nb != prev_idx]
+        out: List[DecodedFrame] = []
+        for k0 in range(0, count, len(slots)):
+            batch = slots[:min(len(slots), count - k0)]
+            first = start + k0 * stride
+            results = self.index.Play(first - self.index_first, [self.buffers[nb] for nb in batch], stride)
+            for nb in batch:
+                self.holds[nb] = None
+            for j, (nb, res) in enumerate(zip(batch, results)):
+                i = first + j * stride
+                self.holds[nb] = range(i, i + 1)
+                self.frame_of_interest = i
+                d = DecodedFrame(i, key_flags is not None and i < len(key_flags) and bool(key_flags[i]), nb, res.significant_changes)
+                self.log.append(d)
+                out.append(d)
+                if on_frame:
+                    on_frame(d, self.buffers[nb])
         return out
 
     def _known_significance(self) -> Dict[int, bool]:
