@@ -198,6 +198,10 @@ int jsp_key_frame_differs(jsp_codec* c);
  *                        frame — or the frame's tiles did not report in time);
  *   "lookback_fallbacks" staged MSVideo1 batches re-run through the descriptor kernels after a tile gave up waiting for
  *                        the tiles before it;
+ *   "host_parsed_frames" (MSVideo1) frames staged with the on-GPU parse on ("msv1_parse" = "gpu") whose block table came
+ *                        from the host parser all the same: the stream ends before every block is covered, an 8-bit end
+ *                        marker or a skip code without a previous frame lies on the chain, or a 16-bit frame is short
+ *                        enough for the all-skips early-out.  Every other frame is settled by the parse kernels alone;
  *   "sp_groups_held", "sp_spare_decoders"  (ScreenPressor) groups of pictures the asynchronous path keeps a record of, and
  *                        host decoders on its shelf: both stay bounded however long a stream runs without jsp_sync.
  *   "msv1_block_changes" (MSVideo1, for tests) not a count: the persistent per-row flags (MSVideo1.hx:122,305) of block

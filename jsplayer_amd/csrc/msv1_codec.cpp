@@ -562,6 +562,7 @@ struct Msv1Codec : jsp_codec {
     long long counter(const char* name) override {
         if (std::strcmp(name, "prefetched_frames") == 0) return prefetched_frames;
         if (std::strcmp(name, "paired_frames") == 0) return paired_frames;
+        if (std::strcmp(name, "host_parsed_frames") == 0) return host_parsed_frames;
         if (std::strcmp(name, "msv1_block_changes") == 0) {   // (tests) the per-row flags of block rows 0..61 as bits
             std::vector<uint8_t> rows;
             try {
@@ -605,6 +606,7 @@ struct Msv1Codec : jsp_codec {
     unsigned range_next = 0;
     hipStream_t prefetch_stream = nullptr;
     long long prefetched_frames = 0;          // jsp_counter("prefetched_frames"): asynchronous frames that found their bytes on the device
+    long long host_parsed_frames = 0;         // jsp_counter("host_parsed_frames"): frames staged with the on-GPU parse on that the host parser settled (frame_parse)
     int prefetch(const void* host, size_t n) override {
         if (!host || n == 0) {                // give every range up (the caller's memory changes or goes away)
             for (UpRange& r : ranges) { r.host = nullptr; r.bytes = 0; }
@@ -1225,6 +1227,7 @@ struct Msv1Codec : jsp_codec {
         host_parse(f.src, f.n, (uint32_t)plan.beg[i], desc, pr);
         if (pr.early_out) std::fill(desc, desc + geo.nblocks, MSV1_DESC_UNTOUCHED);
         if (st.gpu_parse) {  // this frame's table comes from the host from now on
+            ++host_parsed_frames;
             plan.h_pf[i].host_parsed = 1;
             plan.pframes_dirty = true;
             upload(static_cast<uint32_t*>(st.d_desc.p) + (size_t)i * nblk, desc, sizeof(uint32_t) * geo.nblocks);
