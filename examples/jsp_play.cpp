@@ -18,6 +18,10 @@
 //                                ScreenPressor: ONE seek index over the clip (jsp_sp_index_build), then frames FIRST, FIRST + STRIDE, ...
 //                                (COUNT of them; default: to the end of the clip) out of it, ONE jsp_sp_index_play per batch of the
 //                                pool's buffers; prints "<index> <key|inter> <significant> <crc32>" per frame, the plain run's values.
+//   jsp_play clip.avi --index-run FIRST[:COUNT[:STRIDE]]
+//                                MSVideo1: ONE seek index over the clip (jsp_index_build), then frames FIRST, FIRST + STRIDE, ... (COUNT
+//                                of them; default: to the end of the clip) out of it, ONE jsp_index_play per batch of the pool's
+//                                buffers; prints "<index> <key|inter> <significant> <crc32>" per frame, the plain run's values.
 //   jsp_play clip.avi --step-back   ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build and
 //                                jsp_sp_index_show), then the last frame and every frame down
 //                                to 0, one jsp_index_show each (Main.on_prevframe, Manager.hx:191-196); prints "<index> <key|inter>
@@ -389,7 +393,7 @@ long play_batched(const Clip& clip, int batch, int repeat, bool quiet, int warmu
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]]\n", argv[0]); return 2; }
     // (throughput runs: several files, separated by commas — stream s plays file s modulo their number, so that the streams of a
     // multi-stream run are independent inputs)
     std::deque<Clip> clips;                                   // (a deque: elements never move)
@@ -413,6 +417,7 @@ int main(int argc, char** argv) {
     bool step_back = false;                                   // --step-back: a seek index over the clip, shown from the last frame down to 0
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
     long play_first = -1, play_count = -1, play_stride = 1;   // --play-index FIRST[:COUNT[:STRIDE]]: frames played out of a ScreenPressor seek index
+    long run_first = -1, run_count = -1, run_stride = 1;      // --index-run FIRST[:COUNT[:STRIDE]]: frames played out of an MSVideo1 seek index
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -444,6 +449,14 @@ int main(int argc, char** argv) {
             if (c2 != std::string::npos) play_stride = std::atol(v.substr(c2 + 1).c_str());
             if (play_first < 0 || (c1 != std::string::npos && play_count < 1) || play_stride < 1) { std::fprintf(stderr, "--play-index: FIRST >= 0, COUNT >= 1, STRIDE >= 1\n"); return 2; }
         }
+        else if (o == "--index-run" && a + 1 < argc) {
+            const std::string v = argv[++a];
+            const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? std::string::npos : v.find(':', c1 + 1);
+            run_first = std::atol(v.substr(0, c1).c_str());
+            if (c1 != std::string::npos) run_count = std::atol(v.substr(c1 + 1, c2 == std::string::npos ? std::string::npos : c2 - c1 - 1).c_str());
+            if (c2 != std::string::npos) run_stride = std::atol(v.substr(c2 + 1).c_str());
+            if (run_first < 0 || (c1 != std::string::npos && run_count < 1) || run_stride < 1) { std::fprintf(stderr, "--index-run: FIRST >= 0, COUNT >= 1, STRIDE >= 1\n"); return 2; }
+        }
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
             for (size_t at = 0; at <= list.size();) {
@@ -461,6 +474,8 @@ int main(int argc, char** argv) {
     if (strip > 0 && (step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--filmstrip goes alone\n"); return 2; }
     if (play_first >= 0 && (strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--play-index goes alone\n"); return 2; }
     if (play_first >= 0 && clip.kind != JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--play-index: ScreenPressor only (an MSVideo1 index adopts: --seek and the plain run play on from any frame)\n"); return 2; }
+    if (run_first >= 0 && (play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--index-run goes alone\n"); return 2; }
+    if (run_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--index-run: MSVideo1 only (--play-index plays a ScreenPressor index)\n"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
         if (!quiet) return play_batched(clip, batch, 1, false) < 0 ? 1 : 0;
@@ -700,6 +715,46 @@ int main(int argc, char** argv) {
             }
         }
         jsp_sp_index_destroy(sidx);
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        return rc;
+    }
+    if (run_first >= 0) {   // a run of frames out of an MSVideo1 index: one index build, then ONE jsp_index_play per batch of the pool's buffers
+        const size_t n = clip.frames.size();
+        std::vector<const uint8_t*> srcs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> keys;
+        for (size_t i = 0; i < n; ++i) {
+            srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+            lens.push_back(clip.frames[i].second);
+            keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        if ((size_t)run_first >= n) { std::fprintf(stderr, "--index-run %ld: the clip has %zu frames\n", run_first, n); rc = 2; }
+        const long fits = rc == 0 ? ((long)n - 1 - run_first) / run_stride + 1 : 0;   // frames from FIRST to the end of the clip
+        if (rc == 0 && run_count > fits) { std::fprintf(stderr, "--index-run: only %ld frames from %ld at stride %ld\n", fits, run_first, run_stride); rc = 2; }
+        const long count = run_count < 0 ? fits : run_count;
+        jsp_index* idx = rc == 0 ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        if (rc == 0 && !idx) { std::fprintf(stderr, "jsp_index_build: %s\n", jsp_last_error()); rc = 1; }
+        std::vector<int> sig(n, 0);   // the Manager's verdict per frame (what the plain run prints)
+        if (idx) jsp_index_significance(idx, sig.data());
+        std::vector<int32_t*> dsts, data((size_t)nbuf, nullptr);
+        for (int k = 0; k < nbuf; ++k) dsts.push_back(jsp_pool_buffer(pool, k));
+        for (long k0 = 0; rc == 0 && k0 < count; k0 += nbuf) {
+            const int m = (int)(count - k0 < nbuf ? count - k0 : nbuf);
+            const long f0 = run_first + k0 * run_stride;
+            if (jsp_index_play(dec, idx, (int)f0, m, (int)run_stride, dsts.data(), -1, data.data(), nullptr) != JSP_ZERO_STATE) {
+                std::fprintf(stderr, "jsp_index_play: %s\n", jsp_last_error());
+                rc = 1;
+                break;
+            }
+            for (int k = 0; k < m; ++k) {
+                const size_t t = (size_t)(f0 + k * run_stride);
+                uint32_t crc = 0;
+                if (data[(size_t)k] && jsp_download(data[(size_t)k], host.data(), npx) == 0) crc = crc32(reinterpret_cast<const uint8_t*>(host.data()), npx * 4);
+                std::printf("%zu %s %d %08x\n", t, keys[t] ? "key" : "inter", sig[t], crc);
+            }
+        }
+        jsp_index_destroy(idx);
         jsp_pool_destroy(pool);
         jsp_codec_destroy(dec);
         return rc;

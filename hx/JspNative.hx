@@ -56,6 +56,9 @@ extern class JspNative {
     @:native("jsp_index_thumb_size")   static function indexThumbSize(idx:RawPointer<JspIndex>, scale:Int, width:RawPointer<Int>, height:RawPointer<Int>):Int;
     @:native("jsp_index_thumbs")       static function indexThumbs(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, n:Int, frames:RawConstPointer<Int>, scale:Int, cols:Int,
                                                                    out:RawPointer<cpp.Int32>, outPixels:SizeT):Int;
+    @:native("jsp_index_play")         static function indexPlay(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, first:Int, n:Int, stride:Int,
+                                                                 dsts:RawPointer<RawPointer<cpp.Int32>>, adoptK:Int,
+                                                                 dataPnts:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)

@@ -183,6 +183,9 @@ int jsp_set_stream(jsp_codec* c, void* hip_stream);
  *       *significant_changes stays what the decode reported and jsp_key_frame_differs() says -1).  Staged batches are not compared. */
 /*   "msv1_seek_chunk_frames" = "auto" (default) | "1".."n" : MSVideo1 only, jsp_seek and jsp_find_change.  Frames staged and composed per chunk of a
  *       seek's range; auto: as many as keep the chunk's stream bytes and block tables under 1 GiB.  Results do not depend on it. */
+/*   "msv1_index_play_segments" = "auto" (default) | "1".."64" : MSVideo1 only, jsp_index_play.  The run's destinations are split into this many
+ *       contiguous segments along the launch grid (never more than frames in the run), each composing its own first frame; auto:
+ *       enough segments for about 8 waves per SIMD.  Results do not depend on it. */
 /*   "async_depth" = "1".."16" (default "4") : any codec.  Frames that may be in flight between jsp_decompress_*_async and
  *       jsp_wait. */
 int jsp_set_option(jsp_codec* c, const char* key, const char* value);
@@ -416,6 +419,32 @@ void jsp_index_destroy(jsp_index* idx);
  *       precondition: JSP_ERROR_OCCURED, jsp_last_error(), nothing written. */
 int jsp_index_thumb_size(const jsp_index* idx, int scale, int* width, int* height);
 int jsp_index_thumbs(jsp_codec* c, jsp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels);
+
+/* ---- playback from an MSVideo1 index: reverse play and the step-back button held down, xs fast-forward, filling the free frame
+ * buffers around the frame of interest — a run of frames of the index, each into a buffer of its own ----------------------------------
+ * Play: EQUIVALENCE  for k = 0 .. n-1 let t_k = first + k * stride.  dsts[k] ends exactly as jsp_index_show(c, idx, t_k, dsts[k], 0, ..)
+ *       leaves a buffer that held the same content before; data_pnts[k] (n entries; may be NULL) is that call's *data_pnt and
+ *       significant_changes[k] (may be NULL) its verdict.  That includes everything Show leaves unwritten: a frame before the index's
+ *       first adopting frame writes nothing to its buffer (its data_pnt is the previous frame of the build's time); a block that no
+ *       frame <= t_k has coded is left untouched in dsts[k] when the index holds no picture before the range; the W % 4 / H % 4
+ *       remainder pixels are copied only when there is a picture before the range.
+ *   ADOPT  adopt_k = -1: the codec is not touched.  0 <= adopt_k < n: the codec ends exactly as jsp_index_show(t_adopt_k,
+ *       dsts[adopt_k], adopt = 1) leaves it — previous frame, per-row block_changes, what the on-GPU parse needs — so a following
+ *       DecompressP(t + 1) behaves as after sequential decoding.  Reverse play adopts k = 0 of an ascending run and shows the buffers
+ *       in reverse.  jsp_key_frame_differs() answers -1 after an adopting call.
+ *   ONE kernel launch whatever n and stride (msv1_index_play_kernel): per block frame `first` is composed as Show composes it, once;
+ *       the 16 pixels then stay in registers, and for each further frame only the LAST writer of the gap (t_{k-1}, t_k] is decoded (a
+ *       coded block overwrites the whole block), found in the bitmap with a lower bound.  Option "msv1_index_play_segments" splits the
+ *       run along the grid.  Runs on the codec's stream and returns synchronised.  The destination pointers travel through pinned
+ *       memory into a device array the index owns (both grown on demand, counted in jsp_index_info; an index never asked to play
+ *       holds neither); a destination that Show would not write goes to the device as a null entry.
+ *   ERRORS, each before anything is queued, with nothing changed and nothing written (jsp_last_error() starts with "index_play:", but
+ *       for a ScreenPressor codec's "index: MSVideo1 only"): a null c, idx or dsts or a null entry of dsts, a ScreenPressor codec, an
+ *       index built by another codec, n outside 1..4096, stride < 1, first < 0 or first + (n - 1) * stride (computed in 64 bits)
+ *       outside the index, adopt_k outside -1..n-1, an asynchronous frame in flight, a codec in host-pointer mode or a host-pointer
+ *       buffer, a buffer that is the codec's current previous frame, the same pointer twice in dsts. */
+int jsp_index_play(jsp_codec* c, jsp_index* idx, int first, int n, int stride, int32_t* const* dsts, int adopt_k, int32_t** data_pnts,
+                   int* significant_changes);
 
 /* ---- ScreenPressor seek index: previous frame, seek-bar clicks and skip idle over a range whose host-stage records stay resident in
  * HBM (the calls above refuse ScreenPressor: its entropy stage is sequential host work, and the Manager's fallback decodes again from

@@ -97,6 +97,8 @@ SIGNATURES = {
                                   C.POINTER(C.c_void_p)]),
     "jsp_index_build": (C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p, C.c_int]),
     "jsp_index_show": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "jsp_index_play": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_int)]),
     "jsp_index_significance": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "jsp_index_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "jsp_index_destroy": (None, [C.c_void_p]),

@@ -448,7 +448,8 @@ class _IndexThumbs:
 
 
 class SeekIndex(_IndexThumbs):
-    """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch.  `significance` = FindChange's verdict
+    """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch, Play(first, dsts, stride) one launch for
+    a run of frames, each into a buffer of its own (jsp_index_play).  `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
     ADOPTS = True   # Show(adopt=True) leaves the decoder at frame t: a Manager moves its decode position with it
@@ -486,6 +487,38 @@ class SeekIndex(_IndexThumbs):
         else:
             data = self._prev_at_build
         return PFrameResult(data, bool(signif.value))
+
+    def Play(self, first: int, dsts, stride: int = 1, adopt: Optional[int] = None) -> list:
+        """Frames first, first + stride, ... of the index, one per buffer of `dsts` (device buffers, all different, none the
+        codec's previous frame): dsts[k] ends exactly as Show(first + k * stride, dsts[k], adopt=False) leaves it — ONE launch
+        whatever len(dsts) and stride (jsp_index_play): frame `first` is composed once, the pixels are carried forward in
+        registers and only the last writer of each gap is decoded.  Returns Show's PFrameResult per buffer.  adopt: an index into
+        `dsts`; the codec ends as Show(that frame, that buffer, adopt=True) leaves it (None: it is not touched).  Reverse
+        playback: the same call with adopt=0, the buffers shown in reverse."""
+        codec = self._open("index_play")
+        dsts = list(dsts)
+        n = len(dsts)
+        addrs = [_frame_ptr(d, codec.X * codec.Y) for d in dsts]
+        ptrs = (C.c_void_p * max(n, 1))(*addrs)
+        outs = (C.c_void_p * max(n, 1))()
+        signif = (C.c_int * max(n, 1))()
+        adopt_k = -1 if adopt is None else int(adopt)
+        if adopt is not None and not 0 <= adopt_k < n:
+            raise CodecError("index_play: adopt is outside dsts")
+        if 0 <= adopt_k < n:
+            codec._bufs[addrs[adopt_k]] = dsts[adopt_k]
+        if self._lib.jsp_index_play(codec._h, self._h, int(first), n, int(stride), ptrs, adopt_k, outs, signif) != 0:
+            raise CodecError(N.last_error())
+        if adopt_k >= 0:
+            codec._track_prev()
+        dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first Play adds the destination list, a longer run a longer one)
+        self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
+        self.device_bytes, self.host_bytes = dev.value, host.value
+        results = []
+        for k, d in enumerate(dsts):
+            data = None if not outs[k] else d if outs[k] == addrs[k] else self._prev_at_build
+            results.append(PFrameResult(data, bool(signif[k])))
+        return results
 
     def _open(self, who: str) -> _NativeCodec:
         if not self._h:

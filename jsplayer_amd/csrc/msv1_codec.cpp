@@ -790,6 +790,14 @@ struct Msv1Codec : jsp_codec {
             seek_chunk_frames = (int)v;
             return 0;
         }
+        if (std::strcmp(key, "msv1_index_play_segments") == 0) {   // jsp_index_play: segments of the run along grid.y ("auto": ~8 waves per SIMD)
+            if (std::strcmp(value, "auto") == 0) { index_play_segments = 0; return 0; }
+            char* end = nullptr;
+            const long v = std::strtol(value, &end, 10);
+            if (end == value || *end || v < 1 || v > 64) return -1;
+            index_play_segments = (int)v;
+            return 0;
+        }
         if (std::strcmp(key, "msv1_scrub_tables") == 0) {   // tests: a replay must rebuild every block table it reads
             opt_scrub_tables = std::strcmp(value, "1") == 0;
             return 0;

@@ -31,14 +31,16 @@ struct jsp_index {
     int32_t* prev_dev = nullptr;
     PinnedBuffer h_thumb_frames;           // jsp_index_thumbs: the call's frame list on its way to ...
     DeviceBuffer d_thumb_frames;           // ... the array the kernel reads (both grown on demand)
+    PinnedBuffer h_play_dsts;              // jsp_index_play: the call's destinations on their way to ...
+    DeviceBuffer d_play_dsts;              // ... the array the kernel reads (both grown on demand; nothing until the first call)
     uint64_t device_bytes() const {
-        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_thumb_frames.cap;
+        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_thumb_frames.cap + d_play_dsts.cap;
         for (const auto& c : chunks) n += c->stream.cap + c->desc.cap + c->frames.cap;
         return n;
     }
     uint64_t host_bytes() const {
         return sizeof(*this) + chunks.size() * sizeof(Chunk) + significance.size() * sizeof(int) + reported.size() + block_changes.size() +
-               h_thumb_frames.cap;
+               h_thumb_frames.cap + h_play_dsts.cap;
     }
 };
 
@@ -511,6 +513,21 @@ extern "C" jsp_index* jsp_index_build(jsp_codec* c, int nframes, const uint8_t* 
     }
 }
 
+// What adopting frame t of the index, shown in `dst`, does to the codec once the picture is written: it ends as jsp_seek of frames
+// 0..t leaves it.
+namespace {
+void adopt_frame(jsp_codec* c, const jsp_index* idx, int t, int32_t* dst) {
+    const bool adopted = t >= idx->first_adopted;
+    take_over(c);   // (as on a seek)
+    const int nby = std::max(idx->geo.nby, 0);
+    Msv1HostState s;
+    s.prev_dev = adopted ? dst : idx->prev_dev;
+    s.block_changes.assign(idx->block_changes.begin() + (size_t)t * (size_t)nby, idx->block_changes.begin() + (size_t)(t + 1) * (size_t)nby);
+    msv1_restore_state(c, s);   // (exact per-row flags: nothing stale, nothing that points into the index)
+    c->prev_caller = adopted ? dst : idx->prev_caller;
+}
+}  // namespace
+
 extern "C" int jsp_index_show(jsp_codec* c, jsp_index* idx, int t, int32_t* dst, int adopt, int32_t** data_pnt, int* significant_changes) {
     if (data_pnt) *data_pnt = c ? c->prev_caller : nullptr;
     if (significant_changes) *significant_changes = 0;
@@ -531,17 +548,70 @@ extern "C" int jsp_index_show(jsp_codec* c, jsp_index* idx, int t, int32_t* dst,
             JSP_HIP(hipStreamSynchronize(c->stream));
         }
         int32_t* shown = adopted ? dst : idx->prev_caller;
-        if (adopt) {
-            take_over(c);   // (as on a seek)
-            const int nby = std::max(idx->geo.nby, 0);
-            Msv1HostState s;
-            s.prev_dev = adopted ? dst : idx->prev_dev;
-            s.block_changes.assign(idx->block_changes.begin() + (size_t)t * (size_t)nby, idx->block_changes.begin() + (size_t)(t + 1) * (size_t)nby);
-            msv1_restore_state(c, s);   // (exact per-row flags: nothing stale, nothing that points into the index)
-            c->prev_caller = shown;
-        }
+        if (adopt) adopt_frame(c, idx, t, dst);
         if (data_pnt) *data_pnt = shown;
         if (significant_changes) *significant_changes = idx->reported[(size_t)t];
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- playback: a run of frames of the index, each into a buffer of its own — reverse play and the step-back button held down, xs
+// fast-forward, filling the Manager's free buffers around the frame of interest — in ONE launch of msv1_index_play_kernel instead of a
+// loop of Shows, each a launch and a synchronise that walks the bitmap and decodes every block of the picture again.
+extern "C" int jsp_index_play(jsp_codec* c, jsp_index* idx, int first, int n, int stride, int32_t* const* dsts, int adopt_k,
+                              int32_t** data_pnts, int* significant_changes) {
+    if (!c || !idx || !dsts) return fail("index_play: null argument");
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_play: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("index_play: n is outside 1..4096");
+    if (stride < 1) return fail("index_play: stride must be at least 1");
+    if (first < 0 || (int64_t)first + (int64_t)(n - 1) * (int64_t)stride >= (int64_t)idx->nframes) return fail("index_play: the run is outside the index");
+    if (adopt_k < -1 || adopt_k >= n) return fail("index_play: adopt_k is outside -1..n-1");
+    for (int k = 0; k < n; ++k)
+        if (!dsts[k]) return fail("index_play: null argument (an entry of dsts)");
+    if (!nothing_in_flight(c, "index_play")) return JSP_ERROR_OCCURED;
+    bool aligned16 = true;
+    {
+        std::vector<const int32_t*> sorted(dsts, dsts + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail("index_play: the same buffer twice in dsts");
+        for (int k = 0; k < n; ++k) {
+            if (!dst_not_previous(c, dsts[k], "index_play")) return JSP_ERROR_OCCURED;
+            aligned16 = aligned16 && (reinterpret_cast<uintptr_t>(dsts[k]) & 15) == 0;
+        }
+    }
+    try {
+        c->activate();
+        for (int k = 0; k < n; ++k)
+            if (!dst_on_device(dsts[k], "index_play")) return JSP_ERROR_OCCURED;
+        if (!device_pointers(c, "index_play")) return JSP_ERROR_OCCURED;
+        if (n == 1) stride = 1;
+        // a frame before the first adopting one writes nothing (jsp_seek of frames 0..t would not): a null entry for the kernel
+        const int first_written = first >= idx->first_adopted ? 0 : (int)std::min<int64_t>(n, ((int64_t)idx->first_adopted - first + stride - 1) / stride);
+        if (first_written < n) {
+            idx->h_play_dsts.reserve(sizeof(int32_t*) * (size_t)n);
+            idx->d_play_dsts.reserve(sizeof(int32_t*) * (size_t)n);
+            int32_t** h = static_cast<int32_t**>(idx->h_play_dsts.p);
+            std::fill(h, h + first_written, nullptr);
+            std::copy(dsts + first_written, dsts + n, h + first_written);
+            JSP_HIP(hipMemcpyAsync(idx->d_play_dsts.p, h, sizeof(int32_t*) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            const int segs = c->index_play_segments > 0 ? c->index_play_segments : msv1_index_play_auto_segments(idx->geo, n);
+            msv1_launch_index_play(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
+                                   static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p), first, n, stride, segs,
+                                   static_cast<int32_t* const*>(idx->d_play_dsts.p), aligned16,
+                                   idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, c->stream);
+            JSP_HIP(hipGetLastError());
+            JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned destination list is free for the next call)
+        }
+        if (adopt_k >= 0) adopt_frame(c, idx, first + adopt_k * stride, dsts[adopt_k]);
+        for (int k = 0; k < n; ++k) {
+            const int t = first + k * stride;
+            if (data_pnts) data_pnts[k] = t >= idx->first_adopted ? dsts[k] : idx->prev_caller;
+            if (significant_changes) significant_changes[k] = idx->reported[(size_t)t];
+        }
         return JSP_ZERO_STATE;
     } catch (const std::exception& e) {
         set_error("%s", e.what());

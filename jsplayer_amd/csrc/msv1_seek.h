@@ -73,6 +73,15 @@ void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, 
 // ONE launch of msv1_index_show_kernel: frame t of the index into dst.
 void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
                             const uint32_t* d_bitmap, int t, int32_t* dst, const int32_t* before, hipStream_t stream);
+// ONE launch of msv1_index_play_kernel: index frames first + k * stride, k < n, each into d_dsts[k] (a device array; a null entry is
+// walked but not written) exactly as msv1_launch_index_show writes it.  The run is split into `segs` (clamped to 1..n) contiguous
+// segments of destinations along grid.y, each composing its own first frame; the pictures do not depend on the split.
+// dsts_aligned16: every non-null destination is 16-byte aligned (else the scalar instantiation).
+void msv1_launch_index_play(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                            const uint32_t* d_bitmap, int first, int n, int stride, int segs, int32_t* const* d_dsts, bool dsts_aligned16,
+                            const int32_t* before, hipStream_t stream);
+// Segments for a run of n frames when the caller leaves it to the library (option "msv1_index_play_segments" = "auto").
+int msv1_index_play_auto_segments(const Msv1Geometry& geo, int n);
 // ONE launch of msv1_index_thumbs_kernel: the pictures of index frames d_frames[0..n) (a device array), each reduced scale x scale
 // pixels to one (scale 4, 8 or 16; box mean, rounded half up), into the sheet `out`: thumbnails of (4 nbx / scale) x (4 nby / scale)
 // pixels, `cols` to a sheet row, row pitch cols thumbnail widths.  A block nothing up to its frame coded comes from `before`, else is 0.

@@ -355,6 +355,116 @@ __global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexChun
     store_block<VEC>(dst + di, X, px);
 }
 
+// index_last_writer with a lower bound: the bitmap word of block `blk` that holds the last frame in (tp, t] coding it, masked to those
+// frames (highest set bit = that frame; w is set), or 0 when nothing in the span coded the block.  The top word is masked to the frames
+// <= t, the bottom word (that of frame tp + 1) to the frames > tp, and the walk down (SCAN words in flight per step) stops at the bottom
+// word.  (cw, cv) is the top word the lane fetched last and (pw, pv) the one before it: consecutive spans of a run fetch a word once
+// while the run's frames stay in it, and a span of stride <= 32 — two words at most — finds its bottom word in (pw, pv).
+__device__ __forceinline__ uint32_t index_last_writer_span(const uint32_t* __restrict__ bitmap, int nblocks, int blk, int tp, int t, int& w,
+                                                           int& cw, uint32_t& cv, int& pw, uint32_t& pv) {
+    const int lo = tp + 1, wb = lo >> 5;
+    const uint32_t mask_lo = 0xFFFFFFFFu << (lo & 31);
+    w = t >> 5;
+    if (w != cw) {
+        pw = cw; pv = cv;
+        cw = w; cv = *(scgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk);
+    }
+    uint32_t m = cv & (0xFFFFFFFFu >> (31 - (t & 31)));
+    if (w == wb) return m & mask_lo;
+    while (m == 0u && w > wb) {
+        uint32_t e[SCAN];
+#pragma unroll
+        for (int k = 0; k < SCAN; ++k) {
+            const int i = w - 1 - k;
+            e[k] = i < wb ? 0u : i == pw ? pv : *(scgu32*)(bitmap + (size_t)i * (size_t)nblocks + blk);
+            if (i == wb) e[k] &= mask_lo;
+        }
+        int step = SCAN;
+#pragma unroll
+        for (int k = SCAN - 1; k >= 0; --k)
+            if (e[k] != 0u) { m = e[k]; step = k + 1; }
+        w -= step;
+    }
+    return m;
+}
+
+// The 16 pixels frame f of the index makes of block `blk`, which it codes: its chunk's table entry and stream, as the show kernel.
+template <int BITS>
+__device__ __forceinline__ void index_decode(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk, size_t pitch,
+                                             int f, int blk, const uint32_t* s_pal, uint32_t (&px)[16]) {
+    const Msv1IndexChunk ch = chunks[frame_chunk[f]];
+    const int lf = f - (int)ch.first;
+    const uint32_t o = *(scgu32*)(ch.desc + (size_t)lf * pitch + blk);
+    decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
+}
+
+// Play (jsp_index_play): frames t_k = first + k * stride, k < n, each into dsts[k] exactly as msv1_index_show_kernel(t_k) writes it — ONE
+// launch.  One work-item per block as there, and per SEGMENT of the run (blockIdx.y: destinations [y * seg, (y + 1) * seg)).  The lane
+// composes its segment's first frame as the show kernel does and keeps the 16 pixels in registers; `have` says whether the block is
+// defined yet (no writer so far and no `before`: Show leaves such a block alone, and so does every store here).  For each further
+// frame it asks for the last writer in (t_{k-1}, t_k] (index_last_writer_span): a coded block overwrites the whole block, so only the
+// last writer of the gap is decoded, and the registers stay when there is none.  A null dsts[k] (a frame before the index's first
+// adopting one, where Show writes nothing) is walked but not stored.  k is wave-uniform: all lanes of a wave store to the same
+// destination in the same iteration, with the show kernel's row stores.  Work-items past the last block copy the pixels no block covers
+// from `before` into every non-null destination of the segment.
+template <int BITS, bool VEC>
+__global__ __launch_bounds__(WG) void msv1_index_play_kernel(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk,
+                                                             const int32_t* __restrict__ palette, const uint32_t* __restrict__ bitmap, size_t pitch,
+                                                             int first, int n, int stride, int seg, uint32_t* const* __restrict__ dsts,
+                                                             const uint32_t* __restrict__ before, int nblocks, int nbx, int X, int cx, int cy,
+                                                             long nrem) {
+    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
+    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
+    if (BITS == 8) __syncthreads();
+    const int k0 = (int)blockIdx.y * seg;
+    const int k1 = min(n, k0 + seg);
+    const long gid = (long)blockIdx.x * WG + threadIdx.x;
+    if (gid >= nblocks) {   // a pixel no block covers, as in msv1_seek_kernel
+        const long r = gid - nblocks;
+        if (r >= nrem || before == nullptr) return;
+        const long rw = (long)(X - cx) * cy;
+        const size_t i = r < rw ? (size_t)(r / (X - cx)) * (size_t)X + (size_t)cx + (size_t)(r % (X - cx)) : (size_t)cy * (size_t)X + (size_t)(r - rw);
+        const uint32_t v = *(scgu32*)(before + i);
+        for (int k = k0; k < k1; ++k) {
+            uint32_t* d = dsts[k];
+            if (d != nullptr) *(sgu32*)(d + i) = v;
+        }
+        return;
+    }
+    const int blk = (int)gid;
+    const int by = blk / nbx;
+    const int bx = blk - by * nbx;
+    const size_t di = (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
+    int t = first + k0 * stride;
+    int w;
+    uint32_t m = index_last_writer(bitmap, nblocks, blk, t, w);
+    uint32_t px[16];
+    bool have = true;
+    if (m != 0u) {
+        index_decode<BITS>(chunks, frame_chunk, pitch, 32 * w + 31 - __builtin_clz(m), blk, s_pal, px);
+    } else if (before != nullptr) {
+        load_block<VEC>(before + di, X, px);
+    } else {   // nothing up to t_k0 coded the block and there is no picture before the range
+        have = false;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) px[i] = 0u;
+    }
+    int cw = -1, pw = -1;
+    uint32_t cv = 0u, pv = 0u;
+    for (int k = k0;;) {
+        uint32_t* d = dsts[k];
+        if (have && d != nullptr) store_block<VEC>(d + di, X, px);
+        if (++k >= k1) break;
+        const int tp = t;
+        t += stride;
+        m = index_last_writer_span(bitmap, nblocks, blk, tp, t, w, cw, cv, pw, pv);
+        if (m != 0u) {
+            index_decode<BITS>(chunks, frame_chunk, pitch, 32 * w + 31 - __builtin_clz(m), blk, s_pal, px);
+            have = true;
+        }
+    }
+}
+
 // Thumbnails (jsp_index_thumbs): the pictures of n frames of the index, each reduced S x S pixels to one (box mean, rounded half up),
 // into one sheet — ONE launch, no full-size picture anywhere.  blockIdx.y is the thumbnail, frames[blockIdx.y] its frame; a lane per
 // 4x4 block and thumbnail finds the block's last writer <= t as the show kernel does (index_last_writer), decodes that one code (or
@@ -507,6 +617,30 @@ void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chu
     if (geo.bits == 16) { if (g.vec) JSP_SHOW(16, true); else JSP_SHOW(16, false); }
     else { if (g.vec) JSP_SHOW(8, true); else JSP_SHOW(8, false); }
 #undef JSP_SHOW
+}
+
+int msv1_index_play_auto_segments(const Msv1Geometry& geo, int n) {
+    // the rule of scan_grid: enough work-items for ~8 waves per SIMD (a 1080p picture alone gives ~2), never more segments than frames
+    const long waves_one = std::max(1L, ((long)geo.nblocks + 63) / 64);
+    const long nseg = std::max(1L, (8L * 1024L + waves_one - 1) / waves_one);
+    return (int)std::min(nseg, (long)std::max(n, 1));
+}
+
+void msv1_launch_index_play(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                            const uint32_t* d_bitmap, int first, int n, int stride, int segs, int32_t* const* d_dsts, bool dsts_aligned16,
+                            const int32_t* before, hipStream_t stream) {
+    PictureGrid g;
+    if (n <= 0 || !picture_grid(geo, nullptr, before, g)) return;
+    const bool vec = g.vec && dsts_aligned16;
+    const int seg = (n + std::min(std::max(segs, 1), n) - 1) / std::min(std::max(segs, 1), n);   // destinations per segment
+    const dim3 grid(g.grid.x, (unsigned)((n + seg - 1) / seg));
+    const size_t pitch = (size_t)std::max(geo.nblocks, 1);
+#define JSP_PLAY(BITS, VEC) hipLaunchKernelGGL((msv1_index_play_kernel<BITS, VEC>), grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk, d_palette, \
+                                               d_bitmap, pitch, first, n, stride, seg, reinterpret_cast<uint32_t* const*>(d_dsts),               \
+                                               reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem)
+    if (geo.bits == 16) { if (vec) JSP_PLAY(16, true); else JSP_PLAY(16, false); }
+    else { if (vec) JSP_PLAY(8, true); else JSP_PLAY(8, false); }
+#undef JSP_PLAY
 }
 
 void msv1_launch_index_thumbs(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,

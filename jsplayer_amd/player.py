@@ -330,6 +330,73 @@ class Manager:
                     on_frame(d, self.buffers[nb])
         return out
 
+    def run_from_index(self, start: int, count: Optional[int] = None, stride: int = 1, reverse: bool = False,
+                       on_frame: Optional[Callable[[DecodedFrame, object], None]] = None,
+                       key_flags: Optional[Sequence[bool]] = None) -> List[DecodedFrame]:
+        """Clip frames start, start + stride, ... — or, with `reverse`, start, start - stride, ... — (`count` of them; None: to the
+        end, or the start, of the index) served from an attached index that adopts and has `Play` (MSVideo1's SeekIndex): reverse
+        play and the step-back button held down, fast-forward, filling the free buffers around the frame of interest.  The frames
+        go out in batches of the buffers that are not the decoder's previous frame, ONE `Play` launch per batch (for reverse the
+        batch's lowest frame is its first and the buffer list is reversed).  `on_frame(frame, buffer)` is called per frame in shown
+        order, before the next batch overwrites its buffer; holds follow each frame's data_pnt as in seek() (a frame that wrote
+        nothing extends the hold of the buffer that shows it), `log` gets a DecodedFrame per frame.  The last frame shown is
+        adopted, in the final batch only: afterwards the decoder stands at it, `next_frame_to_decode` is that frame + 1,
+        `frame_of_interest` that frame, and worker / play go on from there.  `key_flags` as for seek().  ValueError: no index
+        attached, a frame outside it, an index that does not adopt (play_from_index serves it), an index object without `Play`."""
+        if self.index is None:
+            raise ValueError("no seek index attached")
+        if not self._index_adopts():
+            raise ValueError("the attached seek index does not adopt: play_from_index serves it")
+        if not hasattr(self.index, "Play"):
+            raise ValueError("the attached seek index cannot play")
+        start, stride = int(start), int(stride)
+        if stride < 1:
+            raise ValueError("stride must be at least 1")
+        step = -stride if reverse else stride
+        if count is None:
+            room = start - self.index_first if reverse else self.index_first + self.index.frames - 1 - start
+            count = room // stride + 1 if self._in_index(start) else 0
+        count = int(count)
+        if count < 1 or not self._in_index(start) or not self._in_index(start + (count - 1) * step):
+            raise ValueError(f"frames {start} .. {start + (max(count, 1) - 1) * step} are not all in the attached seek index")
+        prev = self.decoder.PreviousFrame()
+        prev_idx = self._slot_of(prev) if prev is not None else -1
+        slots = [nb for nb in range(len(self.buffers)) if nb != prev_idx]
+        out: List[DecodedFrame] = []
+        for k0 in range(0, count, len(slots)):
+            batch = slots[:min(len(slots), count - k0)]
+            m = len(batch)
+            shown_first = start + k0 * step                     # the batch's frames in shown order: shown_first + j * step
+            final = k0 + m >= count
+            bufs = [self.buffers[nb] for nb in batch]
+            if reverse:   # an ascending run from the batch's lowest frame, the last one shown: buffer j holds run frame m - 1 - j
+                results = self.index.Play(shown_first + (m - 1) * step - self.index_first, bufs[::-1], stride, adopt=0 if final else None)[::-1]
+            else:
+                results = self.index.Play(shown_first - self.index_first, bufs, stride, adopt=m - 1 if final else None)
+            for nb in batch:
+                self.holds[nb] = None
+            for j, (nb, res) in enumerate(zip(batch, results)):
+                i = shown_first + j * step
+                shown = nb
+                if res.data_pnt is not None:
+                    held = self._slot_of(res.data_pnt)
+                    if res.data_pnt is not self.buffers[nb] and held >= 0:      # nothing up to frame i changed the picture
+                        h = self.holds[held]
+                        self.holds[held] = range(min(h.start, i), max(h.stop, i + 1)) if h else range(i, i + 1)
+                        shown = held
+                    else:
+                        self.holds[nb] = range(i, i + 1)
+                self.frame_of_interest = i
+                key = key_flags is not None and i < len(key_flags) and bool(key_flags[i])
+                d = DecodedFrame(i, key, shown, None if key else res.significant_changes)
+                self.log.append(d)
+                out.append(d)
+                if on_frame:
+                    on_frame(d, self.buffers[shown])
+        self.next_frame_to_decode = out[-1].index + 1
+        self._last_was_key = out[-1].key
+        return out
+
     def _known_significance(self) -> Dict[int, bool]:
         """frames[i].significant_changes of the reference's loader: what decoding frame i recorded (missing = not known)."""
         known = {}
