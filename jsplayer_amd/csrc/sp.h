@@ -13,6 +13,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <functional>
 #include <memory>
 #include <vector>
@@ -265,6 +266,13 @@ struct PGroupFrame {   // one per frame of the group, in decode order
 };
 void launch_pframe_group(const Geometry& g, const PGroupFrame* d_frames, int nframes, const int32_t* prev,
                          const PBlock* d_blocks, const uint32_t* d_payload, bool aligned16, hipStream_t stream);
+// Which of the two group kernels that launch takes: sp_pframe_group_kernel (a loader wave, whole 16-byte chunks everywhere) when the
+// width is a multiple of 4 and `prev` and every destination (aligned16) are 16-byte aligned, else sp_pframe_group1_kernel, which
+// stages its own chunks.  The one place that decides it: the launcher and what a staged batch reports both ask here.
+inline bool pframe_group_takes_loader(const Geometry& g, const int32_t* prev, bool aligned16) {
+    static const bool old_form = std::getenv("JSP_SP_GROUP_OLD") != nullptr;   // lab: the kernel that stages its own chunks
+    return (g.X & 3) == 0 && aligned16 && (reinterpret_cast<uintptr_t>(prev) & 15) == 0 && !old_form;
+}
 // Seek index (sp_index_kernels.hip): frame t of a resident range — the key picture `key` of frame k <= t under the literal rectangles of the
 // LAST frame in (k, t] that covers each pixel.  Frame f's block table is d_blocks + (f + slot_base) * nblocks; PBlock::payload counts in
 // 16-byte units of d_payload there; d_bitmap[w * nblocks + b] bit j: frame 32 w + j changes block b.  Every pixel of dst is written.

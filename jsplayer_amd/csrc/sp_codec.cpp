@@ -624,7 +624,7 @@ struct SpCodec : jsp_codec, DstColumns, IndexLender {
                     st->note_kernel(op.tiles ? "sp_iframe_tile_kernel" : "sp_iframe_rows_search_kernel");
                 } else if (op.kind == SpStaged::Op::InterGroup) {
                     moved += 4 * npx * op.count + 4 * npx;
-                    st->note_kernel("sp_pframe_group_kernel");
+                    st->note_kernel(pframe_group_takes_loader(st->geo, op.prev, st->geo.aligned16) ? "sp_pframe_group_kernel" : "sp_pframe_group1_kernel");
                 } else {
                     moved += 8 * npx;
                     st->note_kernel("sp_pframe_kernel");

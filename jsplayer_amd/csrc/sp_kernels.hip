@@ -959,8 +959,7 @@ void launch_pframe_group(const Geometry& g, const PGroupFrame* d_frames, int nfr
     // pixels of a chunk fetched by a flat index space in one round trip (3 % slower than rectangle by rectangle).
     // With the block records withheld (every block "unchanged", nothing staged but the destinations) the same loop
     // takes 483 us — the temporal fill ceiling; without the literal fetches 539 us.
-    static const bool old_form = std::getenv("JSP_SP_GROUP_OLD") != nullptr;   // lab: the kernel that stages its own chunks
-    if (vec && (g.X & 3) == 0 && !old_form) {   // whole 16-byte chunks everywhere: the loader-wave kernel
+    if (pframe_group_takes_loader(g, prev, aligned16)) {   // whole 16-byte chunks everywhere: the loader-wave kernel
         static std::once_flag attr_once;
         std::call_once(attr_once, [] {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sp_pframe_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
