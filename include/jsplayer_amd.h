@@ -96,26 +96,32 @@ const char* jsp_last_error(void);
 /* ---- frame pool in HBM (Manager.hx:114-118: num_buffers+1 frame buffers) ---------------- */
 
 /* A pool of 32 frames or more (what batch decoding writes into: tile j of every frame at about the same time, or every frame of a clip one after
- * the other from the same workgroups) is PLACED.  What the decode kernels' stores get from a pool depends on where its frames lie relative to each
- * other: frames that are neighbours in memory cost the frame-walking kernels a sixth and can cost the batch kernels a quarter (no query
- * reveals it).  The pool therefore allocates, in one run, four times the 16-frame chunks it needs, takes every fourth (candidate k: chunks k, k + 4, ...)
- * and DEALS its frames round-robin over them — buffer i and buffer i + 1 never lie in the same chunk —, measures the candidate with the kernels' store
- * shape (a few milliseconds), keeps the first that takes what a plain fill takes and gives the other chunks back; only when none of the four comes
- * near do the older forms (one allocation, two frames per allocation, one per frame — frames taken in a strided order) get a try; boards differ in
- * which form their memory likes, so the form that won the last probe of the process is tried first by the next pool.  Decode consecutive
- * frames into consecutive buffers of the pool and they are far apart.  JSP_POOL_PROBE=0 in the environment: one allocation per frame, first come — what
- * smaller pools (a player's num_buffers + 1) always get.  The probe's appetite is bounded (jsp_pool_probe_info; while it chooses it holds four times
- * the pool, or what JSP_POOL_PROBE_HOLD_GB / a quarter of the free memory allows). */
+ * the other from the same workgroups) is PLACED.  What the decode kernels' stores get from a pool depends on where its frames lie in physical memory,
+ * relative to each other (no query reveals it), so the pool measures candidates with the kernels' store shape (a few milliseconds each)
+ * against what a plain fill takes from the same device, and keeps the best:
+ *   - first the MAPPED forms: one address range backed by physical allocations of the pool's own making (hipMemCreate / hipMemMap), in three
+ *     arrangements — an allocation per frame; sixteen frames per allocation, dealt over them; sixteen per allocation, in order.  The first that comes
+ *     within 3 % of the fill is kept; when none does, up to six more candidates of the first arrangement are made of other memory (for at most
+ *     JSP_POOL_PROBE_MS milliseconds, default 250) and the best of all is kept.  The buffers are device pointers, but not hipMalloc allocations;
+ *   - the bounds: at most JSP_POOL_PROBE_MAX candidates are measured (default 16), and what the probe holds while it chooses (the best so far and
+ *     the rejects, so that the next candidate is made of other memory) stays within a quarter of the device memory that was free when it began, or
+ *     JSP_POOL_PROBE_HOLD_GB (GB) if that is lower, never less than the pool itself (jsp_pool_probe_info);
+ *   - the hipMalloc forms are tried only when no mapped form can be made (JSP_POOL_PROBE_MAPPED=0: as if none could), or after the mapped ones when
+ *     JSP_POOL_PROBE_THOROUGH=1 and none of those came within 3 % of the fill: the older form that won the last probe of the process on this device
+ *     (JSP_POOL_PROBE_FORM=0|1|2 names one: two frames per allocation, one allocation, one per frame); then chunks of 16 frames — a quarter of a run
+ *     four times as long, the frames dealt round-robin over them, up to four choices of chunks —; then the older forms in turn, their frames taken
+ *     in a strided order.
+ * In the dealt, chunked and strided forms consecutive buffers of the pool are not neighbours in memory (unless the whole pool fits one physical allocation).  JSP_POOL_PROBE=0 in the environment: one
+ * allocation per frame, first come — what smaller pools (a player's num_buffers + 1) always get.  JSP_POOL_PROBE_LOG: a line per candidate on stderr. */
 jsp_pool* jsp_pool_create(int device_id, int width, int height, int nbuf);
 int32_t* jsp_pool_buffer(jsp_pool* p, int i); /* device pointer, width*height ints, zeroed */
-/* GB/s the chosen allocation took from the probe (0: a pool that is not probed); *attempts = allocations tried. */
+/* GB/s the chosen candidate took from the probe (0: a pool that is not probed); *attempts = candidates measured. */
 double jsp_pool_store_rate(jsp_pool* p, int* attempts);
 /* What placing the pool cost: wall time of the probe, the most device memory it held at one time (rejected candidates are kept until it
- * has chosen) and what it was allowed to hold — a quarter of the device memory free when it began, JSP_POOL_PROBE_HOLD_GB (GB) if lower,
- * never more than JSP_POOL_PROBE_MAX candidates (default 16).  All 0 for a pool that is not probed.  Returns 0, -1 for a null pool. */
+ * has chosen) and what it was allowed to hold (the bounds: jsp_pool_create above).  All 0 for a pool that is not probed.  Returns 0, -1 for a null pool. */
 int jsp_pool_probe_info(jsp_pool* p, double* probe_ms, uint64_t* held_peak_bytes, uint64_t* hold_limit_bytes);
-/* What every candidate the probe measured took (GB/s, in the order tried: first the chunked candidates, then the older forms): up to `cap` of them
- * into `rates`; returns how many were measured (0 for a pool that is not probed, -1 for a null pool). */
+/* What every candidate the probe measured took (GB/s, in the order tried: the mapped candidates, then — when they are tried at all — the older
+ * form hinted at, the chunked candidates, the older forms in turn): up to `cap` of them into `rates`; returns how many were measured (0 for a pool that is not probed, -1 for a null pool). */
 int jsp_pool_probe_rates(jsp_pool* p, double* rates, int cap);
 int jsp_pool_count(jsp_pool* p);
 void jsp_pool_destroy(jsp_pool* p);

@@ -67,7 +67,7 @@ def test_product_does_not_reference_the_oracle():
 
 
 def test_threaded_host_layers_are_clean_under_thread_sanitizer(tmp_path):
-    """tools/tsan_cpu.sh: jsp_api.cpp, msv1_codec.cpp, sp_codec.cpp, jsp_shard.cpp and the host stages built with -fsanitize=thread against
+    """tools/tsan_cpu.sh: jsp_api.cpp, jsp_pool.cpp, msv1_codec.cpp, sp_codec.cpp, jsp_shard.cpp and the host stages built with -fsanitize=thread against
     the stub HIP runtime under tests/tsan/ and driven on 26 host threads (asynchronous submit / wait out of phase, drains, prefetch ranges
     given up mid-flight, staged batches, pools created and destroyed side by side).  Round 6's first run found a race — the caller's thread
     reading the stream decoder's settings while the first group's worker wrote its key-frame layout into the same decoder (sp_codec.cpp,

@@ -2,7 +2,7 @@
 // host layers (tools/tsan_cpu.sh; stub HIP runtime and kernels in this directory: no GPU, nothing is painted).  Every scenario runs on several
 // host threads at once, each with codecs of its own — the layers under test are the ones that start threads or share state between codecs:
 // sp_codec.cpp's worker groups and shared host-thread budget, msv1_codec.cpp's asynchronous ring / held frames / prefetch ranges / re-runs,
-// jsp_api.cpp's pools, option table and error string.  The run is clean when ThreadSanitizer prints nothing and the driver ends with "tsan driver: ok".
+// jsp_pool.cpp's pools, jsp_api.cpp's option table and error string.  The run is clean when ThreadSanitizer prints nothing and the driver ends with "tsan driver: ok".
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>

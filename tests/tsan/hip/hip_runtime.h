@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE, not product: a stand-in for <hip/hip_runtime.h> so that the product's threaded HOST layers (jsp_api.cpp, msv1_codec.cpp,
+// TEST INFRASTRUCTURE, not product: a stand-in for <hip/hip_runtime.h> so that the product's threaded HOST layers (jsp_api.cpp, jsp_pool.cpp, msv1_codec.cpp,
 // sp_codec.cpp, jsp_shard.cpp and the host stages) can be built with g++ -fsanitize=thread and driven without a GPU (GPU sanitizers are not
 // available on this pool; tools/tsan_cpu.sh).  "Device memory" is host memory, every stream operation runs at the call, kernels are no-ops
 // (tests/tsan/kernel_stubs.cpp) — what is under test is the host threads' synchronisation with EACH OTHER, not pixels.  What a real runtime
@@ -73,6 +73,13 @@ hipError_t hipMemRelease(hipMemGenericAllocationHandle_t);
 hipError_t hipMemMap(void*, size_t, size_t offset, hipMemGenericAllocationHandle_t, unsigned long long flags);
 hipError_t hipMemUnmap(void*, size_t);
 hipError_t hipMemSetAccess(void*, size_t, const hipMemAccessDesc*, size_t count);
+
+// Two test-only hooks, both unset by default (tests/pool_probe/trace.cpp sets them).  The observer is called on every hipMalloc, hipFree, hipMemset,
+// hipMemGetInfo, hipMemAddressReserve / Free, hipMemCreate / Release and hipMemMap / Unmap with the call's name, its result, the address and size it
+// concerns and, for the physical-allocation calls, the handle.  The budget: hipMalloc and hipMemCreate fail with hipErrorOutOfMemory when the request
+// would take what the two have outstanding past `max_bytes`, or once `max_calls` of them have succeeded since it was set (-1: no limit on calls).
+extern void (*stub_mem_observer)(const char* call, hipError_t result, const void* p, size_t bytes, const void* handle);
+void stub_alloc_budget(size_t max_bytes, long max_calls);
 
 // what the kernel stubs call: "a kernel was queued on this stream"
 void stub_stream_work(hipStream_t stream);

@@ -65,8 +65,10 @@ void msv1_launch_blocks(const Msv1Geometry&, const uint8_t*, const uint32_t*, co
 void msv1_launch_blocks_temporal(const Msv1Geometry&, const uint8_t*, const uint32_t*, const Msv1FrameArgs*, int, const int32_t*, hipStream_t s) { stub_stream_work(s); }
 void msv1_launch_edge_compare(const Msv1Geometry&, const Msv1FrameArgs*, int, hipStream_t s) { stub_stream_work(s); }
 void launch_frames_differ(const int32_t*, const int32_t*, size_t, size_t, uint32_t* d_flag, hipStream_t s) { if (d_flag) *d_flag = 0; stub_stream_work(s); }
+#ifndef JSP_STUB_NO_POOL_RATES                     // (tests/pool_probe/trace.cpp scripts the two measurements itself)
 double pool_store_rate(uint32_t* const*, int, int, int, uint32_t) { return 6900.0; }
 double pool_fill_rate(uint32_t*, size_t) { return 6900.0; }
+#endif
 
 namespace sp {
 int choose_band_rows(const Geometry& g, int nframes) {

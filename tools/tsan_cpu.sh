@@ -1,5 +1,5 @@
 #!/bin/bash
-# ThreadSanitizer over the product's threaded HOST layers, without a GPU (GPU sanitizers are not available on this pool): jsp_api.cpp,
+# ThreadSanitizer over the product's threaded HOST layers, without a GPU (GPU sanitizers are not available on this pool): jsp_api.cpp, jsp_pool.cpp,
 # msv1_codec.cpp, sp_codec.cpp, jsp_shard.cpp and the host stages built with g++ -fsanitize=thread against the stub HIP runtime and the
 # kernel stubs under tests/tsan/, driven by tests/tsan/driver.cpp (asynchronous submit / wait out of phase, drains, prefetch ranges given up
 # mid-flight, staged batches, sixteen-odd streams on as many threads, pools created and destroyed side by side).
@@ -10,7 +10,7 @@ OUT="${JSP_TSAN_DIR:-$(mktemp -d /tmp/jsp_tsan.XXXX)}"
 C="$ROOT/jsplayer_amd/csrc"; T="$ROOT/tests/tsan"
 FLAGS="-std=c++17 -O1 -g -fsanitize=thread -fPIC -pthread -I$T -I$C -I$ROOT/include"
 pids=()
-for f in jsp_api jsp_shard msv1_codec msv1_host sp_codec sp_entropy sp_host sp_models; do
+for f in jsp_api jsp_pool jsp_shard msv1_codec msv1_host sp_codec sp_entropy sp_host sp_models; do
   g++ $FLAGS -c "$C/$f.cpp" -o "$OUT/$f.o" & pids+=($!)
   if [ ${#pids[@]} -ge 4 ]; then wait "${pids[0]}"; pids=("${pids[@]:1}"); fi
 done
