@@ -2,6 +2,10 @@
 // what a native host (or an hxcpp build of the player) would do with libjsplayer_amd.so.
 //
 //   jsp_play clip.avi            prints one line per frame:  index key|inter slot significant crc32
+//   jsp_play clip.avi --present WxH[:zoom[:hpos:vpos]]
+//                                the plain run, and every frame shown is also presented into a W x H device window (jsp_view_matrix +
+//                                jsp_display_present, bilinear: zoom 0 = "Fit" (default), 1 = "100%", 2 = "200%"; view positions in 0..1,
+//                                default 0.5 — Main.on_stage_resize, Main.hx:288-319); the lines end in the window's crc32
 //   jsp_play clip.avi --pipelined [--depth D]
 //                                the same lines, decoded through jsp_decompress_*_async / jsp_wait with D frames in
 //                                flight: the host stage of frame n+1 overlaps the uploads and kernels of frame n
@@ -393,7 +397,7 @@ long play_batched(const Clip& clip, int batch, int repeat, bool quiet, int warmu
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]]\n", argv[0]); return 2; }
     // (throughput runs: several files, separated by commas — stream s plays file s modulo their number, so that the streams of a
     // multi-stream run are independent inputs)
     std::deque<Clip> clips;                                   // (a deque: elements never move)
@@ -418,6 +422,8 @@ int main(int argc, char** argv) {
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
     long play_first = -1, play_count = -1, play_stride = 1;   // --play-index FIRST[:COUNT[:STRIDE]]: frames played out of a ScreenPressor seek index
     long run_first = -1, run_count = -1, run_stride = 1;      // --index-run FIRST[:COUNT[:STRIDE]]: frames played out of an MSVideo1 seek index
+    int present_w = 0, present_h = 0;                         // --present WxH[:zoom[:hpos:vpos]]: every frame shown also goes into a device window
+    double present_zoom = 0, present_hpos = 0.5, present_vpos = 0.5;
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -457,6 +463,11 @@ int main(int argc, char** argv) {
             if (c2 != std::string::npos) run_stride = std::atol(v.substr(c2 + 1).c_str());
             if (run_first < 0 || (c1 != std::string::npos && run_count < 1) || run_stride < 1) { std::fprintf(stderr, "--index-run: FIRST >= 0, COUNT >= 1, STRIDE >= 1\n"); return 2; }
         }
+        else if (o == "--present" && a + 1 < argc) {
+            const std::string v = argv[++a];
+            const int got = std::sscanf(v.c_str(), "%dx%d:%lf:%lf:%lf", &present_w, &present_h, &present_zoom, &present_hpos, &present_vpos);
+            if ((got != 2 && got != 3 && got != 5) || present_w < 1 || present_h < 1) { std::fprintf(stderr, "--present: WxH[:zoom[:hpos:vpos]]\n"); return 2; }
+        }
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
             for (size_t at = 0; at <= list.size();) {
@@ -476,6 +487,7 @@ int main(int argc, char** argv) {
     if (play_first >= 0 && clip.kind != JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--play-index: ScreenPressor only (an MSVideo1 index adopts: --seek and the plain run play on from any frame)\n"); return 2; }
     if (run_first >= 0 && (play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--index-run goes alone\n"); return 2; }
     if (run_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--index-run: MSVideo1 only (--play-index plays a ScreenPressor index)\n"); return 2; }
+    if (present_w > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--present goes with the plain per-frame run\n"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
         if (!quiet) return play_batched(clip, batch, 1, false) < 0 ? 1 : 0;
@@ -835,6 +847,23 @@ int main(int argc, char** argv) {
         std::printf("%ld %s %d %d %08x\n", seek_to, last_was_key ? "key" : "inter", shown, last_was_key ? -1 : signif, crc);
         begin = (size_t)seek_to + 1;
     }
+    // --present: the window Main.on_stage_resize would draw (Main.hx:301-318), one launch per frame shown; the display mode as
+    // Manager.hx:121 chooses convert_fromRGB15
+    jsp_pool* window = nullptr;
+    std::vector<int32_t> window_host;
+    double view_k = 1, view_dx = 0, view_dy = 0;
+    const int present_mode = clip.bpp == 16 && clip.kind == JSP_CODEC_SCREENPRESSOR ? JSP_DISPLAY_CANVAS_RGB15 : JSP_DISPLAY_CANVAS;
+    if (present_w > 0) {
+        if (jsp_view_matrix(clip.X, clip.Y, present_w, present_h, present_zoom, present_hpos, present_vpos, &view_k, &view_dx, &view_dy) != 0) {
+            std::fprintf(stderr, "--present: %s\n", jsp_last_error());
+            jsp_pool_destroy(pool);
+            jsp_codec_destroy(dec);
+            return 2;
+        }
+        window = jsp_pool_create(0, present_w, present_h, 1);
+        if (!window) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); jsp_pool_destroy(pool); jsp_codec_destroy(dec); return 1; }
+        window_host.resize((size_t)present_w * present_h);
+    }
     for (size_t i = begin; i < clip.frames.size(); ++i) {
         const uint8_t* src = clip.bytes.data() + clip.frames[i].first;
         const size_t len = clip.frames[i].second;
@@ -884,8 +913,24 @@ int main(int argc, char** argv) {
         uint32_t crc = 0;
         if (shown >= 0 && jsp_download(jsp_pool_buffer(pool, shown), host.data(), npx) == 0)
             crc = crc32(reinterpret_cast<const uint8_t*>(host.data()), npx * 4);
-        std::printf("%zu %s %d %d %08x\n", i, key ? "key" : "inter", shown, signif, crc);
+        if (window) {
+            uint32_t wcrc = 0;
+            if (shown >= 0) {
+                int32_t* win = jsp_pool_buffer(window, 0);
+                if (jsp_display_present(jsp_pool_buffer(pool, shown), clip.X, clip.Y, win, present_w, present_h, (size_t)present_w, view_k, view_dx, view_dy,
+                                        present_mode, JSP_PRESENT_BILINEAR, 0xFF000000u, nullptr) != 0) {
+                    std::fprintf(stderr, "jsp_display_present: %s\n", jsp_last_error());
+                    rc = 1;
+                    break;
+                }
+                if (jsp_download(win, window_host.data(), window_host.size()) == 0)
+                    wcrc = crc32(reinterpret_cast<const uint8_t*>(window_host.data()), window_host.size() * 4);
+            }
+            std::printf("%zu %s %d %d %08x %08x\n", i, key ? "key" : "inter", shown, signif, crc, wcrc);
+        } else
+            std::printf("%zu %s %d %d %08x\n", i, key ? "key" : "inter", shown, signif, crc);
     }
+    if (window) jsp_pool_destroy(window);
     jsp_pool_destroy(pool);
     jsp_codec_destroy(dec);
     return rc;

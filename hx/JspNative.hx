@@ -88,6 +88,12 @@ extern class JspNative {
     @:native("jsp_pool_destroy")       static function poolDestroy(p:RawPointer<JspPool>):Void;
     @:native("jsp_download")           static function download(deviceFrame:RawConstPointer<cpp.Int32>, host:RawPointer<cpp.Int32>, npixels:SizeT):Int;
     @:native("jsp_display_convert")    static function displayConvert(frame:RawConstPointer<cpp.Int32>, out:RawPointer<cpp.Int32>, w:Int, h:Int, mode:Int, flipRows:Int, stream:RawPointer<cpp.Void>):Int;
+    // the display matrix of Main.on_stage_resize (Main.hx:301-318) and the window it shows, one launch: conversion, row flip, crop, resampling
+    @:native("jsp_view_matrix")        static function viewMatrix(frameW:Int, frameH:Int, winW:Int, winH:Int, zoom:Float, horViewPos:Float, verViewPos:Float,
+                                                                  k:RawPointer<Float>, dx:RawPointer<Float>, dy:RawPointer<Float>):Int;
+    @:native("jsp_display_present")    static function displayPresent(frame:RawConstPointer<cpp.Int32>, frameW:Int, frameH:Int, out:RawPointer<cpp.Int32>, winW:Int, winH:Int,
+                                                                      outPitch:SizeT, k:Float, dx:Float, dy:Float, mode:Int, filter:Int, background:cpp.UInt32,
+                                                                      stream:RawPointer<cpp.Void>):Int;
     @:native("jsp_frames_differ")      static function framesDiffer(a:RawConstPointer<cpp.Int32>, b:RawConstPointer<cpp.Int32>, firstPixel:SizeT, npixels:SizeT, differ:RawPointer<Int>, stream:RawPointer<cpp.Void>):Int;
 }
 

@@ -563,6 +563,53 @@ enum {
  * order (the reference leaves that to its display matrix, Main.hx:318).  Asynchronous on `hip_stream`. */
 int jsp_display_convert(const int32_t* frame, int32_t* out, int width, int height, int mode, int flip_rows,
                         void* hip_stream);
+
+/* ---- a frame in a window: zoom, scroll and fit (Main.on_stage_resize, Main.hx:288-319) ------ */
+
+/* The reference never shows its bitmap one-to-one: it draws it through the display matrix
+ *     screen (sx, sy) = (k x - dx, -k y + win_h + dy)                                   (Main.hx:318)
+ * with bitmap.smoothing = true (Main.hx:948), and leaves the resampling to the browser.  The two calls below are that step:
+ * jsp_view_matrix is Main's view geometry, jsp_display_present turns a frame buffer into the canvas pixels of a window of any size in
+ * ONE kernel launch — the conversion of jsp_display_convert, the row flip, the crop and the resampling fused; no full-size converted
+ * frame is written anywhere. */
+enum { JSP_PRESENT_NEAREST = 0, JSP_PRESENT_BILINEAR = 1 };   /* bitmap.smoothing false / true (Main.hx:948) */
+
+/* Main.hx:301-315 in doubles; pure host arithmetic, no device needed.
+ *   zoom == 0 ("Fit"): *k = min(win_w / frame_w, win_h / frame_h), *dx = *dy = 0.
+ *   zoom > 0 (Main's table holds 1 and 2; any positive factor is taken): *k = zoom,
+ *       *dx = fit(frame_w * k * hor_view_pos - win_w / 2, 0, frame_w * k - win_w)
+ *       *dy = fit(frame_h * k * (1 - ver_view_pos) - win_h / 2, 0, frame_h * k - win_h)
+ *     fit(a, mn, mx): if a < mn return mn; if a > mx return mx; return a   (Main.hx:282-286) — kept with its quirk: a zoomed picture
+ *     narrower than the window makes mx negative, and a view position past the middle then gives a negative dx, which pushes the
+ *     picture to the window's right edge.  win_w / 2 is a real division: an odd window gives a half-pixel offset.
+ *   Returns 0, or JSP_ERROR_OCCURED (jsp_last_error() starts with "view_matrix:", nothing written) for a non-positive size, a null
+ *   output, a negative or non-finite zoom or view position. */
+int jsp_view_matrix(int frame_w, int frame_h, int win_w, int win_h, double zoom,
+                    double hor_view_pos, double ver_view_pos, double* k, double* dx, double* dy);
+
+/* Writes the win_w x win_h window, top row first, into `out` (row pitch `out_pitch` ints, out_pitch >= win_w).  `frame` is a frame
+ * buffer as the codecs leave it (bottom-up rows, stride frame_w; bitmap row y = buffer row y).  ONE kernel launch on `hip_stream`,
+ * asynchronous, as jsp_display_convert.
+ *   THE RULE, in integers (the reference's resampler is the browser's; this one is pinned so that a test can ask for bit equality):
+ *     F(v) = floor(v * 65536.0 + 0.5) in double precision;  step = F(1.0 / k), ax = F((0.5 + dx) / k), ay = F((win_h + dy - 0.5) / k).
+ *     Output pixel (ox, oy): X = ax + ox * step, Y = ay - oy * step in 64-bit integers — the 16.16 bitmap coordinates of its centre.
+ *     It shows the picture when 0 <= X < frame_w * 65536 and 0 <= Y < frame_h * 65536; otherwise it is `background`, as given.
+ *     Every source pixel a tap reads is first converted by `mode` (the four JSP_DISPLAY_* conversions, bit for bit).
+ *     JSP_PRESENT_NEAREST: the converted pixel at (X >> 16, Y >> 16).
+ *     JSP_PRESENT_BILINEAR: U = X - 32768, V = Y - 32768; x0 = U >> 16, y0 = V >> 16 (arithmetic shifts); wx = (U & 0xFFFF) >> 8,
+ *       wy = (V & 0xFFFF) >> 8; taps x0, x0 + 1, y0, y0 + 1, each clamped into the picture; each of the four bytes of the converted
+ *       words on its own:  (p00 (256-wx)(256-wy) + p10 wx (256-wy) + p01 (256-wx) wy + p11 wx wy + 32768) >> 16.
+ *     Hence at k = 1 with integral dx, dy both filters give the same plain crop.
+ *   ARGUMENTS: `frame`, `out` device pointers; `out` holds (win_h - 1) * out_pitch + win_w ints, does not overlap `frame` and needs no
+ *     alignment (rows that start on 16-byte boundaries get 16-byte stores).  Only the window's pixels are written: pitch padding and
+ *     memory behind the window are not.  Sizes 1 .. 16384, 1/64 <= k <= 64.
+ *   ERRORS (JSP_ERROR_OCCURED, jsp_last_error() starts with "display_present:", nothing queued, nothing written): a null pointer, a
+ *     size or k outside its bounds, a non-finite k, dx or dy, out_pitch < win_w, an unknown mode or filter. */
+int jsp_display_present(const int32_t* frame, int frame_w, int frame_h,
+                        int32_t* out, int win_w, int win_h, size_t out_pitch,
+                        double k, double dx, double dy, int mode, int filter,
+                        uint32_t background, void* hip_stream);
+
 /* The pixel loop of frames_differ_significantly (Manager.hx:413-419): *differ = any a[i] != b[i] for
  * first_pixel <= i < npixels.  Device pointers; synchronous. */
 int jsp_frames_differ(const int32_t* a, const int32_t* b, size_t first_pixel, size_t npixels, int* differ,

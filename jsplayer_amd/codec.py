@@ -753,6 +753,41 @@ def display_convert(frame, out, width: int, height: int, mode: int = DISPLAY_CAN
         raise CodecError(N.last_error())
 
 
+# ---- a frame in a window: Main's view geometry and the browser's resampling (Main.hx:288-319, 948), one launch ----
+PRESENT_NEAREST, PRESENT_BILINEAR = 0, 1
+# what one workgroup of the present kernel covers (csrc/present_kernels.hip: kPresentSpanX, kPresentBandRows); results do not depend on it
+PRESENT_SPAN_X, PRESENT_BAND_ROWS = 256, 8
+
+
+def view_matrix(frame_w: int, frame_h: int, win_w: int, win_h: int, zoom: float = 0.0, hor_view_pos: float = 0.5,
+                ver_view_pos: float = 0.5):
+    """Main.on_stage_resize's display matrix (Main.hx:301-315) -> (k, dx, dy): zoom 0 is "Fit", a positive zoom is the factor with
+    the window centred by the two view positions.  Host arithmetic; needs no GPU."""
+    k, dx, dy = C.c_double(0), C.c_double(0), C.c_double(0)
+    rc = N.lib().jsp_view_matrix(int(frame_w), int(frame_h), int(win_w), int(win_h), float(zoom), float(hor_view_pos),
+                                 float(ver_view_pos), C.byref(k), C.byref(dx), C.byref(dy))
+    if rc != 0:
+        raise CodecError(N.last_error())
+    return k.value, dx.value, dy.value
+
+
+def display_present(frame, frame_w: int, frame_h: int, out, win_w: int, win_h: int, k: float, dx: float, dy: float,
+                    mode: int = DISPLAY_CANVAS, filter: int = PRESENT_BILINEAR, background: int = 0xFF000000,
+                    out_pitch: Optional[int] = None, stream: int = 0) -> None:
+    """The win_w x win_h window onto `frame` (a device frame buffer, bottom-up) under the display matrix (k, dx, dy), as canvas
+    pixels, top row first, into the device tensor `out` (row pitch `out_pitch` ints, default win_w): conversion by `mode`, row
+    flip, crop and resampling in one launch on `stream`, asynchronous."""
+    lib = N.lib()
+    pitch = int(win_w) if out_pitch is None else int(out_pitch)
+    need = max((int(win_h) - 1) * pitch + int(win_w), 1)
+    rc = lib.jsp_display_present(C.c_void_p(_frame_ptr(frame, max(int(frame_w) * int(frame_h), 1))), int(frame_w), int(frame_h),
+                                 C.c_void_p(_frame_ptr(out, need)), int(win_w), int(win_h), C.c_size_t(max(pitch, 0)),
+                                 float(k), float(dx), float(dy), int(mode), int(filter), C.c_uint32(int(background) & 0xFFFFFFFF),
+                                 C.c_void_p(stream) if stream else None)
+    if rc != 0:
+        raise CodecError(N.last_error())
+
+
 def frames_differ(a, b, first_pixel: int, npixels: int, stream: int = 0) -> bool:
     """The pixel compare of Manager.frames_differ_significantly on device tensors."""
     lib = N.lib()

@@ -16,8 +16,9 @@ attached (`Manager.attach_index`: a range kept resident by the decoder's `BuildI
 shown — ScreenPressor's, `ADOPTS` false — serves the frame and leaves the decode position where it is); `next_frame` / `prev_frame` / `next_key` /
 `prev_key` are the navigation of Manager.hx:184-208 over `seek`; `play_from_index` plays a run of frames out of such a non-adopting
 index, one `Play` launch per batch of free buffers; `preview` / `filmstrip` are the seek bar's small pictures, one
-`Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex).  Timers, bitmaps and audio of the reference's
-Manager are not rebuilt.
+`Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex).  `View` is the zoom / scroll / fit state of Main
+(Main.hx:288-319, 1186-1278) and `Manager.present` draws the window it shows of a frame buffer, one launch.  Timers, bitmaps and audio
+of the reference's Manager are not rebuilt.
 """
 from __future__ import annotations
 
@@ -78,6 +79,61 @@ def _differ(a, b, start: int) -> bool:
     return frames_differ(a, b, start, a.numel())
 
 
+class View:
+    """What Main keeps about the part of the picture a window shows: `zoom_index` into ZOOM_FACTORS ("Fit", "100%", "200%",
+    Main.hx:170-171) and the two view positions in 0..1.  The slider drawing (calc_slider_handles) is not rebuilt."""
+
+    ZOOM_FACTORS = (0, 1, 2)
+
+    def __init__(self):
+        self.zoom_index = 0
+        self.hor_view_pos = 0.5
+        self.ver_view_pos = 0.5
+
+    @staticmethod
+    def _fit(a: float, mn: float, mx: float) -> float:   # Main.hx:282-286
+        if a < mn:
+            return mn
+        if a > mx:
+            return mx
+        return a
+
+    def zoom_in(self) -> None:                            # on_zoomin, Main.hx:1257-1263
+        if self.zoom_index < len(self.ZOOM_FACTORS) - 1:
+            self.zoom_index += 1
+
+    def zoom_out(self) -> None:                           # on_zoomout, :1264-1271
+        if self.zoom_index > 0:
+            self.zoom_index -= 1
+
+    def zoom_fit(self) -> None:                           # on_zoomfit, :1272-1278
+        self.zoom_index = 0
+
+    def scroll(self, hor: bool, pos: float) -> None:      # Main.hx:1234-1239; pos in 0..1
+        if hor:
+            self.hor_view_pos = pos
+        else:
+            self.ver_view_pos = pos
+
+    def key(self, code: int) -> None:
+        """on_key_down (Main.hx:1186-1193): the arrow keys move the view by a tenth, clamped to 0..1; nothing happens in Fit."""
+        if self.zoom_index == 0:
+            return
+        if code == 37:
+            self.scroll(True, self._fit(self.hor_view_pos - 0.1, 0, 1))     # left
+        elif code == 38:
+            self.scroll(False, self._fit(self.ver_view_pos - 0.1, 0, 1))    # up
+        elif code == 39:
+            self.scroll(True, self._fit(self.hor_view_pos + 0.1, 0, 1))     # right
+        elif code == 40:
+            self.scroll(False, self._fit(self.ver_view_pos + 0.1, 0, 1))    # down
+
+    def matrix(self, frame_w: int, frame_h: int, win_w: int, win_h: int):
+        """(k, dx, dy) of the display matrix for the current state (Main.hx:301-315, jsp_view_matrix)."""
+        from .codec import view_matrix
+        return view_matrix(frame_w, frame_h, win_w, win_h, self.ZOOM_FACTORS[self.zoom_index], self.hor_view_pos, self.ver_view_pos)
+
+
 class Manager:
     """Feeds compressed frames to an IVideoCodec in order, with the reference's buffer discipline."""
 
@@ -97,6 +153,23 @@ class Manager:
         self.judged: Dict[int, bool] = {}   # significance of frames a FindChange call judged (skip_stills)
         self.index = None                   # attach_index: a seek index over clip frames index_first .. index_first + index.frames - 1
         self.index_first = 0
+        self.view = View()                  # zoom and view positions of the window present() draws (Main.hx:288-319)
+
+    def present(self, buf, out, win_w: int, win_h: int, filter: Optional[int] = None, background: int = 0xFF000000, stream: int = 0) -> None:
+        """The window `self.view` shows of one of this Manager's frame buffers (`buf`: the buffer, or its slot number), as canvas
+        pixels, top row first, into the device tensor `out` (win_w * win_h ints): one launch (jsp_display_present), the frame stays
+        in HBM.  The conversion is chosen as Manager.hx:121 chooses convert_fromRGB15: 16-bpp ScreenPressor frames hold 5-bit
+        components.  `filter` defaults to bilinear (bitmap.smoothing = true, Main.hx:948).  HIP frame buffers only."""
+        from .codec import DISPLAY_CANVAS, DISPLAY_CANVAS_RGB15, PRESENT_BILINEAR, display_present
+        if isinstance(buf, (int, np.integer)):
+            buf = self.buffers[int(buf)]
+        elif self._slot_of(buf) < 0:
+            raise ValueError("present: not one of this Manager's frame buffers")
+        from_rgb15 = self.vi.bpp == 16 and self.vi.codec == CODEC_SCREENPRESSOR
+        k, dx, dy = self.view.matrix(self.vi.X, self.vi.Y, win_w, win_h)
+        display_present(buf, self.vi.X, self.vi.Y, out, win_w, win_h, k, dx, dy,
+                        mode=DISPLAY_CANVAS_RGB15 if from_rgb15 else DISPLAY_CANVAS,
+                        filter=PRESENT_BILINEAR if filter is None else filter, background=background, stream=stream)
 
     def attach_index(self, index, first: int = 0) -> None:
         """Serve seeks to clip frames first .. first + index.frames - 1 from `index` (the decoder's BuildIndex over those frames,
