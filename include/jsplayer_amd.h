@@ -560,7 +560,13 @@ enum {
     JSP_DISPLAY_SETPIXELS_RGB15 = 3 /* c << 11                                     (Manager.hx:340) */
 };
 /* `frame`, `out`: device pointers, width*height ints.  flip_rows != 0 also undoes the bottom-up row
- * order (the reference leaves that to its display matrix, Main.hx:318).  Asynchronous on `hip_stream`. */
+ * order (the reference leaves that to its display matrix, Main.hx:318).  Asynchronous on `hip_stream`.
+ *   ARGUMENTS: width and height 1 .. 65535 (height is the launch's grid y; 65535 is the limit HIP documents for it, taken from the
+ *     documentation and not measured).  Neither pointer needs alignment: a width divisible by 4 with both pointers on 16-byte
+ *     boundaries gets 16-byte loads and stores.  Only the width*height ints of `out` are written.  out == frame (conversion in
+ *     place) is allowed without flip_rows; any other overlap of the two buffers is the caller's error.
+ *   ERRORS (JSP_ERROR_OCCURED, jsp_last_error() starts with "display_convert:", nothing queued, nothing written): a null pointer, a
+ *     width or height outside its bounds, an unknown mode. */
 int jsp_display_convert(const int32_t* frame, int32_t* out, int width, int height, int mode, int flip_rows,
                         void* hip_stream);
 

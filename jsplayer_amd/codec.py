@@ -97,6 +97,15 @@ def _frame_ptr(buf, npixels: int) -> int:
     raise CodecError(f"unsupported frame buffer type {type(buf)!r}")
 
 
+def _device_frame_ptr(buf, npixels: int, what: str) -> int:
+    """Address of a frame buffer that a kernel reads or writes directly: a device tensor, nothing else.  The display calls launch on
+    whatever pointer they are given, so a host array is refused here, before the native library is touched."""
+    if isinstance(buf, np.ndarray) or not getattr(buf, "is_cuda", False):
+        raise CodecError(f"{what}: frame buffers must be device tensors (got {type(buf).__name__}"
+                         f"{' on the host' if hasattr(buf, 'data_ptr') else ''})")
+    return _frame_ptr(buf, npixels)
+
+
 class _NativeCodec:
     """Common part of the three codec classes: owns one jsp_codec handle."""
 
@@ -745,9 +754,11 @@ DISPLAY_CANVAS, DISPLAY_CANVAS_RGB15, DISPLAY_SETPIXELS, DISPLAY_SETPIXELS_RGB15
 
 def display_convert(frame, out, width: int, height: int, mode: int = DISPLAY_CANVAS, flip_rows: bool = False,
                     stream: int = 0) -> None:
-    """Manager.fill_bitmap_data on device tensors (int32, width*height)."""
+    """Manager.fill_bitmap_data on device tensors (int32, width*height; width and height 1 .. 65535).  `out` may be `frame` itself
+    when flip_rows is false."""
+    src, dst = _device_frame_ptr(frame, width * height, "display_convert"), _device_frame_ptr(out, width * height, "display_convert")
     lib = N.lib()
-    rc = lib.jsp_display_convert(C.c_void_p(_frame_ptr(frame, width * height)), C.c_void_p(_frame_ptr(out, width * height)),
+    rc = lib.jsp_display_convert(C.c_void_p(src), C.c_void_p(dst),
                                  width, height, mode, 1 if flip_rows else 0, C.c_void_p(stream) if stream else None)
     if rc != 0:
         raise CodecError(N.last_error())
@@ -777,11 +788,13 @@ def display_present(frame, frame_w: int, frame_h: int, out, win_w: int, win_h: i
     """The win_w x win_h window onto `frame` (a device frame buffer, bottom-up) under the display matrix (k, dx, dy), as canvas
     pixels, top row first, into the device tensor `out` (row pitch `out_pitch` ints, default win_w): conversion by `mode`, row
     flip, crop and resampling in one launch on `stream`, asynchronous."""
-    lib = N.lib()
     pitch = int(win_w) if out_pitch is None else int(out_pitch)
     need = max((int(win_h) - 1) * pitch + int(win_w), 1)
-    rc = lib.jsp_display_present(C.c_void_p(_frame_ptr(frame, max(int(frame_w) * int(frame_h), 1))), int(frame_w), int(frame_h),
-                                 C.c_void_p(_frame_ptr(out, need)), int(win_w), int(win_h), C.c_size_t(max(pitch, 0)),
+    src = _device_frame_ptr(frame, max(int(frame_w) * int(frame_h), 1), "display_present")
+    dst = _device_frame_ptr(out, need, "display_present")
+    lib = N.lib()
+    rc = lib.jsp_display_present(C.c_void_p(src), int(frame_w), int(frame_h),
+                                 C.c_void_p(dst), int(win_w), int(win_h), C.c_size_t(max(pitch, 0)),
                                  float(k), float(dx), float(dy), int(mode), int(filter), C.c_uint32(int(background) & 0xFFFFFFFF),
                                  C.c_void_p(stream) if stream else None)
     if rc != 0:
@@ -789,10 +802,14 @@ def display_present(frame, frame_w: int, frame_h: int, out, win_w: int, win_h: i
 
 
 def frames_differ(a, b, first_pixel: int, npixels: int, stream: int = 0) -> bool:
-    """The pixel compare of Manager.frames_differ_significantly on device tensors."""
+    """The pixel compare of Manager.frames_differ_significantly on device tensors: any a[i] != b[i] for first_pixel <= i < npixels."""
+    first_pixel, npixels = int(first_pixel), int(npixels)
+    if first_pixel < 0 or npixels < 0:
+        raise CodecError(f"frames_differ: first_pixel and npixels must not be negative (got {first_pixel}, {npixels})")
+    pa, pb = _device_frame_ptr(a, npixels, "frames_differ"), _device_frame_ptr(b, npixels, "frames_differ")
     lib = N.lib()
     out = C.c_int(0)
-    rc = lib.jsp_frames_differ(C.c_void_p(_frame_ptr(a, npixels)), C.c_void_p(_frame_ptr(b, npixels)), first_pixel, npixels,
+    rc = lib.jsp_frames_differ(C.c_void_p(pa), C.c_void_p(pb), first_pixel, npixels,
                                C.byref(out), C.c_void_p(stream) if stream else None)
     if rc != 0:
         raise CodecError(N.last_error())

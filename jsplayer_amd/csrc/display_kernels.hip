@@ -26,6 +26,7 @@ __device__ __forceinline__ uint32_t convert(uint32_t c, int mode) {
 
 __global__ __launch_bounds__(256) void display_convert_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                                                               int X, int Y, int mode, int flip, int vec) {
+    // (dst == src without flip is allowed by the header: a lane reads only the words it then writes, each once, load before store)
     const int y = blockIdx.y;
     const int ys = flip ? Y - 1 - y : y;
     const uint32_t* s = src + (size_t)ys * X;
@@ -185,6 +186,8 @@ int jsp_display_convert(const int32_t* frame, int32_t* out, int width, int heigh
                         void* hip_stream) {
     try {
         if (!frame || !out || width <= 0 || height <= 0 || mode < 0 || mode > 3) throw std::runtime_error("bad argument");
+        // (height is the launch's grid y: 65535 is the limit HIP documents for it)
+        if (width > 65535 || height > 65535) throw std::runtime_error("width and height are 1 .. 65535");
         const int vec = ((width & 3) == 0 && (((uintptr_t)frame | (uintptr_t)out) & 15) == 0) ? 1 : 0;
         int gx = (width / (vec ? 4 : 1) + 255) / 256;
         if (gx < 1) gx = 1;
@@ -194,7 +197,7 @@ int jsp_display_convert(const int32_t* frame, int32_t* out, int width, int heigh
         JSP_HIP(hipGetLastError());
         return 0;
     } catch (const std::exception& e) {
-        jsp::set_error("%s", e.what());
+        jsp::set_error("display_convert: %s", e.what());
         return JSP_ERROR_OCCURED;
     }
 }
