@@ -5,7 +5,6 @@
 // (msv1_parse_kernels.hip, option "msv1_parse" = "gpu").
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
 #include <memory>
 #include <exception>
 #include <thread>
@@ -49,6 +48,7 @@ inline Msv1TileRec tile_rec(uint32_t beg, uint32_t even_end, uint32_t data_end, 
 // fronts stand at different depths of their frames instead of all at tile j.  What the memory system makes of
 // hundreds of fronts depends on where the frames lie in physical memory; staggered by 64, the same frames
 // take 2 - 6 % less time whichever way they lie (one process, same buffers: profiles/archive/r03_stagger_one_process.txt).  stagger 0: in step.
+constexpr uint32_t MSV1_TILE_STAGGER = 64;
 template <class Emit>
 inline void staggered_tile_order(int f0, int f1, const std::vector<uint32_t>& ntiles, uint32_t stagger, Emit&& emit) {
     uint32_t maxt = 0;
@@ -340,22 +340,15 @@ struct Msv1Staged : jsp_staged {
         }
         // Launch order (staggered_tile_order): a launch covers the contiguous record range of its frames; the records are
         // permuted inside that range (a record carries its own byte offset and its number in stream order).
-        const uint32_t stagger = [] { const char* e = std::getenv("JSP_MSV1_STAGGER"); return e ? (uint32_t)std::atoi(e) : 64u; }();   // (lab: read at every staging)
         auto tile_major = [&](int f0, int f1) {   // frames [f0, f1)
             if (f1 - f0 < 2) return;
             const uint32_t t0 = h_pf[f0].first_tile, t1 = h_pf[f1 - 1].first_tile + h_pf[f1 - 1].ntiles;
             const std::vector<Msv1TileRec> tmp(recs + t0, recs + t1);
             uint32_t o = t0;
-            staggered_tile_order(f0, f1, nt16, stagger, [&](int i, uint32_t k) { recs[o++] = tmp[h_pf[i].first_tile - t0 + k]; });
+            staggered_tile_order(f0, f1, nt16, MSV1_TILE_STAGGER, [&](int i, uint32_t k) { recs[o++] = tmp[h_pf[i].first_tile - t0 + k]; });
         };
-        static const int major_frames = [] { const char* e = std::getenv("JSP_MSV1_TILE_MAJOR_FRAMES"); return e ? std::atoi(e) : 0; }();   // lab: permute within runs of this many frames
         for (const auto& g : groups)
-            if (g.fused) {
-                if (major_frames > 0)
-                    for (int f = g.first; f < g.first + g.count; f += major_frames) tile_major(f, std::min(f + major_frames, g.first + g.count));
-                else
-                    tile_major(g.first, g.first + g.count);
-            }
+            if (g.fused) tile_major(g.first, g.first + g.count);
         JSP_HIP(hipMemcpyAsync(d_recs.p, recs, sizeof(Msv1TileRec) * (size_t)ntiles, hipMemcpyHostToDevice, stream));
     }
     // The same for the descriptor form: `dst` = the frame's block table; frames whose table nobody reads (fused groups) or that came from the
@@ -385,9 +378,9 @@ struct Msv1Staged : jsp_staged {
         std::vector<uint8_t> in_fused(nf, 0);
         for (const auto& g : groups)
             if (g.fused) std::fill(in_fused.begin() + g.first, in_fused.begin() + g.first + g.count, 1);
-        // written straight in launch order: over the whole batch, staggered by 64 whatever the lab's setting for the pixel-writing form
+        // written straight in launch order: over the whole batch
         uint32_t o = 0;
-        staggered_tile_order(0, nf, n8, 64u, [&](int i, uint32_t k) {
+        staggered_tile_order(0, nf, n8, MSV1_TILE_STAGGER, [&](int i, uint32_t k) {
             er[o++] = tile_rec(h_pf[i].beg, h_pf[i].end, geo.bits == 16 ? h_pf[i].end : h_frames[i].stream_end, k, tile8, first8[i], n8[i],
                                reinterpret_cast<int32_t*>(static_cast<uint32_t*>(d_desc.p) + (size_t)i * nblk), nullptr, h_frames[i].signif, 0xFFFFFFFFu,
                                (h_pf[i].host_parsed || in_fused[i]) ? MSV1_TILE_SKIP : 0u);
@@ -580,13 +573,10 @@ struct Msv1Codec : jsp_codec {
     bool counted_async = false;   // this instance is in g_async_streams
     // The copy engine takes a frame's bytes up on a stream of its own, next to the previous frame's kernel.  One such stream is enough: a
     // megabyte per copy goes at ~30 GB/s on one stream where the bus takes 57 (bench.py: e2e.h2d_ceiling_GBs), but taking consecutive frames up
-    // on 2 - 4 streams in turn (JSP_MSV1_UP_STREAMS, lab) changes nothing for one player stream (55.5 Gpixels/s with 1, 2, 3 or 4: the frames'
+    // on 2 - 4 streams in turn changes nothing for one player stream (55.5 Gpixels/s with 1, 2, 3 or 4: the frames'
     // kernels follow each other on one HIP stream, 37 us apiece, and that chain is the bound) and costs 3 - 40 % with two (profiles/
     // r04_msv1_up_streams.txt).
-    static constexpr int kUpStreamsMax = 4;
-    hipStream_t up_streams[kUpStreamsMax] = {nullptr, nullptr, nullptr, nullptr};
-    int up_count = [] { const char* e = std::getenv("JSP_MSV1_UP_STREAMS"); const int v = e ? std::atoi(e) : 1; return v < 1 ? 1 : (v > kUpStreamsMax ? kUpStreamsMax : v); }();
-    unsigned up_next = 0;
+    hipStream_t up_stream = nullptr;
     // jsp_prefetch: ranges of the caller's host memory that are (being) copied to the device in ONE piece each, on a stream of their own.
     // An asynchronous frame whose bytes lie inside such a range takes them from the device copy: no copy of its own is queued and
     // nothing crosses the bus inside its kernel.  A megabyte per copy goes at 24 - 39 GB/s, 64 MB at 57 (bench.py: e2e.h2d_ceiling_GBs),
@@ -653,7 +643,7 @@ struct Msv1Codec : jsp_codec {
             if (r.last_use) (void)hipEventDestroy(r.last_use);
         }
         if (prefetch_stream) (void)hipStreamDestroy(prefetch_stream);
-        for (hipStream_t s : up_streams) if (s) (void)hipStreamDestroy(s);
+        if (up_stream) (void)hipStreamDestroy(up_stream);
         if (counted_async) g_async_streams.fetch_sub(1);
     }
     // block_changes is only maintained by the host parser; after frames parsed on the GPU it is
@@ -669,16 +659,15 @@ struct Msv1Codec : jsp_codec {
         if (d_poison.p) JSP_HIP(hipMemsetAsync(d_poison.p, 0, sizeof(uint32_t), stream));
     }
     // Replays of staged inter-frame batches (Msv1Staged::decode): "msv1_parse_ahead" (default on).
-    bool opt_parse_ahead = [] { const char* e = std::getenv("JSP_MSV1_PARSE_AHEAD"); return !(e && e[0] == '0'); }();
+    bool opt_parse_ahead = true;
     // Several frames per launch (option "msv1_async_pairs", default on): a one-launch frame is HELD until enough frames are submitted behind it
     // — half of what may be in flight ("async_depth"), at most 1 + MSV1_MAX_RIDERS — and they go out together (Msv1AsyncStaged::decode_with);
     // or with whatever is held, as soon as anybody waits for one of them or anything else needs the stream.
-    bool opt_async_pairs = [] { const char* e = std::getenv("JSP_MSV1_ASYNC_PAIRS"); return !(e && e[0] == '0'); }();
+    bool opt_async_pairs = true;
     std::vector<jsp_async_job*> held;
     long long paired_frames = 0;      // jsp_counter("paired_frames"): frames that shared a launch with others
     int frames_per_launch() const {
-        static const int lab = [] { const char* e = std::getenv("JSP_MSV1_FRAMES_PER_LAUNCH"); return e ? std::atoi(e) : 0; }();
-        const int k = lab > 0 ? lab : async_depth / 2;
+        const int k = async_depth / 2;
         return k < 1 ? 1 : (k > 1 + MSV1_MAX_RIDERS ? 1 + MSV1_MAX_RIDERS : k);
     }
     void launch_held() {
@@ -904,8 +893,7 @@ struct Msv1Codec : jsp_codec {
 
     jsp_staged* stage_async(const jsp_frame_in& f, jsp_staged* reuse) override {
         activate();
-        static const size_t small_limit = [] { const char* e = std::getenv("JSP_MSV1_SMALL_TILE_BYTES"); return e ? (size_t)std::atoll(e) : MSV1_SMALL_TILE_FRAME_BYTES; }();   // (lab)
-        const bool small_tiles = f.n <= small_limit;
+        const bool small_tiles = f.n <= MSV1_SMALL_TILE_FRAME_BYTES;
         const size_t tile_bytes = small_tiles ? msv1_small_tile_bytes() : msv1_parse_tile_bytes();
         const Prescan ps = prescan(f.src, f.n);
         if (sync_staging(f, ps)) {
@@ -966,7 +954,6 @@ struct Msv1Codec : jsp_codec {
             st->dma = opt_async_auto ? g_async_streams.load() <= kDmaStreams : opt_async_dma;
             if (fb.range) st->dma = false;      // (the kernel reads the device copy of the range and leaves the frame's own copy in d_stream, as when it reads pinned memory)
             if (st->dma) {   // the copy engine brings the bytes up on a stream of its own, next to the previous frame's kernel
-                hipStream_t& up_stream = up_streams[up_next++ % (unsigned)up_count];
                 if (!up_stream) JSP_HIP(hipStreamCreateWithFlags(&up_stream, hipStreamNonBlocking));
                 if (!st->uploaded) JSP_HIP(hipEventCreateWithFlags(&st->uploaded, hipEventDisableTiming));
                 JSP_HIP(hipMemcpyAsync(st->d_stream.p, fb.up, f.n, hipMemcpyHostToDevice, up_stream));
@@ -1075,10 +1062,9 @@ struct Msv1Codec : jsp_codec {
         const size_t nblk = (size_t)std::max(geo.nblocks, 1);
         plan.beg.resize(nf);
         const size_t frame_align = st.gpu_parse ? (size_t)msv1_parse_tile_bytes() : 16;
-        static const size_t lab_gap = [] { const char* e = std::getenv("JSP_MSV1_FRAME_GAP"); return e ? (size_t)std::atoll(e) & ~size_t(15) : size_t(0); }();   // lab: bytes left free after every frame's slot
         for (int i = 0; i < nf; ++i) {
             plan.beg[i] = plan.total_stream;
-            plan.total_stream += (frames[i].n + frame_align - 1) / frame_align * frame_align + (st.gpu_parse ? lab_gap : 0);
+            plan.total_stream += (frames[i].n + frame_align - 1) / frame_align * frame_align;
         }
         if (plan.total_stream + 64 > 0xFFFFFFF0u) throw std::runtime_error("batch stream exceeds 4 GiB");
         // Where the frames' bytes are: a frame in pinned host memory (jsp_host_alloc, or memory the caller registered) is uploaded

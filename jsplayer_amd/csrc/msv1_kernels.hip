@@ -8,44 +8,19 @@
 //
 // Reference semantics reproduced per block: MSVideo1.hx:124-181 (16-bit), :307-364 (8-bit),
 // copy_block :74-84, fromRGB15 :211-214, stage-2 significance compare :195-204.
-#include <cstdlib>
 #include <mutex>
 
-#include "msv1.h"
-#include "msv1_decode.h"
+#include "msv1_block_io.h"
 
 namespace jsp {
 namespace {
 
 constexpr int WG = 256;
 
-__device__ __forceinline__ uint32_t rgb555_to_rgb32(uint32_t c) {
-    return ((c & 0x1Fu) << 3) | ((c & 0x3E0u) << 6) | ((c & 0x7C00u) << 9);
-}
-
 // Little-endian 16-bit read at an even offset; 0 when either byte lies beyond `end`
 // (the reference reads NaN there, which every later expression turns into 0).
 __device__ __forceinline__ uint32_t ld16(const uint8_t* __restrict__ s, uint32_t o, uint32_t end) {
     return (o + 1u < end) ? (uint32_t) * reinterpret_cast<const uint16_t*>(s + o) : 0u;
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// Frame rows are written once and never read back by this launch: nontemporal stores keep them from
-// evicting the stream / descriptor lines out of L2 (measured: 168 -> 91 us per 64-frame batch together
-// with the LDS staging below, tools/msv1_lab.hip).
-// (dst/prev reach the kernel inside a struct read from memory: without the explicit global address
-// space the accesses would be FLAT instructions)
-typedef __attribute__((address_space(1))) u32x4 gu32x4;
-typedef const __attribute__((address_space(1))) u32x4 cgu32x4;
-typedef __attribute__((address_space(1))) uint32_t gu32;
-typedef const __attribute__((address_space(1))) uint32_t cgu32;
-__device__ __forceinline__ void store_row(uint32_t* p, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    __builtin_nontemporal_store(u32x4{a, b, c, d}, (gu32x4*)p);
-}
-__device__ __forceinline__ uint4 load_row(const uint32_t* p) {
-    const u32x4 v = *(cgu32x4*)p;
-    return make_uint4(v.x, v.y, v.z, v.w);
 }
 
 template <int BITS, bool VEC>
@@ -58,7 +33,7 @@ __global__ __launch_bounds__(WG) void msv1_blocks_kernel(
     __shared__ __align__(16) uint8_t sbuf[WG * MAXCODE + 64];
     __shared__ uint32_t s_wlo[NW], s_whi[NW];
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
+    load_palette<BITS, false>(s_pal, palette);
     const Msv1FrameArgs fa = frames[blockIdx.y];
     const int blk = blockIdx.x * WG + threadIdx.x;
     const bool live = blk < nblocks;
@@ -144,18 +119,18 @@ __global__ __launch_bounds__(WG) void msv1_blocks_kernel(
             flags = w ^ 0xFFFFu;
             const uint32_t q0 = ld16(code, r + 2u, end);
             const uint32_t q1 = ld16(code, r + 4u, end);
-            c[0] = rgb555_to_rgb32(q0);
-            c[1] = rgb555_to_rgb32(q1);
+            c[0] = rgb555(q0);
+            c[1] = rgb555(q1);
             if (q0 & 0x8000u) {
 #pragma unroll
-                for (int k = 2; k < 8; ++k) c[k] = rgb555_to_rgb32(ld16(code, r + 2u + 2u * k, end));
+                for (int k = 2; k < 8; ++k) c[k] = rgb555(ld16(code, r + 2u + 2u * k, end));
             } else {
                 c[2] = c[4] = c[6] = c[0];
                 c[3] = c[5] = c[7] = c[1];
             }
         } else {
             flags = 0;
-            const uint32_t v = rgb555_to_rgb32(w);
+            const uint32_t v = rgb555(w);
 #pragma unroll
             for (int k = 0; k < 8; ++k) c[k] = v;
         }
@@ -217,153 +192,7 @@ __global__ __launch_bounds__(WG) void msv1_blocks_kernel(
                 }
             }
         }
-        // one word per frame: thousands of waves OR-ing the same address serialise (measured: 24 us per
-        // inter frame, almost all of it here), so look before setting — an agent-scope load is enough,
-        // a stale 0 only costs one more atomic
-        if (__ballot(diff) != 0ull && (threadIdx.x & 63) == __ffsll((long long)__ballot(diff)) - 1 &&
-            __hip_atomic_load(fa.signif, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-            atomicOr(fa.signif, 1u);
-    }
-}
-
-// Inter-frame batches in ONE launch.  A block's pixels depend only on the same block of earlier
-// frames, so a workgroup takes a spatial tile of 256 blocks and walks the frames in order, keeping
-// the tile's current pixels in registers: a skipped block is a plain re-store of what the lane already
-// holds (no previous-frame read, no launch boundary between frames), the stage-2 compare is a register
-// compare.  Frames of the group must write all their blocks or none (no UNTOUCHED sentinels apart
-// from no-op frames) — msv1_codec.cpp forms the groups.
-// Measured alternatives (64 x 1080p inter frames, this kernel: 163 us): a wave per pixel row with
-// wave-private code slices and no barriers, loads issued a frame ahead: 410 us (four times the waves, each
-// paying the store round trip that a vmcnt wait after a store implies — loads and stores share the
-// counter); two row waves fed through LDS by a loader wave that never stores: 254 us (one load latency
-// under full write pressure per frame on the critical path).  Both bit-exact, both dropped.
-template <int BITS>
-__global__ __launch_bounds__(WG) void msv1_blocks_temporal1_kernel(
-    const uint8_t* __restrict__ stream, const uint32_t* __restrict__ desc,
-    const Msv1FrameArgs* __restrict__ frames, int nframes, const int32_t* __restrict__ palette, int nblocks,
-    int nbx, int X) {
-    constexpr int NW = WG / 64;
-    constexpr int MAXCODE = 18;
-    __shared__ __align__(16) uint8_t sbuf[WG * MAXCODE + 64];
-    __shared__ uint32_t s_wlo[NW], s_whi[NW];
-    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
-    const int blk = blockIdx.x * WG + threadIdx.x;
-    const bool live = blk < nblocks;
-    const int by = blk / nbx;
-    const int bx = blk - by * nbx;
-    const size_t di = (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
-    uint32_t px[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) px[i] = 0;
-    bool have = false;  // px holds the pixels of the latest written frame
-    uint32_t o_next = live ? desc[frames[0].desc_base + blk] : MSV1_DESC_UNTOUCHED;
-    for (int f = 0; f < nframes; ++f) {
-        const Msv1FrameArgs fa = frames[f];
-        const uint32_t o = o_next;
-        if (f + 1 < nframes) o_next = live ? desc[frames[f + 1].desc_base + blk] : MSV1_DESC_UNTOUCHED;
-        if (fa.pad & MSV1_FRAME_NOOP) continue;       // early-out frame: nothing is written
-        const bool coded = o < MSV1_DESC_UNTOUCHED;
-        // the first written frame of the group may need the frame before the group
-        if (!have && live && (fa.pad & MSV1_FRAME_USES_PREV)) {
-            const uint32_t* __restrict__ prev = reinterpret_cast<const uint32_t*>(fa.prev) + di;
-#pragma unroll
-            for (int y = 0; y < 4; ++y) {
-                const uint4 r = load_row(prev + (size_t)y * X);
-                px[y * 4] = r.x; px[y * 4 + 1] = r.y; px[y * 4 + 2] = r.z; px[y * 4 + 3] = r.w;
-            }
-        }
-        have = true;
-        {
-            const unsigned long long m = __ballot(coded);
-            const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-            if (m == 0ull) {
-                if (lane == 0) { s_wlo[wv] = 0xFFFFFFFFu; s_whi[wv] = 0u; }
-            } else {
-                if (lane == __ffsll((long long)m) - 1) s_wlo[wv] = o;
-                if (lane == 63 - __clzll((long long)m)) s_whi[wv] = o + MAXCODE;
-            }
-        }
-        __syncthreads();
-        uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) { lo = min(lo, s_wlo[k]); hi = max(hi, s_whi[k]); }
-        lo &= ~15u;
-        hi = hi < fa.stream_end ? hi : fa.stream_end;
-        for (uint32_t p = lo + threadIdx.x * 16u; p < hi; p += WG * 16u)
-            *reinterpret_cast<uint4*>(sbuf + (p - lo)) = *reinterpret_cast<const uint4*>(stream + p);
-        __syncthreads();
-        bool diff = false;
-        if (coded) {
-            const uint8_t* __restrict__ code = sbuf;
-            const uint32_t end = hi > lo ? hi - lo : 0u;
-            const uint32_t r = o - lo;
-            const bool b_ok = r + 1u < end;
-            const uint32_t w = b_ok ? (uint32_t) * reinterpret_cast<const uint16_t*>(code + r)
-                                    : (r < end ? (uint32_t)code[r] : 0u);
-            const uint32_t b = w >> 8;
-            uint32_t c[8];
-            uint32_t flags;
-            if (BITS == 16) {
-                if (b_ok && b < 0x80u) {
-                    flags = w ^ 0xFFFFu;
-                    const uint32_t q0 = ld16(code, r + 2u, end);
-                    const uint32_t q1 = ld16(code, r + 4u, end);
-                    c[0] = rgb555_to_rgb32(q0);
-                    c[1] = rgb555_to_rgb32(q1);
-                    if (q0 & 0x8000u) {
-#pragma unroll
-                        for (int k = 2; k < 8; ++k) c[k] = rgb555_to_rgb32(ld16(code, r + 2u + 2u * k, end));
-                    } else {
-                        c[2] = c[4] = c[6] = c[0];
-                        c[3] = c[5] = c[7] = c[1];
-                    }
-                } else {
-                    flags = 0;
-                    const uint32_t v = rgb555_to_rgb32(w);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) c[k] = v;
-                }
-            } else {
-                if (b_ok && b < 0x80u) {
-                    flags = w;
-                    const uint32_t i0 = (r + 2u < end) ? s_pal[code[r + 2u]] : 0u;
-                    const uint32_t i1 = (r + 3u < end) ? s_pal[code[r + 3u]] : 0u;
-                    c[0] = c[2] = c[4] = c[6] = i1;
-                    c[1] = c[3] = c[5] = c[7] = i0;
-                } else if (b_ok && b >= 0x90u) {
-                    flags = w ^ 0xFFFFu;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) c[k] = (r + 2u + k < end) ? s_pal[code[r + 2u + k]] : 0u;
-                } else {
-                    flags = 0;
-                    const uint32_t v = (r < end) ? s_pal[w & 0xFFu] : 0u;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) c[k] = v;
-                }
-            }
-#pragma unroll
-            for (int y = 0; y < 4; ++y)
-#pragma unroll
-                for (int x = 0; x < 4; ++x) {
-                    const int q = ((y & 2) << 1) + (x & 2);
-                    const uint32_t v = ((flags >> (y * 4 + x)) & 1u) ? c[q + 1] : c[q];
-                    if (fa.cmp_row_lo != 0xFFFFFFFFu && (uint32_t)(by * 4 + y) >= fa.cmp_row_lo) diff |= v != px[y * 4 + x];
-                    px[y * 4 + x] = v;
-                }
-        }
-        if (o != MSV1_DESC_UNTOUCHED) {  // coded or skipped: the block is (re)written in this frame's buffer
-            uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(fa.dst) + di;
-#pragma unroll
-            for (int y = 0; y < 4; ++y) store_row(dst + (size_t)y * X, px[y * 4], px[y * 4 + 1], px[y * 4 + 2], px[y * 4 + 3]);
-        }
-        if (fa.cmp_row_lo != 0xFFFFFFFFu) {
-            const unsigned long long dm = __ballot(diff);
-            if (dm != 0ull && (threadIdx.x & 63) == __ffsll((long long)dm) - 1 &&
-                __hip_atomic_load(fa.signif, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-                atomicOr(fa.signif, 1u);
-        }
-        // (the next iteration's first barrier comes after its ballot; sbuf is only rewritten after it)
+        raise_flag(fa.signif, diff);   // one word per frame
     }
 }
 
@@ -393,23 +222,30 @@ __global__ __launch_bounds__(WG) void msv1_edge_compare_kernel(const Msv1FrameAr
             diff |= fa.dst[k] != fa.prev[k];
         }
     }
-    if (__ballot(diff) != 0ull && (threadIdx.x & 63) == __ffsll((long long)__ballot(diff)) - 1 &&
-        __hip_atomic_load(fa.signif, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-        atomicOr(fa.signif, 1u);
+    raise_flag(fa.signif, diff);
 }
 
-
 // ---------------------------------------------------------------------------------------------------------
-// Inter-frame groups, second form: a LOADER wave next to the four worker waves.
+// Inter-frame batches in ONE launch: the walk in registers, fed by a LOADER wave next to the four worker waves.
 //
-// A workgroup owns 256 blocks and walks the group's frames with their pixels in registers, as above.  What bounds
-// that walk is not bandwidth but latency: a CU's loads and stores share one in-order queue (and a wave's vmcnt counts
-// both), so the per-frame fetches — block table entry, then the code bytes it points at — each waited behind the row
-// stores of the frame before: ~3 us per frame, 1.5 ms per 512 frames at 0.37 of peak.  Here the worker waves never
+// A block's pixels depend only on the same block of earlier frames, so a workgroup takes a spatial tile of 256 blocks and walks
+// the frames in order, keeping the tile's current pixels in registers: a skipped block is a plain re-store of what the lane
+// already holds (no previous-frame read, no launch boundary between frames), the stage-2 compare is a register compare.  Frames
+// of the group must write all their blocks or none (no UNTOUCHED sentinels apart from no-op frames) — msv1_codec.cpp forms the
+// groups.
+// What bounds that walk is not bandwidth but latency: a CU's loads and stores share one in-order queue (and a wave's vmcnt counts
+// both), so when the walking waves fetched for themselves — block table entry, then the code bytes it points at, a frame at a
+// time — each fetch waited behind the row stores of the frame before: ~3 us per frame, 1.5 ms per 512 frames at 0.37 of peak
+// (that kernel is in the history of this file; DESIGN 3.2 has its figures).  Here the worker waves never
 // issue a load inside the frame loop: a fifth wave fetches, CHUNK frames at a time, the tile's table entries and the
 // slice of the code stream they point into straight into LDS (global_load_lds: no registers), a whole chunk ahead of
 // the workers (two chunk buffers), and its own vmcnt only ever holds loads.  Chunks are handed over through two LDS
 // counters (`ready`, `consumed`); nobody waits at a workgroup barrier inside the loop.
+// Measured alternatives to the walk with a lane per block (64 x 1080p inter frames, the frame-at-a-time walk: 163 us): a wave per
+// pixel row with wave-private code slices and no barriers, loads issued a frame ahead: 410 us (four times the waves, each paying
+// the store round trip that a vmcnt wait after a store implies — loads and stores share the counter); two row waves fed through
+// LDS by a loader wave that never stores: 254 us (one load latency under full write pressure per frame on the critical path).
+// Both bit-exact, both dropped.
 constexpr int TW = 4;                        // worker waves (lane = block)
 constexpr int TWG = (TW + 1) * 64;
 constexpr int T_NF = 16;                     // frames per chunk, at most
@@ -455,7 +291,7 @@ __global__ __launch_bounds__(TWG) void msv1_blocks_temporal_kernel(
     lds_vu32* s_done = s_ready + 1;                                             // [TW] chunks each worker wave is through with
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (provably uniform: the loader's loops then run on the scalar unit, its frame records are scalar loads)
-    if (BITS == 8 && tid < 256) s_pal[tid] = (uint32_t)palette[tid];
+    if (tid < 256) load_palette<BITS, false>(s_pal, palette);
     for (int i = tid; i < ((nframes + 31) >> 5) + 1 + TW; i += TWG) s_sig[i] = 0u;   // (+ ready, done[TW])
     __syncthreads();
     const int blk0 = blockIdx.x * WG;
@@ -612,7 +448,7 @@ __global__ __launch_bounds__(TWG) void msv1_blocks_temporal_kernel(
                 if (BITS == 16 ? (tail != 0u && o == tf.end) : avail == 1u) {
                     // only the first byte of the code word exists: neither a skip nor a pattern test holds, the reference paints it solid
                     const uint32_t a = BITS == 16 ? tail : (uint32_t)ck.code[tf.code_at + (o - tf.lo)];
-                    const uint32_t v = BITS == 16 ? rgb555_to_rgb32(a) : s_pal[a];
+                    const uint32_t v = BITS == 16 ? rgb555(a) : s_pal[a];
 #pragma unroll
                     for (int k = 0; k < 16; ++k) nx[k] = v;
                 } else if (avail == 0u) {
@@ -660,38 +496,16 @@ void msv1_launch_blocks(const Msv1Geometry& geo, const uint8_t* d_stream, const 
                         bool vec_ok, hipStream_t stream) {
     if (geo.nblocks <= 0 || nframes <= 0) return;
     dim3 grid((geo.nblocks + WG - 1) / WG, nframes), block(WG);
-    if (geo.bits == 16) {
-        if (vec_ok)
-            hipLaunchKernelGGL((msv1_blocks_kernel<16, true>), grid, block, 0, stream, d_stream, d_desc,
-                               d_frames, d_palette, geo.nblocks, geo.nbx, geo.X);
-        else
-            hipLaunchKernelGGL((msv1_blocks_kernel<16, false>), grid, block, 0, stream, d_stream, d_desc,
-                               d_frames, d_palette, geo.nblocks, geo.nbx, geo.X);
-    } else {
-        if (vec_ok)
-            hipLaunchKernelGGL((msv1_blocks_kernel<8, true>), grid, block, 0, stream, d_stream, d_desc,
-                               d_frames, d_palette, geo.nblocks, geo.nbx, geo.X);
-        else
-            hipLaunchKernelGGL((msv1_blocks_kernel<8, false>), grid, block, 0, stream, d_stream, d_desc,
-                               d_frames, d_palette, geo.nblocks, geo.nbx, geo.X);
-    }
+    dispatch_bits_vec(geo.bits, vec_ok, [&](auto B, auto V) {
+        hipLaunchKernelGGL((msv1_blocks_kernel<decltype(B)::value, decltype(V)::value>), grid, block, 0, stream, d_stream, d_desc, d_frames,
+                           d_palette, geo.nblocks, geo.nbx, geo.X);
+    });
 }
 
 void msv1_launch_blocks_temporal(const Msv1Geometry& geo, const uint8_t* d_stream, const uint32_t* d_desc,
                                  const Msv1FrameArgs* d_frames, int nframes, const int32_t* d_palette,
                                  hipStream_t stream) {
     if (geo.nblocks <= 0 || nframes <= 0) return;
-    static const bool old_form = std::getenv("JSP_MSV1_TEMPORAL_OLD") != nullptr;   // lab: the frame-at-a-time kernel
-    if (old_form) {
-        dim3 grid((geo.nblocks + WG - 1) / WG), block(WG);
-        if (geo.bits == 16)
-            hipLaunchKernelGGL((msv1_blocks_temporal1_kernel<16>), grid, block, 0, stream, d_stream, d_desc, d_frames, nframes,
-                               d_palette, geo.nblocks, geo.nbx, geo.X);
-        else
-            hipLaunchKernelGGL((msv1_blocks_temporal1_kernel<8>), grid, block, 0, stream, d_stream, d_desc, d_frames, nframes,
-                               d_palette, geo.nblocks, geo.nbx, geo.X);
-        return;
-    }
     const size_t lds = 2 * sizeof(TChunk) + 256 * 4 + (((size_t)nframes + 31) / 32 + 1 + TW) * 4;
     static std::once_flag attr_once;
     std::call_once(attr_once, [] {

@@ -13,8 +13,7 @@
 //     SECOND writer left it (or taken from the picture before) and compared, rows >= cmp_row_lo.
 // Every pixel of `dst` is written at most once, with the same 16-byte row stores as the other block kernels.  Work-items past
 // the last block copy the pixels no block covers (X % 4 / Y % 4 remainders) from the picture before.
-#include "msv1_decode.h"
-#include "msv1_seek.h"
+#include "msv1_block_io.h"
 
 namespace jsp {
 namespace {
@@ -22,89 +21,17 @@ namespace {
 constexpr int WG = 256;
 constexpr int SCAN = 4;   // table entries a lane has in flight per step of its backward walk
 
-typedef uint32_t su32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) su32x4 sgu32x4;
-typedef const __attribute__((address_space(1))) su32x4 scgu32x4;
-typedef __attribute__((address_space(1))) uint32_t sgu32;
-typedef const __attribute__((address_space(1))) uint32_t scgu32;
-
 // The last frame <= `from` whose table codes block `blk` (its code offset in `o`), or -1.
 __device__ __forceinline__ int last_writer(const uint32_t* __restrict__ desc, size_t pitch, int blk, int from, uint32_t& o) {
     for (int g = from; g >= 0; g -= SCAN) {
         uint32_t e[SCAN];
 #pragma unroll
-        for (int k = 0; k < SCAN; ++k) e[k] = g - k >= 0 ? *(scgu32*)(desc + (size_t)(g - k) * pitch + blk) : MSV1_DESC_SKIP;
+        for (int k = 0; k < SCAN; ++k) e[k] = g - k >= 0 ? *(cgu32*)(desc + (size_t)(g - k) * pitch + blk) : MSV1_DESC_SKIP;
 #pragma unroll
         for (int k = 0; k < SCAN; ++k)
             if (e[k] < MSV1_DESC_UNTOUCHED) { o = e[k]; return g - k; }
     }
     return -1;
-}
-
-// The 16 pixels of the code at `o` of a frame whose data ends at `stream_end` (MSVideo1.hx:135-181 / 319-364; bytes past the end
-// read as missing, which the reference turns into 0).
-template <int BITS>
-__device__ __forceinline__ void decode_at(const uint8_t* __restrict__ stream, uint32_t o, uint32_t stream_end, const uint32_t* s_pal,
-                                          uint32_t (&px)[16]) {
-    // 16-bit: `end` counts whole words and a code word cut in two (only its first byte exists) is painted solid from that byte
-    const uint32_t end = BITS == 16 ? (stream_end & ~1u) : stream_end;
-    const uint32_t avail = end > o ? end - o : 0u;
-    const bool half = BITS == 16 ? ((stream_end & 1u) && o == end) : avail == 1u;
-    if (half) {
-        const uint32_t a = stream[BITS == 16 ? stream_end - 1u : o];
-        const uint32_t v = BITS == 16 ? rgb555(a) : s_pal[a];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) px[k] = v;
-        return;
-    }
-    if (avail == 0u) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) px[k] = 0u;
-        return;
-    }
-    // o is even (codes are whole words from a 16-byte aligned frame start): six aligned dwords from o & ~3 hold the 20 bytes
-    // decode_block may read; every dword lies inside the batch's stream buffer (64 bytes of slack past its last frame)
-    const uint32_t a0 = o & ~3u;
-    uint32_t w[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const uint32_t at = a0 + 4u * (uint32_t)k;
-        const uint32_t v = at < end ? *(scgu32*)(stream + at) : 0u;
-        const uint32_t have = end - at;   // bytes of this dword that are data (when at < end)
-        w[k] = at >= end ? 0u : (have >= 4u ? v : v & ((1u << (8u * have)) - 1u));
-    }
-    const uint32_t sh = (o & 2u) * 8u;
-    uint32_t cw[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) cw[k] = __builtin_amdgcn_alignbit(w[k + 1], w[k], sh);
-    decode_block<BITS>(reinterpret_cast<const uint8_t*>(cw), avail, s_pal, px);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void load_block(const uint32_t* __restrict__ p, int X, uint32_t (&px)[16]) {
-#pragma unroll
-    for (int y = 0; y < 4; ++y) {
-        if (VEC) {
-            const su32x4 r = *(scgu32x4*)(p + (size_t)y * X);
-            px[y * 4] = r.x; px[y * 4 + 1] = r.y; px[y * 4 + 2] = r.z; px[y * 4 + 3] = r.w;
-        } else {
-#pragma unroll
-            for (int x = 0; x < 4; ++x) px[y * 4 + x] = *(scgu32*)(p + (size_t)y * X + x);
-        }
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store_block(uint32_t* __restrict__ p, int X, const uint32_t (&px)[16]) {
-#pragma unroll
-    for (int y = 0; y < 4; ++y) {
-        if (VEC) {
-            __builtin_nontemporal_store(su32x4{px[y * 4], px[y * 4 + 1], px[y * 4 + 2], px[y * 4 + 3]}, (sgu32x4*)(p + (size_t)y * X));
-        } else {
-#pragma unroll
-            for (int x = 0; x < 4; ++x) *(sgu32*)(p + (size_t)y * X + x) = px[y * 4 + x];
-        }
-    }
 }
 
 template <int BITS, bool VEC>
@@ -113,15 +40,13 @@ __global__ __launch_bounds__(WG) void msv1_seek_kernel(const uint8_t* __restrict
                                                        uint32_t* __restrict__ dst, const uint32_t* __restrict__ base, uint32_t cmp_row_lo,
                                                        uint32_t* __restrict__ signif, int nblocks, int nbx, int X, int cx, int cy, long nrem) {
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
-    if (BITS == 8) __syncthreads();
+    load_palette<BITS>(s_pal, palette);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
     if (gid >= nblocks) {   // a pixel no block covers: the right strip [0, cy) x [cx, X), then the rows [cy, Y)
         const long r = gid - nblocks;
         if (r >= nrem || base == nullptr || base == dst) return;
-        const long rw = (long)(X - cx) * cy;
-        const size_t i = r < rw ? (size_t)(r / (X - cx)) * (size_t)X + (size_t)cx + (size_t)(r % (X - cx)) : (size_t)cy * (size_t)X + (size_t)(r - rw);
-        *(sgu32*)(dst + i) = *(scgu32*)(base + i);
+        const size_t i = uncovered_pixel(r, X, cx, cy);
+        *(gu32*)(dst + i) = *(cgu32*)(base + i);
         return;
     }
     const int blk = (int)gid;
@@ -154,7 +79,7 @@ __global__ __launch_bounds__(WG) void msv1_seek_kernel(const uint8_t* __restrict
                 diff |= (pv[y * 4] != px[y * 4]) | (pv[y * 4 + 1] != px[y * 4 + 1]) | (pv[y * 4 + 2] != px[y * 4 + 2]) | (pv[y * 4 + 3] != px[y * 4 + 3]);
     }
     store_block<VEC>(dst + di, X, px);
-    // one word per launch: look before setting (see msv1_blocks_kernel)
+    // one word per launch: raise_flag's rule, with the ballot taken once (the instructions this kernel has always had)
     const unsigned long long m = __ballot(diff);
     if (m != 0ull && (threadIdx.x & 63) == __ffsll((long long)m) - 1 &&
         __hip_atomic_load(signif, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
@@ -169,7 +94,7 @@ __device__ __forceinline__ int last_writer_walk(const uint32_t* __restrict__ des
     for (int g = j - 1; g >= 0; g -= SCAN) {
         uint32_t e[SCAN];
 #pragma unroll
-        for (int k = 0; k < SCAN; ++k) e[k] = g - k >= 0 ? *(scgu32*)(desc + (size_t)walk[g - k] * pitch + blk) : MSV1_DESC_SKIP;
+        for (int k = 0; k < SCAN; ++k) e[k] = g - k >= 0 ? *(cgu32*)(desc + (size_t)walk[g - k] * pitch + blk) : MSV1_DESC_SKIP;
 #pragma unroll
         for (int k = 0; k < SCAN; ++k)
             if (e[k] < MSV1_DESC_UNTOUCHED) { o = e[k]; return (int)walk[g - k]; }
@@ -194,8 +119,7 @@ __global__ __launch_bounds__(WG) void msv1_change_scan_kernel(const uint8_t* __r
                                                               uint32_t* __restrict__ signif, uint32_t* __restrict__ first_hit,
                                                               const uint32_t* __restrict__ before, int nblocks, int nbx, int X) {
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
-    if (BITS == 8) __syncthreads();
+    load_palette<BITS>(s_pal, palette);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
     if (gid >= nblocks) return;
     const int blk = (int)gid;
@@ -210,7 +134,7 @@ __global__ __launch_bounds__(WG) void msv1_change_scan_kernel(const uint8_t* __r
         if (!ALL && walk[j] > __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
         uint32_t e[SCAN];
 #pragma unroll
-        for (int k = 0; k < SCAN; ++k) e[k] = j + k < j1 ? *(scgu32*)(desc + (size_t)walk[j + k] * pitch + blk) : MSV1_DESC_UNTOUCHED;
+        for (int k = 0; k < SCAN; ++k) e[k] = j + k < j1 ? *(cgu32*)(desc + (size_t)walk[j + k] * pitch + blk) : MSV1_DESC_UNTOUCHED;
 #pragma unroll
         for (int k = 0; k < SCAN; ++k) {
             if (e[k] >= MSV1_DESC_UNTOUCHED) continue;
@@ -227,10 +151,8 @@ __global__ __launch_bounds__(WG) void msv1_change_scan_kernel(const uint8_t* __r
                 for (int y = 0; y < 4; ++y)
                     if ((uint32_t)(by * 4 + y) >= row)
                         diff |= (pv[y * 4] != px[y * 4]) | (pv[y * 4 + 1] != px[y * 4 + 1]) | (pv[y * 4 + 2] != px[y * 4 + 2]) | (pv[y * 4 + 3] != px[y * 4 + 3]);
-                if (diff) {
-                    if (__hip_atomic_load(signif + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) atomicOr(signif + f, 1u);
-                    if (!ALL && __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)f) atomicMin(first_hit, (uint32_t)f);
-                }
+                raise_flag_lane(signif + f, diff);
+                if (!ALL && diff && __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)f) atomicMin(first_hit, (uint32_t)f);
             }
             wf = f;
             wo = e[k];
@@ -262,7 +184,7 @@ __global__ __launch_bounds__(WG) void msv1_coded_bitmap_kernel(const uint32_t* _
 #pragma unroll
         for (int k = 0; k < 32; ++k) {
             const int f = 32 * w + k;
-            e[k] = f >= f0 && f < f1 ? *(scgu32*)(desc + (size_t)(f - a) * pitch + blk) : MSV1_DESC_SKIP;
+            e[k] = f >= f0 && f < f1 ? *(cgu32*)(desc + (size_t)(f - a) * pitch + blk) : MSV1_DESC_SKIP;
         }
 #pragma unroll
         for (int k = 0; k < 32; ++k) {
@@ -297,11 +219,11 @@ __global__ __launch_bounds__(WG) void msv1_coded_bitmap_kernel(const uint32_t* _
 // per step.  Shared by the show and the thumbnail kernel.
 __device__ __forceinline__ uint32_t index_last_writer(const uint32_t* __restrict__ bitmap, int nblocks, int blk, int t, int& w) {
     w = t >> 5;
-    uint32_t m = *(scgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
+    uint32_t m = *(cgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
     while (m == 0u && w > 0) {
         uint32_t e[SCAN];
 #pragma unroll
-        for (int k = 0; k < SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(scgu32*)(bitmap + (size_t)(w - 1 - k) * (size_t)nblocks + blk) : 0u;
+        for (int k = 0; k < SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(cgu32*)(bitmap + (size_t)(w - 1 - k) * (size_t)nblocks + blk) : 0u;
         int step = SCAN;
 #pragma unroll
         for (int k = SCAN - 1; k >= 0; --k)
@@ -322,15 +244,13 @@ __global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexChun
                                                              uint32_t* __restrict__ dst, const uint32_t* __restrict__ before, int nblocks, int nbx, int X,
                                                              int cx, int cy, long nrem) {
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
-    if (BITS == 8) __syncthreads();
+    load_palette<BITS>(s_pal, palette);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
     if (gid >= nblocks) {   // a pixel no block covers, as in msv1_seek_kernel
         const long r = gid - nblocks;
         if (r >= nrem || before == nullptr) return;
-        const long rw = (long)(X - cx) * cy;
-        const size_t i = r < rw ? (size_t)(r / (X - cx)) * (size_t)X + (size_t)cx + (size_t)(r % (X - cx)) : (size_t)cy * (size_t)X + (size_t)(r - rw);
-        *(sgu32*)(dst + i) = *(scgu32*)(before + i);
+        const size_t i = uncovered_pixel(r, X, cx, cy);
+        *(gu32*)(dst + i) = *(cgu32*)(before + i);
         return;
     }
     const int blk = (int)gid;
@@ -347,11 +267,7 @@ __global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexChun
         }
         return;
     }
-    const int f = 32 * w + 31 - __builtin_clz(m);
-    const Msv1IndexChunk ch = chunks[frame_chunk[f]];
-    const int lf = f - (int)ch.first;
-    const uint32_t o = *(scgu32*)(ch.desc + (size_t)lf * pitch + blk);
-    decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
+    index_decode<BITS>(chunks, frame_chunk, pitch, 32 * w + 31 - __builtin_clz(m), blk, s_pal, px);
     store_block<VEC>(dst + di, X, px);
 }
 
@@ -367,7 +283,7 @@ __device__ __forceinline__ uint32_t index_last_writer_span(const uint32_t* __res
     w = t >> 5;
     if (w != cw) {
         pw = cw; pv = cv;
-        cw = w; cv = *(scgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk);
+        cw = w; cv = *(cgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk);
     }
     uint32_t m = cv & (0xFFFFFFFFu >> (31 - (t & 31)));
     if (w == wb) return m & mask_lo;
@@ -376,7 +292,7 @@ __device__ __forceinline__ uint32_t index_last_writer_span(const uint32_t* __res
 #pragma unroll
         for (int k = 0; k < SCAN; ++k) {
             const int i = w - 1 - k;
-            e[k] = i < wb ? 0u : i == pw ? pv : *(scgu32*)(bitmap + (size_t)i * (size_t)nblocks + blk);
+            e[k] = i < wb ? 0u : i == pw ? pv : *(cgu32*)(bitmap + (size_t)i * (size_t)nblocks + blk);
             if (i == wb) e[k] &= mask_lo;
         }
         int step = SCAN;
@@ -386,16 +302,6 @@ __device__ __forceinline__ uint32_t index_last_writer_span(const uint32_t* __res
         w -= step;
     }
     return m;
-}
-
-// The 16 pixels frame f of the index makes of block `blk`, which it codes: its chunk's table entry and stream, as the show kernel.
-template <int BITS>
-__device__ __forceinline__ void index_decode(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk, size_t pitch,
-                                             int f, int blk, const uint32_t* s_pal, uint32_t (&px)[16]) {
-    const Msv1IndexChunk ch = chunks[frame_chunk[f]];
-    const int lf = f - (int)ch.first;
-    const uint32_t o = *(scgu32*)(ch.desc + (size_t)lf * pitch + blk);
-    decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
 }
 
 // Play (jsp_index_play): frames t_k = first + k * stride, k < n, each into dsts[k] exactly as msv1_index_show_kernel(t_k) writes it — ONE
@@ -414,20 +320,18 @@ __global__ __launch_bounds__(WG) void msv1_index_play_kernel(const Msv1IndexChun
                                                              const uint32_t* __restrict__ before, int nblocks, int nbx, int X, int cx, int cy,
                                                              long nrem) {
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
-    if (BITS == 8) __syncthreads();
+    load_palette<BITS>(s_pal, palette);
     const int k0 = (int)blockIdx.y * seg;
     const int k1 = min(n, k0 + seg);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
     if (gid >= nblocks) {   // a pixel no block covers, as in msv1_seek_kernel
         const long r = gid - nblocks;
         if (r >= nrem || before == nullptr) return;
-        const long rw = (long)(X - cx) * cy;
-        const size_t i = r < rw ? (size_t)(r / (X - cx)) * (size_t)X + (size_t)cx + (size_t)(r % (X - cx)) : (size_t)cy * (size_t)X + (size_t)(r - rw);
-        const uint32_t v = *(scgu32*)(before + i);
+        const size_t i = uncovered_pixel(r, X, cx, cy);
+        const uint32_t v = *(cgu32*)(before + i);
         for (int k = k0; k < k1; ++k) {
             uint32_t* d = dsts[k];
-            if (d != nullptr) *(sgu32*)(d + i) = v;
+            if (d != nullptr) *(gu32*)(d + i) = v;
         }
         return;
     }
@@ -489,8 +393,7 @@ __global__ __launch_bounds__(WG) void msv1_index_thumbs_kernel(const Msv1IndexCh
     constexpr int LG = S == 4 ? 0 : S == 8 ? 1 : 2;                 // log2(G)
     constexpr uint32_t SH = 4 + 2 * LG, HALF = (uint32_t)(S * S) / 2u;   // log2(S * S), the rounding term
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    if (BITS == 8) s_pal[threadIdx.x] = (uint32_t)palette[threadIdx.x];
-    if (BITS == 8) __syncthreads();
+    load_palette<BITS>(s_pal, palette);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
     const long q = gid >> (2 * LG);                                 // output pixel of the thumbnail, raster order
     if (q >= (long)tw * th) return;
@@ -506,11 +409,7 @@ __global__ __launch_bounds__(WG) void msv1_index_thumbs_kernel(const Msv1IndexCh
     const uint32_t m = index_last_writer(bitmap, nblocks, blk, t, w);
     uint32_t px[16];
     if (m != 0u) {
-        const int f = 32 * w + 31 - __builtin_clz(m);
-        const Msv1IndexChunk ch = chunks[frame_chunk[f]];
-        const int lf = f - (int)ch.first;
-        const uint32_t o = *(scgu32*)(ch.desc + (size_t)lf * pitch + blk);
-        decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
+        index_decode<BITS>(chunks, frame_chunk, pitch, 32 * w + 31 - __builtin_clz(m), blk, s_pal, px);
     } else if (before != nullptr) {   // nothing up to t coded the block: the picture before the index
         const uint32_t* p = before + (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
         if (before_vec) load_block<true>(p, X, px);
@@ -534,7 +433,7 @@ __global__ __launch_bounds__(WG) void msv1_index_thumbs_kernel(const Msv1IndexCh
     const uint32_t r = ((rb >> 16) + HALF) >> SH, b = ((rb & 0xFFFFu) + HALF) >> SH;
     const size_t sheet_pitch = (size_t)cols * (size_t)tw;
     const size_t at = (size_t)(k / cols) * (size_t)th * sheet_pitch + (size_t)(k % cols) * (size_t)tw + (size_t)py * sheet_pitch + (size_t)px_;
-    *(sgu32*)(out + at) = (r << 16) | (((g + HALF) >> SH) << 8) | b;
+    *(gu32*)(out + at) = (r << 16) | (((g + HALF) >> SH) << 8) | b;
 }
 
 // The seek and show kernels' work: one work-item per block, then one per pixel no block covers (nrem of them: the columns from cx on
@@ -569,12 +468,11 @@ void msv1_launch_seek(const Msv1SeekView& v, int32_t* dst, const int32_t* base, 
     PictureGrid g;
     if (v.nframes <= 0 || !picture_grid(geo, dst, base, g)) return;
     uint32_t* signif = v.d_signif + (v.nframes - 1);
-#define JSP_SEEK(BITS, VEC) hipLaunchKernelGGL((msv1_seek_kernel<BITS, VEC>), g.grid, dim3(WG), 0, stream, v.d_stream, v.d_desc, v.desc_pitch, v.d_frames, \
-                                               v.nframes, v.d_palette, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(base),      \
-                                               cmp_row_lo, signif, geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem)
-    if (geo.bits == 16) { if (g.vec) JSP_SEEK(16, true); else JSP_SEEK(16, false); }
-    else { if (g.vec) JSP_SEEK(8, true); else JSP_SEEK(8, false); }
-#undef JSP_SEEK
+    dispatch_bits_vec(geo.bits, g.vec, [&](auto B, auto V) {
+        hipLaunchKernelGGL((msv1_seek_kernel<decltype(B)::value, decltype(V)::value>), g.grid, dim3(WG), 0, stream, v.d_stream, v.d_desc, v.desc_pitch,
+                           v.d_frames, v.nframes, v.d_palette, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(base), cmp_row_lo,
+                           signif, geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem);
+    });
 }
 
 void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int nwalk, const uint32_t* d_rows, uint32_t* d_first_hit,
@@ -584,17 +482,15 @@ void msv1_launch_change_scan(const Msv1SeekView& v, const uint32_t* d_walk, int 
     int seg = 0;
     const dim3 grid = scan_grid(geo, nwalk, seg), block(WG);
     const bool vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
-#define JSP_SCAN(BITS, VEC, ALL) hipLaunchKernelGGL((msv1_change_scan_kernel<BITS, VEC, ALL>), grid, block, 0, stream, v.d_stream, v.d_desc, v.desc_pitch, \
-                                                    v.d_frames, v.d_palette, d_walk, nwalk, seg, d_rows, v.d_signif, d_first_hit,                         \
-                                                    reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X)
-    if (d_first_hit) {
-        if (geo.bits == 16) { if (vec) JSP_SCAN(16, true, false); else JSP_SCAN(16, false, false); }
-        else { if (vec) JSP_SCAN(8, true, false); else JSP_SCAN(8, false, false); }
-    } else {
-        if (geo.bits == 16) { if (vec) JSP_SCAN(16, true, true); else JSP_SCAN(16, false, true); }
-        else { if (vec) JSP_SCAN(8, true, true); else JSP_SCAN(8, false, true); }
-    }
-#undef JSP_SCAN
+    dispatch_bits_vec(geo.bits, vec, [&](auto B, auto V) {
+        auto launch = [&](auto ALL) {
+            hipLaunchKernelGGL((msv1_change_scan_kernel<decltype(B)::value, decltype(V)::value, decltype(ALL)::value>), grid, block, 0, stream, v.d_stream,
+                               v.d_desc, v.desc_pitch, v.d_frames, v.d_palette, d_walk, nwalk, seg, d_rows, v.d_signif, d_first_hit,
+                               reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X);
+        };
+        if (d_first_hit) launch(std::false_type{});
+        else launch(std::true_type{});
+    });
 }
 
 void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, uint32_t* d_rows, uint32_t* d_stop, hipStream_t stream) {
@@ -611,12 +507,11 @@ void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chu
     PictureGrid g;
     if (!picture_grid(geo, dst, before, g)) return;
     const size_t pitch = (size_t)std::max(geo.nblocks, 1);
-#define JSP_SHOW(BITS, VEC) hipLaunchKernelGGL((msv1_index_show_kernel<BITS, VEC>), g.grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk, d_palette, \
-                                               d_bitmap, pitch, t, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(before),     \
-                                               geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem)
-    if (geo.bits == 16) { if (g.vec) JSP_SHOW(16, true); else JSP_SHOW(16, false); }
-    else { if (g.vec) JSP_SHOW(8, true); else JSP_SHOW(8, false); }
-#undef JSP_SHOW
+    dispatch_bits_vec(geo.bits, g.vec, [&](auto B, auto V) {
+        hipLaunchKernelGGL((msv1_index_show_kernel<decltype(B)::value, decltype(V)::value>), g.grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk,
+                           d_palette, d_bitmap, pitch, t, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(before), geo.nblocks,
+                           std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem);
+    });
 }
 
 int msv1_index_play_auto_segments(const Msv1Geometry& geo, int n) {
@@ -635,12 +530,11 @@ void msv1_launch_index_play(const Msv1Geometry& geo, const Msv1IndexChunk* d_chu
     const int seg = (n + std::min(std::max(segs, 1), n) - 1) / std::min(std::max(segs, 1), n);   // destinations per segment
     const dim3 grid(g.grid.x, (unsigned)((n + seg - 1) / seg));
     const size_t pitch = (size_t)std::max(geo.nblocks, 1);
-#define JSP_PLAY(BITS, VEC) hipLaunchKernelGGL((msv1_index_play_kernel<BITS, VEC>), grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk, d_palette, \
-                                               d_bitmap, pitch, first, n, stride, seg, reinterpret_cast<uint32_t* const*>(d_dsts),               \
-                                               reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem)
-    if (geo.bits == 16) { if (vec) JSP_PLAY(16, true); else JSP_PLAY(16, false); }
-    else { if (vec) JSP_PLAY(8, true); else JSP_PLAY(8, false); }
-#undef JSP_PLAY
+    dispatch_bits_vec(geo.bits, vec, [&](auto B, auto V) {
+        hipLaunchKernelGGL((msv1_index_play_kernel<decltype(B)::value, decltype(V)::value>), grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk,
+                           d_palette, d_bitmap, pitch, first, n, stride, seg, reinterpret_cast<uint32_t* const*>(d_dsts),
+                           reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem);
+    });
 }
 
 void msv1_launch_index_thumbs(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,

@@ -13,7 +13,6 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <cstdlib>
 #include <functional>
 #include <memory>
 #include <vector>
@@ -270,8 +269,7 @@ void launch_pframe_group(const Geometry& g, const PGroupFrame* d_frames, int nfr
 // width is a multiple of 4 and `prev` and every destination (aligned16) are 16-byte aligned, else sp_pframe_group1_kernel, which
 // stages its own chunks.  The one place that decides it: the launcher and what a staged batch reports both ask here.
 inline bool pframe_group_takes_loader(const Geometry& g, const int32_t* prev, bool aligned16) {
-    static const bool old_form = std::getenv("JSP_SP_GROUP_OLD") != nullptr;   // lab: the kernel that stages its own chunks
-    return (g.X & 3) == 0 && aligned16 && (reinterpret_cast<uintptr_t>(prev) & 15) == 0 && !old_form;
+    return (g.X & 3) == 0 && aligned16 && (reinterpret_cast<uintptr_t>(prev) & 15) == 0;
 }
 // Seek index (sp_index_kernels.hip): frame t of a resident range — the key picture `key` of frame k <= t under the literal rectangles of the
 // LAST frame in (k, t] that covers each pixel.  Frame f's block table is d_blocks + (f + slot_base) * nblocks; PBlock::payload counts in

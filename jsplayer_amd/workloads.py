@@ -126,7 +126,7 @@ def digest(frame) -> str:
 _KERNEL_SOURCES = (      # kernel name prefix -> the files under csrc/ its code comes from
     ("msv1_fused", ("msv1_parse_kernels.hip", "msv1_lanes.h", "msv1_decode.h", "msv1_fused_hooks.h", "msv1.h")),
     ("msv1_parse", ("msv1_parse_kernels.hip", "msv1_lanes.h", "msv1.h")),
-    ("msv1_blocks", ("msv1_kernels.hip", "msv1_decode.h", "msv1.h")),
+    ("msv1_blocks", ("msv1_kernels.hip", "msv1_block_io.h", "msv1_decode.h", "msv1.h")),
     ("sp_", ("sp_kernels.hip", "sp.h")),
 )
 

@@ -66,6 +66,26 @@ def test_product_does_not_reference_the_oracle():
                     f"{f} refers to the oracle"
 
 
+def test_every_environment_variable_the_library_reads_is_documented():
+    """The shipped library reads exactly the environment variables INTEGRATION.md documents: the string literals passed to getenv and
+    to jsp_pool.cpp's env() helper under jsplayer_amd/csrc/ and include/, against the JSP_* names in the paragraphs of INTEGRATION.md
+    that speak of environment variables.  (Lab switches are not shipped: a measurement that needs one builds a variant.)"""
+    read = set()
+    for top in (os.path.join(ROOT, "jsplayer_amd", "csrc"), os.path.join(ROOT, "include")):
+        for dirpath, _, files in os.walk(top):
+            for f in files:
+                if f.endswith((".cpp", ".h", ".hip")):
+                    text = open(os.path.join(dirpath, f), errors="replace").read()
+                    read.update(re.findall(r'\b(?:getenv|env)\(\s*"([^"]+)"', text))
+    paragraphs = re.split(r"\n(?=\* |#|\s*\n)", open(os.path.join(ROOT, "INTEGRATION.md")).read())
+    documented = set()
+    for p in paragraphs:
+        if "environment variable" in p:
+            documented.update(re.findall(r"`(JSP_[A-Z0-9_]+)", p))
+    assert read, "no getenv found: the scan is broken"
+    assert read == documented, f"read but not documented: {sorted(read - documented)}; documented but not read: {sorted(documented - read)}"
+
+
 def test_threaded_host_layers_are_clean_under_thread_sanitizer(tmp_path):
     """tools/tsan_cpu.sh: jsp_api.cpp, jsp_pool.cpp, msv1_codec.cpp, sp_codec.cpp, jsp_shard.cpp and the host stages built with -fsanitize=thread against
     the stub HIP runtime under tests/tsan/ and driven on 26 host threads (asynchronous submit / wait out of phase, drains, prefetch ranges
