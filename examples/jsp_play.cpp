@@ -6,6 +6,8 @@
 //                                the plain run, and every frame shown is also presented into a W x H device window (jsp_view_matrix +
 //                                jsp_display_present, bilinear: zoom 0 = "Fit" (default), 1 = "100%", 2 = "200%"; view positions in 0..1,
 //                                default 0.5 — Main.on_stage_resize, Main.hx:288-319); the lines end in the window's crc32
+//   jsp_play clip.avi --present-area WxH[:zoom[:hpos:vpos]]
+//                                the same with the window area-averaged (jsp_display_present_area): what Fit into a small window needs
 //   jsp_play clip.avi --pipelined [--depth D]
 //                                the same lines, decoded through jsp_decompress_*_async / jsp_wait with D frames in
 //                                flight: the host stage of frame n+1 overlaps the uploads and kernels of frame n
@@ -397,7 +399,7 @@ long play_batched(const Clip& clip, int batch, int repeat, bool quiet, int warmu
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]] | --present-area WxH[:zoom[:hpos:vpos]]\n", argv[0]); return 2; }
     // (throughput runs: several files, separated by commas — stream s plays file s modulo their number, so that the streams of a
     // multi-stream run are independent inputs)
     std::deque<Clip> clips;                                   // (a deque: elements never move)
@@ -424,6 +426,7 @@ int main(int argc, char** argv) {
     long run_first = -1, run_count = -1, run_stride = 1;      // --index-run FIRST[:COUNT[:STRIDE]]: frames played out of an MSVideo1 seek index
     int present_w = 0, present_h = 0;                         // --present WxH[:zoom[:hpos:vpos]]: every frame shown also goes into a device window
     double present_zoom = 0, present_hpos = 0.5, present_vpos = 0.5;
+    bool present_area = false;                                // --present-area: the window from jsp_display_present_area
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -463,10 +466,11 @@ int main(int argc, char** argv) {
             if (c2 != std::string::npos) run_stride = std::atol(v.substr(c2 + 1).c_str());
             if (run_first < 0 || (c1 != std::string::npos && run_count < 1) || run_stride < 1) { std::fprintf(stderr, "--index-run: FIRST >= 0, COUNT >= 1, STRIDE >= 1\n"); return 2; }
         }
-        else if (o == "--present" && a + 1 < argc) {
+        else if ((o == "--present" || o == "--present-area") && a + 1 < argc) {
             const std::string v = argv[++a];
             const int got = std::sscanf(v.c_str(), "%dx%d:%lf:%lf:%lf", &present_w, &present_h, &present_zoom, &present_hpos, &present_vpos);
-            if ((got != 2 && got != 3 && got != 5) || present_w < 1 || present_h < 1) { std::fprintf(stderr, "--present: WxH[:zoom[:hpos:vpos]]\n"); return 2; }
+            if ((got != 2 && got != 3 && got != 5) || present_w < 1 || present_h < 1) { std::fprintf(stderr, "%s: WxH[:zoom[:hpos:vpos]]\n", o.c_str()); return 2; }
+            present_area = o == "--present-area";
         }
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
@@ -917,9 +921,13 @@ int main(int argc, char** argv) {
             uint32_t wcrc = 0;
             if (shown >= 0) {
                 int32_t* win = jsp_pool_buffer(window, 0);
-                if (jsp_display_present(jsp_pool_buffer(pool, shown), clip.X, clip.Y, win, present_w, present_h, (size_t)present_w, view_k, view_dx, view_dy,
-                                        present_mode, JSP_PRESENT_BILINEAR, 0xFF000000u, nullptr) != 0) {
-                    std::fprintf(stderr, "jsp_display_present: %s\n", jsp_last_error());
+                const int prc = present_area
+                    ? jsp_display_present_area(jsp_pool_buffer(pool, shown), clip.X, clip.Y, win, present_w, present_h, (size_t)present_w, view_k, view_dx, view_dy,
+                                               present_mode, 0xFF000000u, nullptr)
+                    : jsp_display_present(jsp_pool_buffer(pool, shown), clip.X, clip.Y, win, present_w, present_h, (size_t)present_w, view_k, view_dx, view_dy,
+                                          present_mode, JSP_PRESENT_BILINEAR, 0xFF000000u, nullptr);
+                if (prc != 0) {
+                    std::fprintf(stderr, "%s: %s\n", present_area ? "jsp_display_present_area" : "jsp_display_present", jsp_last_error());
                     rc = 1;
                     break;
                 }

@@ -94,6 +94,10 @@ extern class JspNative {
     @:native("jsp_display_present")    static function displayPresent(frame:RawConstPointer<cpp.Int32>, frameW:Int, frameH:Int, out:RawPointer<cpp.Int32>, winW:Int, winH:Int,
                                                                       outPitch:SizeT, k:Float, dx:Float, dy:Float, mode:Int, filter:Int, background:cpp.UInt32,
                                                                       stream:RawPointer<cpp.Void>):Int;
+    // the same window area-averaged (Fit into a small window); takes no filter — jsp_display_present refuses JSP_PRESENT_AREA
+    @:native("jsp_display_present_area") static function displayPresentArea(frame:RawConstPointer<cpp.Int32>, frameW:Int, frameH:Int, out:RawPointer<cpp.Int32>, winW:Int, winH:Int,
+                                                                      outPitch:SizeT, k:Float, dx:Float, dy:Float, mode:Int, background:cpp.UInt32,
+                                                                      stream:RawPointer<cpp.Void>):Int;
     @:native("jsp_frames_differ")      static function framesDiffer(a:RawConstPointer<cpp.Int32>, b:RawConstPointer<cpp.Int32>, firstPixel:SizeT, npixels:SizeT, differ:RawPointer<Int>, stream:RawPointer<cpp.Void>):Int;
 }
 

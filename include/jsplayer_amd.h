@@ -578,7 +578,11 @@ int jsp_display_convert(const int32_t* frame, int32_t* out, int width, int heigh
  * jsp_view_matrix is Main's view geometry, jsp_display_present turns a frame buffer into the canvas pixels of a window of any size in
  * ONE kernel launch — the conversion of jsp_display_convert, the row flip, the crop and the resampling fused; no full-size converted
  * frame is written anywhere. */
-enum { JSP_PRESENT_NEAREST = 0, JSP_PRESENT_BILINEAR = 1 };   /* bitmap.smoothing false / true (Main.hx:948) */
+enum {
+    JSP_PRESENT_NEAREST = 0, JSP_PRESENT_BILINEAR = 1,        /* bitmap.smoothing false / true (Main.hx:948) */
+    JSP_PRESENT_AREA = 2   /* the area average, for the layers above: jsp_display_present does NOT take it (it refuses every filter but
+                            * 0 and 1) — jsp_display_present_area is the call */
+};
 
 /* Main.hx:301-315 in doubles; pure host arithmetic, no device needed.
  *   zoom == 0 ("Fit"): *k = min(win_w / frame_w, win_h / frame_h), *dx = *dy = 0.
@@ -615,6 +619,35 @@ int jsp_display_present(const int32_t* frame, int frame_w, int frame_h,
                         int32_t* out, int win_w, int win_h, size_t out_pitch,
                         double k, double dx, double dy, int mode, int filter,
                         uint32_t background, void* hip_stream);
+
+/* The same window, area-averaged: what "Fit" of a large picture into a small window needs (k = 1/3 samples four source pixels out of
+ * nine with the two filters above; a browser's compositor averages when it minifies).  Same contract as jsp_display_present in
+ * everything except the filter, which it does not take: ONE kernel launch on `hip_stream`, asynchronous, no full-size intermediate.
+ *   THE RULE, in integers:
+ *     Geometry: F, step, ax, ay, X = ax + ox * step, Y = ay - oy * step exactly as above (the same +-2^62 hold).  An output pixel
+ *       shows the picture under the SAME condition — its centre lies inside: 0 <= X < frame_w * 65536 and 0 <= Y < frame_h * 65536 —
+ *       and is `background` otherwise: the three filters agree on which pixels are picture.
+ *     Footprint, per axis, in 1/256 source pixels: s = step >> 8 (4 .. 16384).  Columns: c = X >> 8, lo = c - (s >> 1), hi = lo + s,
+ *       clipped to the picture: lo' = max(lo, 0), hi' = min(hi, frame_w * 256) (a covered pixel has hi' > lo').  Source column x has
+ *       the weight wx(x) = max(0, min(hi', (x + 1) * 256) - max(lo', x * 256)), and Wx = hi' - lo'.  Rows likewise from Y and frame_h
+ *       (wy, Wy); bitmap row y = buffer row y.
+ *     Average: every source pixel is first converted by `mode` (the four JSP_DISPLAY_* conversions, bit for bit); each of the four
+ *       bytes of the converted words on its own:  S = sum_y wy(y) * sum_x wx(x) * p(x, y),  D = Wx * Wy,
+ *       result = floor((S + (D >> 1)) / D).  (Wx, Wy <= 16384, D <= 2^28, S < 2^36: S needs more than 32 bits below k of about 1/16,
+ *       and the quotient is exact.)
+ *     Hence: at k = 1 with integral dx, dy the footprint is exactly one pixel — the plain crop of the other two filters; at k = 1/n
+ *     with dx = dy = 0 it is the n x n box mean with halves rounded up, (sum + n*n/2) / (n*n), the rounding of the filmstrip calls;
+ *     the alpha byte 0xFF of the canvas modes stays 0xFF.  The rule holds for every k in bounds; for k > 1 it is a box under one
+ *     pixel wide — legal and pinned, not the recommended use.
+ *   ARGUMENTS: `frame`, `out` device pointers; `out` holds (win_h - 1) * out_pitch + win_w ints, does not overlap `frame` and needs no
+ *     alignment (rows that start on 16-byte boundaries get 16-byte stores).  Only the window's pixels are written: pitch padding and
+ *     memory behind the window are not.  Sizes 1 .. 16384, 1/64 <= k <= 64.
+ *   ERRORS (JSP_ERROR_OCCURED, jsp_last_error() starts with "display_present_area:", nothing queued, nothing written): a null
+ *     pointer, a size or k outside its bounds, a non-finite k, dx or dy, out_pitch < win_w, an unknown mode. */
+int jsp_display_present_area(const int32_t* frame, int frame_w, int frame_h,
+                             int32_t* out, int win_w, int win_h, size_t out_pitch,
+                             double k, double dx, double dy, int mode,
+                             uint32_t background, void* hip_stream);
 
 /* The pixel loop of frames_differ_significantly (Manager.hx:413-419): *differ = any a[i] != b[i] for
  * first_pixel <= i < npixels.  Device pointers; synchronous. */

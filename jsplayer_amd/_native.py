@@ -117,6 +117,8 @@ SIGNATURES = {
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "jsp_display_present": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t,
                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "jsp_display_present_area": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t,
+                                           C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32, C.c_void_p]),
     "jsp_measure_fill": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "jsp_frames_differ": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_int), C.c_void_p]),
     "jsp_version": (C.c_char_p, []),

@@ -766,8 +766,11 @@ def display_convert(frame, out, width: int, height: int, mode: int = DISPLAY_CAN
 
 # ---- a frame in a window: Main's view geometry and the browser's resampling (Main.hx:288-319, 948), one launch ----
 PRESENT_NEAREST, PRESENT_BILINEAR = 0, 1
+PRESENT_AREA = 2          # the area average: display_present_area's rule (display_present itself refuses it); Manager.present routes it
 # what one workgroup of the present kernel covers (csrc/present_kernels.hip: kPresentSpanX, kPresentBandRows); results do not depend on it
 PRESENT_SPAN_X, PRESENT_BAND_ROWS = 256, 8
+# the same of the area kernel (csrc/present_area_kernels.hip: kAreaLanes — a lane owns one pixel —, kAreaBandRows)
+PRESENT_AREA_SPAN_X, PRESENT_AREA_BAND_ROWS = 64, 1
 
 
 def view_matrix(frame_w: int, frame_h: int, win_w: int, win_h: int, zoom: float = 0.0, hor_view_pos: float = 0.5,
@@ -797,6 +800,25 @@ def display_present(frame, frame_w: int, frame_h: int, out, win_w: int, win_h: i
                                  C.c_void_p(dst), int(win_w), int(win_h), C.c_size_t(max(pitch, 0)),
                                  float(k), float(dx), float(dy), int(mode), int(filter), C.c_uint32(int(background) & 0xFFFFFFFF),
                                  C.c_void_p(stream) if stream else None)
+    if rc != 0:
+        raise CodecError(N.last_error())
+
+
+def display_present_area(frame, frame_w: int, frame_h: int, out, win_w: int, win_h: int, k: float, dx: float, dy: float,
+                         mode: int = DISPLAY_CANVAS, background: int = 0xFF000000, out_pitch: Optional[int] = None,
+                         stream: int = 0) -> None:
+    """display_present's window with every covered pixel the area average of the converted source pixels under it (the rule of
+    jsp_display_present_area): what Fit of a large picture into a small window needs.  Same arguments, no filter; one launch on
+    `stream`, asynchronous."""
+    pitch = int(win_w) if out_pitch is None else int(out_pitch)
+    need = max((int(win_h) - 1) * pitch + int(win_w), 1)
+    src = _device_frame_ptr(frame, max(int(frame_w) * int(frame_h), 1), "display_present_area")
+    dst = _device_frame_ptr(out, need, "display_present_area")
+    lib = N.lib()
+    rc = lib.jsp_display_present_area(C.c_void_p(src), int(frame_w), int(frame_h),
+                                      C.c_void_p(dst), int(win_w), int(win_h), C.c_size_t(max(pitch, 0)),
+                                      float(k), float(dx), float(dy), int(mode), C.c_uint32(int(background) & 0xFFFFFFFF),
+                                      C.c_void_p(stream) if stream else None)
     if rc != 0:
         raise CodecError(N.last_error())
 

@@ -157,16 +157,20 @@ class Manager:
 
     def present(self, buf, out, win_w: int, win_h: int, filter: Optional[int] = None, background: int = 0xFF000000, stream: int = 0) -> None:
         """The window `self.view` shows of one of this Manager's frame buffers (`buf`: the buffer, or its slot number), as canvas
-        pixels, top row first, into the device tensor `out` (win_w * win_h ints): one launch (jsp_display_present), the frame stays
-        in HBM.  The conversion is chosen as Manager.hx:121 chooses convert_fromRGB15: 16-bpp ScreenPressor frames hold 5-bit
+        pixels, top row first, into the device tensor `out` (win_w * win_h ints): one launch (jsp_display_present, or
+        jsp_display_present_area for filter = PRESENT_AREA), the frame stays in HBM.  The conversion is chosen as Manager.hx:121 chooses convert_fromRGB15: 16-bpp ScreenPressor frames hold 5-bit
         components.  `filter` defaults to bilinear (bitmap.smoothing = true, Main.hx:948).  HIP frame buffers only."""
-        from .codec import DISPLAY_CANVAS, DISPLAY_CANVAS_RGB15, PRESENT_BILINEAR, display_present
+        from .codec import DISPLAY_CANVAS, DISPLAY_CANVAS_RGB15, PRESENT_AREA, PRESENT_BILINEAR, display_present, display_present_area
         if isinstance(buf, (int, np.integer)):
             buf = self.buffers[int(buf)]
         elif self._slot_of(buf) < 0:
             raise ValueError("present: not one of this Manager's frame buffers")
         from_rgb15 = self.vi.bpp == 16 and self.vi.codec == CODEC_SCREENPRESSOR
         k, dx, dy = self.view.matrix(self.vi.X, self.vi.Y, win_w, win_h)
+        if filter == PRESENT_AREA:
+            display_present_area(buf, self.vi.X, self.vi.Y, out, win_w, win_h, k, dx, dy,
+                                 mode=DISPLAY_CANVAS_RGB15 if from_rgb15 else DISPLAY_CANVAS, background=background, stream=stream)
+            return
         display_present(buf, self.vi.X, self.vi.Y, out, win_w, win_h, k, dx, dy,
                         mode=DISPLAY_CANVAS_RGB15 if from_rgb15 else DISPLAY_CANVAS,
                         filter=PRESENT_BILINEAR if filter is None else filter, background=background, stream=stream)

@@ -19,7 +19,13 @@ sits on), so the kernels' own durations come from a profiler run of its own:
                   its dispatches, the first three dropped) and its fraction of the fill KERNEL's time over max(window bytes, bytes
                   read) to the records of --out.
 
-    python tools/present_latency.py [--launches 200] [--rounds 7] [--out profiles/present_latency.json]
+  --area          the area-averaged call instead (jsp_display_present_area): the windows a shrunk picture goes into —
+                  1280x720 Fit, 640x360 Fit, 480x270 Fit and 30x17 at k = 1/64 — each as area, nearest and bilinear, beside the same
+                  jsp_display_convert (which reads the same 8.3 MB once: the floor for a kernel that reads the whole frame) and fills;
+                  each area window is first checked against tests/view_area_ref.py.  Goes with the three forms above; --out defaults
+                  to profiles/present_area_latency.json, --plan to present_area_kernel_plan.json beside it.
+
+    python tools/present_latency.py [--area] [--launches 200] [--rounds 7] [--out profiles/present_latency.json]
 """
 from __future__ import annotations
 
@@ -41,6 +47,10 @@ CASES = [("1280x720 fit", (1280, 720), 0, 0.5, 0.5),
          ("1920x1080 200% centre", (1920, 1080), 2, 0.5, 0.5),
          ("3840x2160 fit", (3840, 2160), 0, 0.5, 0.5),
          ("640x360 fit", (640, 360), 0, 0.5, 0.5)]
+AREA_CASES = [("1280x720 fit", (1280, 720), 0, 0.5, 0.5),
+              ("640x360 fit", (640, 360), 0, 0.5, 0.5),
+              ("480x270 fit", (480, 270), 0, 0.5, 0.5),
+              ("30x17 k=1/64", (30, 17), 1.0 / 64, 0.5, 0.5)]
 
 
 def bytes_read(ww, wh, k, dx, dy):
@@ -50,7 +60,7 @@ def bytes_read(ww, wh, k, dx, dy):
     return int(max(0.0, x_hi - x_lo) * max(0.0, y_hi - y_lo)) * 4
 
 
-KERNELS = {"present": "display_present_kernel", "display_convert": "display_convert_kernel", "fill": "ceiling_fill_kernel"}
+KERNELS = {"present": "display_present_kernel", "present_area": "display_present_area_kernel", "display_convert": "display_convert_kernel", "fill": "ceiling_fill_kernel"}
 DROP = 3      # dispatches of each form that count as warm-up in the kernel trace
 
 
@@ -100,13 +110,15 @@ def main() -> int:
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "present_latency.json"))
+    ap.add_argument("--area", action="store_true")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--kernel-launches", type=int, default=23)
     ap.add_argument("--plan", default=None)
     ap.add_argument("--reduce", default=None, metavar="DIR")
     args = ap.parse_args()
-    plan_path = args.plan or os.path.join(os.path.dirname(args.out), "present_kernel_plan.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "present_area_latency.json" if args.area else "present_latency.json")
+    plan_path = args.plan or os.path.join(os.path.dirname(args.out), "present_area_kernel_plan.json" if args.area else "present_kernel_plan.json")
     if args.reduce:
         return reduce_trace(args.reduce, plan_path, args.out)
 
@@ -115,6 +127,7 @@ def main() -> int:
     if not torch.cuda.is_available():
         print("present_latency: needs a GPU (nothing is measured without one)", file=sys.stderr)
         return 1
+    import view_area_ref as ar
     import view_ref as vr
     from jsplayer_amd import _native as N
     from jsplayer_amd import codec as cm
@@ -129,28 +142,36 @@ def main() -> int:
 
     forms = {}      # name -> (callable queuing ONE launch on `stream`, record)
     fills = {}      # window name -> the tensor the fill is measured over
-    for name, (ww, wh), zoom, hor, ver in CASES:
+    AREA = "area"       # (no filter value of jsp_display_present: the call of its own)
+    filters = ((cm.PRESENT_NEAREST, "nearest"), (cm.PRESENT_BILINEAR, "bilinear"))
+
+    def present(out, ww, wh, k, dx, dy, filt):
+        if filt == AREA:
+            cm.display_present_area(frame, FW, FH, out, ww, wh, k, dx, dy, stream=handle)
+        else:
+            cm.display_present(frame, FW, FH, out, ww, wh, k, dx, dy, filter=filt, stream=handle)
+
+    for name, (ww, wh), zoom, hor, ver in (AREA_CASES if args.area else CASES):
         k, dx, dy = cm.view_matrix(FW, FH, ww, wh, zoom, hor, ver)
-        out = torch.empty(ww * wh, dtype=torch.int32, device="cuda")
+        out = torch.empty(max(ww * wh, 1024), dtype=torch.int32, device="cuda")    # (jsp_measure_fill takes 4096 bytes or more: the fill of the 30x17 window is over 4096)
         rate = C.c_double(0)
         torch.cuda.synchronize()
         fills[name] = out
         if not args.kernel_only and lib.jsp_measure_fill(C.c_void_p(out.data_ptr()), C.c_size_t(out.numel() * 4), 50, C.byref(rate), C.c_void_p(handle)) != 0:
             raise RuntimeError(N.last_error())
-        for filt, fname in ((cm.PRESENT_NEAREST, "nearest"), (cm.PRESENT_BILINEAR, "bilinear")):
+        for filt, fname in (((AREA, "area"),) + filters if args.area else filters):
+            what = "present_area" if filt == AREA else "present"
             if args.kernel_only:
-                forms[f"{name} {fname}"] = (lambda out=out, ww=ww, wh=wh, k=k, dx=dx, dy=dy, filt=filt:
-                                            cm.display_present(frame, FW, FH, out, ww, wh, k, dx, dy, filter=filt, stream=handle), {"what": "present"})
+                forms[f"{name} {fname}"] = (lambda out=out, ww=ww, wh=wh, k=k, dx=dx, dy=dy, filt=filt: present(out, ww, wh, k, dx, dy, filt), {"what": what})
                 continue
-            cm.display_present(frame, FW, FH, out, ww, wh, k, dx, dy, filter=filt, stream=handle)
+            present(out, ww, wh, k, dx, dy, filt)
             stream.synchronize()
-            want = vr.present(pixels, FW, FH, ww, wh, k, dx, dy, vr.CANVAS, filt)
-            if not np.array_equal(out.cpu().numpy().view(np.uint32).reshape(wh, ww), want):
+            want = ar.present_area(pixels, FW, FH, ww, wh, k, dx, dy, ar.CANVAS) if filt == AREA else vr.present(pixels, FW, FH, ww, wh, k, dx, dy, vr.CANVAS, filt)
+            if not np.array_equal(out.cpu().numpy().view(np.uint32)[:ww * wh].reshape(wh, ww), want):
                 raise RuntimeError(f"{name} {fname}: the window differs from the reference")
-            rec = {"what": "present", "window": name, "filter": fname, "k": k, "dx": dx, "dy": dy, "window_bytes": ww * wh * 4,
+            rec = {"what": what, "window": name, "filter": fname, "k": k, "dx": dx, "dy": dy, "window_bytes": ww * wh * 4,
                    "bytes_read": bytes_read(ww, wh, k, dx, dy), "fill_gbps_over_window": rate.value}
-            forms[f"{name} {fname}"] = (lambda out=out, ww=ww, wh=wh, k=k, dx=dx, dy=dy, filt=filt:
-                                        cm.display_present(frame, FW, FH, out, ww, wh, k, dx, dy, filter=filt, stream=handle), rec)
+            forms[f"{name} {fname}"] = (lambda out=out, ww=ww, wh=wh, k=k, dx=dx, dy=dy, filt=filt: present(out, ww, wh, k, dx, dy, filt), rec)
     rate = C.c_double(0)
     fills["1920x1080 one-to-one"] = full
     if not args.kernel_only and lib.jsp_measure_fill(C.c_void_p(full.data_ptr()), C.c_size_t(FW * FH * 4), 50, C.byref(rate), C.c_void_p(handle)) != 0:
