@@ -251,6 +251,18 @@ int choose_band_rows(const Geometry& g, int nframes);
 bool iframe_tiles_ok(const Geometry& g);
 int iframe_tile_span(const Geometry& g);   // columns per tile (256 or 512): what set_iframe_layout must be given
 void launch_iframe_tiles(const Geometry& g, const IFrameArgs* d_args, int nframes, int band_rows, hipStream_t stream);
+// What one wave of the tile kernel gets for a band of `rows` rows and spans of `span` columns: the records its window holds and the LDS words of its slice.
+// Per wave: head row + row index + {left pixel, kind counts} per row + record window (4-byte records) + 64 words a row's unconditional read of "the next
+// row's records" may run into; ~4.5 KB keeps 32 waves on a CU.  (Pure arithmetic, here so that the host-stage tests plan windows with the launch's own figure.)
+struct TileWindow { int win_cap; size_t lds_words; };
+inline TileWindow tile_window(int rows, int span) {
+    const size_t fixed = (size_t)span + (((size_t)rows + 1 + 3) & ~size_t(3)) + 2 * (((size_t)rows + 1) & ~size_t(1)) + 64;
+    const size_t budget = 4608 / 4;
+    size_t cap = budget > fixed + 2 ? (budget - fixed - 2) & ~size_t(1) : 0;
+    if (cap < 128) cap = 128;                                  // (a row with more records is scattered from global memory)
+    if (cap > 510) cap = 510;                                  // the kernel fetches a window with four two-record loads per lane (512 records, one may be the pad in front)
+    return {(int)cap, (fixed + cap + 2 + 3) & ~size_t(3)};     // (a multiple of 16 bytes: every wave's head row is read and cleared 16 bytes per lane)
+}
 int iframe_tile_max_band_rows();        // the tallest band one wave's LDS slice can index (taller frames must be cut into bands)
 // band_rows <= 0 or >= Y: one band per frame
 void launch_iframes(const Geometry& g, const IFrameArgs* d_args, int nframes, int band_rows, hipStream_t stream);

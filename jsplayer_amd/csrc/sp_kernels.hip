@@ -907,15 +907,9 @@ TilePlan tile_plan(const Geometry& g, int band_rows) {
     t.rows = rows_in_band(g, band_rows);
     t.span = iframe_tile_span(g);
     t.nspans = (g.X + t.span - 1) / t.span;
-    // per wave: head row + row index + {left pixel, kind counts} per row + record window (4-byte records) + 64 words a row's unconditional read of "the next
-    // row's records" may run into; ~4.5 KB keeps 32 waves on a CU
-    const size_t fixed = (size_t)t.span + (((size_t)t.rows + 1 + 3) & ~size_t(3)) + 2 * (((size_t)t.rows + 1) & ~size_t(1)) + 64;
-    const size_t budget = 4608 / 4;
-    size_t cap = budget > fixed + 2 ? (budget - fixed - 2) & ~size_t(1) : 0;
-    if (cap < 128) cap = 128;                                  // (a row with more records is scattered from global memory)
-    if (cap > 510) cap = 510;                                  // the kernel fetches a window with four two-record loads per lane (512 records, one may be the pad in front)
-    t.win_cap = (int)cap;
-    t.lds = 4 * ((fixed + cap + 2 + 3) & ~size_t(3));          // (a multiple of 16 bytes: every wave's head row is read and cleared 16 bytes per lane)
+    const TileWindow tw = tile_window(t.rows, t.span);         // (sp.h: the window's records and the wave's LDS words)
+    t.win_cap = tw.win_cap;
+    t.lds = 4 * tw.lds_words;
     // A tile's index and left pixels grow with the band (12 bytes per row): a workgroup takes as many neighbouring spans as fit its LDS — eight up to ~550 rows,
     // four at 1080 (one band per frame), one at 4096, the tallest band there is (sp_codec.cpp cuts taller frames).
     size_t waves = kTileGroupLds / t.lds;

@@ -32,6 +32,11 @@ void hs_fetch_tiles(void* p, uint32_t* idx, uint32_t* left) {
     if (idx && !o.tile_idx.empty()) std::memcpy(idx, o.tile_idx.data(), o.tile_idx.size() * 4);
     if (left && !o.left.empty()) std::memcpy(left, o.left.data(), o.left.size() * 4);
 }
+// the tile kernel's window for a band of `rows` rows (sp.h tile_window, what launch_iframe_tiles passes): out = {records, LDS words per wave}
+void hs_tile_window(int rows, int span, uint64_t* out) {
+    const TileWindow w = tile_window(rows, span);
+    out[0] = (uint64_t)w.win_cap; out[1] = w.lds_words;
+}
 size_t hs_seed_words(void* p) { return ((Shim*)p)->out.seeds.size(); }
 void hs_fetch_seeds(void* p, uint32_t* seeds) {
     const FrameOut& o = ((Shim*)p)->out;

@@ -44,8 +44,17 @@ def lib():
         L.hs_seed_words.argtypes = [C.c_void_p]
         L.hs_fetch_seeds.argtypes = [C.c_void_p, C.c_void_p]
         L.hs_set_dst_column.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.hs_tile_window.argtypes = [C.c_int, C.c_int, C.c_void_p]
         _lib = L
     return _lib
+
+
+def tile_window(rows: int, span: int = 256):
+    """(records a window of the tile kernel holds, LDS words of a wave's slice) for bands of `rows` rows: the product's own
+    arithmetic (sp.h tile_window), which launch_iframe_tiles passes to the kernel."""
+    out = np.zeros(2, dtype=np.uint64)
+    lib().hs_tile_window(rows, span, out.ctypes.data)
+    return int(out[0]), int(out[1])
 
 
 class HostStage:
@@ -140,9 +149,37 @@ def _add_bytes(u, d):
     return ((((u & 0x00FF00FF) + (d & 0x00FF00FF)) & 0x00FF00FF) | (((u & 0xFF00) + (d & 0xFF00)) & 0xFF00)).astype(np.uint32)
 
 
-def expand_iframe(desc, X, Y):
+def _add_carry(u, d):
+    return ((u.astype(np.uint32) + (d & 0xFFFFFF)) & 0xFFFFFF).astype(np.uint32)
+
+
+# Named faults for the `fault` argument of expand_iframe / expand_iframe_tiles: what a kernel with that one mistake would compute.
+# (Off by default; the directed key pictures must notice every one: tests/test_sp_key_pictures_cpu.py.)
+ROW_FAULTS = ("above_left_as_above", "left0_zero", "seed_word0_zero", "seed_last_zero", "byte_carry")
+TILE_FAULTS = ("above_left_as_above", "left0_zero", "byte_carry", "const_plus1_dropped", "const_count_off_by_one", "repeat_ignored", "past_64_dropped")
+MAX_WINDOW_ROWS = 62           # restated from sp_iframe_tile_kernel (plan_and_fetch): a window's index entries live one per lane
+
+
+def plan_windows(offsets, cap):
+    """A RESTATEMENT of plan_and_fetch (sp_iframe_tile_kernel): the windows of a tile whose rows' records start at offsets[0..R] (R the
+    end): rows are added while the records from the window's first stay within `cap`, 62 rows at most; a first row that does not fit
+    alone is a window of its own, scattered from memory (`direct`).  -> [(first row, rows, direct)]"""
+    rows, out, f = len(offsets) - 1, [], 0
+    while f < rows:
+        n = 0
+        while n < min(MAX_WINDOW_ROWS, rows - f) and offsets[f + n + 1] - offsets[f] <= cap:
+            n += 1
+        out.append((f, max(n, 1), n == 0))
+        f += max(n, 1)
+    return out
+
+
+def expand_iframe(desc, X, Y, fault=None):
     """What sp_iframe_rows_kernel computes from the run table (row wavefront).  With band seeds every
-    band is expanded on its own, from nothing but its seed row — as its workgroup does."""
+    band is expanded on its own, from nothing but its seed row — as its workgroup does.
+    `fault`: one of ROW_FAULTS, the same with that mistake built in."""
+    assert fault is None or fault in ROW_FAULTS, fault
+    add = _add_carry if fault == "byte_carry" else _add_bytes
     if desc["kind"] == KIND_FLAT:
         return np.full(X * Y, desc["flat_colour"], dtype=np.uint32)
     runs, rows = desc["runs"], desc["rows"]
@@ -165,22 +202,27 @@ def expand_iframe(desc, X, Y):
             left = np.empty(X, dtype=np.uint32)
             left[1:] = up[:-1]
             if band_first:
-                left[0] = sd[0]
+                left[0] = 0 if fault == "seed_word0_zero" else sd[0]
             elif band_rows > 0 and y % band_rows == 1 and y > 1:
-                left[0] = seeds[(y // band_rows - 1) * (X + 1) + X]      # last pixel of the seed row
+                left[0] = 0 if fault == "seed_last_zero" else seeds[(y // band_rows - 1) * (X + 1) + X]      # last pixel of the seed row
             else:
                 left[0] = out[y - 2, X - 1] if y >= 2 else 0
-            v = np.where(kind == RUN_ABOVE, _add_bytes(up, val), v)
-            v = np.where(kind == RUN_ABOVE_LEFT, left, v)
+            if fault == "left0_zero":
+                left[0] = 0
+            v = np.where(kind == RUN_ABOVE, add(up, val), v)
+            v = np.where(kind == RUN_ABOVE_LEFT, up if fault == "above_left_as_above" else left, v)
         else:
             v = np.where(kind == RUN_CONST, v, 0)
         out[y] = v
     return out.reshape(-1)
 
 
-def expand_iframe_tiles(desc, X, Y):
+def expand_iframe_tiles(desc, X, Y, fault=None):
     """What sp_iframe_tile_kernel computes: every tile (band x 256-column span) on its own, from its records,
-    the seed row above its band and its column of left pixels — nothing another tile produced."""
+    the seed row above its band and its column of left pixels — nothing another tile produced.
+    `fault`: one of TILE_FAULTS, the same with that mistake built in."""
+    assert fault is None or fault in TILE_FAULTS, fault
+    add = _add_carry if fault == "byte_carry" else _add_bytes
     if desc["kind"] == KIND_FLAT:
         return np.full(X * Y, desc["flat_colour"], dtype=np.uint32)
     span, idx, seeds = desc["span_px"], desc["tile_idx"], desc["seeds"]
@@ -196,18 +238,29 @@ def expand_iframe_tiles(desc, X, Y):
             t = b * nspans + s
             xs, xe = s * span, min(X, (s + 1) * span)
             up = seeds[(b - 1) * (X + 1) + 1 + xs:(b - 1) * (X + 1) + 1 + xe].copy() if b > 0 else np.zeros(xe - xs, np.uint32)
-            for r in range(min(rows_per, Y - b * rows_per)):
+            rows_here = min(rows_per, Y - b * rows_per)
+            if fault == "past_64_dropped":             # a window's first row is scattered by a loop of its own; the rows behind it 64 records at a time
+                offs = [int(v) & 0x7FFFFFFF for v in idx[t * (rows_per + 1):t * (rows_per + 1) + rows_here + 1]]
+                firsts = {f for f, _, _ in plan_windows(offs, tile_window(rows_per, span)[0])}
+            for r in range(rows_here):
                 y = b * rows_per + r
                 e = int(idx[t * (rows_per + 1) + r])
                 lo, hi = e & 0x7FFFFFFF, int(idx[t * (rows_per + 1) + r + 1]) & 0x7FFFFFFF
                 if e >> 31:        # kRowRepeats: no records of its own, the words of the row above stay in force
                     assert r > 0 and lo == hi, (b, s, r)
+                    if fault == "repeat_ignored":      # the cleared head row: word 0 everywhere, which is "the pixel above, plus nothing"
+                        cols, vals, kinds = np.zeros(1, np.int64), np.zeros(1, np.uint32), np.full(1, RUN_ABOVE, np.uint32)
                 else:
                     rec = recs[lo:hi]
                     covered[lo:hi] = True
                     counts = int(left[t * rows_per + r, 1])
                     nc, na = counts & 0xFFFF, counts >> 16
                     assert nc + na <= len(rec), (b, s, r)
+                    if fault == "past_64_dropped" and r not in firsts and len(rec) > 64:
+                        rec, nc = rec[:64], min(nc, 64)
+                        na = min(na, 64 - nc)
+                    if fault == "const_count_off_by_one" and nc > 0:   # (the kernel's second count is the sum of the two: both borders move)
+                        nc -= 1
                     # a record's kind is its place among the row's records: constants, then "above", then "above-left"
                     kinds_sorted = np.concatenate([np.full(nc, RUN_CONST), np.full(na, RUN_ABOVE), np.full(len(rec) - nc - na, TILE_ABOVE_LEFT)]).astype(np.uint32)
                     order = np.argsort(rec >> 24, kind="stable")
@@ -215,18 +268,22 @@ def expand_iframe_tiles(desc, X, Y):
                     vals = (rec & 0xFFFFFF)[order]
                     kinds = kinds_sorted[order]
                     for part in (slice(0, nc), slice(nc, nc + na), slice(nc + na, len(rec))):   # inside a kind the columns ascend
-                        assert np.all(np.diff((rec[part] >> 24).astype(np.int64)) > 0), (b, s, r)
-                assert len(rec) and cols[0] == 0 and np.all(np.diff(cols) > 0) and cols[-1] < xe - xs, (b, s, r)
-                k = np.searchsorted(cols, np.arange(xe - xs), side="right") - 1
+                        assert fault is not None or np.all(np.diff((rec[part] >> 24).astype(np.int64)) > 0), (b, s, r)
+                assert len(rec) and (cols[0] == 0 or fault == "past_64_dropped") and np.all(np.diff(cols) > 0) and cols[-1] < xe - xs, (b, s, r)
+                k = np.maximum(np.searchsorted(cols, np.arange(xe - xs), side="right") - 1, 0)
                 kind, val = kinds[k], vals[k]
                 lft = np.empty(xe - xs, np.uint32)
                 lft[1:] = up[:-1]
-                lft[0] = left[t * rows_per + r, 0]
+                lft[0] = 0 if fault == "left0_zero" else left[t * rows_per + r, 0]
+                if fault == "above_left_as_above":
+                    lft = up
                 # every kind is "start value + record value, byte by byte": the pixel above, the pixel above-left (value 0), or 0xFFFFFF for a
                 # constant, whose record carries the colour plus one in every byte (sp.h: tile_record32)
                 start = np.where(kind == RUN_ABOVE, up, np.where(kind == TILE_ABOVE_LEFT, lft, np.uint32(0xFFFFFF)))
-                assert np.all(val[kind == TILE_ABOVE_LEFT] == 0)
-                v = _add_bytes(start, val).astype(np.uint32)
+                assert fault is not None or np.all(val[kind == TILE_ABOVE_LEFT] == 0)
+                if fault == "const_plus1_dropped":     # the record as if it carried the colour itself
+                    val = np.where(kind == RUN_CONST, _add_bytes(val, np.uint32(0xFFFFFF)), val)
+                v = add(start, val).astype(np.uint32)
                 out[y, xs:xe] = v
                 up = v
     assert covered[:int(idx[-1]) & 0x7FFFFFFF].all()
