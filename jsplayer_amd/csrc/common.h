@@ -72,6 +72,7 @@ inline double now_ms() {
 struct DeviceBuffer {
     void* p = nullptr;
     size_t cap = 0;
+    template <class T> T* as() const { return static_cast<T*>(p); }
     void reserve(size_t n) {
         if (n <= cap) return;
         if (p) JSP_HIP(hipFree(p));
@@ -96,6 +97,7 @@ struct DeviceBuffer {
 struct PinnedBuffer {
     void* p = nullptr;
     size_t cap = 0;
+    template <class T> T* as() const { return static_cast<T*>(p); }
     void reserve(size_t n) {
         if (n <= cap) return;
         if (p) JSP_HIP(hipHostFree(p));

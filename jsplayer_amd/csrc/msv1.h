@@ -73,7 +73,7 @@ struct Msv1FrameInfo {    // counters the parse kernels return per frame
     uint32_t pad[3];
 };
 uint32_t msv1_parse_tile_bytes();    // 16 KiB: staged batches (frames start on tile boundaries of the stream buffer)
-uint32_t msv1_small_tile_bytes();    // 8 KiB: `small_tiles` launches (one frame per launch: modes 1, 2, 3 of msv1_launch_fused)
+uint32_t msv1_small_tile_bytes();    // 8 KiB: `small_tiles` launches (one frame per launch: the scout, decode and group launchers below)
 void msv1_launch_parse(const Msv1Geometry& geo, const uint8_t* d_stream, const Msv1ParseFrame* d_frames, int nframes,
                        const uint32_t* d_tile_frame, int ntiles, int max_tiles_per_frame, uint32_t* d_tile_tab,
                        uint32_t* d_tile_entry, uint32_t* d_tile_block0, uint32_t* d_desc, Msv1FrameInfo* d_info,
@@ -97,40 +97,92 @@ struct alignas(16) Msv1TileRec {
     uint64_t pad;
 };
 static_assert(sizeof(Msv1TileRec) == 64, "one record = 64 bytes");
-// Tiles [tile0, tile0 + ntiles) in one launch (no descriptor table).  `d_agg`: 9 words per tile of the batch, zeroed
-// once; `epoch` (> 0) must differ from launch to launch on the same `d_agg`.  *d_fault becomes non-zero if a tile
-// gave up waiting for the tables of the tiles before it (the caller reports the batch as failed).
-// mode 1 / 2 (one frame per launch, `d_info` != null): the scout pass that reports what the descriptor path's parse would
-// have told the host (Msv1AsyncInfo), then the decode pass, which does nothing when d_info->flags & bad_mask; the
-// frame's significance word is d_info->signif; *d_poison (one word per codec instance) is set by a vetoed decode pass
-// and vetoes every later one until the host clears it.  mode 0: the batch form.
+// msv1_fused_kernel is launched in four forms, each with a launcher of its own below: the batch form writing pixels or block tables, the
+// scout + decode pair and the one-launch form of the asynchronous per-frame path.  In all of them the tiles publish where the code chain stands
+// in `agg`: 9 words per tile, zeroed once; `epoch` (> 0) must differ from launch to launch on the same `agg`.
+constexpr size_t MSV1_AGG_PUBLISHED = 9;
+// A staged batch's `agg` has room behind the published words of all its tiles for 8 counters per tile, and its fault word (two words) for 64 bytes
+// more: only a lab build's phase clocks use either (tools/lab/hooks_clocks/msv1_fused_hooks.h).
+constexpr size_t MSV1_AGG_LAB_CLOCKS = 8;
+constexpr size_t MSV1_SYNC_BYTES = 2 * sizeof(uint32_t) + 64;
+
+// ---- the batch forms: tiles [tile0, tile0 + ntiles) of a staged batch in one launch, one record per tile ----
+// *fault becomes non-zero if a tile gave up waiting for the tiles before it (the caller reports the batch as failed).
+struct Msv1FusedBatch {
+    const uint8_t* stream = nullptr;     // the batch's stream buffer
+    const Msv1TileRec* recs = nullptr;   // device records, in launch order
+    const int32_t* palette = nullptr;
+    unsigned long long* agg = nullptr;   // published tile words
+    uint32_t epoch = 0;
+    uint32_t tile0 = 0;
+    int ntiles = 0;
+    uint32_t* fault = nullptr;
+    uint32_t agg_tiles = 0;              // tiles `agg` was sized for.  Only a lab build reads it: its phase clocks keep their counters behind that
+                                         // many tiles' published words
+};
+// Pixels straight from the stream bytes, no descriptor table (kernel mode 0): 16 KiB tiles, frames laid out on 16 KiB boundaries.
+void msv1_launch_fused_pixels(const Msv1Geometry& geo, const Msv1FusedBatch& batch, hipStream_t stream);
+// Nothing is rebuilt (kernel mode 4): every tile writes its blocks' entries of the frame's descriptor table (the record's `dst` points at it) —
+// the on-GPU descriptor parse in ONE launch, for the batches whose frames depend on each other.  8 KiB tiles: the records say where each begins.
+void msv1_launch_fused_tables(const Msv1Geometry& geo, const Msv1FusedBatch& batch, hipStream_t stream);
+
+// ---- the asynchronous per-frame path: what a frame's launches report ----
 constexpr uint32_t MSV1_ASYNC_SHORT = 1u;     // the stream does not cover every block: the host parser has to settle it
 constexpr uint32_t MSV1_ASYNC_S1 = 2u;        // a coded block lies in a significant block row (MSVideo1.hx:187-194)
 constexpr uint32_t MSV1_ASYNC_END = 4u;       // an 8-bit end-of-data marker sits on the code chain
 constexpr uint32_t MSV1_ASYNC_SKIPCODE = 8u;  // a skip code sits on the code chain
-constexpr uint32_t MSV1_ASYNC_STUCK = 16u;    // mode 3: the frame's tiles did not all report in time (the GPU is shared with something that
+constexpr uint32_t MSV1_ASYNC_STUCK = 16u;    // one-launch form: the frame's tiles did not all report in time (the GPU is shared with something that
                                               // keeps them from being resident together): the host path settles the frame
 struct Msv1AsyncInfo {
     uint32_t flags;
     uint32_t signif;   // stage-2 significance word (OR-ed with 1 when a compared pixel differs)
     uint32_t fault;    // look-back gave up
-    uint32_t arrived;  // mode 3: workgroups whose findings are in `flags` / that have written their last pixel; both run
+    uint32_t arrived;  // one-launch form: workgroups whose findings are in `flags` / that have written their last pixel; both run
     uint32_t finished; //         on from launch to launch (see `want`)
-    uint32_t verdict;  // mode 3: 0 undecided, MSV1_VERDICT_GO / _VETO — set ONCE per launch (compare-and-swap), obeyed by every tile
+    uint32_t verdict;  // one-launch form: 0 undecided, MSV1_VERDICT_GO / _VETO — set ONCE per launch (compare-and-swap), obeyed by every tile
     uint32_t pad[2];
 };
 constexpr uint32_t MSV1_VERDICT_GO = 1u, MSV1_VERDICT_VETO = 2u;
-constexpr uint32_t MSV1_LAB_DEAF = 0x80000000u;   // in `bad_mask` (tests): mode 3 tiles never see all reports in — the verdict is the time-out's
-// mode 4 (batch form): nothing is rebuilt; every tile writes its blocks' entries of the frame's descriptor table (the record's
-// `dst` points at it) — the on-GPU descriptor parse in ONE launch, for the batches whose frames depend on each other.
-// mode 3 (one frame per launch, at most MSV1_MERGED_MAX_TILES tiles): scout and decode in ONE launch — every tile parses
-// and reports, waits until all `ntiles` reports are in (`want` = the value of d_info->arrived / finished once this launch is
-// through), and only then writes, or does not.  All tiles share `*one_rec` (k = the tile's index); the last workgroup copies
-// flags / signif / fault to `h_info` (pinned host memory) and clears them in d_info.  `d_stream` may be pinned HOST memory
-// (any alignment, nothing read past the frame's last byte): each tile reads its bytes once, over the bus, and leaves a copy
-// in `d_keep` (HBM, the frame's size rounded up to 16 bytes).
+constexpr uint32_t MSV1_LAB_DEAF = 0x80000000u;   // in `bad_mask` (tests): one-launch tiles never see all reports in — the verdict is the time-out's
+// One-frame launches of a small frame (an inter frame, an 8-bit frame: a few hundred KB) use 8 KiB tiles — `small_tiles` —: twice the
+// workgroups, half the serial work in each; the kernel's time is a chain of dependent steps per tile, and such a launch has the
+// GPU to itself.  (1080p inter frames with 70 % skipped blocks: 28.8 -> 37.9 Gpixels/s on one stream, 8-bit key frames 42.4 -> 52.8;
+// frames of a megabyte gain nothing on one stream and lose a fifth on sixteen: they keep 16 KiB tiles — with their uploads gone, jsp_prefetch,
+// they lose an eighth on one stream as well: profiles/r04_msv1_small_tiles_e2e.txt.)
+constexpr size_t MSV1_SMALL_TILE_FRAME_BYTES = 640 * 1024;
+
+// What a frame's launches have in common with those of the frames around it:
+struct Msv1AsyncShared {
+    const int32_t* palette = nullptr;
+    int insignificant_blocks = 0;
+    uint32_t* poison = nullptr;          // one word per codec instance: set by a vetoed decode, it vetoes every later one until the host clears it
+    bool small_tiles = false;
+};
+
+// ---- scout + decode (kernel modes 1, 2): one frame in two launches, one record per tile ----
+// The scout pass reports what the descriptor path's parse would have told the host (info->flags), then the decode pass, which does nothing when
+// info->flags & bad_mask; the frame's significance word is info->signif, its fault word info->fault.
+struct Msv1FusedPass {
+    const uint8_t* stream = nullptr;
+    const Msv1TileRec* recs = nullptr;
+    unsigned long long* agg = nullptr;
+    uint32_t epoch = 0;                  // (a new one for each of the two passes)
+    int ntiles = 0;
+    Msv1AsyncInfo* info = nullptr;       // the report, in device memory
+    uint32_t bad_mask = 0;
+    Msv1AsyncShared shared;
+};
+void msv1_launch_fused_scout(const Msv1Geometry& geo, const Msv1FusedPass& pass, hipStream_t stream);
+void msv1_launch_fused_decode(const Msv1Geometry& geo, const Msv1FusedPass& pass, hipStream_t stream);
+
+// ---- one launch per group of frames (kernel mode 3; each frame at most MSV1_MERGED_MAX_TILES tiles) ----
+// Scout and decode in ONE launch — every tile parses and reports, waits until all of its frame's reports are in (`want` = the value of
+// info->arrived / finished once this launch is through), and only then writes, or does not.  All tiles of a frame share `rec` (k = the tile's
+// index, rec.ntiles = the frame's tiles); the last workgroup copies flags / signif / fault to `host_info` (pinned host memory) and clears them in
+// `info`.  `stream` may be pinned HOST memory (any alignment, nothing read past the frame's last byte): each tile reads its bytes once, over the
+// bus, and leaves a copy in `keep` (HBM, the frame's size rounded up to 16 bytes; null: none is kept).
 constexpr int MSV1_MERGED_MAX_TILES = 128;
-// mode 3 with SEVERAL frames in one launch: the frames submitted right behind the first one (up to 3) ride along — workgroups
+// SEVERAL frames in one launch: the frames submitted right behind the first one (up to 3) ride along — workgroups
 // [0, f[0].first_wg) are the first frame's tiles, [f[i].first_wg, f[i].first_wg + f[i].rec.ntiles) those of rider i.  All frames load, parse
 // and reach their verdicts side by side (none of that touches a pixel); a rider's tiles then wait until every tile of the frame in front
 // has finished (that frame's `finished` has reached its `want`) before they write — a frame may copy from the pixels of the one before it
@@ -151,18 +203,10 @@ struct Msv1Riders {
     uint32_t count = 0, pad = 0;
     Msv1Rider f[MSV1_MAX_RIDERS];
 };
-// One-frame launches of a small frame (an inter frame, an 8-bit frame: a few hundred KB) use 8 KiB tiles — `small_tiles` —: twice the
-// workgroups, half the serial work in each; the kernel's time is a chain of dependent steps per tile, and such a launch has the
-// GPU to itself.  (1080p inter frames with 70 % skipped blocks: 28.8 -> 37.9 Gpixels/s on one stream, 8-bit key frames 42.4 -> 52.8;
-// frames of a megabyte gain nothing on one stream and lose a fifth on sixteen: they keep 16 KiB tiles — with their uploads gone, jsp_prefetch,
-// they lose an eighth on one stream as well: profiles/r04_msv1_small_tiles_e2e.txt.)
-constexpr size_t MSV1_SMALL_TILE_FRAME_BYTES = 640 * 1024;
-void msv1_launch_fused(const Msv1Geometry& geo, const uint8_t* d_stream, const Msv1TileRec* d_recs, const int32_t* d_palette,
-                       unsigned long long* d_agg, uint32_t epoch, uint32_t tile0, int ntiles, uint32_t* d_fault,
-                       hipStream_t stream, Msv1AsyncInfo* d_info = nullptr, int insignificant_blocks = 0, int mode = 0,
-                       uint32_t bad_mask = 0, uint32_t* d_poison = nullptr, const Msv1TileRec* one_rec = nullptr,
-                       Msv1AsyncInfo* h_info = nullptr, uint32_t want = 0, uint8_t* d_keep = nullptr, bool small_tiles = false,
-                       const Msv1Riders* riders = nullptr);   // (mode 3 only: more frames in the same launch; first_wg is filled in here)
+// A frame of such a launch as its caller describes it: the first one like those behind it (`first_wg` is the launcher's to fill in).
+using Msv1GroupFrame = Msv1Rider;
+// frames[0 .. nframes), 1 <= nframes <= 1 + MSV1_MAX_RIDERS, in the order they were submitted.
+void msv1_launch_fused_group(const Msv1Geometry& geo, const Msv1GroupFrame* frames, int nframes, const Msv1AsyncShared& shared, hipStream_t stream);
 
 // Kernel launchers (msv1_kernels.hip).  All asynchronous on `stream`.
 void msv1_launch_blocks(const Msv1Geometry& geo, const uint8_t* d_stream, const uint32_t* d_desc,

@@ -21,6 +21,9 @@ namespace {
 // Published tile tables carry the launch's epoch; 0 is what freshly zeroed memory reads as, so the counter skips it when it wraps.
 inline uint32_t next_epoch(uint32_t& e) { if (++e == 0) ++e; return e; }
 
+// Bytes of a staged batch's published tile words (d_agg, d_agg_emit), the lab build's counters behind them included (msv1.h).
+inline size_t agg_bytes(size_t tiles) { return sizeof(unsigned long long) * (MSV1_AGG_PUBLISHED + MSV1_AGG_LAB_CLOCKS) * std::max<size_t>(tiles, 1); }
+
 // One tile's record for msv1_fused_kernel (msv1.h): tile k of `ntiles` (the first is number `first_tile` of the launch's published words), `tile_bytes`
 // each, of the frame whose bytes start at `beg` of the stream buffer; `even_end`: the end without an odd last byte, `data_end`: of what may be read.
 inline Msv1TileRec tile_rec(uint32_t beg, uint32_t even_end, uint32_t data_end, uint32_t k, uint32_t tile_bytes, uint32_t first_tile, uint32_t ntiles,
@@ -131,7 +134,7 @@ struct Msv1Staged : jsp_staged {
         bool made = false;
         void drop() { wide.release(); recs.release(); made = false; }
     } sets[2];
-    uint32_t* wide_tables(int i) { return static_cast<uint32_t*>(i == 0 ? d_desc.p : sets[i].wide.p); }
+    uint32_t* wide_tables(int i) { return (i == 0 ? d_desc : sets[i].wide).as<uint32_t>(); }
     void make_set(int i, hipStream_t stream) {
         TableSet& t = sets[i];
         if (t.made) return;
@@ -141,7 +144,7 @@ struct Msv1Staged : jsp_staged {
             const size_t table_bytes = sizeof(uint32_t) * (size_t)std::max(geo.nblocks, 1) * (size_t)nframes;
             t.wide.reserve(table_bytes);
             JSP_HIP(hipMemcpyAsync(t.wide.p, d_desc.p, table_bytes, hipMemcpyDeviceToDevice, stream));
-            for (auto& r : recs) r.dst = reinterpret_cast<int32_t*>(static_cast<uint32_t*>(t.wide.p) + (reinterpret_cast<uint32_t*>(r.dst) - static_cast<uint32_t*>(d_desc.p)));
+            for (auto& r : recs) r.dst = reinterpret_cast<int32_t*>(t.wide.as<uint32_t>() + (reinterpret_cast<uint32_t*>(r.dst) - d_desc.as<uint32_t>()));
             t.recs.reserve(sizeof(Msv1TileRec) * std::max<size_t>(recs.size(), 1));
             JSP_HIP(hipMemcpy(t.recs.p, recs.data(), sizeof(Msv1TileRec) * recs.size(), hipMemcpyHostToDevice));
         }
@@ -152,9 +155,15 @@ struct Msv1Staged : jsp_staged {
         const TableSet& t = sets[set];
         for (uint32_t i : scrub)
             JSP_HIP(hipMemsetAsync(wide_tables(set) + (size_t)i * (size_t)std::max(geo.nblocks, 1), 0xEE, sizeof(uint32_t) * (size_t)geo.nblocks, on));
-        msv1_launch_fused(geo, static_cast<const uint8_t*>(d_stream.p), static_cast<const Msv1TileRec*>(t.recs.p ? t.recs.p : d_recs_emit.p), d_palette,
-                          static_cast<unsigned long long*>(d_agg_emit.p), next_epoch(epoch), 0, ntiles_emit, static_cast<uint32_t*>(d_sync.p), on,
-                          nullptr, 0, 4, 0, nullptr, nullptr, nullptr, (uint32_t)ntiles_emit, nullptr, /*small_tiles=*/true);   // (`want`: where a lab build's phase clocks go)
+        msv1_launch_fused_tables(geo, fused_batch(t.recs.p ? t.recs : d_recs_emit, d_agg_emit, ntiles_emit, 0, ntiles_emit), on);
+    }
+    // A launch of one of the kernel's batch forms over tiles [tile0, tile0 + n) of `recs`, which publish in `agg` (sized for `agg_tiles` tiles).
+    Msv1FusedBatch fused_batch(const DeviceBuffer& recs, const DeviceBuffer& agg, int agg_tiles, uint32_t tile0, int n) {
+        Msv1FusedBatch b;
+        b.stream = d_stream.as<const uint8_t>(); b.recs = recs.as<const Msv1TileRec>(); b.palette = d_palette;
+        b.agg = agg.as<unsigned long long>();    b.agg_tiles = (uint32_t)agg_tiles;     b.epoch = next_epoch(epoch);
+        b.tile0 = tile0;                         b.ntiles = n;                          b.fault = d_sync.as<uint32_t>();
+        return b;
     }
     void drop_sets() { for (auto& t : sets) t.drop(); }
     void quiesce_side() {              // nothing of this batch is left running beside the stream (before its buffers are reused or freed)
@@ -169,11 +178,9 @@ struct Msv1Staged : jsp_staged {
     }
 
     void launch_parse(hipStream_t stream) {
-        msv1_launch_parse(geo, static_cast<const uint8_t*>(d_stream.p), static_cast<const Msv1ParseFrame*>(d_pframes.p),
-                          nframes, static_cast<const uint32_t*>(d_tile_frame.p), ntiles, max_tiles,
-                          static_cast<uint32_t*>(d_tile_tab.p), static_cast<uint32_t*>(d_tile_entry.p),
-                          static_cast<uint32_t*>(d_tile_block0.p), static_cast<uint32_t*>(d_desc.p),
-                          static_cast<Msv1FrameInfo*>(d_info.p), insignificant_blocks, stream);
+        msv1_launch_parse(geo, d_stream.as<const uint8_t>(), d_pframes.as<const Msv1ParseFrame>(), nframes, d_tile_frame.as<const uint32_t>(), ntiles, max_tiles,
+                          d_tile_tab.as<uint32_t>(), d_tile_entry.as<uint32_t>(), d_tile_block0.as<uint32_t>(), d_desc.as<uint32_t>(), d_info.as<Msv1FrameInfo>(),
+                          insignificant_blocks, stream);
     }
 
     void decode(hipStream_t stream) override {
@@ -188,7 +195,7 @@ struct Msv1Staged : jsp_staged {
             if (run_ahead && ahead_valid) JSP_HIP(hipStreamWaitEvent(stream, ev_tables, 0));   // written beside the replay before this one
             else launch_table_parse(cur_set, stream);
         }
-        const uint32_t* tables = replay ? wide_tables(cur_set) : static_cast<const uint32_t*>(d_desc.p);
+        const uint32_t* tables = replay ? wide_tables(cur_set) : d_desc.as<const uint32_t>();
         if (run_ahead && decoded) {
             // the next replay's tables, into the other set, beside the launches below: the other set's last readers (the replay before this one) and the
             // last table-writing launch (it shares the published tile words and the fault word) are all in front of `ev_fork` on the stream
@@ -260,7 +267,7 @@ struct Msv1Staged : jsp_staged {
     // ---- stage(), phase 6: what the plan launches and moves (info.*, kernels, needs_desc, any_fused) ----
     void account(const StagePlan& plan) {
         const int nf = nframes;
-        const auto* h_frames = static_cast<const Msv1FrameArgs*>(this->h_frames.p);
+        const auto* h_frames = this->h_frames.as<const Msv1FrameArgs>();
         need_signif = false;
         for (int v : significant) need_signif |= v < 0;
         info.frames = nf;
@@ -311,25 +318,25 @@ struct Msv1Staged : jsp_staged {
     // ---- stage(), phase 7: what msv1_fused_kernel needs to know about every tile, for the launches that write pixels and the one that writes tables ----
     void build_tile_records(const std::vector<jsp_frame_in>& frames, const StagePlan& plan, bool scrub_tables, hipStream_t stream) {
         if (!any_fused && !needs_desc) return;
-        d_agg.reserve(sizeof(unsigned long long) * (9 + 8) * (size_t)std::max(ntiles, 1));   // (+ 8 per tile: the lab build's phase clocks)
-        d_sync.reserve(2 * sizeof(uint32_t) + 64);   // (+ room for the lab build's phase clocks)
+        d_agg.reserve(agg_bytes((size_t)ntiles));
+        d_sync.reserve(MSV1_SYNC_BYTES);
         h_fault.reserve(sizeof(uint32_t));
-        *static_cast<uint32_t*>(h_fault.p) = 0;
+        *h_fault.as<uint32_t>() = 0;
         epoch = 0;
         build_pixel_records(plan, stream);
         if (needs_desc) build_table_records(frames, plan, scrub_tables, stream);
         // published tile tables carry the launch epoch (first launch: 1), so stale words must read as epoch 0
-        JSP_HIP(hipMemsetAsync(d_agg.p, 0, sizeof(unsigned long long) * (9 + 8) * (size_t)std::max(ntiles, 1), stream));
-        JSP_HIP(hipMemsetAsync(d_sync.p, 0, 2 * sizeof(uint32_t) + 64, stream));   // the fault word
+        JSP_HIP(hipMemsetAsync(d_agg.p, 0, agg_bytes((size_t)ntiles), stream));
+        JSP_HIP(hipMemsetAsync(d_sync.p, 0, MSV1_SYNC_BYTES, stream));   // the fault word
     }
     // one record per 16 KiB tile, in stream order; then in launch order inside every fused launch
     void build_pixel_records(const StagePlan& plan, hipStream_t stream) {
         const int nf = nframes;
         const Msv1ParseFrame* h_pf = plan.h_pf;
-        const auto* h_frames = static_cast<const Msv1FrameArgs*>(this->h_frames.p);
+        const auto* h_frames = this->h_frames.as<const Msv1FrameArgs>();
         h_recs.reserve(sizeof(Msv1TileRec) * (size_t)std::max(ntiles, 1));
         d_recs.reserve(sizeof(Msv1TileRec) * (size_t)std::max(ntiles, 1));
-        auto* recs = static_cast<Msv1TileRec*>(h_recs.p);
+        auto* recs = h_recs.as<Msv1TileRec>();
         std::vector<uint32_t> nt16((size_t)nf);
         for (int i = 0; i < nf; ++i) {
             nt16[i] = h_pf[i].ntiles;
@@ -360,7 +367,7 @@ struct Msv1Staged : jsp_staged {
     void build_table_records(const std::vector<jsp_frame_in>& frames, const StagePlan& plan, bool scrub_tables, hipStream_t stream) {
         const int nf = nframes;
         const Msv1ParseFrame* h_pf = plan.h_pf;
-        const auto* h_frames = static_cast<const Msv1FrameArgs*>(this->h_frames.p);
+        const auto* h_frames = this->h_frames.as<const Msv1FrameArgs>();
         const size_t nblk = (size_t)std::max(geo.nblocks, 1);
         const uint32_t tile8 = msv1_small_tile_bytes();
         std::vector<uint32_t> first8((size_t)nf), n8((size_t)nf);
@@ -373,8 +380,8 @@ struct Msv1Staged : jsp_staged {
         ntiles_emit = (int)nt8;
         h_recs_emit.reserve(sizeof(Msv1TileRec) * (size_t)std::max<uint32_t>(nt8, 1));
         d_recs_emit.reserve(sizeof(Msv1TileRec) * (size_t)std::max<uint32_t>(nt8, 1));
-        d_agg_emit.reserve(sizeof(unsigned long long) * (9 + 8) * (size_t)std::max<uint32_t>(nt8, 1));
-        auto* er = static_cast<Msv1TileRec*>(h_recs_emit.p);
+        d_agg_emit.reserve(agg_bytes(nt8));
+        auto* er = h_recs_emit.as<Msv1TileRec>();
         std::vector<uint8_t> in_fused(nf, 0);
         for (const auto& g : groups)
             if (g.fused) std::fill(in_fused.begin() + g.first, in_fused.begin() + g.first + g.count, 1);
@@ -382,11 +389,11 @@ struct Msv1Staged : jsp_staged {
         uint32_t o = 0;
         staggered_tile_order(0, nf, n8, MSV1_TILE_STAGGER, [&](int i, uint32_t k) {
             er[o++] = tile_rec(h_pf[i].beg, h_pf[i].end, geo.bits == 16 ? h_pf[i].end : h_frames[i].stream_end, k, tile8, first8[i], n8[i],
-                               reinterpret_cast<int32_t*>(static_cast<uint32_t*>(d_desc.p) + (size_t)i * nblk), nullptr, h_frames[i].signif, 0xFFFFFFFFu,
+                               reinterpret_cast<int32_t*>(d_desc.as<uint32_t>() + (size_t)i * nblk), nullptr, h_frames[i].signif, 0xFFFFFFFFu,
                                (h_pf[i].host_parsed || in_fused[i]) ? MSV1_TILE_SKIP : 0u);
         });
         JSP_HIP(hipMemcpyAsync(d_recs_emit.p, er, sizeof(Msv1TileRec) * (size_t)nt8, hipMemcpyHostToDevice, stream));
-        JSP_HIP(hipMemsetAsync(d_agg_emit.p, 0, sizeof(unsigned long long) * (9 + 8) * (size_t)std::max<uint32_t>(nt8, 1), stream));
+        JSP_HIP(hipMemsetAsync(d_agg_emit.p, 0, agg_bytes(nt8), stream));
         scrub.clear();
         if (scrub_tables)
             for (int i = 0; i < nf; ++i)
@@ -397,19 +404,17 @@ struct Msv1Staged : jsp_staged {
     // planned as fused launches go straight from the stream bytes; else (the look-back fall-back) they paint from the tables like the others.
     void launch_groups(const uint32_t* tables, bool fused, hipStream_t stream) {
         if (need_signif) JSP_HIP(hipMemsetAsync(d_signif.p, 0, sizeof(uint32_t) * nframes, stream));
-        const auto* frames = static_cast<const Msv1FrameArgs*>(d_frames.p);
+        const auto* frames = d_frames.as<const Msv1FrameArgs>();
         for (const Group& g : groups) {
             if (g.fused && fused) {
-                const auto* pf = static_cast<const Msv1ParseFrame*>(h_pframes.p);
+                const auto* pf = h_pframes.as<const Msv1ParseFrame>();
                 const uint32_t tile0 = pf[g.first].first_tile;
                 const Msv1ParseFrame& last = pf[g.first + g.count - 1];
-                msv1_launch_fused(geo, static_cast<const uint8_t*>(d_stream.p), static_cast<const Msv1TileRec*>(d_recs.p), d_palette,
-                                  static_cast<unsigned long long*>(d_agg.p), next_epoch(epoch), tile0, (int)(last.first_tile + last.ntiles - tile0),
-                                  static_cast<uint32_t*>(d_sync.p), stream, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, (uint32_t)ntiles);
+                msv1_launch_fused_pixels(geo, fused_batch(d_recs, d_agg, ntiles, tile0, (int)(last.first_tile + last.ntiles - tile0)), stream);
             } else if (g.temporal) {
-                msv1_launch_blocks_temporal(geo, static_cast<const uint8_t*>(d_stream.p), tables, frames + g.first, g.count, d_palette, stream);
+                msv1_launch_blocks_temporal(geo, d_stream.as<const uint8_t>(), tables, frames + g.first, g.count, d_palette, stream);
             } else {
-                msv1_launch_blocks(geo, static_cast<const uint8_t*>(d_stream.p), tables, frames + g.first, g.count, d_palette, vec_ok, stream);
+                msv1_launch_blocks(geo, d_stream.as<const uint8_t>(), tables, frames + g.first, g.count, d_palette, vec_ok, stream);
             }
             if (g.edge_compare) msv1_launch_edge_compare(geo, frames + g.first, g.count, stream);
         }
@@ -419,8 +424,8 @@ struct Msv1Staged : jsp_staged {
     int clock_launches = 0;                                    // (read by the lab build's phase clocks only: msv1_fused_hooks.h)
     void after_sync() override {
         if (kFusedClocks && clock_launches) {   // lab build only: per-phase cycle sums since the last sync (see JSP_CLOCK), printed and cleared
-            std::vector<unsigned long long> c((size_t)ntiles * 8);
-            unsigned long long* dev = static_cast<unsigned long long*>(d_agg.p) + (size_t)ntiles * 9;
+            std::vector<unsigned long long> c((size_t)ntiles * MSV1_AGG_LAB_CLOCKS);
+            unsigned long long* dev = d_agg.as<unsigned long long>() + (size_t)ntiles * MSV1_AGG_PUBLISHED;   // (behind `agg_tiles` tiles' published words)
             JSP_HIP(hipMemcpy(c.data(), dev, c.size() * 8, hipMemcpyDeviceToHost));
             JSP_HIP(hipMemset(dev, 0, c.size() * 8));
             unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -430,7 +435,7 @@ struct Msv1Staged : jsp_staged {
                          ntiles, clock_launches, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[5] / n);
         }
         clock_launches = 0;
-        if ((any_fused || needs_desc) && (*static_cast<const uint32_t*>(h_fault.p) || inject_fault)) {
+        if ((any_fused || needs_desc) && (*h_fault.as<const uint32_t>() || inject_fault)) {
             // A tile gave up waiting for the tile before it.  That says something about the GPU's timing (shared with other
             // work, serialised by a profiler), nothing about the stream: the batch is decoded again through the descriptor
             // path — msv1_parse_tiles / _chain / _emit build the block tables in three launches with no hand-off inside a
@@ -439,12 +444,12 @@ struct Msv1Staged : jsp_staged {
             ++fallback_runs;
             if (fallback_total) ++*fallback_total;
             note_kernel("msv1_parse_tiles (look-back fallback)");
-            *static_cast<uint32_t*>(h_fault.p) = 0;
+            *h_fault.as<uint32_t>() = 0;
             hipStream_t stream = last_stream;
             quiesce_side();                            // (a table-writing launch may be running beside the stream: it shares the fault word, and its tables are not to be trusted either)
-            JSP_HIP(hipMemsetAsync(d_sync.p, 0, 2 * sizeof(uint32_t) + 64, stream));
+            JSP_HIP(hipMemsetAsync(d_sync.p, 0, MSV1_SYNC_BYTES, stream));
             launch_parse(stream);
-            launch_groups(static_cast<const uint32_t*>(d_desc.p), /*fused=*/false, stream);
+            launch_groups(d_desc.as<const uint32_t>(), /*fused=*/false, stream);
             JSP_HIP(hipStreamSynchronize(stream));
         }
     }
@@ -463,12 +468,11 @@ struct Msv1Staged : jsp_staged {
 struct Msv1AsyncStaged : jsp_staged {
     Msv1AsyncStaged() { verdict_pending = true; }
     Msv1Geometry geo{};
-    const int32_t* d_palette = nullptr;
-    int ntiles = 0, insignificant_blocks = 0;
+    Msv1AsyncShared shared;                   // the codec's palette, insignificant blocks and veto word, and this frame's tile size
+    int ntiles = 0;
     size_t nbytes = 0;
     bool have_prev = false, compare = false, key = false;
     bool key_compare = false;                 // a key frame whose stage-2 compare answers option "key_frame_compare" (the kernel compares as it decodes)
-    uint32_t* d_poison = nullptr;             // the codec's veto word (see msv1_launch_fused)
     DeviceBuffer d_stream, d_meta, d_agg;     // d_meta = [tile records | Msv1AsyncInfo] (two-launch form)
     PinnedBuffer h_stream, h_meta, h_info;
     uint32_t epoch = 0;                        // never reset: d_agg is zeroed only when it is (re)allocated
@@ -476,7 +480,7 @@ struct Msv1AsyncStaged : jsp_staged {
     // one-launch form (frames of at most MSV1_MERGED_MAX_TILES tiles): the record all tiles share travels as a kernel
     // argument, the report comes back through pinned memory, and the kernel reads the frame's bytes from pinned host
     // memory itself (the caller's, or h_stream), leaving a copy in d_stream: no copy is queued at all
-    bool merged = false, small_tiles = false;
+    bool merged = false;
     bool deaf = false;                        // tests: see MSV1_LAB_DEAF
     Msv1TileRec rec{};
     DeviceBuffer d_report;                    // one Msv1AsyncInfo, allocated (and zeroed) once: its counters run on
@@ -487,48 +491,43 @@ struct Msv1AsyncStaged : jsp_staged {
     ~Msv1AsyncStaged() override { if (uploaded) (void)hipEventDestroy(uploaded); }
 
     Msv1AsyncInfo* d_info() const {
-        if (merged) return static_cast<Msv1AsyncInfo*>(d_report.p);
-        return reinterpret_cast<Msv1AsyncInfo*>(static_cast<uint8_t*>(d_meta.p) + sizeof(Msv1TileRec) * (size_t)ntiles);
+        if (merged) return d_report.as<Msv1AsyncInfo>();
+        return reinterpret_cast<Msv1AsyncInfo*>(d_meta.as<uint8_t>() + sizeof(Msv1TileRec) * (size_t)ntiles);
     }
     uint32_t bad_mask() const { return MSV1_ASYNC_SHORT | MSV1_ASYNC_END | MSV1_ASYNC_STUCK | (have_prev ? 0u : MSV1_ASYNC_SKIPCODE) | (deaf ? MSV1_LAB_DEAF : 0u); }
+    // This frame as the one-launch form takes it (msv1.h, Msv1GroupFrame); the launch it goes into is counted on: `want` and the epoch move on, and
+    // `stream` waits for the frame's bytes where the copy engine brings them up.
+    Msv1GroupFrame group_frame(hipStream_t stream) {
+        want += (uint32_t)ntiles;
+        if (dma) JSP_HIP(hipStreamWaitEvent(stream, uploaded, 0));
+        Msv1GroupFrame f;
+        f.stream = src_dev;  f.keep = dma ? nullptr : d_stream.as<uint8_t>();  f.rec = rec;
+        f.info = d_info();   f.host_info = h_info.as<Msv1AsyncInfo>();         f.want = want;
+        f.agg = d_agg.as<unsigned long long>();  f.epoch = next_epoch(epoch);  f.bad_mask = bad_mask();
+        return f;
+    }
     // This frame and the ones submitted right behind it (at most MSV1_MAX_RIDERS) in ONE launch: all one-launch frames with the same tile
     // size (msv1.h, Msv1Riders).
     void decode_with(const std::vector<Msv1AsyncStaged*>& behind, hipStream_t stream) {
-        want += (uint32_t)ntiles;
-        if (dma) JSP_HIP(hipStreamWaitEvent(stream, uploaded, 0));
-        Msv1Riders riders;
-        for (Msv1AsyncStaged* next : behind) {
-            next->want += (uint32_t)next->ntiles;
-            if (next->dma) JSP_HIP(hipStreamWaitEvent(stream, next->uploaded, 0));
-            Msv1Rider& r = riders.f[riders.count++];
-            r.stream = next->src_dev;
-            r.agg = static_cast<unsigned long long*>(next->d_agg.p);
-            r.info = next->d_info();
-            r.host_info = static_cast<Msv1AsyncInfo*>(next->h_info.p);
-            r.keep = next->dma ? nullptr : static_cast<uint8_t*>(next->d_stream.p);
-            r.rec = next->rec;
-            r.epoch = next_epoch(next->epoch);
-            r.bad_mask = next->bad_mask();
-            r.want = next->want;
-        }
-        auto* info_dev = d_info();
-        msv1_launch_fused(geo, src_dev, nullptr, d_palette, static_cast<unsigned long long*>(d_agg.p),
-                          next_epoch(epoch), 0, ntiles, &info_dev->fault, stream, info_dev, insignificant_blocks, 3, bad_mask(), d_poison, &rec,
-                          static_cast<Msv1AsyncInfo*>(h_info.p), want, dma ? nullptr : static_cast<uint8_t*>(d_stream.p), small_tiles, &riders);
+        Msv1GroupFrame frames[1 + MSV1_MAX_RIDERS] = {group_frame(stream)};
+        int n = 1;
+        for (Msv1AsyncStaged* next : behind) frames[n++] = next->group_frame(stream);
+        msv1_launch_fused_group(geo, frames, n, shared, stream);
         JSP_HIP(hipGetLastError());
         decoded = true;
         for (Msv1AsyncStaged* next : behind) next->decoded = true;
     }
     void decode(hipStream_t stream) override {
         if (merged) { decode_with({}, stream); return; }
-        auto* info_dev = d_info();
-        const uint32_t bad = bad_mask();
-        for (int mode = 1; mode <= 2; ++mode)   // scout, then the decode it may veto
-            msv1_launch_fused(geo, static_cast<const uint8_t*>(d_stream.p), static_cast<const Msv1TileRec*>(d_meta.p), d_palette,
-                              static_cast<unsigned long long*>(d_agg.p), next_epoch(epoch), 0, ntiles, &info_dev->fault, stream, info_dev,
-                              insignificant_blocks, mode, bad, d_poison, nullptr, nullptr, 0, nullptr, small_tiles);
+        Msv1FusedPass pass;
+        pass.stream = d_stream.as<const uint8_t>();  pass.recs = d_meta.as<const Msv1TileRec>();  pass.ntiles = ntiles;
+        pass.agg = d_agg.as<unsigned long long>();   pass.info = d_info();  pass.bad_mask = bad_mask();  pass.shared = shared;
+        pass.epoch = next_epoch(epoch);
+        msv1_launch_fused_scout(geo, pass, stream);
+        pass.epoch = next_epoch(epoch);
+        msv1_launch_fused_decode(geo, pass, stream);   // (the scout may have vetoed it)
         JSP_HIP(hipGetLastError());
-        JSP_HIP(hipMemcpyAsync(h_info.p, info_dev, sizeof(Msv1AsyncInfo), hipMemcpyDeviceToHost, stream));
+        JSP_HIP(hipMemcpyAsync(h_info.p, pass.info, sizeof(Msv1AsyncInfo), hipMemcpyDeviceToHost, stream));
         decoded = true;
     }
 };
@@ -618,7 +617,7 @@ struct Msv1Codec : jsp_codec {
         }
         r.dev.reserve(n + 128);               // (growing frees the old copy: hipFree waits for the device)
         r.skew = (size_t)(reinterpret_cast<uintptr_t>(host) & 63u);
-        JSP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(r.dev.p) + r.skew, host, n, hipMemcpyHostToDevice, prefetch_stream));
+        JSP_HIP(hipMemcpyAsync(r.dev.as<uint8_t>() + r.skew, host, n, hipMemcpyHostToDevice, prefetch_stream));
         JSP_HIP(hipEventRecord(r.up, prefetch_stream));
         r.host = static_cast<const uint8_t*>(host);
         r.bytes = n;
@@ -690,7 +689,7 @@ struct Msv1Codec : jsp_codec {
         auto* st = dynamic_cast<Msv1AsyncStaged*>(j.st.get());
         const int k = frames_per_launch();
         if (!st || !st->merged || !opt_async_pairs || k < 2) { launch_held(); return false; }
-        if (!held.empty() && static_cast<Msv1AsyncStaged*>(held[0]->st.get())->small_tiles != st->small_tiles) launch_held();
+        if (!held.empty() && static_cast<Msv1AsyncStaged*>(held[0]->st.get())->shared.small_tiles != st->shared.small_tiles) launch_held();
         held.push_back(&j);
         if ((int)held.size() >= k) launch_held();
         return true;
@@ -881,14 +880,14 @@ struct Msv1Codec : jsp_codec {
             }
             range->used = true;
             ++prefetched_frames;
-            return {f.src, static_cast<const uint8_t*>(range->dev.p) + range->skew + (f.src - range->host), range};
+            return {f.src, range->dev.as<const uint8_t>() + range->skew + (f.src - range->host), range};
         }
         if (hipPointerGetAttributes(&attr, f.src) == hipSuccess && attr.type == hipMemoryTypeHost)
             return {f.src, static_cast<const uint8_t*>(attr.devicePointer ? attr.devicePointer : f.src), nullptr};
         (void)hipGetLastError();
         st.h_stream.reserve(f.n + 16);
         std::memcpy(st.h_stream.p, f.src, f.n);
-        return {st.h_stream.p, static_cast<const uint8_t*>(st.h_stream.p), nullptr};
+        return {st.h_stream.p, st.h_stream.as<const uint8_t>(), nullptr};
     }
 
     jsp_staged* stage_async(const jsp_frame_in& f, jsp_staged* reuse) override {
@@ -905,8 +904,8 @@ struct Msv1Codec : jsp_codec {
         std::unique_ptr<Msv1AsyncStaged> guard;
         if (!st) { st = new Msv1AsyncStaged(); guard.reset(st); }
         st->geo = geo;
-        st->d_palette = static_cast<const int32_t*>(d_palette.p);
-        st->insignificant_blocks = insignificant_blocks;
+        st->shared.palette = d_palette.as<const int32_t>();
+        st->shared.insignificant_blocks = insignificant_blocks;
         st->decoded = false;
         st->why.clear();
         st->status.assign(1, JSP_ZERO_STATE);
@@ -920,7 +919,7 @@ struct Msv1Codec : jsp_codec {
             d_poison.reserve(sizeof(uint32_t));
             JSP_HIP(hipMemsetAsync(d_poison.p, 0, sizeof(uint32_t), stream));
         }
-        st->d_poison = static_cast<uint32_t*>(d_poison.p);
+        st->shared.poison = d_poison.as<uint32_t>();
         // inter frames with a previous frame are compared against it in any case (whether the result counts is known
         // only with the stage-1 flag the kernel reports)
         st->compare = geo.bits == 16 && insign_lines_set && !f.key && prev_dev != nullptr;
@@ -933,7 +932,7 @@ struct Msv1Codec : jsp_codec {
         const int nt = (int)((f.n + tile_bytes - 1) / tile_bytes);
         st->ntiles = nt;
         st->merged = opt_async_merged && nt <= MSV1_MERGED_MAX_TILES;
-        st->small_tiles = small_tiles;
+        st->shared.small_tiles = small_tiles;
         st->deaf = st->merged && opt_inject_deaf;
         if (st->deaf) opt_inject_deaf = false;
         reserve_async_buffers(*st, nt, tile_bytes);
@@ -958,10 +957,10 @@ struct Msv1Codec : jsp_codec {
                 if (!st->uploaded) JSP_HIP(hipEventCreateWithFlags(&st->uploaded, hipEventDisableTiming));
                 JSP_HIP(hipMemcpyAsync(st->d_stream.p, fb.up, f.n, hipMemcpyHostToDevice, up_stream));
                 JSP_HIP(hipEventRecord(st->uploaded, up_stream));
-                st->src_dev = static_cast<const uint8_t*>(st->d_stream.p);
+                st->src_dev = st->d_stream.as<const uint8_t>();
             }
         } else {
-            auto* recs = static_cast<Msv1TileRec*>(st->h_meta.p);
+            auto* recs = st->h_meta.as<Msv1TileRec>();
             for (int k = 0; k < nt; ++k) recs[k] = rec(k);
             std::memset(recs + nt, 0, sizeof(Msv1AsyncInfo));
             if (fb.range) JSP_HIP(hipMemcpyAsync(st->d_stream.p, fb.up_dev, f.n, hipMemcpyDeviceToDevice, stream));   // (larger frames: from the range's copy to the frame's own)
@@ -987,7 +986,7 @@ struct Msv1Codec : jsp_codec {
     bool async_finish(jsp_staged* base) override {
         auto* st = dynamic_cast<Msv1AsyncStaged*>(base);
         if (!st) return true;                                    // went through the synchronous staging: already settled
-        const Msv1AsyncInfo& in = *static_cast<const Msv1AsyncInfo*>(st->h_info.p);
+        const Msv1AsyncInfo& in = *st->h_info.as<const Msv1AsyncInfo>();
         if (in.fault) return false;                              // a tile gave up waiting (timing, not the stream): the host path settles the frame
         if ((in.flags & (MSV1_ASYNC_SHORT | MSV1_ASYNC_END | MSV1_ASYNC_STUCK)) || ((in.flags & MSV1_ASYNC_SKIPCODE) && !st->have_prev))
             return false;                                        // the host parser has to settle this stream
@@ -1051,7 +1050,7 @@ struct Msv1Codec : jsp_codec {
             d_palette.reserve(sizeof palette);
             JSP_HIP(hipMemcpy(d_palette.p, palette, sizeof palette, hipMemcpyHostToDevice));
         }
-        st.d_palette = static_cast<const int32_t*>(d_palette.p);
+        st.d_palette = d_palette.as<const int32_t>();
     }
 
     // ---- phase 2: lay the frames out in one stream buffer (16-byte aligned starts) and gather those that are not in pinned memory ----
@@ -1091,7 +1090,7 @@ struct Msv1Codec : jsp_codec {
         st.d_frames.reserve(sizeof(Msv1FrameArgs) * std::max(nf, 1));
         // gathered on several threads when there is much to gather: one thread copies ~6 GB/s, a batch of 512 1080p frames
         // is half a gigabyte
-        auto* h_stream = static_cast<uint8_t*>(st.h_stream.p);
+        auto* h_stream = st.h_stream.as<uint8_t>();
         auto gather = [&](int lo, int hi) {
             for (int i = lo; i < hi; ++i) {
                 if (plan.in_pinned[i]) continue;
@@ -1120,8 +1119,8 @@ struct Msv1Codec : jsp_codec {
     // the batch's stream buffer in HBM: runs of gathered frames go up in one copy each, pinned frames one by one
     void upload_stream(const std::vector<jsp_frame_in>& frames, Msv1Staged& st, const StagePlan& plan) {
         const int nf = (int)frames.size();
-        const auto* h_stream = static_cast<const uint8_t*>(st.h_stream.p);
-        auto* d_stream = static_cast<uint8_t*>(st.d_stream.p);
+        const auto* h_stream = st.h_stream.as<const uint8_t>();
+        auto* d_stream = st.d_stream.as<uint8_t>();
         int i = 0;
         while (i < nf) {
             if (plan.in_pinned[i]) {
@@ -1143,7 +1142,7 @@ struct Msv1Codec : jsp_codec {
         const size_t nblk = (size_t)std::max(geo.nblocks, 1);
         const uint32_t tile_bytes = msv1_parse_tile_bytes();
         st.h_pframes.reserve(sizeof(Msv1ParseFrame) * nf);
-        Msv1ParseFrame* h_pf = plan.h_pf = static_cast<Msv1ParseFrame*>(st.h_pframes.p);
+        Msv1ParseFrame* h_pf = plan.h_pf = st.h_pframes.as<Msv1ParseFrame>();
         int ntiles = 0, max_tiles = 1;
         for (int i = 0; i < nf; ++i) {
             // an odd trailing byte is left to the host parser (it only matters when the chain reaches it,
@@ -1162,7 +1161,7 @@ struct Msv1Codec : jsp_codec {
         st.ntiles = ntiles;
         st.max_tiles = max_tiles;
         st.h_tile_frame.reserve(sizeof(uint32_t) * std::max(ntiles, 1));
-        auto* h_tf = static_cast<uint32_t*>(st.h_tile_frame.p);
+        auto* h_tf = st.h_tile_frame.as<uint32_t>();
         for (int i = 0; i < nf; ++i)
             for (uint32_t k = 0; k < h_pf[i].ntiles; ++k) h_tf[h_pf[i].first_tile + k] = (uint32_t)i;
         st.d_pframes.reserve(sizeof(Msv1ParseFrame) * nf);
@@ -1181,7 +1180,7 @@ struct Msv1Codec : jsp_codec {
         JSP_HIP(hipMemcpyAsync(st.h_info.p, st.d_info.p, sizeof(Msv1FrameInfo) * nf, hipMemcpyDeviceToHost, stream));
         JSP_HIP(hipStreamSynchronize(stream));   // the one wait of the staging pass: counters are needed now
         plan.gpu_parse_ms = now_ms() - tu;        // uploads + parse, not separable without more waits
-        plan.h_info = static_cast<const Msv1FrameInfo*>(st.h_info.p);
+        plan.h_info = st.h_info.as<const Msv1FrameInfo>();
     }
 
     // block_changes is rebuilt on demand from the bytes of the last frame parsed on the GPU: they are kept before the host parser needs them, and
@@ -1217,14 +1216,14 @@ struct Msv1Codec : jsp_codec {
         }
         keep_last_gpu_frame(frames, last_gpu_frame);
         st.h_desc.reserve(sizeof(uint32_t) * nblk * std::max(st.nframes, 1));   // (on-GPU parse: allocated when the first such frame turns up)
-        uint32_t* desc = static_cast<uint32_t*>(st.h_desc.p) + (size_t)i * nblk;
+        uint32_t* desc = st.h_desc.as<uint32_t>() + (size_t)i * nblk;
         host_parse(f.src, f.n, (uint32_t)plan.beg[i], desc, pr);
         if (pr.early_out) std::fill(desc, desc + geo.nblocks, MSV1_DESC_UNTOUCHED);
         if (st.gpu_parse) {  // this frame's table comes from the host from now on
             ++host_parsed_frames;
             plan.h_pf[i].host_parsed = 1;
             plan.pframes_dirty = true;
-            upload(static_cast<uint32_t*>(st.d_desc.p) + (size_t)i * nblk, desc, sizeof(uint32_t) * geo.nblocks);
+            upload(st.d_desc.as<uint32_t>() + (size_t)i * nblk, desc, sizeof(uint32_t) * geo.nblocks);
         }
         return pr;
     }
@@ -1233,8 +1232,8 @@ struct Msv1Codec : jsp_codec {
     void decide_frames(const std::vector<jsp_frame_in>& frames, Msv1Staged& st, StagePlan& plan) {
         const int nf = (int)frames.size();
         const size_t nblk = (size_t)std::max(geo.nblocks, 1);
-        auto* h_frames = static_cast<Msv1FrameArgs*>(st.h_frames.p);
-        auto* d_signif = static_cast<uint32_t*>(st.d_signif.p);
+        auto* h_frames = st.h_frames.as<Msv1FrameArgs>();
+        auto* d_signif = st.d_signif.as<uint32_t>();
         plan.vec_ok = (X & 3) == 0;
         plan.attr.assign(nf, StagePlan::Attr{false, false, false, false});
         plan.frame_stream.assign(nf, 0);
@@ -1310,14 +1309,14 @@ bool msv1_seek_view(jsp_staged* base, Msv1SeekView& out) {
     auto* st = dynamic_cast<Msv1Staged*>(base);
     if (!st) return false;
     out.geo = st->geo;
-    out.d_stream = static_cast<const uint8_t*>(st->d_stream.p);
-    out.d_desc = static_cast<const uint32_t*>(st->d_desc.p);
+    out.d_stream = st->d_stream.as<const uint8_t>();
+    out.d_desc = st->d_desc.as<const uint32_t>();
     out.desc_pitch = (size_t)std::max(st->geo.nblocks, 1);
-    out.d_frames = static_cast<const Msv1FrameArgs*>(st->d_frames.p);
-    out.h_frames = static_cast<const Msv1FrameArgs*>(st->h_frames.p);
+    out.d_frames = st->d_frames.as<const Msv1FrameArgs>();
+    out.h_frames = st->h_frames.as<const Msv1FrameArgs>();
     out.d_palette = st->d_palette;
-    out.d_signif = static_cast<uint32_t*>(st->d_signif.p);
-    out.h_signif = static_cast<uint32_t*>(st->h_signif.p);
+    out.d_signif = st->d_signif.as<uint32_t>();
+    out.h_signif = st->h_signif.as<uint32_t>();
     out.nframes = st->nframes;
     return true;
 }

@@ -439,7 +439,7 @@ __global__ __launch_bounds__(PWG, MODE == 4 ? JSP_FUSED_WAVES_TABLES : JSP_FUSED
     // one LDS arena: [tile bytes | lane tables | look-back scratch]; the tables' space becomes the staging window once every
     // lane knows where the chain enters its slots
     // The batch forms take their tiles tile-major over the batch's frames (tile j of every frame before tile j + 1 of any,
-    // see msv1_launch_order): when a tile starts, its predecessor in the frame finished about a thousand workgroups ago and has
+    // see staggered_tile_order in msv1_codec.cpp): when a tile starts, its predecessor in the frame finished about a thousand workgroups ago and has
     // left the one value this tile needs — where the chain stands at the tile's first slot — so the look-back is ONE word,
     // asked for before anything else and there when it is needed (PREFIX).  The one-frame launches have all of a frame's
     // tiles in flight together: those publish their tables and every tile chains the tables of all tiles before it.
@@ -967,7 +967,7 @@ __global__ __launch_bounds__(PWG, MODE == 4 ? JSP_FUSED_WAVES_TABLES : JSP_FUSED
 }  // namespace
 
 uint32_t msv1_parse_tile_bytes() { return TSLOTS * 2; }
-uint32_t msv1_small_tile_bytes() { return PWG * 16 * 2; }   // `small_tiles` of msv1_launch_fused: 16 slots per lane
+uint32_t msv1_small_tile_bytes() { return PWG * 16 * 2; }   // `small_tiles` launches: 16 slots per lane
 
 void msv1_launch_parse(const Msv1Geometry& geo, const uint8_t* d_stream, const Msv1ParseFrame* d_frames, int nframes,
                        const uint32_t* d_tile_frame, int ntiles, int max_tiles_per_frame, uint32_t* d_tile_tab,
@@ -992,31 +992,102 @@ void msv1_launch_parse(const Msv1Geometry& geo, const uint8_t* d_stream, const M
 }
 
 
-void msv1_launch_fused(const Msv1Geometry& geo, const uint8_t* d_stream, const Msv1TileRec* d_recs, const int32_t* d_palette,
-                       unsigned long long* d_agg, uint32_t epoch, uint32_t tile0, int ntiles, uint32_t* d_fault,
-                       hipStream_t stream, Msv1AsyncInfo* d_info, int insignificant_blocks, int mode, uint32_t bad_mask,
-                       uint32_t* d_poison, const Msv1TileRec* one_rec, Msv1AsyncInfo* h_info, uint32_t want, uint8_t* d_keep,
-                       bool small_tiles, const Msv1Riders* riders) {
-    if (ntiles <= 0) return;
-    Msv1Riders two{};
-    if (riders && mode == 3) {
-        two = *riders;
-        for (uint32_t q = 0; q < two.count; ++q) { two.f[q].first_wg = (uint32_t)ntiles; ntiles += (int)two.f[q].rec.ntiles; }
-    }
-    const uint32_t s1_first = (uint32_t)(insignificant_blocks < 0 ? 0 : insignificant_blocks) * (uint32_t)geo.nbx;
-    const Msv1TileRec rec = one_rec ? *one_rec : Msv1TileRec{};
-    if (mode == 0) small_tiles = false;                        // the batch form lays frames out on 16 KiB boundaries (the table-writing form, mode 4, may take them in 8 KiB tiles: its records say where each begins)
-#define JSP_FUSED(BITS, MODE, LS)                                                                                            \
-    hipLaunchKernelGGL((msv1_fused_kernel<BITS, MODE, LS>), dim3(ntiles), dim3(PWG), 0, stream, d_stream, d_recs, d_palette, \
-                       d_agg, epoch, tile0, d_fault, (uint32_t)geo.nblocks, geo.nbx, geo.X, d_info, s1_first, bad_mask, d_poison, rec, h_info, want, d_keep, two)
+namespace {
+
+// What msv1_fused_kernel is given, in its parameters' order; every form fills in what it reads and leaves the rest as it is here.
+struct FusedArgs {
+    const uint8_t* stream = nullptr;
+    const Msv1TileRec* recs = nullptr;
+    const int32_t* palette = nullptr;
+    unsigned long long* agg = nullptr;
+    uint32_t epoch = 0, tile0 = 0;
+    uint32_t* fault = nullptr;
+    Msv1AsyncInfo* info = nullptr;
+    int insignificant_blocks = 0;
+    uint32_t bad_mask = 0;
+    uint32_t* poison = nullptr;
+    Msv1TileRec one_rec{};
+    Msv1AsyncInfo* host_info = nullptr;
+    uint32_t want = 0;
+    uint8_t* keep = nullptr;
+    Msv1Riders riders{};
+};
+
+enum FusedMode { FUSED_PIXELS = 0, FUSED_SCOUT = 1, FUSED_DECODE = 2, FUSED_GROUP = 3, FUSED_TABLES = 4 };   // the kernel's MODE
+
+// (The kernels lie in the code object in the order they are named below.)
+// `grid` workgroups of msv1_fused_kernel<geo.bits, mode, .>: 8 KiB tiles when `small_tiles`, else the batch forms' tile size.  (The pixel-writing
+// batch form exists in the batch size only; the table-writing one is only ever launched small, its other size is compiled all the same.)
+void launch_fused(const Msv1Geometry& geo, FusedMode mode, const FusedArgs& a, int grid, bool small_tiles, hipStream_t stream) {
+    if (grid <= 0) return;
+    const uint32_t s1_first = (uint32_t)(a.insignificant_blocks < 0 ? 0 : a.insignificant_blocks) * (uint32_t)geo.nbx;
+#define JSP_FUSED(BITS, MODE, LS)                                                                                                 \
+    hipLaunchKernelGGL((msv1_fused_kernel<BITS, MODE, LS>), dim3(grid), dim3(PWG), 0, stream, a.stream, a.recs, a.palette, a.agg, \
+                       a.epoch, a.tile0, a.fault, (uint32_t)geo.nblocks, geo.nbx, geo.X, a.info, s1_first, a.bad_mask, a.poison,   \
+                       a.one_rec, a.host_info, a.want, a.keep, a.riders)
 #define JSP_FUSED_LS(BITS, MODE) do { if (small_tiles) JSP_FUSED(BITS, MODE, 16); else JSP_FUSED(BITS, MODE, JSP_BATCH_LS); } while (0)
-#define JSP_FUSED_MODES(BITS)                                                                                                \
-    switch (mode) { case 1: JSP_FUSED_LS(BITS, 1); break; case 2: JSP_FUSED_LS(BITS, 2); break; case 3: JSP_FUSED_LS(BITS, 3); break; \
-                    case 4: JSP_FUSED_LS(BITS, 4); break; default: JSP_FUSED(BITS, 0, JSP_BATCH_LS); }
+#define JSP_FUSED_MODES(BITS)                                                                                                     \
+    switch (mode) {                                                                                                               \
+        case FUSED_SCOUT: JSP_FUSED_LS(BITS, 1); break;                                                                           \
+        case FUSED_DECODE: JSP_FUSED_LS(BITS, 2); break;                                                                          \
+        case FUSED_GROUP: JSP_FUSED_LS(BITS, 3); break;                                                                           \
+        case FUSED_TABLES: JSP_FUSED_LS(BITS, 4); break;                                                                          \
+        case FUSED_PIXELS: JSP_FUSED(BITS, 0, JSP_BATCH_LS); break;                                                               \
+    }
     if (geo.bits == 16) { JSP_FUSED_MODES(16) } else { JSP_FUSED_MODES(8) }
 #undef JSP_FUSED_MODES
 #undef JSP_FUSED_LS
 #undef JSP_FUSED
+}
+
+FusedArgs batch_args(const Msv1FusedBatch& b) {
+    FusedArgs a;
+    a.stream = b.stream;  a.recs = b.recs;    a.palette = b.palette;  a.agg = b.agg;
+    a.epoch = b.epoch;    a.tile0 = b.tile0;  a.fault = b.fault;      a.want = b.agg_tiles;
+    return a;
+}
+
+FusedArgs pass_args(const Msv1FusedPass& p) {
+    FusedArgs a;
+    a.stream = p.stream;  a.recs = p.recs;  a.agg = p.agg;  a.epoch = p.epoch;
+    a.info = p.info;      a.fault = &p.info->fault;         a.bad_mask = p.bad_mask;
+    a.palette = p.shared.palette;  a.insignificant_blocks = p.shared.insignificant_blocks;  a.poison = p.shared.poison;
+    return a;
+}
+
+}  // namespace
+
+void msv1_launch_fused_pixels(const Msv1Geometry& geo, const Msv1FusedBatch& batch, hipStream_t stream) {
+    launch_fused(geo, FUSED_PIXELS, batch_args(batch), batch.ntiles, /*small_tiles=*/false, stream);
+}
+
+void msv1_launch_fused_tables(const Msv1Geometry& geo, const Msv1FusedBatch& batch, hipStream_t stream) {
+    launch_fused(geo, FUSED_TABLES, batch_args(batch), batch.ntiles, /*small_tiles=*/true, stream);
+}
+
+void msv1_launch_fused_scout(const Msv1Geometry& geo, const Msv1FusedPass& pass, hipStream_t stream) {
+    launch_fused(geo, FUSED_SCOUT, pass_args(pass), pass.ntiles, pass.shared.small_tiles, stream);
+}
+
+void msv1_launch_fused_decode(const Msv1Geometry& geo, const Msv1FusedPass& pass, hipStream_t stream) {
+    launch_fused(geo, FUSED_DECODE, pass_args(pass), pass.ntiles, pass.shared.small_tiles, stream);
+}
+
+void msv1_launch_fused_group(const Msv1Geometry& geo, const Msv1GroupFrame* frames, int nframes, const Msv1AsyncShared& shared, hipStream_t stream) {
+    if (nframes < 1 || nframes > 1 + MSV1_MAX_RIDERS) return;
+    const Msv1GroupFrame& f0 = frames[0];
+    int grid = (int)f0.rec.ntiles;
+    if (grid <= 0) return;
+    FusedArgs a;                                               // the first frame travels in the kernel's leading parameters ...
+    a.stream = f0.stream;  a.keep = f0.keep;            a.one_rec = f0.rec;  a.agg = f0.agg;    a.epoch = f0.epoch;
+    a.info = f0.info;      a.fault = &f0.info->fault;   a.host_info = f0.host_info;  a.want = f0.want;  a.bad_mask = f0.bad_mask;
+    a.palette = shared.palette;  a.insignificant_blocks = shared.insignificant_blocks;  a.poison = shared.poison;
+    for (int q = 1; q < nframes; ++q) {                        // ... the frames behind it as riders, each knowing where its workgroups begin
+        Msv1Rider& r = a.riders.f[a.riders.count++] = frames[q];
+        r.first_wg = (uint32_t)grid;
+        grid += (int)r.rec.ntiles;
+    }
+    launch_fused(geo, FUSED_GROUP, a, grid, shared.small_tiles, stream);
 }
 
 }  // namespace jsp

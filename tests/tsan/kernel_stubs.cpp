@@ -34,30 +34,30 @@ void msv1_launch_parse(const Msv1Geometry& geo, const uint8_t* d_stream, const M
     stub_stream_work(stream);
 }
 
-void msv1_launch_fused(const Msv1Geometry&, const uint8_t*, const Msv1TileRec*, const int32_t*, unsigned long long*, uint32_t, uint32_t, int, uint32_t*,
-                       hipStream_t stream, Msv1AsyncInfo* d_info, int, int mode, uint32_t bad_mask, uint32_t* d_poison, const Msv1TileRec*, Msv1AsyncInfo* h_info,
-                       uint32_t want, uint8_t*, bool, const Msv1Riders* riders) {
+// What a launch of msv1_fused_kernel leaves in a frame's report (the batch forms leave none).  `host`: where the one-launch form hands the report
+// over; the scout has none and leaves its findings in `dev`.
+static void settle(Msv1AsyncInfo* dev, Msv1AsyncInfo* host, uint32_t want, uint32_t bad, uint32_t* d_poison) {
     static std::atomic<unsigned> n{0};
-    auto settle = [&](Msv1AsyncInfo* dev, Msv1AsyncInfo* host, uint32_t w, uint32_t bad) {
-        if (!dev) return;
-        const bool vetoed_before = d_poison && *d_poison;
-        const uint32_t flags = (n.fetch_add(1, std::memory_order_relaxed) % 7 == 6) ? MSV1_ASYNC_SHORT : 0u;
-        dev->arrived = dev->finished = w;
-        if (host) {
-            Msv1AsyncInfo r{};
-            r.flags = flags;
-            *host = r;
-        } else
-            dev->flags |= flags;
-        if (((flags & bad) || vetoed_before) && d_poison) *d_poison = 1u;
-    };
-    if (mode == 3) {
-        settle(d_info, h_info, want, bad_mask);
-        if (riders)
-            for (uint32_t i = 0; i < riders->count; ++i) settle(riders->f[i].info, riders->f[i].host_info, riders->f[i].want, riders->f[i].bad_mask);
-    } else if (mode == 1 && d_info) {
-        settle(d_info, nullptr, want, bad_mask);
-    }
+    const bool vetoed_before = d_poison && *d_poison;
+    const uint32_t flags = (n.fetch_add(1, std::memory_order_relaxed) % 7 == 6) ? MSV1_ASYNC_SHORT : 0u;
+    dev->arrived = dev->finished = want;
+    if (host) {
+        Msv1AsyncInfo r{};
+        r.flags = flags;
+        *host = r;
+    } else
+        dev->flags |= flags;
+    if (((flags & bad) || vetoed_before) && d_poison) *d_poison = 1u;
+}
+void msv1_launch_fused_pixels(const Msv1Geometry&, const Msv1FusedBatch&, hipStream_t stream) { stub_stream_work(stream); }
+void msv1_launch_fused_tables(const Msv1Geometry&, const Msv1FusedBatch&, hipStream_t stream) { stub_stream_work(stream); }
+void msv1_launch_fused_scout(const Msv1Geometry&, const Msv1FusedPass& pass, hipStream_t stream) {
+    settle(pass.info, nullptr, 0, pass.bad_mask, pass.shared.poison);
+    stub_stream_work(stream);
+}
+void msv1_launch_fused_decode(const Msv1Geometry&, const Msv1FusedPass&, hipStream_t stream) { stub_stream_work(stream); }
+void msv1_launch_fused_group(const Msv1Geometry&, const Msv1GroupFrame* frames, int nframes, const Msv1AsyncShared& shared, hipStream_t stream) {
+    for (int i = 0; i < nframes; ++i) settle(frames[i].info, frames[i].host_info, frames[i].want, frames[i].bad_mask, shared.poison);
     stub_stream_work(stream);
 }
 
