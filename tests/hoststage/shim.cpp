@@ -42,25 +42,25 @@ void hs_fetch_seeds(void* p, uint32_t* seeds) {
     const FrameOut& o = ((Shim*)p)->out;
     if (seeds && !o.seeds.empty()) std::memcpy(seeds, o.seeds.data(), o.seeds.size() * 4);
 }
-// returns status; fills meta: [kind, adopted, significant, prev_cleared, nruns, nrows, nblocks, npayload, flat_colour]
 void hs_set_dst_column(void* p, const int32_t* col, int n) {
     auto* s = (Shim*)p;
     s->dst_column.assign(col, col + (col ? n : 0));
 }
-int hs_decode(void* p, int key, const uint8_t* src, size_t n, uint64_t* meta) {
-    auto* s = (Shim*)p;
-    s->host.set_destination_column([s]() -> const int32_t* { return s->dst_column.empty() ? nullptr : s->dst_column.data(); });
-    if (key) s->host.decode_i(src, n, s->out); else s->host.decode_p(src, n, s->out);
-    const FrameOut& o = s->out;
-    meta[0] = (uint64_t)o.kind; meta[1] = o.adopted; meta[2] = o.significant; meta[3] = o.prev_cleared;
-    meta[4] = o.runs.size(); meta[5] = o.row_run.size(); meta[6] = o.blocks.size(); meta[7] = o.payload.size();
-    meta[8] = o.flat_colour; meta[9] = o.prev_pixels; meta[10] = o.data_pixels; meta[11] = o.stream_bytes;
-    return o.status;
-}
+// meta (16 words): [kind, adopted, significant, prev_cleared, nruns, nrows, nblocks, npayload, flat_colour, prev_pixels, data_pixels,
+// stream_bytes, (hs_select: literalised), motion_pixels]
 static void fill_meta(const FrameOut& o, uint64_t* meta) {
     meta[0] = (uint64_t)o.kind; meta[1] = o.adopted; meta[2] = o.significant; meta[3] = o.prev_cleared;
     meta[4] = o.runs.size(); meta[5] = o.row_run.size(); meta[6] = o.blocks.size(); meta[7] = o.payload.size();
     meta[8] = o.flat_colour; meta[9] = o.prev_pixels; meta[10] = o.data_pixels; meta[11] = o.stream_bytes;
+    meta[13] = o.motion_pixels;
+}
+// returns status; fills meta
+int hs_decode(void* p, int key, const uint8_t* src, size_t n, uint64_t* meta) {
+    auto* s = (Shim*)p;
+    s->host.set_destination_column([s]() -> const int32_t* { return s->dst_column.empty() ? nullptr : s->dst_column.data(); });
+    if (key) s->host.decode_i(src, n, s->out); else s->host.decode_p(src, n, s->out);
+    fill_meta(s->out, meta);
+    return s->out.status;
 }
 // decode_frames(): a run of frames, groups of pictures side by side on `threads` host threads; results kept for hs_select
 void hs_decode_batch(void* p, int n, const uint8_t* const* srcs, const size_t* lens, const uint8_t* keys, int threads, int literalise) {
@@ -68,7 +68,7 @@ void hs_decode_batch(void* p, int n, const uint8_t* const* srcs, const size_t* l
     std::vector<HostFrame> hf(n);
     for (int i = 0; i < n; ++i) hf[i] = HostFrame{srcs[i], lens[i], keys[i] != 0};
     s->outs.assign(n, FrameOut{});
-    decode_frames(s->host, s->spare, hf.data(), n, s->outs.data(), threads, literalise != 0);
+    decode_frames(s->host, s->spare, hf.data(), n, s->outs.data(), threads, literalise != 0, nullptr, literalise == 2);   // 2: literalise_all, as the seek index stages
 }
 // make frame i of the last batch "the frame just decoded" for the hs_fetch* calls; returns its status, meta as hs_decode
 int hs_select(void* p, int i, uint64_t* meta) {

@@ -76,12 +76,13 @@ class HostStage:
 
     def decode_batch(self, frames, keys, threads: int, literalise: bool = False):
         """HostDecoder-level decode_frames(): the frames of a stream, groups of pictures side by side; one dict per frame as
-        decode() returns (plus `literalised`)."""
+        decode() returns (plus `literalised`).  literalise: True = the staged batch's quarter rule, "all" = every inter frame,
+        as the seek index stages them."""
         n = len(frames)
         keep = [bytes(f) for f in frames]
         srcs = (C.c_char_p * n)(*keep)
         lens = (C.c_size_t * n)(*[len(f) for f in keep])
-        self.L.hs_decode_batch(self.h, n, srcs, lens, bytes(bytearray(1 if k else 0 for k in keys)), threads, 1 if literalise else 0)
+        self.L.hs_decode_batch(self.h, n, srcs, lens, bytes(bytearray(1 if k else 0 for k in keys)), threads, 2 if literalise == "all" else 1 if literalise else 0)
         outs = []
         for i in range(n):
             meta = np.zeros(16, dtype=np.uint64)
@@ -101,14 +102,14 @@ class HostStage:
             self.L.hs_set_dst_column(self.h, col.ctypes.data, int(col.size))
 
     def decode(self, key: bool, src: bytes):
-        meta = np.zeros(12, dtype=np.uint64)
+        meta = np.zeros(16, dtype=np.uint64)
         src = bytes(src)
         status = self.L.hs_decode(self.h, 1 if key else 0, src, len(src), meta.ctypes.data)
         return self._fetch(status, [int(v) for v in meta])
 
     def _fetch(self, status, m):
         out = dict(status=status, error=self.L.hs_error(self.h).decode(), kind=m[0], adopted=bool(m[1]), significant=bool(m[2]), prev_cleared=bool(m[3]),
-                   flat_colour=m[8], prev_pixels=m[9], data_pixels=m[10], stream_bytes=m[11])
+                   flat_colour=m[8], prev_pixels=m[9], data_pixels=m[10], stream_bytes=m[11], motion_pixels=m[13])
         runs = np.zeros((m[4], 2), dtype=np.uint32)
         rows = np.zeros(m[5], dtype=np.uint32)
         blocks = np.zeros((m[6], 16), dtype=np.uint8)
@@ -126,7 +127,7 @@ class HostStage:
 
     def literalise_motion(self, desc):
         """HostDecoder::literalise_motion on the frame just decoded: new block table + payload."""
-        meta = np.zeros(12, dtype=np.uint64)
+        meta = np.zeros(16, dtype=np.uint64)
         self.L.hs_literalise_motion(self.h, meta.ctypes.data)
         blocks = np.zeros((int(meta[6]), 16), dtype=np.uint8)
         payload = np.zeros(int(meta[7]), dtype=np.uint32)
@@ -290,13 +291,23 @@ def expand_iframe_tiles(desc, X, Y, fault=None):
     return out.reshape(-1)
 
 
-def expand_pframe(desc, prev, X, Y):
-    """What sp_pframe_kernel computes from the block table + payload."""
+# Named faults for the `fault` argument of expand_pframe: what sp_pframe_kernel's motion branch would compute with that one mistake.
+# (Off by default; the directed motion clips must notice every one: tests/test_sp_motion_clips_cpu.py.)
+MOTION_FAULTS = ("clip_per_axis", "oob_is_colocated", "reads_written_frame", "subrect_ignored", "vector_swapped")
+
+
+def expand_pframe(desc, prev, X, Y, fault=None):
+    """What sp_pframe_kernel computes from the block table + payload.
+    `fault`: one of MOTION_FAULTS, the same with that mistake built in — clip_per_axis: a source column outside [0, X) gives 0
+    instead of wrapping into the neighbouring row; oob_is_colocated: a source outside the buffer gives the previous frame's pixel at
+    the destination; reads_written_frame: the source is the frame being written (blocks in raster order, over a copy of the previous
+    frame); subrect_ignored: the whole block is moved; vector_swapped: mx and my are exchanged."""
+    assert fault is None or fault in MOTION_FAULTS, fault
     nbx, nby = (X + 15) // 16, (Y + 15) // 16
     prev2 = prev.reshape(Y, X)
-    out = np.zeros((Y, X), dtype=np.uint32)
+    out = prev2.astype(np.uint32).copy() if fault == "reads_written_frame" else np.zeros((Y, X), dtype=np.uint32)
     blocks, payload = desc["blocks"], desc["payload"]
-    flat_prev = prev.reshape(-1)
+    flat_prev = out.reshape(-1) if fault == "reads_written_frame" else prev.reshape(-1)
     for by in range(nby):
         for bx in range(nbx):
             b = blocks[by * nbx + bx]
@@ -308,6 +319,10 @@ def expand_pframe(desc, prev, X, Y):
                 continue
             x1, y1, x2, y2 = int(b[1]), int(b[2]), int(b[3]), int(b[4])
             mx, my = np.frombuffer(b[8:12].tobytes(), dtype=np.int16)
+            if fault == "vector_swapped":
+                mx, my = my, mx
+            if fault == "subrect_ignored" and flags & PB_MOTION:
+                x1, y1, x2, y2 = 0, 0, 16, 16
             off = int(np.frombuffer(b[12:16].tobytes(), dtype=np.uint32)[0])
             w = x2 - x1
             for ly in range(y1, y2):
@@ -317,7 +332,10 @@ def expand_pframe(desc, prev, X, Y):
                         continue
                     if flags & PB_MOTION:
                         j = (y + int(my)) * X + x + int(mx)
-                        out[y, x] = flat_prev[j] if 0 <= j < X * Y else 0
+                        inside = 0 <= j < X * Y
+                        if fault == "clip_per_axis" and not 0 <= x + int(mx) < X:
+                            inside = False
+                        out[y, x] = flat_prev[j] if inside else prev2[y, x] if fault == "oob_is_colocated" else 0
                     else:
                         out[y, x] = payload[off + (ly - y1) * w + (lx - x1)]
     return out.reshape(-1)

@@ -13,13 +13,14 @@ from oracle_binding import OracleAbort, OracleMSVideo1, OracleScreenPressor
 pytestmark = pytest.mark.gpu
 
 
-def drive(gpu, orc, w, h, chunks, keys, depth=4, pinned=False, lines=36, before_close=None, prefetch=0, drop_ranges_at=None):
+def drive(gpu, orc, w, h, chunks, keys, depth=4, pinned=False, lines=36, before_close=None, prefetch=0, drop_ranges_at=None, alloc=None):
+    """alloc(n): the caller's own device buffers of n int32 (whatever they hold: frames that adopt are compared whole)."""
     import torch
     gpu.Preinit(lines)
     orc.Preinit(lines)
     gpu.set_option("async_depth", str(depth))
     nbuf = 2 * depth + 3   # in flight: a destination each, plus the picture each frame is checked against
-    gbufs = [torch.full((w * h,), 0x00A5A5A5, dtype=torch.int32, device="cuda") for _ in range(nbuf)]
+    gbufs = [alloc(w * h) if alloc else torch.full((w * h,), 0x00A5A5A5, dtype=torch.int32, device="cuda") for _ in range(nbuf)]
     obufs = [np.full(w * h, 0x00A5A5A5, dtype=np.int32) for _ in range(nbuf)]
     torch.cuda.synchronize()
     arena = None
