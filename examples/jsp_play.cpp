@@ -37,6 +37,11 @@
 //                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
 //                                8) — the seek bar's hover preview / a contact sheet (Main.on_mouse_move, Main.hx:1147-1215); prints
 //                                "<frame> <crc32 of the thumbnail's words>" per thumbnail
+//   jsp_play clip.avi --index-present WxH[:zoom[:hpos:vpos]] N[:filter]
+//                                ONE seek index over the clip of either codec, then ONE jsp_index_present / jsp_sp_index_present call
+//                                for N frames spread evenly over it (frame (k * frames) / N for k < N): the W x H window of --present
+//                                (zoom 0 = Fit) of each, without a full-size frame, as one sheet of N cells; filter 0 nearest, 1
+//                                bilinear (default), 2 area; prints "<frame> <crc32 of the cell's words>" per cell
 //   jsp_play clip.avi --seek N   MSVideo1: frame N first, through ONE jsp_seek from the nearest key frame (DataLoader.hx:125-132;
 //                                Manager.hx:216-259), then on frame by frame; the lines from N on carry the CRCs of a plain run
 //   jsp_play a.avi,b.avi --pipelined --devices 0,1,... [--streams T] [--quiet ...]
@@ -399,7 +404,7 @@ long play_batched(const Clip& clip, int batch, int repeat, bool quiet, int warmu
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]] | --present-area WxH[:zoom[:hpos:vpos]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]] | --present-area WxH[:zoom[:hpos:vpos]] | --index-present WxH[:zoom[:hpos:vpos]] N[:filter]\n", argv[0]); return 2; }
     // (throughput runs: several files, separated by commas — stream s plays file s modulo their number, so that the streams of a
     // multi-stream run are independent inputs)
     std::deque<Clip> clips;                                   // (a deque: elements never move)
@@ -427,6 +432,7 @@ int main(int argc, char** argv) {
     int present_w = 0, present_h = 0;                         // --present WxH[:zoom[:hpos:vpos]]: every frame shown also goes into a device window
     double present_zoom = 0, present_hpos = 0.5, present_vpos = 0.5;
     bool present_area = false;                                // --present-area: the window from jsp_display_present_area
+    int ip_n = 0, ip_filter = JSP_PRESENT_BILINEAR;           // --index-present WxH[:zoom[:hpos:vpos]] N[:filter]: N windows out of a seek index, one sheet
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -472,6 +478,15 @@ int main(int argc, char** argv) {
             if ((got != 2 && got != 3 && got != 5) || present_w < 1 || present_h < 1) { std::fprintf(stderr, "%s: WxH[:zoom[:hpos:vpos]]\n", o.c_str()); return 2; }
             present_area = o == "--present-area";
         }
+        else if (o == "--index-present" && a + 2 < argc) {
+            const std::string v = argv[++a], m = argv[++a];
+            const int got = std::sscanf(v.c_str(), "%dx%d:%lf:%lf:%lf", &present_w, &present_h, &present_zoom, &present_hpos, &present_vpos);
+            const int got_n = std::sscanf(m.c_str(), "%d:%d", &ip_n, &ip_filter);
+            if ((got != 2 && got != 3 && got != 5) || present_w < 1 || present_h < 1 || got_n < 1 || ip_n < 1 || ip_n > 4096 || ip_filter < 0 || ip_filter > 2) {
+                std::fprintf(stderr, "--index-present: WxH[:zoom[:hpos:vpos]] N[:filter], N 1..4096, filter 0..2\n");
+                return 2;
+            }
+        }
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
             for (size_t at = 0; at <= list.size();) {
@@ -491,7 +506,8 @@ int main(int argc, char** argv) {
     if (play_first >= 0 && clip.kind != JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--play-index: ScreenPressor only (an MSVideo1 index adopts: --seek and the plain run play on from any frame)\n"); return 2; }
     if (run_first >= 0 && (play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--index-run goes alone\n"); return 2; }
     if (run_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--index-run: MSVideo1 only (--play-index plays a ScreenPressor index)\n"); return 2; }
-    if (present_w > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--present goes with the plain per-frame run\n"); return 2; }
+    if (ip_n > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--index-present goes alone\n"); return 2; }
+    if (ip_n == 0 && present_w > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--present goes with the plain per-frame run\n"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
         if (!quiet) return play_batched(clip, batch, 1, false) < 0 ? 1 : 0;
@@ -813,6 +829,50 @@ int main(int argc, char** argv) {
             }
             for (int k = 0; rc == 0 && k < strip; ++k)
                 std::printf("%d %08x\n", picks[k], crc32(reinterpret_cast<const uint8_t*>(thumbs.data() + cell * (size_t)k), cell * 4));
+        }
+        if (sheet) jsp_pool_destroy(sheet);
+        jsp_sp_index_destroy(sidx);
+        jsp_index_destroy(idx);
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        return rc;
+    }
+    if (ip_n > 0) {   // windows straight out of a seek index: one index build, then ONE jsp_index_present / jsp_sp_index_present for all of them
+        const size_t n = clip.frames.size();
+        std::vector<const uint8_t*> srcs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> keys;
+        for (size_t i = 0; i < n; ++i) {
+            srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+            lens.push_back(clip.frames[i].second);
+            keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        const bool sp = clip.kind == JSP_CODEC_SCREENPRESSOR;   // the same call on the index of either codec
+        double k = 1, dx = 0, dy = 0;
+        if (jsp_view_matrix(clip.X, clip.Y, present_w, present_h, present_zoom, present_hpos, present_vpos, &k, &dx, &dy) != 0) {
+            std::fprintf(stderr, "jsp_view_matrix: %s\n", jsp_last_error());
+            rc = 2;
+        }
+        jsp_index* idx = rc == 0 && n && !sp ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        jsp_sp_index* sidx = rc == 0 && n && sp ? jsp_sp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        if (rc == 0 && !idx && !sidx) { std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_build" : "jsp_index_build", n ? jsp_last_error() : "no frames"); rc = 1; }
+        jsp_pool* sheet = nullptr;   // cols = 1: a plain [N][H][W] array, one "frame" of W x N H pixels
+        if (rc == 0 && !(sheet = jsp_pool_create(0, present_w, ip_n * present_h, 1))) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
+        if (rc == 0) {
+            std::vector<int> picks;
+            for (int i = 0; i < ip_n; ++i) picks.push_back((int)(((long long)i * (long long)n) / ip_n));
+            const size_t cell = (size_t)present_w * present_h;
+            std::vector<int32_t> cells(cell * (size_t)ip_n);
+            int32_t* out = jsp_pool_buffer(sheet, 0);
+            const int mode = clip.bpp == 16 && sp ? JSP_DISPLAY_CANVAS_RGB15 : JSP_DISPLAY_CANVAS;
+            if ((sp ? jsp_sp_index_present(dec, sidx, ip_n, picks.data(), out, cells.size(), present_w, present_h, (size_t)present_w, 1, k, dx, dy, mode, ip_filter, 0xFF000000u)
+                    : jsp_index_present(dec, idx, ip_n, picks.data(), out, cells.size(), present_w, present_h, (size_t)present_w, 1, k, dx, dy, mode, ip_filter, 0xFF000000u)) != JSP_ZERO_STATE ||
+                jsp_download(out, cells.data(), cells.size()) != 0) {
+                std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_present" : "jsp_index_present", jsp_last_error());
+                rc = 1;
+            }
+            for (int i = 0; rc == 0 && i < ip_n; ++i)
+                std::printf("%d %08x\n", picks[i], crc32(reinterpret_cast<const uint8_t*>(cells.data() + cell * (size_t)i), cell * 4));
         }
         if (sheet) jsp_pool_destroy(sheet);
         jsp_sp_index_destroy(sidx);

@@ -426,6 +426,40 @@ void jsp_index_destroy(jsp_index* idx);
 int jsp_index_thumb_size(const jsp_index* idx, int scale, int* width, int* height);
 int jsp_index_thumbs(jsp_codec* c, jsp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels);
 
+/* ---- windows of an index: frames of a seek index straight into a window — the hover preview at the size the UI wants (a 320 x 180
+ * preview of a 1080p clip is k = 1/6, none of the thumbnails' three scales), a scrub at 200 % with the view scrolled, a contact sheet
+ * whose cells are what the page needs — without a full-size frame in between -------------------------------------------------------------
+ * Present: THE PICTURE of frame t is the one jsp_index_thumbs reduces: what jsp_index_show(t) writes into a destination that held
+ *       zeros — every block from the last frame <= t that coded it, else from the index's copy of the picture before the range, else 0;
+ *       the X % 4 / Y % 4 remainder pixels no block covers from that picture, or 0.  Unlike Thumbs the WHOLE X x Y picture takes part,
+ *       remainders included.
+ *   EQUIVALENCE  cell i of the sheet holds exactly the win_w x win_h ints that
+ *         jsp_display_present(P, X, Y, cell, win_w, win_h, out_pitch, k, dx, dy, mode, filter, background)        (filter 0 or 1)
+ *         jsp_display_present_area(P, X, Y, cell, win_w, win_h, out_pitch, k, dx, dy, mode, background)           (filter JSP_PRESENT_AREA)
+ *       write for P = the picture of frames[i]: THE RULE of jsp_display_present / jsp_display_present_area below — geometry, which
+ *       pixels are picture, taps, weights, rounding and `background` — is not restated here.  All three filter values are taken.
+ *       jsp_view_matrix supplies k, dx, dy as it does for those calls.
+ *   SHEET  cell i has its pixel (0, 0) at (i / cols) * win_h * out_pitch + (i % cols) * win_w; out_pitch >= cols * win_w.  The sheet
+ *       occupies (ceil(n / cols) * win_h - 1) * out_pitch + cols * win_w ints and out_ints must be at least that.  Only cell pixels
+ *       are written: pitch padding, the cells of the last sheet row past n and memory behind the sheet are not.  frames[] is any list
+ *       of frames of the index: unordered, repeats allowed.  n = 1, cols = 1 is the plain window.  `out` needs no alignment (cell rows
+ *       that all start on 16-byte boundaries get 16-byte stores).
+ *   ONE kernel launch whatever n (msv1_index_present_kernel): a workgroup composes the source pixels one rectangle of a cell reaches
+ *       into a 64 x 64 tile of on-chip memory and resamples from there, tile by tile where the rectangle reaches further; no full-size
+ *       picture is written anywhere and no frame buffer is touched.  Runs on the codec's stream and returns synchronised.  THE CODEC
+ *       IS ONLY LENT, as for Thumbs: its state, previous frame and per-row flags stay as they were.  The frame list travels through
+ *       pinned memory into the device array of jsp_index_thumbs (grown on demand, counted in jsp_index_info); the index grows by
+ *       nothing the size of a picture.
+ *   BOUNDS  n 1..4096; win_w, win_h 1..16384; 1/64 <= k <= 64; mode one of the four JSP_DISPLAY_*; filter 0, 1 or 2; cols >= 1.
+ *   PRECONDITIONS  `out` is a device buffer of at least out_ints ints; no asynchronous frame in flight.
+ *   ERRORS  A null argument, a ScreenPressor codec ("index: MSVideo1 only"), an index built by another codec, n, a size, k, mode,
+ *       filter or cols outside its bounds, a non-finite k, dx or dy, a frame number outside the index, out_pitch < cols * win_w,
+ *       out_ints below the sheet, a host-pointer `out`, an asynchronous frame in flight: JSP_ERROR_OCCURED, jsp_last_error()
+ *       ("index_present:" ...), before anything is queued: nothing changed, nothing written. */
+int jsp_index_present(jsp_codec* c, jsp_index* idx, int n, const int* frames,
+                      int32_t* out, size_t out_ints, int win_w, int win_h, size_t out_pitch, int cols,
+                      double k, double dx, double dy, int mode, int filter, uint32_t background);
+
 /* ---- playback from an MSVideo1 index: reverse play and the step-back button held down, xs fast-forward, filling the free frame
  * buffers around the frame of interest — a run of frames of the index, each into a buffer of its own ----------------------------------
  * Play: EQUIVALENCE  for k = 0 .. n-1 let t_k = first + k * stride.  dsts[k] ends exactly as jsp_index_show(c, idx, t_k, dsts[k], 0, ..)
@@ -525,6 +559,22 @@ void jsp_sp_index_destroy(jsp_sp_index* idx);
  *       / "sp_index_thumb_size:" ...), nothing written. */
 int jsp_sp_index_thumb_size(const jsp_sp_index* idx, int scale, int* width, int* height);
 int jsp_sp_index_thumbs(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels);
+
+/* ---- windows of a ScreenPressor index: jsp_index_present for a jsp_sp_index, the same contract wherever it can be ---------------------
+ * Present: THE PICTURE of frame t is what jsp_sp_index_show(t) writes, all X x Y pixels of it.
+ *   EQUIVALENCE, SHEET, BOUNDS, PRECONDITIONS  as jsp_index_present: cell i holds exactly the ints jsp_display_present (filter 0 / 1)
+ *       or jsp_display_present_area (filter JSP_PRESENT_AREA) writes for the picture of frames[i] — THE RULE of those two calls.  For
+ *       16 bpp the conversion that gives canvas pixels is JSP_DISPLAY_CANVAS_RGB15, as for a frame.
+ *   ONE kernel launch whatever n (sp_index_present_kernel): per 16x16 block of a rectangle's source tile the walk of
+ *       sp_index_show_kernel, into on-chip memory; no full-size picture is written anywhere.  Runs on the codec's stream and returns
+ *       synchronised.  THE CODEC IS ONLY LENT, as for Show; and since no frame buffer is written, the codec forgets nothing: its
+ *       state, previous frame, entropy state and remembered columns stay as they were.  The per-cell records are those of
+ *       jsp_sp_index_thumbs and travel the same way, into the same device array (grown on demand, counted in jsp_sp_index_info).
+ *   ERRORS  as jsp_index_present, with an MSVideo1 codec for the wrong kind ("sp_index: ScreenPressor only"); jsp_last_error()
+ *       starts with "sp_index_present:" otherwise.  Nothing queued, nothing changed, nothing written. */
+int jsp_sp_index_present(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames,
+                         int32_t* out, size_t out_ints, int win_w, int win_h, size_t out_pitch, int cols,
+                         double k, double dx, double dy, int mode, int filter, uint32_t background);
 
 /* ---- playback from a ScreenPressor index: play on from a shown frame, reverse play, fast-forward by `stride`, filling the free frame
  * buffers around the frame of interest in one go — a run of frames of the index, each into a buffer of its own ---------------------------

@@ -112,6 +112,10 @@ SIGNATURES = {
     "jsp_sp_index_play": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "jsp_index_thumb_size": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "jsp_index_thumbs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "jsp_index_present": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t,
+                                    C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint32]),
+    "jsp_sp_index_present": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t,
+                                       C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint32]),
     "jsp_display_convert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "jsp_view_matrix": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

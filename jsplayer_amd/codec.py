@@ -456,13 +456,49 @@ class _IndexThumbs:
         return out.reshape(-1)[:rows * width].reshape(rows, width)
 
 
-class SeekIndex(_IndexThumbs):
+class _IndexPresent:
+    """Present of a seek index, MSVideo1 or ScreenPressor: the two C calls have one contract (jsp_index_present), so the sheet
+    arithmetic is here once.  A subclass names its C function in `_PRESENT_CALL` and has `_open(who)` and `_present_mode()`."""
+
+    _PRESENT_CALL = ""   # export of the library, without the "jsp_" in front
+
+    def _present_mode(self) -> int:
+        return 0   # DISPLAY_CANVAS
+
+    def Present(self, frames, win_w: int, win_h: int, k: float, dx: float, dy: float, mode: Optional[int] = None, filter: int = 1,
+                background: int = 0xFF000000, cols: int = 1, out=None):
+        """The win_w x win_h windows of `frames` (any frame numbers of the index: unordered, repeats allowed, 1..4096 of them)
+        under the display matrix (k, dx, dy) of view_matrix, `cols` to a sheet row: cell i is exactly what display_present
+        (filter PRESENT_NEAREST / PRESENT_BILINEAR, the default) or display_present_area (PRESENT_AREA) writes for the picture of
+        frames[i] — ONE launch, no full-size picture, no frame buffer written, the codec not touched.  `mode` defaults to the
+        conversion that gives canvas pixels.  Returns the sheet, an int32 device tensor of shape (ceil(n / cols) * win_h,
+        cols * win_w), top row first — `out` (contiguous, at least that many elements, row pitch cols * win_w; cells of the last
+        row past n keep what they held) or a new zero-filled one."""
+        codec = self._open(self._PRESENT_CALL)
+        frames = [int(t) for t in frames]
+        n, cols, win_w, win_h = len(frames), int(cols), int(win_w), int(win_h)
+        rows, width = -(-n // max(cols, 1)) * max(win_h, 0), max(cols, 1) * max(win_w, 0)
+        if out is None:
+            import torch
+            out = torch.zeros(max(rows * width, 1), dtype=torch.int32, device=f"cuda:{codec._device}")
+        arr = (C.c_int * max(n, 1))(*frames)
+        rc = getattr(self._lib, "jsp_" + self._PRESENT_CALL)(
+            codec._h, self._h, n, arr, C.c_void_p(_frame_ptr(out, 0)), int(np.prod(out.shape)), win_w, win_h, width, cols,
+            float(k), float(dx), float(dy), self._present_mode() if mode is None else int(mode), int(filter), int(background) & 0xFFFFFFFF)
+        if rc != 0:
+            raise CodecError(N.last_error())
+        return out.reshape(-1)[:rows * width].reshape(rows, width)
+
+
+class SeekIndex(_IndexThumbs, _IndexPresent):
     """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch, Play(first, dsts, stride) one launch for
-    a run of frames, each into a buffer of its own (jsp_index_play).  `significance` = FindChange's verdict
+    a run of frames, each into a buffer of its own (jsp_index_play), Present(frames, ...) one launch for the windows of any
+    frames (jsp_index_present).  `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
     ADOPTS = True   # Show(adopt=True) leaves the decoder at frame t: a Manager moves its decode position with it
     _THUMB_CALLS = ("index_thumb_size", "index_thumbs")
+    _PRESENT_CALL = "index_present"
 
     def __init__(self, codec: _NativeCodec, handle: int, prev_at_build):
         self._codec, self._h = codec, handle
@@ -581,6 +617,7 @@ class ScreenPressor(_NativeCodec):
 
     def __init__(self, width: int, height: int, bits_per_pixel: int, device: int = 0):
         super().__init__(width, height, bits_per_pixel, None, device)
+        self.bpp = int(bits_per_pixel)
 
     def BuildScrubIndex(self, srcs: Sequence, is_key: Optional[Sequence[bool]] = None, key_row: int = INSIGNIFICANT_LINES) -> "SpScrubIndex":
         """The host entropy stage over the frames `srcs` ONCE (srcs[0] a coded key frame), its records kept in HBM
@@ -599,15 +636,20 @@ class ScreenPressor(_NativeCodec):
         return SpScrubIndex(self, h)
 
 
-class SpScrubIndex(_IndexThumbs):
+class SpScrubIndex(_IndexThumbs, _IndexPresent):
     """A ScreenPressor range resident in HBM (jsp_sp_index_build, via ScreenPressor.BuildScrubIndex): Show(t) is one launch,
     Play(first, dsts, stride) one launch for a run of frames played forward from any frame (jsp_sp_index_play),
-    Thumbs(frames) one launch for any number of downscaled frames (jsp_sp_index_thumbs; _IndexThumbs has the two methods).
+    Thumbs(frames) one launch for any number of downscaled frames (jsp_sp_index_thumbs; _IndexThumbs has the two methods),
+    Present(frames, ...) one launch for their windows of any size (jsp_sp_index_present; _IndexPresent).
     `significance` = the verdict the sequential run records for every frame, `frames`, `device_bytes`, `host_bytes`.  close() (or
     the context manager) frees it; safe after the codec is gone."""
 
     ADOPTS = False   # Show never moves the decoder: a Manager serves the frame and leaves its decode position where it is
     _THUMB_CALLS = ("sp_index_thumb_size", "sp_index_thumbs")
+    _PRESENT_CALL = "sp_index_present"
+
+    def _present_mode(self) -> int:   # 16-bpp frames hold 5-bit components (Manager.hx:121), as Manager.present chooses it
+        return 1 if getattr(self._codec, "bpp", 0) == 16 else 0   # DISPLAY_CANVAS_RGB15 / DISPLAY_CANVAS
 
     def __init__(self, codec: _NativeCodec, handle: int):
         self._codec, self._h = codec, handle

@@ -1,0 +1,91 @@
+// jsp_index_present / jsp_sp_index_present (include/jsplayer_amd.h): what the two calls share on the host — the window's fixed-point
+// geometry, the sheet, the refusals and the output rectangle a workgroup owns.  The kernels are msv1_index_present_kernel
+// (msv1_index_present_kernels.hip) and sp_index_present_kernel (sp_index_present_kernels.hip); what they share on the device is
+// index_present_device.h.  Plain C++: msv1_seek.cpp and sp_index.cpp include it too.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/jsplayer_amd.h"
+
+namespace jsp {
+
+constexpr int kIndexPresentWG = 256;     // lanes per workgroup
+constexpr int kIndexPresentTile = 64;    // a source tile in LDS: 64 x 64 unconverted pixels, 16 KiB
+constexpr int kIndexPresentRun = 4;      // output pixels per lane: one 16-byte store
+
+// One call's window and sheet, as the kernels take them.
+struct IndexPresentArgs {
+    uint32_t* out;
+    size_t pitch;          // ints from one sheet row to the next
+    int cols;              // cells per sheet row
+    int fw, fh, ww, wh;    // picture and window (= cell) size
+    long long ax, ay;      // 16.16 picture coordinates of the centre of a cell's pixel (0, 0)
+    int step;              // 16.16 picture pixels per output pixel
+    uint32_t bg;
+    int rw, rh;            // the output rectangle of a workgroup: rw (a multiple of 4, <= 64) x rh pixels, (rw / 4) * rh <= 256 lanes
+    int vec;               // every cell row starts on a 16-byte boundary
+};
+
+// F(v) of present_kernels.hip: floor(v * 65536 + 0.5) as a 64-bit integer, held at +-2^62
+inline long long index_present_fixed16(double v) {
+    const double f = std::floor(v * 65536.0 + 0.5), lim = 4611686018427387904.0;
+    if (f >= lim) return 1ll << 62;
+    if (f <= -lim) return -(1ll << 62);
+    return (long long)f;
+}
+
+// What of the call can be refused without the codec or the index (null when nothing is wrong): the BOUNDS of the header, the sheet.
+inline const char* index_present_refusal(int n, size_t out_ints, int win_w, int win_h, size_t out_pitch, int cols, double k, double dx, double dy,
+                                         int mode, int filter) {
+    if (n < 1 || n > 4096) return "n is outside 1..4096";
+    if (win_w < 1 || win_w > 16384 || win_h < 1 || win_h > 16384) return "window size outside 1..16384";
+    if (!std::isfinite(k) || !std::isfinite(dx) || !std::isfinite(dy)) return "k, dx, dy must be finite";
+    if (k < 1.0 / 64.0 || k > 64.0) return "k outside 1/64..64";
+    if (mode < JSP_DISPLAY_CANVAS || mode > JSP_DISPLAY_SETPIXELS_RGB15) return "unknown mode";
+    if (filter != JSP_PRESENT_NEAREST && filter != JSP_PRESENT_BILINEAR && filter != JSP_PRESENT_AREA) return "unknown filter";
+    if (cols < 1) return "cols must be at least 1";
+    if ((uint64_t)out_pitch / (uint64_t)win_w < (uint64_t)cols) return "out_pitch below cols * win_w";
+    const uint64_t sheet_rows = ((uint64_t)n + (uint64_t)cols - 1) / (uint64_t)cols;
+    // (rows * win_h <= 2^26 and cols * win_w <= out_pitch: the products below overflow only with out_pitch beyond 2^37, which no out_ints covers)
+    const long double sheet = (long double)(sheet_rows * (uint64_t)win_h - 1) * (long double)out_pitch + (long double)cols * (long double)win_w;
+    if ((long double)out_ints < sheet) return "out_ints is smaller than the sheet";
+    return nullptr;
+}
+
+// Source pixels, per axis, that the taps or footprints of m consecutive output pixels reach at most.
+inline long long index_present_reach(int m, int step, int filter) {
+    const long long span = (((long long)(m - 1) * step) >> 16) + 2;   // from the first tap of the first pixel to that of the last
+    if (filter == JSP_PRESENT_NEAREST) return span;
+    if (filter == JSP_PRESENT_BILINEAR) return span + 1;
+    return span + (step >> 16) + 2;
+}
+
+// The arguments of a validated call.  `align`: what the kernel aligns a source tile's origin down to (the codec's block size), so a
+// rectangle's source pixels fit ONE tile when they reach kIndexPresentTile - align pixels at most per axis; the rectangle is the
+// largest such, at least 4 x 1 (then the kernel loops over tiles).
+inline IndexPresentArgs index_present_args(int32_t* out, int n, int fw, int fh, int win_w, int win_h, size_t out_pitch, int cols, double k, double dx,
+                                           double dy, int filter, uint32_t background, int align) {
+    IndexPresentArgs a{};
+    a.out = reinterpret_cast<uint32_t*>(out);
+    a.pitch = out_pitch;
+    a.cols = cols;
+    a.fw = fw; a.fh = fh; a.ww = win_w; a.wh = win_h;
+    a.step = (int)index_present_fixed16(1.0 / k);                        // 1024 .. 64 * 65536
+    a.ax = index_present_fixed16((0.5 + dx) / k);
+    a.ay = index_present_fixed16(((double)win_h + dy - 0.5) / k);
+    a.bg = background;
+    const int room = kIndexPresentTile - align;
+    int m = 1;                                                           // output pixels per axis whose source fits one tile
+    while (m < 64 && index_present_reach(m + 1, a.step, filter) <= room) ++m;
+    const int ww4 = (win_w + 3) & ~3;
+    a.rw = std::min(std::max(m & ~3, kIndexPresentRun), std::min(ww4, 64));
+    a.rh = std::max(1, std::min(std::min(m, win_h), kIndexPresentWG / (a.rw / kIndexPresentRun)));
+    const bool one_column = cols == 1 || n == 1;
+    a.vec = ((reinterpret_cast<uintptr_t>(out) & 15) == 0 && (out_pitch & 3) == 0 && (one_column || (win_w & 3) == 0)) ? 1 : 0;
+    return a;
+}
+
+}  // namespace jsp

@@ -1,0 +1,252 @@
+// What msv1_index_present_kernel and sp_index_present_kernel share: a workgroup owns one rectangle of output pixels of one cell of the
+// sheet, composes the source pixels the rectangle's taps or footprints reach into a 64 x 64 tile in LDS (phase 1: the codec's part, a
+// functor), and every lane resamples its four output pixels from the tile (phase 2: here).
+//
+// THE RULE is that of jsp_display_present (filter 0 / 1) and jsp_display_present_area (filter 2), bit for bit.  Their kernels
+// (display_present_kernel in present_kernels.hip, display_present_area_kernel in present_area_kernels.hip) read a frame buffer in
+// global memory row by row and are left as they are; the arithmetic is RESTATED here, names kept — convert, hblend, vblend, Span /
+// footprint / weight, small_quotient, constant_byte — for a source that arrives tile by tile:
+//   nearest   the one tap (X >> 16, Y >> 16), taken from the tile that holds it;
+//   bilinear  the four taps, each kept (unconverted) from the tile that holds it; hblend / vblend after the last tile;
+//   area      S per byte = sum of byte * wx * wy over the footprint, added up tile by tile — integer sums, so the order does not
+//             matter — and floor((S + (D >> 1)) / D) after the last tile.  S < 255 * 2^20 fits 32 bits while step >> 8 <= 1024
+//             (WIDE = false); beyond, S < 2^36 is kept in 64 bits (WIDE = true).
+// A rectangle's source pixels usually fit ONE tile (the host sizes the rectangle so: index_present.h); where they do not — always
+// for area below k of about 1/14 (MSVideo1) or 1/11 (ScreenPressor), where even 4 x 1 pixels reach 4 / k + 4 source pixels — the
+// workgroup loops over the tiles of their bounding box, partial results in registers.  A pixel whose centre lies outside the picture
+// is `background`; a workgroup with no centre inside composes nothing.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "index_present.h"
+
+namespace jsp {
+namespace ipresent {
+namespace {
+
+typedef uint32_t p_u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) uint32_t p_gu32;
+typedef __attribute__((address_space(1))) p_u32x4 p_gu32x4;
+
+constexpr int T = kIndexPresentTile;
+constexpr int RUN = kIndexPresentRun;
+
+// the four conversions of display_kernels.hip's convert(), bit for bit
+template <int MODE>
+__device__ __forceinline__ uint32_t convert(uint32_t c) {
+    if (MODE == JSP_DISPLAY_CANVAS) return 0xFF000000u | ((c & 0xFFu) << 16) | (c & 0xFF00u) | ((c >> 16) & 0xFFu);   // Manager.hx:379
+    if (MODE == JSP_DISPLAY_CANVAS_RGB15) return 0xFF000000u | (c << 3);                                               // :370
+    if (MODE == JSP_DISPLAY_SETPIXELS) return 0xFF000000u | c;                                                         // :351
+    return c << 11;                                                                                                    // :340
+}
+
+// ---- present_kernels.hip: bilinear --------------------------------------------------------------------------------------------
+struct HSum { uint32_t e, o; };
+__device__ __forceinline__ HSum hblend(uint32_t p0, uint32_t p1, uint32_t w) {
+    const uint32_t v = 256u - w;
+    return HSum{(p0 & 0x00FF00FFu) * v + (p1 & 0x00FF00FFu) * w, ((p0 >> 8) & 0x00FF00FFu) * v + ((p1 >> 8) & 0x00FF00FFu) * w};
+}
+__device__ __forceinline__ uint32_t vblend(HSum a, HSum b, uint32_t w) {
+    const uint32_t v = 256u - w;
+    const uint32_t b0 = ((a.e & 0xFFFFu) * v + (b.e & 0xFFFFu) * w + 32768u) >> 16;
+    const uint32_t b2 = ((a.e >> 16) * v + (b.e >> 16) * w + 32768u) >> 16;
+    const uint32_t b1 = ((a.o & 0xFFFFu) * v + (b.o & 0xFFFFu) * w + 32768u) >> 16;
+    const uint32_t b3 = ((a.o >> 16) * v + (b.o >> 16) * w + 32768u) >> 16;
+    return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+}
+// One axis of a covered pixel's taps: centre c16 (16.16, inside the picture), picture size n
+struct Taps { int t0, t1; uint32_t w; };
+__device__ __forceinline__ Taps taps(int c16, int n) {
+    const int U = c16 - 32768;
+    const int t = U >> 16;                                     // -1 .. n - 1
+    return Taps{max(t, 0), min(t + 1, n - 1), (uint32_t)(U & 0xFFFF) >> 8};
+}
+
+// ---- present_area_kernels.hip: area -------------------------------------------------------------------------------------------
+constexpr bool constant_byte(int mode, int b) { return mode == JSP_DISPLAY_SETPIXELS_RGB15 ? b == 0 : b == 3; }
+constexpr uint32_t constant_bits(int mode) { return mode == JSP_DISPLAY_SETPIXELS_RGB15 ? 0u : 0xFF000000u; }
+struct Span { int first, last; uint32_t wf, wl, W; };
+__device__ __forceinline__ Span footprint(int c16, int s, int n) {
+    const int c = c16 >> 8;
+    const int lo = max(c - (s >> 1), 0);
+    const int hi = min(c - (s >> 1) + s, n << 8);
+    Span f;
+    f.first = lo >> 8;
+    f.last = (hi - 1) >> 8;
+    f.W = (uint32_t)(hi - lo);
+    f.wf = (uint32_t)(min(hi, (f.first + 1) << 8) - lo);
+    f.wl = f.last > f.first ? (uint32_t)(hi - (f.last << 8)) : 0u;
+    return f;
+}
+__device__ __forceinline__ uint32_t weight(const Span& f, int x) { return x == f.first ? f.wf : x < f.last ? 256u : x == f.last ? f.wl : 0u; }
+__device__ __forceinline__ uint32_t small_quotient(unsigned long long n, uint32_t d) {
+    uint32_t q = (uint32_t)((float)n / (float)d);
+    long long r = (long long)n - (long long)((unsigned long long)q * d);
+    if (r < 0) { --q; r += d; }
+    if (r >= (long long)d) ++q;
+    return q;
+}
+
+// The source columns (rows) [s0, s1] that the output pixels with centres lo16 .. hi16 (16.16, both inside the picture, n wide) reach:
+// the first tap of the first and the last tap of the last — taps and footprints move monotonically with the centre.
+template <int FILTER>
+__device__ __forceinline__ void reach(int lo16, int hi16, int step, int n, int& s0, int& s1) {
+    if (FILTER == JSP_PRESENT_NEAREST) {
+        s0 = lo16 >> 16;
+        s1 = hi16 >> 16;
+    } else if (FILTER == JSP_PRESENT_BILINEAR) {
+        s0 = taps(lo16, n).t0;
+        s1 = taps(hi16, n).t1;
+    } else {
+        s0 = footprint(lo16, step >> 8, n).first;
+        s1 = footprint(hi16, step >> 8, n).last;
+    }
+}
+
+// The rectangle of the workgroup (blockIdx.x, blockIdx.y) of the cell at `cell`, whole.  `tile`: T * T words of LDS.
+// compose(tx0, ty0, sx0, sy0, sx1, sy1), called by every lane: fill the tile whose pixel (0, 0) is picture pixel (tx0, ty0) — both
+// multiples of ALIGN — with the picture's pixels of [sx0, sx1] x [sy0, sy1] (inside the picture) that it holds; the rest of the tile
+// may hold anything.  The barriers around it are here.
+template <int MODE, int FILTER, bool WIDE, int ALIGN, class Compose>
+__device__ __forceinline__ void present_rect(const IndexPresentArgs& a, uint32_t* cell, const uint32_t* tile, Compose&& compose) {
+    typedef typename std::conditional<WIDE, unsigned long long, uint32_t>::type Sum;
+    const int lanes_x = a.rw / RUN;
+    const int ly = (int)threadIdx.x / lanes_x, lx = (int)threadIdx.x - ly * lanes_x;
+    const int rx0 = (int)blockIdx.x * a.rw, ry0 = (int)blockIdx.y * a.rh;
+    const int rx1 = min(rx0 + a.rw, a.ww), ry1 = min(ry0 + a.rh, a.wh);        // the rectangle: [rx0, rx1) x [ry0, ry1), not empty
+    const int ox0 = rx0 + lx * RUN, oy = ry0 + ly;
+    const bool live = ly < a.rh && ox0 < rx1 && oy < ry1;
+    const int n = live ? min(RUN, a.ww - ox0) : 0;
+    const long long x_end = (long long)a.fw << 16, y_end = (long long)a.fh << 16;
+    const int s = a.step >> 8;
+
+    // ---- the lane's four pixels: covered or not, taps / footprints ----------------------------------------------------------------
+    const long long Y = a.ay - (long long)oy * a.step;
+    const bool iny = live && Y >= 0 && Y < y_end;
+    bool in[RUN];
+    int X16[RUN];
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) {
+        const long long X = a.ax + (long long)(ox0 + j) * a.step;
+        in[j] = iny && j < n && X >= 0 && X < x_end;
+        X16[j] = in[j] ? (int)X : 0;                                           // (covered: X < 2^30)
+    }
+    const int Y16 = iny ? (int)Y : 0;
+    uint32_t px[RUN];                                                          // nearest: the result so far
+    uint32_t tap[RUN][4];                                                      // bilinear: (x0, r0) (x1, r0) (x0, r1) (x1, r1), unconverted
+    Sum S[RUN][4];                                                             // area: the doubly weighted sum per byte so far
+    const Taps ty = taps(Y16, a.fh);
+    const Span cy = footprint(Y16, s, a.fh);
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) {
+        px[j] = a.bg;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { tap[j][b] = 0u; S[j][b] = 0; }
+    }
+
+    // ---- the source pixels the rectangle reaches (workgroup-uniform) --------------------------------------------------------------
+    const long long Xa = a.ax + (long long)rx0 * a.step, Xb = a.ax + (long long)(rx1 - 1) * a.step;      // Xa <= Xb
+    const long long Yb = a.ay - (long long)ry0 * a.step, Ya = a.ay - (long long)(ry1 - 1) * a.step;      // Ya <= Yb
+    if (Xb >= 0 && Xa < x_end && Yb >= 0 && Ya < y_end) {
+        int sx0, sx1, sy0, sy1;
+        reach<FILTER>((int)max(Xa, 0ll), (int)min(Xb, x_end - 1), a.step, a.fw, sx0, sx1);
+        reach<FILTER>((int)max(Ya, 0ll), (int)min(Yb, y_end - 1), a.step, a.fh, sy0, sy1);
+        for (int ty0 = sy0 & ~(ALIGN - 1); ty0 <= sy1; ty0 += T) {
+            for (int tx0 = sx0 & ~(ALIGN - 1); tx0 <= sx1; tx0 += T) {
+                __syncthreads();                                               // (the tile before this one has been read)
+                compose(tx0, ty0, sx0, sy0, sx1, sy1);
+                __syncthreads();
+                auto held = [&](int x, int y) { return (unsigned)(x - tx0) < (unsigned)T && (unsigned)(y - ty0) < (unsigned)T; };
+                auto at = [&](int x, int y) { return tile[(y - ty0) * T + (x - tx0)]; };
+#pragma unroll
+                for (int j = 0; j < RUN; ++j) {
+                    if (!in[j]) continue;
+                    if (FILTER == JSP_PRESENT_NEAREST) {
+                        const int x = X16[j] >> 16, y = Y16 >> 16;
+                        if (held(x, y)) px[j] = convert<MODE>(at(x, y));
+                    } else if (FILTER == JSP_PRESENT_BILINEAR) {
+                        const Taps tx = taps(X16[j], a.fw);
+                        if (held(tx.t0, ty.t0)) tap[j][0] = at(tx.t0, ty.t0);
+                        if (held(tx.t1, ty.t0)) tap[j][1] = at(tx.t1, ty.t0);
+                        if (held(tx.t0, ty.t1)) tap[j][2] = at(tx.t0, ty.t1);
+                        if (held(tx.t1, ty.t1)) tap[j][3] = at(tx.t1, ty.t1);
+                    } else {
+                        const Span cx = footprint(X16[j], s, a.fw);
+                        const int xa = max(cx.first, tx0), xb = min(cx.last, tx0 + T - 1);
+                        const int ya = max(cy.first, ty0), yb = min(cy.last, ty0 + T - 1);
+                        for (int y = ya; y <= yb; ++y) {
+                            uint32_t r[4] = {0u, 0u, 0u, 0u};                  // a row of the tile: 64 * 255 * 256 < 2^22 per byte
+                            for (int x = xa; x <= xb; ++x) {
+                                const uint32_t p = convert<MODE>(at(x, y)), wx = weight(cx, x);
+#pragma unroll
+                                for (int b = 0; b < 4; ++b)
+                                    if (!constant_byte(MODE, b)) r[b] += ((p >> (8 * b)) & 0xFFu) * wx;
+                            }
+                            const uint32_t wy = weight(cy, y);
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) S[j][b] += (Sum)r[b] * wy;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (!live) return;
+
+    // ---- finish and store -------------------------------------------------------------------------------------------------------------
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) {
+        if (!in[j]) continue;
+        if (FILTER == JSP_PRESENT_BILINEAR) {
+            const uint32_t wx = taps(X16[j], a.fw).w;
+            px[j] = vblend(hblend(convert<MODE>(tap[j][0]), convert<MODE>(tap[j][1]), wx),
+                           hblend(convert<MODE>(tap[j][2]), convert<MODE>(tap[j][3]), wx), ty.w);
+        } else if (FILTER == JSP_PRESENT_AREA) {
+            const uint32_t D = footprint(X16[j], s, a.fw).W * cy.W;            // <= 2^28
+            uint32_t v = constant_bits(MODE);
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (!constant_byte(MODE, b)) v |= small_quotient((unsigned long long)S[j][b] + (D >> 1), D) << (8 * b);
+            px[j] = v;
+        }
+    }
+    uint32_t* d = cell + (size_t)oy * a.pitch + ox0;
+    if (a.vec && n == RUN) {
+        __builtin_nontemporal_store(p_u32x4{px[0], px[1], px[2], px[3]}, (p_gu32x4*)d);
+    } else {
+#pragma unroll
+        for (int j = 0; j < RUN; ++j)
+            if (j < n) *(p_gu32*)(d + j) = px[j];
+    }
+}
+
+// the cell of blockIdx.z
+__device__ __forceinline__ uint32_t* sheet_cell(const IndexPresentArgs& a) {
+    const unsigned z = blockIdx.z, row = z / (unsigned)a.cols, col = z - row * (unsigned)a.cols;
+    return a.out + (size_t)row * (size_t)a.wh * a.pitch + (size_t)col * (size_t)a.ww;
+}
+
+// Host: f(integral_constant<int, FILTER>, bool_constant<WIDE>) for the instantiation `filter` and `step` select.
+template <class F>
+inline void dispatch_filter(int filter, int step, F&& f) {
+    if (filter == JSP_PRESENT_NEAREST) f(std::integral_constant<int, JSP_PRESENT_NEAREST>{}, std::false_type{});
+    else if (filter == JSP_PRESENT_BILINEAR) f(std::integral_constant<int, JSP_PRESENT_BILINEAR>{}, std::false_type{});
+    else if ((step >> 8) <= 1024) f(std::integral_constant<int, JSP_PRESENT_AREA>{}, std::false_type{});
+    else f(std::integral_constant<int, JSP_PRESENT_AREA>{}, std::true_type{});
+}
+template <class F>
+inline void dispatch_mode(int mode, F&& f) {
+    switch (mode) {
+        case JSP_DISPLAY_CANVAS: f(std::integral_constant<int, JSP_DISPLAY_CANVAS>{}); break;
+        case JSP_DISPLAY_CANVAS_RGB15: f(std::integral_constant<int, JSP_DISPLAY_CANVAS_RGB15>{}); break;
+        case JSP_DISPLAY_SETPIXELS: f(std::integral_constant<int, JSP_DISPLAY_SETPIXELS>{}); break;
+        default: f(std::integral_constant<int, JSP_DISPLAY_SETPIXELS_RGB15>{}); break;
+    }
+}
+inline dim3 present_grid(const IndexPresentArgs& a, int n) {
+    return dim3((unsigned)((a.ww + a.rw - 1) / a.rw), (unsigned)((a.wh + a.rh - 1) / a.rh), (unsigned)n);
+}
+
+}  // namespace
+}  // namespace ipresent
+}  // namespace jsp

@@ -1,6 +1,6 @@
 // What the MSVideo1 block kernels (msv1_kernels.hip, msv1_seek_kernels.hip) share around decode_block (msv1_decode.h): a block's row
 // loads and stores, the look-before-OR of a significance word, the pixels no block covers, the palette prologue, the decode of a
-// code in global memory, and the host's BITS x VEC dispatch.
+// code in global memory, the seek index's last-writer walk, and the host's BITS x VEC dispatch.
 #pragma once
 #include <type_traits>
 
@@ -132,6 +132,27 @@ __device__ __forceinline__ void index_decode(const Msv1IndexChunk* __restrict__ 
     const int lf = f - (int)ch.first;
     const uint32_t o = *(cgu32*)(ch.desc + (size_t)lf * pitch + blk);
     decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
+}
+
+constexpr int INDEX_SCAN = 4;   // bitmap words a lane has in flight per step of its walk down (msv1_seek_kernels.hip's SCAN is this)
+
+// The bitmap word of block `blk` that holds the last frame <= t coding it, masked to the frames <= t (its highest set bit is that
+// frame: 32 * w + 31 - clz; w is set), or 0 when nothing up to t coded the block.  Word t / 32 first, then the words below it,
+// INDEX_SCAN in flight per step.  Shared by the show, play, thumbnail and present kernels.
+__device__ __forceinline__ uint32_t index_last_writer(const uint32_t* __restrict__ bitmap, int nblocks, int blk, int t, int& w) {
+    w = t >> 5;
+    uint32_t m = *(cgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
+    while (m == 0u && w > 0) {
+        uint32_t e[INDEX_SCAN];
+#pragma unroll
+        for (int k = 0; k < INDEX_SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(cgu32*)(bitmap + (size_t)(w - 1 - k) * (size_t)nblocks + blk) : 0u;
+        int step = INDEX_SCAN;
+#pragma unroll
+        for (int k = INDEX_SCAN - 1; k >= 0; --k)
+            if (e[k] != 0u) { m = e[k]; step = k + 1; }
+        w -= step;
+    }
+    return m;
 }
 
 // Host: f(std::integral_constant<int, BITS>{}, std::bool_constant<VEC>{}) for the kernel instantiation that `bits` (16, else 8) and

@@ -29,7 +29,7 @@ struct jsp_index {
     int first_adopted = 0;                 // the first frame that adopts its destination (nframes: none)
     int32_t* prev_caller = nullptr;        // the codec's previous frame at build time (what a show before first_adopted leaves)
     int32_t* prev_dev = nullptr;
-    PinnedBuffer h_thumb_frames;           // jsp_index_thumbs: the call's frame list on its way to ...
+    PinnedBuffer h_thumb_frames;           // jsp_index_thumbs / jsp_index_present: the call's frame list on its way to ...
     DeviceBuffer d_thumb_frames;           // ... the array the kernel reads (both grown on demand)
     PinnedBuffer h_play_dsts;              // jsp_index_play: the call's destinations on their way to ...
     DeviceBuffer d_play_dsts;              // ... the array the kernel reads (both grown on demand; nothing until the first call)
@@ -669,6 +669,45 @@ extern "C" int jsp_index_thumbs(jsp_codec* c, jsp_index* idx, int n, const int* 
                                  static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p),
                                  static_cast<const int32_t*>(idx->d_thumb_frames.p), n, scale, cols, out,
                                  idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, c->stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned list is free for the next call)
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- windows: the hover preview at the size the UI wants, a scrub at 200 % with the view scrolled, a contact sheet — the windows
+// jsp_display_present / jsp_display_present_area would show of n frames of the index, on one sheet, in ONE launch of
+// msv1_index_present_kernel.  The full-size pictures never exist and no frame buffer is written; the codec is only lent, as for the
+// thumbnails, and the frame list travels the thumbnails' way.
+extern "C" int jsp_index_present(jsp_codec* c, jsp_index* idx, int n, const int* frames, int32_t* out, size_t out_ints, int win_w, int win_h,
+                                 size_t out_pitch, int cols, double k, double dx, double dy, int mode, int filter, uint32_t background) {
+    if (!c || !idx || !frames || !out) return fail("index_present: null argument");
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_present: the index was built by another codec");
+    if (const char* why = index_present_refusal(n, out_ints, win_w, win_h, out_pitch, cols, k, dx, dy, mode, filter)) return fail("index_present: %s", why);
+    for (int i = 0; i < n; ++i)
+        if (frames[i] < 0 || frames[i] >= idx->nframes) return fail("index_present: a frame number is outside the index");
+    if (idx->geo.X < 1 || idx->geo.Y < 1) return fail("index_present: the index has no picture");
+    if (!nothing_in_flight(c, "index_present")) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, out) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
+            (void)hipGetLastError();
+            return fail("index_present: out must be a device buffer");
+        }
+        idx->h_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
+        idx->d_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
+        std::copy(frames, frames + n, static_cast<int32_t*>(idx->h_thumb_frames.p));
+        JSP_HIP(hipMemcpyAsync(idx->d_thumb_frames.p, idx->h_thumb_frames.p, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        const IndexPresentArgs a = index_present_args(out, n, idx->geo.X, idx->geo.Y, win_w, win_h, out_pitch, cols, k, dx, dy, filter, background, 4);
+        msv1_launch_index_present(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
+                                  static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p),
+                                  static_cast<const int32_t*>(idx->d_thumb_frames.p), n,
+                                  idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, a, mode, filter, c->stream);
         JSP_HIP(hipGetLastError());
         JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned list is free for the next call)
         return JSP_ZERO_STATE;

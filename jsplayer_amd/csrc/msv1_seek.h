@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "common.h"
+#include "index_present.h"
 #include "msv1.h"
 
 struct jsp_staged;
@@ -88,5 +89,11 @@ int msv1_index_play_auto_segments(const Msv1Geometry& geo, int n);
 void msv1_launch_index_thumbs(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
                               const uint32_t* d_bitmap, const int32_t* d_frames, int n, int scale, int cols, int32_t* out, const int32_t* before,
                               hipStream_t stream);
+// ONE launch of msv1_index_present_kernel (msv1_index_present_kernels.hip): the windows `a` describes of the pictures of index frames
+// d_frames[0..n) (a device array) — the pictures msv1_launch_index_show writes into a destination that held zeros, remainder pixels
+// included — converted by `mode` and resampled by `filter` (0, 1 or JSP_PRESENT_AREA) into the cells of the sheet a.out.
+void msv1_launch_index_present(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                               const uint32_t* d_bitmap, const int32_t* d_frames, int n, const int32_t* before, const IndexPresentArgs& a, int mode,
+                               int filter, hipStream_t stream);
 
 }  // namespace jsp

@@ -19,7 +19,7 @@ namespace jsp {
 namespace {
 
 constexpr int WG = 256;
-constexpr int SCAN = 4;   // table entries a lane has in flight per step of its backward walk
+constexpr int SCAN = INDEX_SCAN;   // table entries a lane has in flight per step of its backward walk: the index walk's (msv1_block_io.h), 4
 
 // The last frame <= `from` whose table codes block `blk` (its code offset in `o`), or -1.
 __device__ __forceinline__ int last_writer(const uint32_t* __restrict__ desc, size_t pitch, int blk, int from, uint32_t& o) {
@@ -214,24 +214,7 @@ __global__ __launch_bounds__(WG) void msv1_coded_bitmap_kernel(const uint32_t* _
     }
 }
 
-// The bitmap word of block `blk` that holds the last frame <= t coding it, masked to the frames <= t (its highest set bit is that
-// frame: 32 * w + 31 - clz; w is set), or 0 when nothing up to t coded the block.  Word t / 32 first, then the words below it, SCAN in flight
-// per step.  Shared by the show and the thumbnail kernel.
-__device__ __forceinline__ uint32_t index_last_writer(const uint32_t* __restrict__ bitmap, int nblocks, int blk, int t, int& w) {
-    w = t >> 5;
-    uint32_t m = *(cgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
-    while (m == 0u && w > 0) {
-        uint32_t e[SCAN];
-#pragma unroll
-        for (int k = 0; k < SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(cgu32*)(bitmap + (size_t)(w - 1 - k) * (size_t)nblocks + blk) : 0u;
-        int step = SCAN;
-#pragma unroll
-        for (int k = SCAN - 1; k >= 0; --k)
-            if (e[k] != 0u) { m = e[k]; step = k + 1; }
-        w -= step;
-    }
-    return m;
-}
+// (index_last_writer, which the show, play and thumbnail kernels share with msv1_index_present_kernel: msv1_block_io.h)
 
 // Show frame t: one work-item per block, as msv1_seek_kernel.  The lane masks bitmap word t / 32 to the frames <= t and walks the words
 // downwards (SCAN in flight per step) to the first non-zero one: its highest set bit is the last frame <= t that coded the block.  That

@@ -19,6 +19,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "index_present.h"
 #include "sp_entropy.h"
 
 namespace jsp::sp {
@@ -300,6 +301,11 @@ static_assert(sizeof(IndexThumbRec) == 24, "IndexThumbRec is 24 bytes");
 void launch_index_thumbs(const Geometry& g, int32_t* out, const int32_t* d_keys, size_t pic_stride, const IndexThumbRec* d_recs, int n,
                          const PBlock* d_blocks, const uint32_t* d_payload, const uint32_t* d_bitmap, int scale, int cols,
                          hipStream_t stream);
+// Windows of the seek index (sp_index_present_kernel, sp_index_present_kernels.hip): the windows `a` describes of the pictures
+// launch_index_show would write for d_recs[0..n), converted by `mode` and resampled by `filter` (0, 1 or JSP_PRESENT_AREA) into the cells
+// of the sheet a.out.  ONE launch; no full-size picture is written.
+void launch_index_present(const Geometry& g, const int32_t* d_keys, size_t pic_stride, const IndexThumbRec* d_recs, int n, const PBlock* d_blocks,
+                          const uint32_t* d_payload, const uint32_t* d_bitmap, const IndexPresentArgs& a, int mode, int filter, hipStream_t stream);
 // Playback from the seek index (sp_index_play_kernel): the pictures launch_index_show would write for frames first, first + stride, ...,
 // first + (n - 1) * stride, into d_dsts[0..n) — ONE launch.  A wave composes frame `first` of its block as the show kernel does, then
 // carries the pixels forward in registers: a set bitmap bit is a literal rectangle laid over them, a key frame (d_keymask, bit j of word w:

@@ -30,7 +30,7 @@ struct jsp_sp_index {
     std::vector<int32_t> key_slot;   // per frame: which picture of d_keys that is
     std::vector<int64_t> slot_base;  // per frame: its block table is d_blocks + (frame + slot_base) * nblocks (key frames: unused)
     std::vector<int> significance;   // per frame: the verdict of the sequential run (1 / 0)
-    PinnedBuffer h_thumb_recs;       // jsp_sp_index_thumbs: the call's per-thumbnail records on their way to ...
+    PinnedBuffer h_thumb_recs;       // jsp_sp_index_thumbs / jsp_sp_index_present: the call's per-cell records on their way to ...
     DeviceBuffer d_thumb_recs;       // ... the array the kernel reads (both grown on demand: nothing until the first call)
     DeviceBuffer d_play_frames;      // jsp_sp_index_play: an IndexPlayFrame per frame, then the key-frame mask (nothing until the first call)
     PinnedBuffer h_play_dsts;        // jsp_sp_index_play: the call's destinations on their way to ...
@@ -398,6 +398,42 @@ extern "C" int jsp_sp_index_thumbs(jsp_codec* c, jsp_sp_index* idx, int n, const
         launch_index_thumbs(idx->geo, out, static_cast<const int32_t*>(idx->d_keys.p), idx->pic_stride,
                             static_cast<const IndexThumbRec*>(idx->d_thumb_recs.p), n, static_cast<const PBlock*>(idx->d_blocks.p),
                             static_cast<const uint32_t*>(idx->d_payload.p), static_cast<const uint32_t*>(idx->d_bitmap.p), scale, cols, c->stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned records are free for the next call)
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- windows: the windows jsp_display_present / jsp_display_present_area would show of n frames of the index, on one sheet, in ONE
+// launch of sp_index_present_kernel.  As for the thumbnails the full-size pictures never exist and no frame buffer is written, so the
+// codec is lent its stream and nothing else (no forget_buffer); the per-cell records are the thumbnails' and travel their way.
+extern "C" int jsp_sp_index_present(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames, int32_t* out, size_t out_ints, int win_w, int win_h,
+                                    size_t out_pitch, int cols, double k, double dx, double dy, int mode, int filter, uint32_t background) {
+    if (!c || !idx || !frames || !out) return fail("sp_index_present: null argument");
+    if (c->kind != JSP_CODEC_SCREENPRESSOR || !dynamic_cast<IndexLender*>(c)) return fail("sp_index: ScreenPressor only");
+    if (idx->codec_serial != c->serial) return fail("sp_index_present: the index was built by another codec");
+    if (const char* why = index_present_refusal(n, out_ints, win_w, win_h, out_pitch, cols, k, dx, dy, mode, filter)) return fail("sp_index_present: %s", why);
+    for (int i = 0; i < n; ++i)
+        if (frames[i] < 0 || frames[i] >= idx->nframes) return fail("sp_index_present: a frame number is outside the index");
+    if (c->next_ticket != c->oldest_ticket) return fail("sp_index_present: an asynchronous frame is in flight (jsp_wait for it first)");
+    try {
+        c->activate();
+        if (!on_device(out)) return fail("sp_index_present: out must be a device buffer");
+        idx->h_thumb_recs.reserve(sizeof(IndexThumbRec) * (size_t)n);
+        idx->d_thumb_recs.reserve(sizeof(IndexThumbRec) * (size_t)n);
+        auto* recs = static_cast<IndexThumbRec*>(idx->h_thumb_recs.p);
+        for (int i = 0; i < n; ++i) {
+            const size_t t = (size_t)frames[i];
+            recs[i] = IndexThumbRec{frames[i], idx->key_of[t], (uint32_t)idx->key_slot[t], 0u, idx->slot_base[t]};
+        }
+        JSP_HIP(hipMemcpyAsync(idx->d_thumb_recs.p, recs, sizeof(IndexThumbRec) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        const IndexPresentArgs a = index_present_args(out, n, idx->geo.X, idx->geo.Y, win_w, win_h, out_pitch, cols, k, dx, dy, filter, background, 16);
+        launch_index_present(idx->geo, static_cast<const int32_t*>(idx->d_keys.p), idx->pic_stride, static_cast<const IndexThumbRec*>(idx->d_thumb_recs.p),
+                             n, static_cast<const PBlock*>(idx->d_blocks.p), static_cast<const uint32_t*>(idx->d_payload.p),
+                             static_cast<const uint32_t*>(idx->d_bitmap.p), a, mode, filter, c->stream);
         JSP_HIP(hipGetLastError());
         JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned records are free for the next call)
         return JSP_ZERO_STATE;

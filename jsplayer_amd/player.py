@@ -215,6 +215,44 @@ class Manager:
         sheet = self.index.Thumbs(picks, scale=scale, cols=n if cols is None else int(cols))
         return [self.index_first + t for t in picks], sheet
 
+    def _index_present_mode(self) -> int:
+        from .codec import DISPLAY_CANVAS, DISPLAY_CANVAS_RGB15
+        return DISPLAY_CANVAS_RGB15 if self.vi.bpp == 16 and self.vi.codec == CODEC_SCREENPRESSOR else DISPLAY_CANVAS
+
+    def present_from_index(self, i: int, out, win_w: int, win_h: int, filter: Optional[int] = None, background: int = 0xFF000000):
+        """The window `self.view` shows of clip frame `i` of the attached index, as canvas pixels, top row first, into the device
+        tensor `out` (win_w * win_h ints): what `present` gives for a buffer holding that frame, straight from the index — one
+        `Present` launch, a pure read as `preview`: no buffer, hold, log entry or decoder state changes.  `filter` as for
+        `present` (None: bilinear; PRESENT_AREA is taken too).  No index attached, `i` outside it, or an index object without
+        `Present`: ValueError."""
+        from .codec import PRESENT_BILINEAR
+        if not self._in_index(i):
+            raise ValueError(f"frame {i} is not in an attached seek index")
+        if not hasattr(self.index, "Present"):
+            raise ValueError("the attached seek index cannot present")
+        k, dx, dy = self.view.matrix(self.vi.X, self.vi.Y, win_w, win_h)
+        return self.index.Present([i - self.index_first], win_w, win_h, k, dx, dy, mode=self._index_present_mode(),
+                                  filter=PRESENT_BILINEAR if filter is None else filter, background=background, cols=1, out=out)
+
+    def contact_sheet(self, n: int, win_w: int, win_h: int, cols: Optional[int] = None, filter: Optional[int] = None):
+        """The `n` frames `filmstrip` picks — clip frame index_first + (k * index.frames) // n for k < n — each Fit into a cell of
+        win_w x win_h canvas pixels, `cols` to a row (None: one row): (clip frame numbers, sheet).  One `Present` launch, a pure
+        read.  `filter` None: PRESENT_AREA, what a shrunk picture needs.  No index attached, or an index object without `Present`:
+        ValueError."""
+        from .codec import PRESENT_AREA, view_matrix
+        if self.index is None:
+            raise ValueError("no seek index attached")
+        if not hasattr(self.index, "Present"):
+            raise ValueError("the attached seek index cannot present")
+        n = int(n)
+        if n < 1:
+            raise ValueError("a contact sheet needs at least one frame")
+        picks = [(k * self.index.frames) // n for k in range(n)]
+        k, dx, dy = view_matrix(self.vi.X, self.vi.Y, win_w, win_h, 0.0)
+        sheet = self.index.Present(picks, win_w, win_h, k, dx, dy, mode=self._index_present_mode(),
+                                   filter=PRESENT_AREA if filter is None else filter, cols=n if cols is None else int(cols))
+        return [self.index_first + t for t in picks], sheet
+
     def _slot_of(self, buf) -> int:
         for i, b in enumerate(self.buffers):
             if b is buf:
