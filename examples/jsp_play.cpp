@@ -37,6 +37,11 @@
 //                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
 //                                8) — the seek bar's hover preview / a contact sheet (Main.on_mouse_move, Main.hx:1147-1215); prints
 //                                "<frame> <crc32 of the thumbnail's words>" per thumbnail
+//   jsp_play clip.avi --index-tensor WxH N[:filter[:dtype[:layout]]]
+//                                ONE seek index over the clip of either codec, then ONE jsp_index_tensor / jsp_sp_index_tensor call: the N
+//                                frames --index-present picks, each Fit into W x H, as a dense tensor (filter 0..2, default 2; dtype f32,
+//                                f16, bf16 or u8, default f32; layout nchw or nhwc, default nchw; scale 1/255, bias 0); prints per frame
+//                                its number and the CRC-32 of its slice of the tensor's bytes
 //   jsp_play clip.avi --index-present WxH[:zoom[:hpos:vpos]] N[:filter]
 //                                ONE seek index over the clip of either codec, then ONE jsp_index_present / jsp_sp_index_present call
 //                                for N frames spread evenly over it (frame (k * frames) / N for k < N): the W x H window of --present
@@ -404,7 +409,7 @@ long play_batched(const Clip& clip, int batch, int repeat, bool quiet, int warmu
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]] | --present-area WxH[:zoom[:hpos:vpos]] | --index-present WxH[:zoom[:hpos:vpos]] N[:filter]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]] | --present-area WxH[:zoom[:hpos:vpos]] | --index-present WxH[:zoom[:hpos:vpos]] N[:filter] | --index-tensor WxH N[:filter[:dtype[:layout]]]\n", argv[0]); return 2; }
     // (throughput runs: several files, separated by commas — stream s plays file s modulo their number, so that the streams of a
     // multi-stream run are independent inputs)
     std::deque<Clip> clips;                                   // (a deque: elements never move)
@@ -433,6 +438,7 @@ int main(int argc, char** argv) {
     double present_zoom = 0, present_hpos = 0.5, present_vpos = 0.5;
     bool present_area = false;                                // --present-area: the window from jsp_display_present_area
     int ip_n = 0, ip_filter = JSP_PRESENT_BILINEAR;           // --index-present WxH[:zoom[:hpos:vpos]] N[:filter]: N windows out of a seek index, one sheet
+    int it_dtype = -1, it_layout = JSP_TENSOR_NCHW;           // --index-tensor WxH N[:filter[:dtype[:layout]]]: the same N frames, Fit, as one dense tensor
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -487,6 +493,21 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (o == "--index-tensor" && a + 2 < argc) {
+            const std::string v = argv[++a], m = argv[++a];
+            char dt[8] = "f32", lay[8] = "nchw", tail = 0;
+            ip_filter = JSP_PRESENT_AREA;
+            const int got = std::sscanf(v.c_str(), "%dx%d%c", &present_w, &present_h, &tail);
+            const int got_n = std::sscanf(m.c_str(), "%d:%d:%7[a-z0-9]:%7[a-z]%c", &ip_n, &ip_filter, dt, lay, &tail);
+            const std::string d = dt, l = lay;
+            it_dtype = d == "f32" ? JSP_TENSOR_F32 : d == "f16" ? JSP_TENSOR_F16 : d == "bf16" ? JSP_TENSOR_BF16 : d == "u8" ? JSP_TENSOR_U8 : -1;
+            it_layout = l == "nchw" ? JSP_TENSOR_NCHW : l == "nhwc" ? JSP_TENSOR_NHWC : -1;
+            if (got != 2 || present_w < 1 || present_h < 1 || got_n < 1 || got_n > 4 || ip_n < 1 || ip_n > 4096 || ip_filter < 0 || ip_filter > 2 || it_dtype < 0 ||
+                it_layout < 0) {
+                std::fprintf(stderr, "--index-tensor: WxH N[:filter[:dtype[:layout]]], N 1..4096, filter 0..2, dtype f32|f16|bf16|u8, layout nchw|nhwc\n");
+                return 2;
+            }
+        }
         else if (o == "--devices" && a + 1 < argc) {
             const std::string list = argv[++a];
             for (size_t at = 0; at <= list.size();) {
@@ -506,7 +527,7 @@ int main(int argc, char** argv) {
     if (play_first >= 0 && clip.kind != JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--play-index: ScreenPressor only (an MSVideo1 index adopts: --seek and the plain run play on from any frame)\n"); return 2; }
     if (run_first >= 0 && (play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--index-run goes alone\n"); return 2; }
     if (run_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--index-run: MSVideo1 only (--play-index plays a ScreenPressor index)\n"); return 2; }
-    if (ip_n > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--index-present goes alone\n"); return 2; }
+    if (ip_n > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "%s goes alone\n", it_dtype >= 0 ? "--index-tensor" : "--index-present"); return 2; }
     if (ip_n == 0 && present_w > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--present goes with the plain per-frame run\n"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
@@ -856,15 +877,30 @@ int main(int argc, char** argv) {
         jsp_index* idx = rc == 0 && n && !sp ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
         jsp_sp_index* sidx = rc == 0 && n && sp ? jsp_sp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
         if (rc == 0 && !idx && !sidx) { std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_build" : "jsp_index_build", n ? jsp_last_error() : "no frames"); rc = 1; }
+        const bool tensor = it_dtype >= 0;   // --index-tensor: 3 elements a pixel, of at most 4 bytes each — three "frames" of W x N H ints hold them
         jsp_pool* sheet = nullptr;   // cols = 1: a plain [N][H][W] array, one "frame" of W x N H pixels
-        if (rc == 0 && !(sheet = jsp_pool_create(0, present_w, ip_n * present_h, 1))) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
-        if (rc == 0) {
-            std::vector<int> picks;
-            for (int i = 0; i < ip_n; ++i) picks.push_back((int)(((long long)i * (long long)n) / ip_n));
+        if (rc == 0 && !(sheet = jsp_pool_create(0, present_w, ip_n * present_h * (tensor ? 3 : 1), 1))) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
+        std::vector<int> picks;
+        for (int i = 0; i < ip_n; ++i) picks.push_back((int)(((long long)i * (long long)n) / ip_n));
+        const int mode = clip.bpp == 16 && sp ? JSP_DISPLAY_CANVAS_RGB15 : JSP_DISPLAY_CANVAS;
+        if (rc == 0 && tensor) {
+            const size_t esize = it_dtype == JSP_TENSOR_F32 ? 4 : it_dtype == JSP_TENSOR_U8 ? 1 : 2;
+            const size_t slice = (size_t)3 * present_w * present_h * esize, bytes = slice * (size_t)ip_n;
+            std::vector<int32_t> host((bytes + 3) / 4);
+            int32_t* out = jsp_pool_buffer(sheet, 0);
+            const float scale[3] = {1.0f / 255.0f, 1.0f / 255.0f, 1.0f / 255.0f}, bias[3] = {0.0f, 0.0f, 0.0f};
+            if ((sp ? jsp_sp_index_tensor(dec, sidx, ip_n, picks.data(), out, bytes, present_w, present_h, k, dx, dy, mode, ip_filter, 0xFF000000u, it_dtype, it_layout, scale, bias)
+                    : jsp_index_tensor(dec, idx, ip_n, picks.data(), out, bytes, present_w, present_h, k, dx, dy, mode, ip_filter, 0xFF000000u, it_dtype, it_layout, scale, bias)) != JSP_ZERO_STATE ||
+                jsp_download(out, host.data(), host.size()) != 0) {
+                std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_tensor" : "jsp_index_tensor", jsp_last_error());
+                rc = 1;
+            }
+            for (int i = 0; rc == 0 && i < ip_n; ++i)
+                std::printf("%d %08x\n", picks[i], crc32(reinterpret_cast<const uint8_t*>(host.data()) + slice * (size_t)i, slice));
+        } else if (rc == 0) {
             const size_t cell = (size_t)present_w * present_h;
             std::vector<int32_t> cells(cell * (size_t)ip_n);
             int32_t* out = jsp_pool_buffer(sheet, 0);
-            const int mode = clip.bpp == 16 && sp ? JSP_DISPLAY_CANVAS_RGB15 : JSP_DISPLAY_CANVAS;
             if ((sp ? jsp_sp_index_present(dec, sidx, ip_n, picks.data(), out, cells.size(), present_w, present_h, (size_t)present_w, 1, k, dx, dy, mode, ip_filter, 0xFF000000u)
                     : jsp_index_present(dec, idx, ip_n, picks.data(), out, cells.size(), present_w, present_h, (size_t)present_w, 1, k, dx, dy, mode, ip_filter, 0xFF000000u)) != JSP_ZERO_STATE ||
                 jsp_download(out, cells.data(), cells.size()) != 0) {

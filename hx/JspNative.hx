@@ -59,6 +59,10 @@ extern class JspNative {
     @:native("jsp_index_present")      static function indexPresent(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, n:Int, frames:RawConstPointer<Int>,
                                                                     out:RawPointer<cpp.Int32>, outInts:SizeT, winW:Int, winH:Int, outPitch:SizeT, cols:Int,
                                                                     k:Float, dx:Float, dy:Float, mode:Int, filter:Int, background:cpp.UInt32):Int;
+    @:native("jsp_index_tensor")       static function indexTensor(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, n:Int, frames:RawConstPointer<Int>,
+                                                                   out:RawPointer<cpp.Void>, outBytes:SizeT, winW:Int, winH:Int,
+                                                                   k:Float, dx:Float, dy:Float, mode:Int, filter:Int, background:cpp.UInt32,
+                                                                   dtype:Int, layout:Int, scale:RawConstPointer<cpp.Float32>, bias:RawConstPointer<cpp.Float32>):Int;
     @:native("jsp_index_play")         static function indexPlay(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, first:Int, n:Int, stride:Int,
                                                                  dsts:RawPointer<RawPointer<cpp.Int32>>, adoptK:Int,
                                                                  dataPnts:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
@@ -75,6 +79,10 @@ extern class JspNative {
     @:native("jsp_sp_index_present")      static function spIndexPresent(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, n:Int, frames:RawConstPointer<Int>,
                                                                          out:RawPointer<cpp.Int32>, outInts:SizeT, winW:Int, winH:Int, outPitch:SizeT, cols:Int,
                                                                          k:Float, dx:Float, dy:Float, mode:Int, filter:Int, background:cpp.UInt32):Int;
+    @:native("jsp_sp_index_tensor")       static function spIndexTensor(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, n:Int, frames:RawConstPointer<Int>,
+                                                                        out:RawPointer<cpp.Void>, outBytes:SizeT, winW:Int, winH:Int,
+                                                                        k:Float, dx:Float, dy:Float, mode:Int, filter:Int, background:cpp.UInt32,
+                                                                        dtype:Int, layout:Int, scale:RawConstPointer<cpp.Float32>, bias:RawConstPointer<cpp.Float32>):Int;
     @:native("jsp_sp_index_play")         static function spIndexPlay(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, first:Int, n:Int, stride:Int,
                                                                       dsts:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
     @:native("jsp_sp_index_significance") static function spIndexSignificance(idx:RawPointer<JspSpIndex>, out:RawPointer<Int>):Int;

@@ -460,6 +460,38 @@ int jsp_index_present(jsp_codec* c, jsp_index* idx, int n, const int* frames,
                       int32_t* out, size_t out_ints, int win_w, int win_h, size_t out_pitch, int cols,
                       double k, double dx, double dy, int mode, int filter, uint32_t background);
 
+/* ---- frames of an index as a model-ready tensor batch: what OCR, UI understanding or an embedding model takes of a screen recording —
+ * N x 3 x H x W or N x H x W x 3, float32 / float16 / bfloat16 / uint8, resized to the model's input and normalised per channel —
+ * straight from the index, without a sheet of packed pixels and the passes over it that unpack, cast, scale and permute ---------------
+ * Tensor: EQUIVALENCE  let P(i, x, y) be the word jsp_index_present writes at pixel (x, y) of cell i for the same frames, win_w, win_h,
+ *       k, dx, dy, mode, filter and background: THE RULE of jsp_display_present / jsp_display_present_area is inherited, not restated,
+ *       and all three filters are taken.  Channel ch (0 = R, 1 = G, 2 = B) has the byte v = (P >> 8 ch) & 0xFF; the top byte is not
+ *       emitted.  A `background` pixel goes through the same mapping as any other.
+ *   MODE  JSP_DISPLAY_CANVAS or JSP_DISPLAY_CANVAS_RGB15, the two conversions whose bytes 0, 1, 2 are R, G, B.
+ *   ELEMENT  JSP_TENSOR_U8: v; scale and bias may be NULL and are ignored.  The float types: scale and bias are three floats each,
+ *       required and finite, and f = (float)((double)v * (double)scale[ch] + (double)bias[ch]) — the product has at most 32
+ *       significant bits and is exact in double (so an fma changes nothing), the sum rounds once to double, the result once to float.
+ *       F32 is f; F16 is f rounded to nearest-even as binary16 (overflow to infinity); BF16 is f rounded to nearest-even as bfloat16.
+ *   LAYOUT  dense, top window row first, no pitch, no cols, no sheet.  JSP_TENSOR_NCHW: element (i, ch, y, x) at
+ *       ((i 3 + ch) win_h + y) win_w + x.  JSP_TENSOR_NHWC: at ((i win_h + y) win_w + x) 3 + ch.  The tensor occupies
+ *       n 3 win_h win_w elements; nothing else is written.  `out` must be aligned to its element and needs no more than that (where
+ *       win_w is a multiple of 4 and `out` lies on a boundary of four elements, four elements go out in one store).
+ *   ONE kernel launch whatever n (msv1_index_tensor_kernel): the kernel of jsp_index_present with another last step; no full-size
+ *       picture and no sheet is written and no frame buffer is touched.  Runs on the codec's stream and returns synchronised.  THE
+ *       CODEC IS ONLY LENT, as for Present.  The frame list travels as Present's does, into the same device array of the index.
+ *   BOUNDS  n, win_w, win_h, k, filter and frames[] as jsp_index_present; out_bytes at least n 3 win_h win_w esize (in 64 bits).
+ *   ERRORS, each before anything is queued, with nothing changed and nothing written (jsp_last_error() starts with "index_tensor:", but
+ *       for a ScreenPressor codec's "index: MSVideo1 only"): a null c, idx, frames or out; null scale or bias with a float dtype; a
+ *       non-finite scale or bias; an unknown dtype or layout; a mode other than the two above; n, a window size, k or filter outside
+ *       its bounds, a non-finite k, dx or dy; a frame number outside the index; out_bytes below the tensor; `out` not aligned to its
+ *       element; a host-pointer `out`; an index built by another codec; a ScreenPressor codec; an asynchronous frame in flight. */
+enum { JSP_TENSOR_F32 = 0, JSP_TENSOR_F16 = 1, JSP_TENSOR_BF16 = 2, JSP_TENSOR_U8 = 3 };
+enum { JSP_TENSOR_NCHW = 0, JSP_TENSOR_NHWC = 1 };
+int jsp_index_tensor(jsp_codec* c, jsp_index* idx, int n, const int* frames,
+                     void* out, size_t out_bytes, int win_w, int win_h,
+                     double k, double dx, double dy, int mode, int filter, uint32_t background,
+                     int dtype, int layout, const float* scale, const float* bias);
+
 /* ---- playback from an MSVideo1 index: reverse play and the step-back button held down, xs fast-forward, filling the free frame
  * buffers around the frame of interest — a run of frames of the index, each into a buffer of its own ----------------------------------
  * Play: EQUIVALENCE  for k = 0 .. n-1 let t_k = first + k * stride.  dsts[k] ends exactly as jsp_index_show(c, idx, t_k, dsts[k], 0, ..)
@@ -575,6 +607,19 @@ int jsp_sp_index_thumbs(jsp_codec* c, jsp_sp_index* idx, int n, const int* frame
 int jsp_sp_index_present(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames,
                          int32_t* out, size_t out_ints, int win_w, int win_h, size_t out_pitch, int cols,
                          double k, double dx, double dy, int mode, int filter, uint32_t background);
+
+/* ---- frames of a ScreenPressor index as a tensor batch: jsp_index_tensor for a jsp_sp_index, the same contract ------------------------
+ * Tensor: EQUIVALENCE, MODE, ELEMENT, LAYOUT, BOUNDS  as jsp_index_tensor, with P(i, x, y) the word jsp_sp_index_present writes.  For
+ *       16 bpp the mode is JSP_DISPLAY_CANVAS_RGB15, as for a frame.
+ *   ONE kernel launch whatever n (sp_index_tensor_kernel): the kernel of jsp_sp_index_present with another last step.  Runs on the
+ *       codec's stream and returns synchronised.  THE CODEC IS ONLY LENT, as for Present: its state, previous frame, entropy state and
+ *       remembered columns stay as they were.  The per-cell records travel as Present's do, into the same device array.
+ *   ERRORS  as jsp_index_tensor, with an MSVideo1 codec for the wrong kind ("sp_index: ScreenPressor only"); jsp_last_error() starts
+ *       with "sp_index_tensor:" otherwise.  Nothing queued, nothing changed, nothing written. */
+int jsp_sp_index_tensor(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames,
+                        void* out, size_t out_bytes, int win_w, int win_h,
+                        double k, double dx, double dy, int mode, int filter, uint32_t background,
+                        int dtype, int layout, const float* scale, const float* bias);
 
 /* ---- playback from a ScreenPressor index: play on from a shown frame, reverse play, fast-forward by `stride`, filling the free frame
  * buffers around the frame of interest in one go — a run of frames of the index, each into a buffer of its own ---------------------------

@@ -116,6 +116,12 @@ SIGNATURES = {
                                     C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint32]),
     "jsp_sp_index_present": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t,
                                        C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint32]),
+    "jsp_index_tensor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                   C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int,
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "jsp_sp_index_tensor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                      C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int,
+                                      C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "jsp_display_convert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "jsp_view_matrix": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

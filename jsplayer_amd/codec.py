@@ -490,15 +490,83 @@ class _IndexPresent:
         return out.reshape(-1)[:rows * width].reshape(rows, width)
 
 
-class SeekIndex(_IndexThumbs, _IndexPresent):
+TENSOR_F32, TENSOR_F16, TENSOR_BF16, TENSOR_U8 = 0, 1, 2, 3   # JSP_TENSOR_*: the element type of Tensor
+TENSOR_NCHW, TENSOR_NHWC = 0, 1                               # ... and its layout
+
+
+def normalisation(mean, std):
+    """(scale, bias) for Tensor from a model's per-channel mean and std over pixel values in 0..1: element = (v / 255 - mean) / std
+    = v * scale + bias with scale = 1 / (255 * std) and bias = -mean / std, computed in Python floats and each rounded to float32."""
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("normalisation: mean and std have one value per channel (R, G, B)")
+    return (tuple(float(np.float32(1.0 / (255.0 * s))) for s in std),
+            tuple(float(np.float32(-m / s)) for m, s in zip(mean, std)))
+
+
+def _tensor_dtype(dtype):
+    """(JSP_TENSOR_* code, torch dtype) of a torch dtype, its name ("float16", "f16", ...) or a JSP_TENSOR_* code."""
+    import torch
+    kinds = ((TENSOR_F32, torch.float32, ("float32", "f32")), (TENSOR_F16, torch.float16, ("float16", "f16")),
+             (TENSOR_BF16, torch.bfloat16, ("bfloat16", "bf16")), (TENSOR_U8, torch.uint8, ("uint8", "u8")))
+    for code, tdtype, names in kinds:
+        if dtype is tdtype or (isinstance(dtype, str) and dtype.lower() in names) or (isinstance(dtype, int) and dtype == code):
+            return code, tdtype
+    raise CodecError(f"index_tensor: unknown dtype {dtype!r}")
+
+
+class _IndexTensor:
+    """Tensor of a seek index, MSVideo1 or ScreenPressor: the two C calls have one contract (jsp_index_tensor).  A subclass names its
+    C function in `_TENSOR_CALL` and has `_open(who)` and `_present_mode()` (_IndexPresent's)."""
+
+    _TENSOR_CALL = ""   # export of the library, without the "jsp_" in front
+
+    def Tensor(self, frames, win_w: int, win_h: int, k: float, dx: float, dy: float, *, mode: Optional[int] = None, filter: int = 2,
+               background: int = 0xFF000000, dtype=None, layout: str = "nchw", scale=(1 / 255,) * 3, bias=(0,) * 3, out=None):
+        """The win_w x win_h windows of `frames` that Present gives (same frames, matrix, mode, filter — default PRESENT_AREA — and
+        background) as a model's input batch: a device tensor of `dtype` (torch.float32, the default, float16, bfloat16 or uint8)
+        and shape (n, 3, win_h, win_w) (`layout` "nchw") or (n, win_h, win_w, 3) ("nhwc"), channels R, G, B, top row first.  An
+        element is the byte v of its channel for uint8, else float32(v * scale[ch] + bias[ch]) computed in double, rounded once
+        more (to nearest-even) for the 16-bit types; `normalisation(mean, std)` gives (scale, bias).  ONE launch, no sheet in
+        between, the codec not touched.  Returns `out` (a contiguous device tensor of that dtype with at least n * 3 * win_h *
+        win_w elements, reshaped) or a new tensor."""
+        import torch
+        codec = self._open(self._TENSOR_CALL)
+        frames = [int(t) for t in frames]
+        n, win_w, win_h = len(frames), int(win_w), int(win_h)
+        code, tdtype = _tensor_dtype(torch.float32 if dtype is None else dtype)
+        lay = {"nchw": TENSOR_NCHW, "nhwc": TENSOR_NHWC}.get(layout.lower() if isinstance(layout, str) else layout, layout)
+        if lay not in (TENSOR_NCHW, TENSOR_NHWC):
+            raise CodecError(f"{self._TENSOR_CALL}: unknown layout {layout!r}")
+        count = n * 3 * max(win_h, 0) * max(win_w, 0)
+        if out is None:
+            out = torch.empty(max(count, 1), dtype=tdtype, device=f"cuda:{codec._device}")
+        elif not hasattr(out, "data_ptr") or out.dtype != tdtype or not out.is_contiguous():
+            raise CodecError(f"{self._TENSOR_CALL}: out must be a contiguous tensor of dtype {tdtype}")
+        arr = (C.c_int * max(n, 1))(*frames)
+        sc = (C.c_float * 3)(*[float(v) for v in scale]) if scale is not None else None
+        bi = (C.c_float * 3)(*[float(v) for v in bias]) if bias is not None else None
+        rc = getattr(self._lib, "jsp_" + self._TENSOR_CALL)(
+            codec._h, self._h, n, arr, C.c_void_p(out.data_ptr()), out.numel() * out.element_size(), win_w, win_h,
+            float(k), float(dx), float(dy), self._present_mode() if mode is None else int(mode), int(filter), int(background) & 0xFFFFFFFF,
+            code, lay, sc, bi)
+        if rc != 0:
+            raise CodecError(N.last_error())
+        shape = (n, 3, win_h, win_w) if lay == TENSOR_NCHW else (n, win_h, win_w, 3)
+        return out.reshape(-1)[:count].reshape(shape)
+
+
+class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor):
     """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch, Play(first, dsts, stride) one launch for
     a run of frames, each into a buffer of its own (jsp_index_play), Present(frames, ...) one launch for the windows of any
-    frames (jsp_index_present).  `significance` = FindChange's verdict
+    frames (jsp_index_present), Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_index_tensor).
+    `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
     ADOPTS = True   # Show(adopt=True) leaves the decoder at frame t: a Manager moves its decode position with it
     _THUMB_CALLS = ("index_thumb_size", "index_thumbs")
     _PRESENT_CALL = "index_present"
+    _TENSOR_CALL = "index_tensor"
 
     def __init__(self, codec: _NativeCodec, handle: int, prev_at_build):
         self._codec, self._h = codec, handle
@@ -636,17 +704,19 @@ class ScreenPressor(_NativeCodec):
         return SpScrubIndex(self, h)
 
 
-class SpScrubIndex(_IndexThumbs, _IndexPresent):
+class SpScrubIndex(_IndexThumbs, _IndexPresent, _IndexTensor):
     """A ScreenPressor range resident in HBM (jsp_sp_index_build, via ScreenPressor.BuildScrubIndex): Show(t) is one launch,
     Play(first, dsts, stride) one launch for a run of frames played forward from any frame (jsp_sp_index_play),
     Thumbs(frames) one launch for any number of downscaled frames (jsp_sp_index_thumbs; _IndexThumbs has the two methods),
-    Present(frames, ...) one launch for their windows of any size (jsp_sp_index_present; _IndexPresent).
+    Present(frames, ...) one launch for their windows of any size (jsp_sp_index_present; _IndexPresent),
+    Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_sp_index_tensor; _IndexTensor).
     `significance` = the verdict the sequential run records for every frame, `frames`, `device_bytes`, `host_bytes`.  close() (or
     the context manager) frees it; safe after the codec is gone."""
 
     ADOPTS = False   # Show never moves the decoder: a Manager serves the frame and leaves its decode position where it is
     _THUMB_CALLS = ("sp_index_thumb_size", "sp_index_thumbs")
     _PRESENT_CALL = "sp_index_present"
+    _TENSOR_CALL = "sp_index_tensor"
 
     def _present_mode(self) -> int:   # 16-bpp frames hold 5-bit components (Manager.hx:121), as Manager.present chooses it
         return 1 if getattr(self._codec, "bpp", 0) == 16 else 0   # DISPLAY_CANVAS_RGB15 / DISPLAY_CANVAS

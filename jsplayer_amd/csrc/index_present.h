@@ -1,7 +1,8 @@
 // jsp_index_present / jsp_sp_index_present (include/jsplayer_amd.h): what the two calls share on the host — the window's fixed-point
 // geometry, the sheet, the refusals and the output rectangle a workgroup owns.  The kernels are msv1_index_present_kernel
 // (msv1_index_present_kernels.hip) and sp_index_present_kernel (sp_index_present_kernels.hip); what they share on the device is
-// index_present_device.h.  Plain C++: msv1_seek.cpp and sp_index.cpp include it too.
+// index_present_device.h.  Plain C++: msv1_seek.cpp and sp_index.cpp include it too.  At the end: what jsp_index_tensor and
+// jsp_sp_index_tensor add to it — the tensor's arguments, refusals and size arithmetic, once for both codecs.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -86,6 +87,52 @@ inline IndexPresentArgs index_present_args(int32_t* out, int n, int fw, int fh, 
     const bool one_column = cols == 1 || n == 1;
     a.vec = ((reinterpret_cast<uintptr_t>(out) & 15) == 0 && (out_pitch & 3) == 0 && (one_column || (win_w & 3) == 0)) ? 1 : 0;
     return a;
+}
+
+// ---- jsp_index_tensor / jsp_sp_index_tensor: the same windows as a dense tensor (msv1_index_tensor_kernel, sp_index_tensor_kernel) ----
+
+// What the tensor kernels take beside the window (IndexPresentArgs with one column of cells; its out, pitch and vec are not used).
+struct IndexTensorArgs {
+    void* out;
+    int dtype, layout;
+    int vec;               // every chunk of four elements (index_present_device.h) starts on a boundary of 4 * esize bytes
+    float scale[3], bias[3];
+};
+
+inline size_t index_tensor_esize(int dtype) { return dtype == JSP_TENSOR_F32 ? 4 : dtype == JSP_TENSOR_U8 ? 1 : 2; }
+
+// What of a tensor call can be refused without the codec or the index (null when nothing is wrong): dtype, layout, mode, the BOUNDS of
+// jsp_index_present that still apply, scale and bias, the size and the alignment of `out`.
+inline const char* index_tensor_refusal(int n, const void* out, size_t out_bytes, int win_w, int win_h, double k, double dx, double dy, int mode,
+                                        int filter, int dtype, int layout, const float* scale, const float* bias) {
+    if (dtype < JSP_TENSOR_F32 || dtype > JSP_TENSOR_U8) return "unknown dtype";
+    if (layout != JSP_TENSOR_NCHW && layout != JSP_TENSOR_NHWC) return "unknown layout";
+    if (mode != JSP_DISPLAY_CANVAS && mode != JSP_DISPLAY_CANVAS_RGB15) return "mode must be JSP_DISPLAY_CANVAS or JSP_DISPLAY_CANVAS_RGB15";
+    if (const char* why = index_present_refusal(n, SIZE_MAX, win_w, win_h, (size_t)std::max(win_w, 1), 1, k, dx, dy, mode, filter)) return why;
+    if (dtype != JSP_TENSOR_U8) {
+        if (!scale || !bias) return "scale and bias are required for a float dtype";
+        for (int ch = 0; ch < 3; ++ch)
+            if (!std::isfinite(scale[ch]) || !std::isfinite(bias[ch])) return "scale and bias must be finite";
+    }
+    // (n <= 2^12, win_w and win_h <= 2^14, esize <= 4: below 2^44)
+    const uint64_t bytes = (uint64_t)n * 3u * (uint64_t)win_h * (uint64_t)win_w * (uint64_t)index_tensor_esize(dtype);
+    if ((uint64_t)out_bytes < bytes) return "out_bytes is smaller than the tensor";
+    if (reinterpret_cast<uintptr_t>(out) % index_tensor_esize(dtype) != 0) return "out is not aligned to its element";
+    return nullptr;
+}
+
+// The arguments of a validated tensor call; the window's come from index_present_args(nullptr, n, ..., out_pitch = win_w, cols = 1, ...).
+inline IndexTensorArgs index_tensor_args(void* out, int win_w, int dtype, int layout, const float* scale, const float* bias) {
+    IndexTensorArgs t{};
+    t.out = out;
+    t.dtype = dtype;
+    t.layout = layout;
+    t.vec = ((win_w & 3) == 0 && reinterpret_cast<uintptr_t>(out) % (4 * index_tensor_esize(dtype)) == 0) ? 1 : 0;
+    for (int ch = 0; ch < 3; ++ch) {
+        t.scale[ch] = dtype == JSP_TENSOR_U8 ? 1.0f : scale[ch];
+        t.bias[ch] = dtype == JSP_TENSOR_U8 ? 0.0f : bias[ch];
+    }
+    return t;
 }
 
 }  // namespace jsp

@@ -103,12 +103,20 @@ __device__ __forceinline__ void reach(int lo16, int hi16, int step, int n, int& 
     }
 }
 
-// The rectangle of the workgroup (blockIdx.x, blockIdx.y) of the cell at `cell`, whole.  `tile`: T * T words of LDS.
+// What a lane has of its workgroup's rectangle once phase 2 is over: the finished words of output pixels (ox0 .. ox0 + n - 1, oy) of the
+// cell, n <= RUN; px[j] is defined for j < n (a pixel whose centre lies outside the picture holds `background`).
+struct PresentLane {
+    uint32_t px[RUN];
+    int n, ox0, oy;
+};
+
+// The rectangle of the workgroup (blockIdx.x, blockIdx.y) of a cell: phases 1 and 2, up to the lane's finished words in `out`; false
+// for a lane that has no pixel (all barriers are behind it then, too).  `tile`: T * T words of LDS.
 // compose(tx0, ty0, sx0, sy0, sx1, sy1), called by every lane: fill the tile whose pixel (0, 0) is picture pixel (tx0, ty0) — both
 // multiples of ALIGN — with the picture's pixels of [sx0, sx1] x [sy0, sy1] (inside the picture) that it holds; the rest of the tile
 // may hold anything.  The barriers around it are here.
 template <int MODE, int FILTER, bool WIDE, int ALIGN, class Compose>
-__device__ __forceinline__ void present_rect(const IndexPresentArgs& a, uint32_t* cell, const uint32_t* tile, Compose&& compose) {
+__device__ __forceinline__ bool present_words(const IndexPresentArgs& a, const uint32_t* tile, Compose&& compose, PresentLane& out) {
     typedef typename std::conditional<WIDE, unsigned long long, uint32_t>::type Sum;
     const int lanes_x = a.rw / RUN;
     const int ly = (int)threadIdx.x / lanes_x, lx = (int)threadIdx.x - ly * lanes_x;
@@ -191,9 +199,12 @@ __device__ __forceinline__ void present_rect(const IndexPresentArgs& a, uint32_t
             }
         }
     }
-    if (!live) return;
+    out.n = n;
+    out.ox0 = ox0;
+    out.oy = oy;
+    if (!live) return false;
 
-    // ---- finish and store -------------------------------------------------------------------------------------------------------------
+    // ---- finish ---------------------------------------------------------------------------------------------------------------------------
 #pragma unroll
     for (int j = 0; j < RUN; ++j) {
         if (!in[j]) continue;
@@ -210,13 +221,103 @@ __device__ __forceinline__ void present_rect(const IndexPresentArgs& a, uint32_t
             px[j] = v;
         }
     }
-    uint32_t* d = cell + (size_t)oy * a.pitch + ox0;
-    if (a.vec && n == RUN) {
-        __builtin_nontemporal_store(p_u32x4{px[0], px[1], px[2], px[3]}, (p_gu32x4*)d);
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) out.px[j] = px[j];
+    return true;
+}
+
+// The epilogue of the present kernels: the lane's words into its cell of the sheet, 16 bytes at once where a.vec allows.
+__device__ __forceinline__ void store_words(const IndexPresentArgs& a, uint32_t* cell, const PresentLane& l) {
+    uint32_t* d = cell + (size_t)l.oy * a.pitch + l.ox0;
+    if (a.vec && l.n == RUN) {
+        __builtin_nontemporal_store(p_u32x4{l.px[0], l.px[1], l.px[2], l.px[3]}, (p_gu32x4*)d);
     } else {
 #pragma unroll
         for (int j = 0; j < RUN; ++j)
-            if (j < n) *(p_gu32*)(d + j) = px[j];
+            if (j < l.n) *(p_gu32*)(d + j) = l.px[j];
+    }
+}
+
+// present_words, then store_words into `cell`: a present kernel's whole rectangle.
+template <int MODE, int FILTER, bool WIDE, int ALIGN, class Compose>
+__device__ __forceinline__ void present_rect(const IndexPresentArgs& a, uint32_t* cell, const uint32_t* tile, Compose&& compose) {
+    PresentLane l;
+    if (present_words<MODE, FILTER, WIDE, ALIGN>(a, tile, compose, l)) store_words(a, cell, l);
+}
+
+// ---- the epilogue of the tensor kernels (jsp_index_tensor / jsp_sp_index_tensor) ------------------------------------------------------
+typedef uint32_t p_u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) p_u32x2 p_gu32x2;
+typedef __attribute__((address_space(1))) uint16_t p_gu16;
+typedef __attribute__((address_space(1))) uint8_t p_gu8;
+
+// The element of byte v (0..255) of channel ch, as the bits that are stored: THE RULE of the header — the product is exact in double, so
+// the fma rounds once to double as the sum does; one rounding to float; f16 / bf16 round that float to nearest-even.
+template <int DTYPE>
+__device__ __forceinline__ uint32_t tensor_element(const IndexTensorArgs& t, uint32_t v, int ch) {
+    if (DTYPE == JSP_TENSOR_U8) return v;
+    const float f = (float)__builtin_fma((double)v, (double)t.scale[ch], (double)t.bias[ch]);
+    const uint32_t bits = __float_as_uint(f);
+    if (DTYPE == JSP_TENSOR_F32) return bits;
+    if (DTYPE == JSP_TENSOR_F16) {
+        const _Float16 h = (_Float16)f;
+        return (uint32_t)__builtin_bit_cast(uint16_t, h);
+    }
+    return (bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16;
+}
+
+// The lane's pixels as elements of cell blockIdx.z of the dense tensor, for one dtype and layout.  In both layouts they are three CHUNKS
+// of four elements, each chunk consecutive in memory: NCHW — chunk c is the four pixels of plane c; NHWC — the twelve interleaved
+// elements cut in three, element m = 4 c + q being channel m % 3 of pixel m / 3.  A chunk goes out in one store of 4 * esize bytes
+// where t.vec says every chunk starts on such a boundary and the lane has all four pixels; element by element otherwise.
+template <int DTYPE, bool NCHW>
+__device__ __forceinline__ void store_elements_as(const IndexPresentArgs& a, const IndexTensorArgs& t, const PresentLane& l) {
+    const size_t W = (size_t)a.ww, H = (size_t)a.wh, z = blockIdx.z;
+    const size_t first = NCHW ? (z * 3 * H + (size_t)l.oy) * W + (size_t)l.ox0      // the lane's first pixel in plane 0
+                              : ((z * H + (size_t)l.oy) * W + (size_t)l.ox0) * 3;   // ... its first element
+    const size_t stride = NCHW ? H * W : 4;                                         // from a chunk to the next
+    uint32_t w[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = NCHW ? q : (4 * c + q) / 3, ch = NCHW ? c : (4 * c + q) % 3;
+            w[c][q] = tensor_element<DTYPE>(t, (l.px[j] >> (8 * ch)) & 0xFFu, ch);
+        }
+    if (t.vec && l.n == RUN) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const size_t at = first + (size_t)c * stride;
+            if (DTYPE == JSP_TENSOR_F32)
+                __builtin_nontemporal_store(p_u32x4{w[c][0], w[c][1], w[c][2], w[c][3]}, (p_gu32x4*)((uint32_t*)t.out + at));
+            else if (DTYPE == JSP_TENSOR_U8)
+                __builtin_nontemporal_store(w[c][0] | (w[c][1] << 8) | (w[c][2] << 16) | (w[c][3] << 24), (p_gu32*)((uint8_t*)t.out + at));
+            else
+                __builtin_nontemporal_store(p_u32x2{w[c][0] | (w[c][1] << 16), w[c][2] | (w[c][3] << 16)}, (p_gu32x2*)((uint16_t*)t.out + at));
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if ((NCHW ? q : (4 * c + q) / 3) >= l.n) continue;
+                const size_t at = first + (size_t)c * stride + (size_t)q;
+                if (DTYPE == JSP_TENSOR_F32) *(p_gu32*)((uint32_t*)t.out + at) = w[c][q];
+                else if (DTYPE == JSP_TENSOR_U8) *(p_gu8*)((uint8_t*)t.out + at) = (uint8_t)w[c][q];
+                else *(p_gu16*)((uint16_t*)t.out + at) = (uint16_t)w[c][q];
+            }
+    }
+}
+
+// dtype and layout are workgroup-uniform and are branched on ONCE, here: one straight-line epilogue per pair inside every tensor kernel,
+// and no instantiation of a kernel per pair.
+__device__ __forceinline__ void store_elements(const IndexPresentArgs& a, const IndexTensorArgs& t, const PresentLane& l) {
+    const bool nchw = t.layout == JSP_TENSOR_NCHW;
+    switch (t.dtype) {
+        case JSP_TENSOR_F32: nchw ? store_elements_as<JSP_TENSOR_F32, true>(a, t, l) : store_elements_as<JSP_TENSOR_F32, false>(a, t, l); break;
+        case JSP_TENSOR_F16: nchw ? store_elements_as<JSP_TENSOR_F16, true>(a, t, l) : store_elements_as<JSP_TENSOR_F16, false>(a, t, l); break;
+        case JSP_TENSOR_BF16: nchw ? store_elements_as<JSP_TENSOR_BF16, true>(a, t, l) : store_elements_as<JSP_TENSOR_BF16, false>(a, t, l); break;
+        default: nchw ? store_elements_as<JSP_TENSOR_U8, true>(a, t, l) : store_elements_as<JSP_TENSOR_U8, false>(a, t, l); break;
     }
 }
 
@@ -242,6 +343,12 @@ inline void dispatch_mode(int mode, F&& f) {
         case JSP_DISPLAY_SETPIXELS: f(std::integral_constant<int, JSP_DISPLAY_SETPIXELS>{}); break;
         default: f(std::integral_constant<int, JSP_DISPLAY_SETPIXELS_RGB15>{}); break;
     }
+}
+// the tensor kernels: `mode` is one of the two canvas conversions (index_tensor_refusal)
+template <class F>
+inline void dispatch_canvas_mode(int mode, F&& f) {
+    if (mode == JSP_DISPLAY_CANVAS_RGB15) f(std::integral_constant<int, JSP_DISPLAY_CANVAS_RGB15>{});
+    else f(std::integral_constant<int, JSP_DISPLAY_CANVAS>{});
 }
 inline dim3 present_grid(const IndexPresentArgs& a, int n) {
     return dim3((unsigned)((a.ww + a.rw - 1) / a.rw), (unsigned)((a.wh + a.rh - 1) / a.rh), (unsigned)n);

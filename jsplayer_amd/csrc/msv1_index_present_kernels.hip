@@ -6,6 +6,9 @@
 // reaches is composed exactly as msv1_index_show_kernel composes it into a destination that held zeros: the last frame <= t that
 // coded it (index_last_writer) decoded from its code (index_decode), else the block of `before`, else zeros; remainder pixels come
 // from `before`, or are zero.  The 16 pixels go to LDS as four 16-byte rows — px[] is only ever indexed by constants.
+//
+// jsp_index_tensor (msv1_index_tensor_kernel) is the same kernel with another last step: the lane's finished words go out as elements of
+// a dense N x 3 x H x W or N x H x W x 3 tensor (store_elements) and not as words of a sheet.
 #include <type_traits>
 
 #include "index_present_device.h"
@@ -28,14 +31,14 @@ struct Msv1PresentSrc {
     int before_vec;            // blocks of `before` may be read 16 bytes a row
 };
 
-template <int BITS, int MODE, int FILTER, bool WIDE>
-__global__ __launch_bounds__(kIndexPresentWG) void msv1_index_present_kernel(const Msv1PresentSrc s, const IndexPresentArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t tile[T * T];
-    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    load_palette<BITS, false>(s_pal, s.palette);   // (present_rect has a barrier before the first decode)
-    const int t = s.frames[blockIdx.z];
-    const int X = a.fw, Y = a.fh;
-    auto compose = [&](int tx0, int ty0, int sx0, int sy0, int sx1, int sy1) {
+// Phase 1 of both kernels below: compose (index_present_device.h) for a tile of 16 x 16 blocks, a lane per block.
+template <int BITS>
+struct Msv1Compose {
+    const Msv1PresentSrc& s;
+    uint32_t* tile;
+    const uint32_t* s_pal;
+    int t, X, Y;           // the cell's frame; the picture's size
+    __device__ __forceinline__ void operator()(int tx0, int ty0, int sx0, int sy0, int sx1, int sy1) const {
         const int lx = (int)threadIdx.x & 15, ly = (int)threadIdx.x >> 4;
         const int x = tx0 + lx * 4, y = ty0 + ly * 4;                  // the lane's 4x4 pixels
         if (x > sx1 || x + 3 < sx0 || y > sy1 || y + 3 < sy0) return;  // (what is left lies inside the picture at least in part)
@@ -65,15 +68,31 @@ __global__ __launch_bounds__(kIndexPresentWG) void msv1_index_present_kernel(con
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             *reinterpret_cast<uint4*>(tile + (ly * 4 + r) * T + lx * 4) = make_uint4(px[r * 4], px[r * 4 + 1], px[r * 4 + 2], px[r * 4 + 3]);
-    };
+    }
+};
+
+template <int BITS, int MODE, int FILTER, bool WIDE>
+__global__ __launch_bounds__(kIndexPresentWG) void msv1_index_present_kernel(const Msv1PresentSrc s, const IndexPresentArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tile[T * T];
+    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
+    load_palette<BITS, false>(s_pal, s.palette);   // (present_words has a barrier before the first decode)
+    const Msv1Compose<BITS> compose{s, tile, s_pal, s.frames[blockIdx.z], a.fw, a.fh};
     present_rect<MODE, FILTER, WIDE, 4>(a, sheet_cell(a), tile, compose);
 }
 
-}  // namespace
+// jsp_index_tensor: the same rectangle, its words stored as elements of a dense tensor.  MODE is one of the two canvas conversions.
+template <int BITS, int MODE, int FILTER, bool WIDE>
+__global__ __launch_bounds__(kIndexPresentWG) void msv1_index_tensor_kernel(const Msv1PresentSrc s, const IndexPresentArgs a, const IndexTensorArgs t) {
+    __shared__ __attribute__((aligned(16))) uint32_t tile[T * T];
+    __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
+    load_palette<BITS, false>(s_pal, s.palette);
+    const Msv1Compose<BITS> compose{s, tile, s_pal, s.frames[blockIdx.z], a.fw, a.fh};
+    PresentLane l;
+    if (present_words<MODE, FILTER, WIDE, 4>(a, tile, compose, l)) store_elements(a, t, l);
+}
 
-void msv1_launch_index_present(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                               const uint32_t* d_bitmap, const int32_t* d_frames, int n, const int32_t* before, const IndexPresentArgs& a, int mode,
-                               int filter, hipStream_t stream) {
+Msv1PresentSrc present_src(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                           const uint32_t* d_bitmap, const int32_t* d_frames, const int32_t* before) {
     Msv1PresentSrc s;
     s.chunks = d_chunks;
     s.frame_chunk = d_frame_chunk;
@@ -86,12 +105,38 @@ void msv1_launch_index_present(const Msv1Geometry& geo, const Msv1IndexChunk* d_
     s.nbx = std::max(geo.nbx, 0);
     s.nby = std::max(geo.nby, 0);
     s.before_vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
+    return s;
+}
+
+}  // namespace
+
+void msv1_launch_index_present(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                               const uint32_t* d_bitmap, const int32_t* d_frames, int n, const int32_t* before, const IndexPresentArgs& a, int mode,
+                               int filter, hipStream_t stream) {
+    const Msv1PresentSrc s = present_src(geo, d_chunks, d_frame_chunk, d_palette, d_bitmap, d_frames, before);
     const dim3 grid = present_grid(a, n);
     auto go = [&](auto B) {
         dispatch_mode(mode, [&](auto M) {
             dispatch_filter(filter, a.step, [&](auto F, auto W) {
                 hipLaunchKernelGGL((msv1_index_present_kernel<decltype(B)::value, decltype(M)::value, decltype(F)::value, decltype(W)::value>), grid,
                                    dim3(kIndexPresentWG), 0, stream, s, a);
+            });
+        });
+    };
+    if (geo.bits == 16) go(std::integral_constant<int, 16>{});
+    else go(std::integral_constant<int, 8>{});
+}
+
+void msv1_launch_index_tensor(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                              const uint32_t* d_bitmap, const int32_t* d_frames, int n, const int32_t* before, const IndexPresentArgs& a,
+                              const IndexTensorArgs& t, int mode, int filter, hipStream_t stream) {
+    const Msv1PresentSrc s = present_src(geo, d_chunks, d_frame_chunk, d_palette, d_bitmap, d_frames, before);
+    const dim3 grid = present_grid(a, n);
+    auto go = [&](auto B) {
+        dispatch_canvas_mode(mode, [&](auto M) {
+            dispatch_filter(filter, a.step, [&](auto F, auto W) {
+                hipLaunchKernelGGL((msv1_index_tensor_kernel<decltype(B)::value, decltype(M)::value, decltype(F)::value, decltype(W)::value>), grid,
+                                   dim3(kIndexPresentWG), 0, stream, s, a, t);
             });
         });
     };

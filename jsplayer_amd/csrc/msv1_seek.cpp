@@ -717,6 +717,47 @@ extern "C" int jsp_index_present(jsp_codec* c, jsp_index* idx, int n, const int*
     }
 }
 
+// ---- tensors: the same windows as a model's input batch — N x 3 x H x W or N x H x W x 3, float32 / float16 / bfloat16 / uint8, scaled and
+// biased per channel — in ONE launch of msv1_index_tensor_kernel: Present's kernel with another last step.  No sheet is written; the
+// codec is only lent and the frame list travels as for Present.
+extern "C" int jsp_index_tensor(jsp_codec* c, jsp_index* idx, int n, const int* frames, void* out, size_t out_bytes, int win_w, int win_h, double k,
+                                double dx, double dy, int mode, int filter, uint32_t background, int dtype, int layout, const float* scale,
+                                const float* bias) {
+    if (!c || !idx || !frames || !out) return fail("index_tensor: null argument");
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_tensor: the index was built by another codec");
+    if (const char* why = index_tensor_refusal(n, out, out_bytes, win_w, win_h, k, dx, dy, mode, filter, dtype, layout, scale, bias))
+        return fail("index_tensor: %s", why);
+    for (int i = 0; i < n; ++i)
+        if (frames[i] < 0 || frames[i] >= idx->nframes) return fail("index_tensor: a frame number is outside the index");
+    if (idx->geo.X < 1 || idx->geo.Y < 1) return fail("index_tensor: the index has no picture");
+    if (!nothing_in_flight(c, "index_tensor")) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, out) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
+            (void)hipGetLastError();
+            return fail("index_tensor: out must be a device buffer");
+        }
+        idx->h_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
+        idx->d_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
+        std::copy(frames, frames + n, static_cast<int32_t*>(idx->h_thumb_frames.p));
+        JSP_HIP(hipMemcpyAsync(idx->d_thumb_frames.p, idx->h_thumb_frames.p, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        const IndexPresentArgs a = index_present_args(nullptr, n, idx->geo.X, idx->geo.Y, win_w, win_h, (size_t)win_w, 1, k, dx, dy, filter, background, 4);
+        const IndexTensorArgs t = index_tensor_args(out, win_w, dtype, layout, scale, bias);
+        msv1_launch_index_tensor(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
+                                 static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p),
+                                 static_cast<const int32_t*>(idx->d_thumb_frames.p), n,
+                                 idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, a, t, mode, filter, c->stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned list is free for the next call)
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
 extern "C" int jsp_index_significance(const jsp_index* idx, int* out) {
     if (!idx || !out) return fail("index_significance: null argument");
     std::copy(idx->significance.begin(), idx->significance.end(), out);

@@ -95,5 +95,9 @@ void msv1_launch_index_thumbs(const Msv1Geometry& geo, const Msv1IndexChunk* d_c
 void msv1_launch_index_present(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
                                const uint32_t* d_bitmap, const int32_t* d_frames, int n, const int32_t* before, const IndexPresentArgs& a, int mode,
                                int filter, hipStream_t stream);
+// The same windows as elements of the dense tensor `t` describes (msv1_index_tensor_kernel): ONE launch; `a` has one column of cells.
+void msv1_launch_index_tensor(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
+                              const uint32_t* d_bitmap, const int32_t* d_frames, int n, const int32_t* before, const IndexPresentArgs& a,
+                              const IndexTensorArgs& t, int mode, int filter, hipStream_t stream);
 
 }  // namespace jsp

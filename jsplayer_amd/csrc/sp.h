@@ -306,6 +306,10 @@ void launch_index_thumbs(const Geometry& g, int32_t* out, const int32_t* d_keys,
 // of the sheet a.out.  ONE launch; no full-size picture is written.
 void launch_index_present(const Geometry& g, const int32_t* d_keys, size_t pic_stride, const IndexThumbRec* d_recs, int n, const PBlock* d_blocks,
                           const uint32_t* d_payload, const uint32_t* d_bitmap, const IndexPresentArgs& a, int mode, int filter, hipStream_t stream);
+// The same windows as elements of the dense tensor `t` describes (sp_index_tensor_kernel): ONE launch; `a` has one column of cells.
+void launch_index_tensor(const Geometry& g, const int32_t* d_keys, size_t pic_stride, const IndexThumbRec* d_recs, int n, const PBlock* d_blocks,
+                         const uint32_t* d_payload, const uint32_t* d_bitmap, const IndexPresentArgs& a, const IndexTensorArgs& t, int mode,
+                         int filter, hipStream_t stream);
 // Playback from the seek index (sp_index_play_kernel): the pictures launch_index_show would write for frames first, first + stride, ...,
 // first + (n - 1) * stride, into d_dsts[0..n) — ONE launch.  A wave composes frame `first` of its block as the show kernel does, then
 // carries the pixels forward in registers: a set bitmap bit is a literal rectangle laid over them, a key frame (d_keymask, bit j of word w:

@@ -443,6 +443,44 @@ extern "C" int jsp_sp_index_present(jsp_codec* c, jsp_sp_index* idx, int n, cons
     }
 }
 
+// ---- tensors: the same windows as a model's input batch (jsp_index_tensor's contract), in ONE launch of sp_index_tensor_kernel: Present's
+// kernel with another last step.  No sheet is written; the codec is lent its stream and nothing else, the records travel as for Present.
+extern "C" int jsp_sp_index_tensor(jsp_codec* c, jsp_sp_index* idx, int n, const int* frames, void* out, size_t out_bytes, int win_w, int win_h,
+                                   double k, double dx, double dy, int mode, int filter, uint32_t background, int dtype, int layout,
+                                   const float* scale, const float* bias) {
+    if (!c || !idx || !frames || !out) return fail("sp_index_tensor: null argument");
+    if (c->kind != JSP_CODEC_SCREENPRESSOR || !dynamic_cast<IndexLender*>(c)) return fail("sp_index: ScreenPressor only");
+    if (idx->codec_serial != c->serial) return fail("sp_index_tensor: the index was built by another codec");
+    if (const char* why = index_tensor_refusal(n, out, out_bytes, win_w, win_h, k, dx, dy, mode, filter, dtype, layout, scale, bias))
+        return fail("sp_index_tensor: %s", why);
+    for (int i = 0; i < n; ++i)
+        if (frames[i] < 0 || frames[i] >= idx->nframes) return fail("sp_index_tensor: a frame number is outside the index");
+    if (c->next_ticket != c->oldest_ticket) return fail("sp_index_tensor: an asynchronous frame is in flight (jsp_wait for it first)");
+    try {
+        c->activate();
+        if (!on_device(out)) return fail("sp_index_tensor: out must be a device buffer");
+        idx->h_thumb_recs.reserve(sizeof(IndexThumbRec) * (size_t)n);
+        idx->d_thumb_recs.reserve(sizeof(IndexThumbRec) * (size_t)n);
+        auto* recs = static_cast<IndexThumbRec*>(idx->h_thumb_recs.p);
+        for (int i = 0; i < n; ++i) {
+            const size_t t = (size_t)frames[i];
+            recs[i] = IndexThumbRec{frames[i], idx->key_of[t], (uint32_t)idx->key_slot[t], 0u, idx->slot_base[t]};
+        }
+        JSP_HIP(hipMemcpyAsync(idx->d_thumb_recs.p, recs, sizeof(IndexThumbRec) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        const IndexPresentArgs a = index_present_args(nullptr, n, idx->geo.X, idx->geo.Y, win_w, win_h, (size_t)win_w, 1, k, dx, dy, filter, background, 16);
+        const IndexTensorArgs ta = index_tensor_args(out, win_w, dtype, layout, scale, bias);
+        launch_index_tensor(idx->geo, static_cast<const int32_t*>(idx->d_keys.p), idx->pic_stride, static_cast<const IndexThumbRec*>(idx->d_thumb_recs.p),
+                            n, static_cast<const PBlock*>(idx->d_blocks.p), static_cast<const uint32_t*>(idx->d_payload.p),
+                            static_cast<const uint32_t*>(idx->d_bitmap.p), a, ta, mode, filter, c->stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned records are free for the next call)
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
 // ---- playback: a run of frames of the index, carried forward in registers from the first one, in ONE launch of sp_index_play_kernel.
 // Everything Show does to the codec, per destination: the buffers are written behind its back, so it forgets their last columns.
 extern "C" int jsp_sp_index_play(jsp_codec* c, jsp_sp_index* idx, int first, int n, int stride, int32_t* const* dsts, int* significant_changes) {

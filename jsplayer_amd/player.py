@@ -253,6 +253,24 @@ class Manager:
                                    filter=PRESENT_AREA if filter is None else filter, cols=n if cols is None else int(cols))
         return [self.index_first + t for t in picks], sheet
 
+    def tensor_from_index(self, frames, win_w: int, win_h: int, **kw):
+        """The clip frames `frames` of the attached index, each Fit into win_w x win_h as `contact_sheet` fits them, as a model's
+        input batch: the index's `Tensor` (dtype, layout, scale, bias, filter — default PRESENT_AREA —, background and out go
+        through `kw`).  One `Tensor` launch, a pure read.  No index attached, a frame outside it, or an index object without
+        `Tensor`: ValueError."""
+        from .codec import view_matrix
+        if self.index is None:
+            raise ValueError("no seek index attached")
+        if not hasattr(self.index, "Tensor"):
+            raise ValueError("the attached seek index has no tensors")
+        frames = [int(i) for i in frames]
+        for i in frames:
+            if not self._in_index(i):
+                raise ValueError(f"frame {i} is not in an attached seek index")
+        k, dx, dy = view_matrix(self.vi.X, self.vi.Y, win_w, win_h, 0.0)
+        kw.setdefault("mode", self._index_present_mode())
+        return self.index.Tensor([i - self.index_first for i in frames], win_w, win_h, k, dx, dy, **kw)
+
     def _slot_of(self, buf) -> int:
         for i, b in enumerate(self.buffers):
             if b is buf:
