@@ -10,19 +10,13 @@
 #include "../../include/jsplayer_amd.h"
 #include "../../include/jsplayer_amd_lab.h"
 #include "common.h"
+#include "present_rule_device.h"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using jsp::present_rule::convert;   // the four conversions
 
-__device__ __forceinline__ uint32_t convert(uint32_t c, int mode) {
-    switch (mode) {
-        case JSP_DISPLAY_CANVAS: return 0xFF000000u | ((c & 0xFFu) << 16) | (c & 0xFF00u) | ((c >> 16) & 0xFFu);  // :379
-        case JSP_DISPLAY_CANVAS_RGB15: return 0xFF000000u | (c << 3);                                           // :370
-        case JSP_DISPLAY_SETPIXELS: return 0xFF000000u | c;                                                      // :351
-        default: return c << 11;                                                                                  // :340
-    }
-}
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void display_convert_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                                                               int X, int Y, int mode, int flip, int vec) {

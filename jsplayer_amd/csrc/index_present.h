@@ -1,5 +1,6 @@
-// jsp_index_present / jsp_sp_index_present (include/jsplayer_amd.h): what the two calls share on the host — the window's fixed-point
-// geometry, the sheet, the refusals and the output rectangle a workgroup owns.  The kernels are msv1_index_present_kernel
+// jsp_index_present / jsp_sp_index_present (include/jsplayer_amd.h): what the two calls share on the host — the sheet, the refusals and
+// the output rectangle a workgroup owns; the window's fixed-point geometry and the bounds are the display calls', from
+// present_rule.h.  The kernels are msv1_index_present_kernel
 // (msv1_index_present_kernels.hip) and sp_index_present_kernel (sp_index_present_kernels.hip); what they share on the device is
 // index_present_device.h.  Plain C++: msv1_seek.cpp and sp_index.cpp include it too.  At the end: what jsp_index_tensor and
 // jsp_sp_index_tensor add to it — the tensor's arguments, refusals and size arithmetic, once for both codecs.
@@ -10,6 +11,7 @@
 #include <cstdint>
 
 #include "../../include/jsplayer_amd.h"
+#include "present_rule.h"
 
 namespace jsp {
 
@@ -30,22 +32,13 @@ struct IndexPresentArgs {
     int vec;               // every cell row starts on a 16-byte boundary
 };
 
-// F(v) of present_kernels.hip: floor(v * 65536 + 0.5) as a 64-bit integer, held at +-2^62
-inline long long index_present_fixed16(double v) {
-    const double f = std::floor(v * 65536.0 + 0.5), lim = 4611686018427387904.0;
-    if (f >= lim) return 1ll << 62;
-    if (f <= -lim) return -(1ll << 62);
-    return (long long)f;
-}
-
-// What of the call can be refused without the codec or the index (null when nothing is wrong): the BOUNDS of the header, the sheet.
+// What of the call can be refused without the codec or the index (null when nothing is wrong): the BOUNDS of the header (those of the
+// display calls from present_rule.h), the sheet.
 inline const char* index_present_refusal(int n, size_t out_ints, int win_w, int win_h, size_t out_pitch, int cols, double k, double dx, double dy,
                                          int mode, int filter) {
     if (n < 1 || n > 4096) return "n is outside 1..4096";
-    if (win_w < 1 || win_w > 16384 || win_h < 1 || win_h > 16384) return "window size outside 1..16384";
-    if (!std::isfinite(k) || !std::isfinite(dx) || !std::isfinite(dy)) return "k, dx, dy must be finite";
-    if (k < 1.0 / 64.0 || k > 64.0) return "k outside 1/64..64";
-    if (mode < JSP_DISPLAY_CANVAS || mode > JSP_DISPLAY_SETPIXELS_RGB15) return "unknown mode";
+    if (const char* why = present_rule::window_refusal(win_w, win_h)) return why;
+    if (const char* why = present_rule::view_refusal(k, dx, dy, mode)) return why;
     if (filter != JSP_PRESENT_NEAREST && filter != JSP_PRESENT_BILINEAR && filter != JSP_PRESENT_AREA) return "unknown filter";
     if (cols < 1) return "cols must be at least 1";
     if ((uint64_t)out_pitch / (uint64_t)win_w < (uint64_t)cols) return "out_pitch below cols * win_w";
@@ -74,9 +67,8 @@ inline IndexPresentArgs index_present_args(int32_t* out, int n, int fw, int fh, 
     a.pitch = out_pitch;
     a.cols = cols;
     a.fw = fw; a.fh = fh; a.ww = win_w; a.wh = win_h;
-    a.step = (int)index_present_fixed16(1.0 / k);                        // 1024 .. 64 * 65536
-    a.ax = index_present_fixed16((0.5 + dx) / k);
-    a.ay = index_present_fixed16(((double)win_h + dy - 0.5) / k);
+    const present_rule::Geometry g = present_rule::geometry(win_h, k, dx, dy);
+    a.step = g.step; a.ax = g.ax; a.ay = g.ay;
     a.bg = background;
     const int room = kIndexPresentTile - align;
     int m = 1;                                                           // output pixels per axis whose source fits one tile

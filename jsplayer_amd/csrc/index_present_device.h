@@ -4,8 +4,9 @@
 //
 // THE RULE is that of jsp_display_present (filter 0 / 1) and jsp_display_present_area (filter 2), bit for bit.  Their kernels
 // (display_present_kernel in present_kernels.hip, display_present_area_kernel in present_area_kernels.hip) read a frame buffer in
-// global memory row by row and are left as they are; the arithmetic is RESTATED here, names kept — convert, hblend, vblend, Span /
-// footprint / weight, small_quotient, constant_byte — for a source that arrives tile by tile:
+// global memory row by row; this one and they take the arithmetic — convert, taps, hblend, vblend, Span / footprint / weight,
+// small_quotient, constant_byte — from ONE statement of it, present_rule_device.h and present_rule.h.  Here it is applied to a source
+// that arrives tile by tile:
 //   nearest   the one tap (X >> 16, Y >> 16), taken from the tile that holds it;
 //   bilinear  the four taps, each kept (unconverted) from the tile that holds it; hblend / vblend after the last tile;
 //   area      S per byte = sum of byte * wx * wy over the footprint, added up tile by tile — integer sums, so the order does not
@@ -19,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "index_present.h"
+#include "present_rule_device.h"
 
 namespace jsp {
 namespace ipresent {
@@ -31,61 +33,7 @@ typedef __attribute__((address_space(1))) p_u32x4 p_gu32x4;
 constexpr int T = kIndexPresentTile;
 constexpr int RUN = kIndexPresentRun;
 
-// the four conversions of display_kernels.hip's convert(), bit for bit
-template <int MODE>
-__device__ __forceinline__ uint32_t convert(uint32_t c) {
-    if (MODE == JSP_DISPLAY_CANVAS) return 0xFF000000u | ((c & 0xFFu) << 16) | (c & 0xFF00u) | ((c >> 16) & 0xFFu);   // Manager.hx:379
-    if (MODE == JSP_DISPLAY_CANVAS_RGB15) return 0xFF000000u | (c << 3);                                               // :370
-    if (MODE == JSP_DISPLAY_SETPIXELS) return 0xFF000000u | c;                                                         // :351
-    return c << 11;                                                                                                    // :340
-}
-
-// ---- present_kernels.hip: bilinear --------------------------------------------------------------------------------------------
-struct HSum { uint32_t e, o; };
-__device__ __forceinline__ HSum hblend(uint32_t p0, uint32_t p1, uint32_t w) {
-    const uint32_t v = 256u - w;
-    return HSum{(p0 & 0x00FF00FFu) * v + (p1 & 0x00FF00FFu) * w, ((p0 >> 8) & 0x00FF00FFu) * v + ((p1 >> 8) & 0x00FF00FFu) * w};
-}
-__device__ __forceinline__ uint32_t vblend(HSum a, HSum b, uint32_t w) {
-    const uint32_t v = 256u - w;
-    const uint32_t b0 = ((a.e & 0xFFFFu) * v + (b.e & 0xFFFFu) * w + 32768u) >> 16;
-    const uint32_t b2 = ((a.e >> 16) * v + (b.e >> 16) * w + 32768u) >> 16;
-    const uint32_t b1 = ((a.o & 0xFFFFu) * v + (b.o & 0xFFFFu) * w + 32768u) >> 16;
-    const uint32_t b3 = ((a.o >> 16) * v + (b.o >> 16) * w + 32768u) >> 16;
-    return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
-}
-// One axis of a covered pixel's taps: centre c16 (16.16, inside the picture), picture size n
-struct Taps { int t0, t1; uint32_t w; };
-__device__ __forceinline__ Taps taps(int c16, int n) {
-    const int U = c16 - 32768;
-    const int t = U >> 16;                                     // -1 .. n - 1
-    return Taps{max(t, 0), min(t + 1, n - 1), (uint32_t)(U & 0xFFFF) >> 8};
-}
-
-// ---- present_area_kernels.hip: area -------------------------------------------------------------------------------------------
-constexpr bool constant_byte(int mode, int b) { return mode == JSP_DISPLAY_SETPIXELS_RGB15 ? b == 0 : b == 3; }
-constexpr uint32_t constant_bits(int mode) { return mode == JSP_DISPLAY_SETPIXELS_RGB15 ? 0u : 0xFF000000u; }
-struct Span { int first, last; uint32_t wf, wl, W; };
-__device__ __forceinline__ Span footprint(int c16, int s, int n) {
-    const int c = c16 >> 8;
-    const int lo = max(c - (s >> 1), 0);
-    const int hi = min(c - (s >> 1) + s, n << 8);
-    Span f;
-    f.first = lo >> 8;
-    f.last = (hi - 1) >> 8;
-    f.W = (uint32_t)(hi - lo);
-    f.wf = (uint32_t)(min(hi, (f.first + 1) << 8) - lo);
-    f.wl = f.last > f.first ? (uint32_t)(hi - (f.last << 8)) : 0u;
-    return f;
-}
-__device__ __forceinline__ uint32_t weight(const Span& f, int x) { return x == f.first ? f.wf : x < f.last ? 256u : x == f.last ? f.wl : 0u; }
-__device__ __forceinline__ uint32_t small_quotient(unsigned long long n, uint32_t d) {
-    uint32_t q = (uint32_t)((float)n / (float)d);
-    long long r = (long long)n - (long long)((unsigned long long)q * d);
-    if (r < 0) { --q; r += d; }
-    if (r >= (long long)d) ++q;
-    return q;
-}
+using namespace present_rule;
 
 // The source columns (rows) [s0, s1] that the output pixels with centres lo16 .. hi16 (16.16, both inside the picture, n wide) reach:
 // the first tap of the first and the last tap of the last — taps and footprints move monotonically with the centre.
@@ -171,7 +119,7 @@ __device__ __forceinline__ bool present_words(const IndexPresentArgs& a, const u
                     if (!in[j]) continue;
                     if (FILTER == JSP_PRESENT_NEAREST) {
                         const int x = X16[j] >> 16, y = Y16 >> 16;
-                        if (held(x, y)) px[j] = convert<MODE>(at(x, y));
+                        if (held(x, y)) px[j] = convert(at(x, y), MODE);
                     } else if (FILTER == JSP_PRESENT_BILINEAR) {
                         const Taps tx = taps(X16[j], a.fw);
                         if (held(tx.t0, ty.t0)) tap[j][0] = at(tx.t0, ty.t0);
@@ -185,7 +133,7 @@ __device__ __forceinline__ bool present_words(const IndexPresentArgs& a, const u
                         for (int y = ya; y <= yb; ++y) {
                             uint32_t r[4] = {0u, 0u, 0u, 0u};                  // a row of the tile: 64 * 255 * 256 < 2^22 per byte
                             for (int x = xa; x <= xb; ++x) {
-                                const uint32_t p = convert<MODE>(at(x, y)), wx = weight(cx, x);
+                                const uint32_t p = convert(at(x, y), MODE), wx = weight(cx, x);
 #pragma unroll
                                 for (int b = 0; b < 4; ++b)
                                     if (!constant_byte(MODE, b)) r[b] += ((p >> (8 * b)) & 0xFFu) * wx;
@@ -210,8 +158,8 @@ __device__ __forceinline__ bool present_words(const IndexPresentArgs& a, const u
         if (!in[j]) continue;
         if (FILTER == JSP_PRESENT_BILINEAR) {
             const uint32_t wx = taps(X16[j], a.fw).w;
-            px[j] = vblend(hblend(convert<MODE>(tap[j][0]), convert<MODE>(tap[j][1]), wx),
-                           hblend(convert<MODE>(tap[j][2]), convert<MODE>(tap[j][3]), wx), ty.w);
+            px[j] = vblend(hblend(convert(tap[j][0], MODE), convert(tap[j][1], MODE), wx),
+                           hblend(convert(tap[j][2], MODE), convert(tap[j][3], MODE), wx), ty.w);
         } else if (FILTER == JSP_PRESENT_AREA) {
             const uint32_t D = footprint(X16[j], s, a.fw).W * cy.W;            // <= 2^28
             uint32_t v = constant_bits(MODE);

@@ -3,7 +3,9 @@
 // pixels under a step x step box around its centre instead of one or four samples of them: what "Fit" of a screen recording into a
 // small window needs.  The rule is in integers (include/jsplayer_amd.h): per axis a footprint [lo', hi') in 1/256 source pixels,
 // clipped to the picture; source column x weighs its overlap with it (0 .. 256), rows likewise; each byte of the converted words is
-// floor((S + (D >> 1)) / D) with S the doubly weighted sum and D = Wx * Wy the clipped footprint's area.
+// floor((S + (D >> 1)) / D) with S the doubly weighted sum and D = Wx * Wy the clipped footprint's area.  Its arithmetic is not written
+// here: convert, Span / footprint / weight and small_quotient are present_rule_device.h's, fixed16, the geometry, the shared bounds and
+// constant_byte present_rule.h's, where the index kernels (index_present_device.h) take them from too.
 //
 // Shape: a lane owns ONE output pixel, a workgroup kAreaLanes pixels of kAreaBandRows output rows.  A shrunk window is small and every
 // pixel of it waits for a chain of loads, so the work is cut fine — 640 x 360 is 3 600 waves — and neighbouring lanes read neighbouring
@@ -23,14 +25,16 @@
 // constant under the rule.  mode and TAPS are template parameters.  No LDS, no full-size converted frame.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
 #include "../../include/jsplayer_amd.h"
 #include "common.h"
+#include "present_rule_device.h"
 
 namespace {
+
+using namespace jsp::present_rule;
 
 constexpr int kAreaLanes = 64;                         // lanes, and output pixels in x, per workgroup (one wave)
 constexpr int kAreaBandRows = 1;                       // output rows a workgroup covers
@@ -46,47 +50,6 @@ struct AreaArgs {
     int step;              // 16.16 bitmap pixels per output pixel
     uint32_t bg;
 };
-
-// the four conversions of display_kernels.hip's convert(), bit for bit
-template <int MODE>
-__device__ __forceinline__ uint32_t convert(uint32_t c) {
-    if (MODE == JSP_DISPLAY_CANVAS) return 0xFF000000u | ((c & 0xFFu) << 16) | (c & 0xFF00u) | ((c >> 16) & 0xFFu);   // Manager.hx:379
-    if (MODE == JSP_DISPLAY_CANVAS_RGB15) return 0xFF000000u | (c << 3);                                               // :370
-    if (MODE == JSP_DISPLAY_SETPIXELS) return 0xFF000000u | c;                                                         // :351
-    return c << 11;                                                                                                    // :340
-}
-
-// byte b of every converted word is the same: 0xFF in the top byte of the canvas modes, 0 in the low byte of c << 11
-constexpr bool constant_byte(int mode, int b) { return mode == JSP_DISPLAY_SETPIXELS_RGB15 ? b == 0 : b == 3; }
-constexpr uint32_t constant_bits(int mode) { return mode == JSP_DISPLAY_SETPIXELS_RGB15 ? 0u : 0xFF000000u; }
-
-// One axis of a covered pixel's footprint: centre c16 (16.16, inside the picture), s = step >> 8, picture size n.  first .. last are
-// the source columns (rows) the clipped footprint [lo', hi') touches, wf and wl the weights of the two (wl = 0 where they are one:
-// that column then weighs W through wf), W = hi' - lo'.
-struct Span { int first, last; uint32_t wf, wl, W; };
-__device__ __forceinline__ Span footprint(int c16, int s, int n) {
-    const int c = c16 >> 8;                                // (covered: c16 < 2^30)
-    const int lo = max(c - (s >> 1), 0);
-    const int hi = min(c - (s >> 1) + s, n << 8);          // hi > lo: the centre lies in the picture and s >= 4
-    Span f;
-    f.first = lo >> 8;
-    f.last = (hi - 1) >> 8;
-    f.W = (uint32_t)(hi - lo);
-    f.wf = (uint32_t)(min(hi, (f.first + 1) << 8) - lo);
-    f.wl = f.last > f.first ? (uint32_t)(hi - (f.last << 8)) : 0u;
-    return f;
-}
-// the weight of column (row) x of a footprint: wf, 256 .. 256, wl
-__device__ __forceinline__ uint32_t weight(const Span& f, int x) { return x == f.first ? f.wf : x < f.last ? 256u : x == f.last ? f.wl : 0u; }
-
-// floor(n / d) for n < 2^37, 0 < d <= 2^28 and a quotient of 255 at most: the float estimate is within one of it
-__device__ __forceinline__ uint32_t small_quotient(unsigned long long n, uint32_t d) {
-    uint32_t q = (uint32_t)((float)n / (float)d);
-    long long r = (long long)n - (long long)((unsigned long long)q * d);
-    if (r < 0) { --q; r += d; }
-    if (r >= (long long)d) ++q;
-    return q;
-}
 
 // TAPS: 3 or 5 — the launch's promise that no footprint touches more columns or rows; 0 — any footprint
 template <int MODE, int TAPS>
@@ -124,7 +87,7 @@ __global__ __launch_bounds__(kAreaLanes) void display_present_area_kernel(const 
                     const uint32_t wy = weight(cy, y);
                     uint32_t p[NARROW ? TAPS : 1];
 #pragma unroll
-                    for (int t = 0; t < TAPS; ++t) p[t] = convert<MODE>(row[tx[t]]);
+                    for (int t = 0; t < TAPS; ++t) p[t] = convert(row[tx[t]], MODE);
 #pragma unroll
                     for (int b = 0; b < 4; ++b) {
                         if (constant_byte(MODE, b)) continue;
@@ -142,11 +105,11 @@ __global__ __launch_bounds__(kAreaLanes) void display_present_area_kernel(const 
                     const uint32_t* row = a.src + (size_t)y * a.fw;
                     const bool outer = y == cy.first || y == cy.last;
                     const uint32_t wy = weight(cy, y);
-                    const uint32_t pf = convert<MODE>(row[cx.first]), pl = convert<MODE>(row[cx.last]);
+                    const uint32_t pf = convert(row[cx.first], MODE), pl = convert(row[cx.last], MODE);
                     uint32_t e = 0u, o = 0u;                   // bytes 0 and 2, 1 and 3 of the columns between: 63 of 255 at most fit 16 bits
 #pragma unroll 8
                     for (int x = cx.first + 1; x < cx.last; ++x) {
-                        const uint32_t p = convert<MODE>(row[x]);
+                        const uint32_t p = convert(row[x], MODE);
                         e += p & 0x00FF00FFu;
                         o += (p >> 8) & 0x00FF00FFu;
                     }
@@ -179,14 +142,6 @@ void launch(dim3 grid, hipStream_t s, const AreaArgs& a) {
     else hipLaunchKernelGGL((display_present_area_kernel<MODE, 0>), grid, dim3(kAreaLanes), 0, s, a);
 }
 
-// F(v) of present_kernels.hip: floor(v * 65536 + 0.5) as a 64-bit integer, held at +-2^62
-long long fixed16(double v) {
-    const double f = std::floor(v * 65536.0 + 0.5), lim = 4611686018427387904.0;
-    if (f >= lim) return 1ll << 62;
-    if (f <= -lim) return -(1ll << 62);
-    return (long long)f;
-}
-
 }  // namespace
 
 extern "C" {
@@ -196,19 +151,16 @@ int jsp_display_present_area(const int32_t* frame, int frame_w, int frame_h, int
     try {
         if (!frame || !out) throw std::runtime_error("null pointer");
         if (frame_w < 1 || frame_w > 16384 || frame_h < 1 || frame_h > 16384) throw std::runtime_error("frame size outside 1..16384");
-        if (win_w < 1 || win_w > 16384 || win_h < 1 || win_h > 16384) throw std::runtime_error("window size outside 1..16384");
+        if (const char* why = window_refusal(win_w, win_h)) throw std::runtime_error(why);
         if (out_pitch < (size_t)win_w) throw std::runtime_error("out_pitch below win_w");
-        if (!std::isfinite(k) || !std::isfinite(dx) || !std::isfinite(dy)) throw std::runtime_error("k, dx, dy must be finite");
-        if (k < 1.0 / 64.0 || k > 64.0) throw std::runtime_error("k outside 1/64..64");
-        if (mode < JSP_DISPLAY_CANVAS || mode > JSP_DISPLAY_SETPIXELS_RGB15) throw std::runtime_error("unknown mode");
+        if (const char* why = view_refusal(k, dx, dy, mode)) throw std::runtime_error(why);
+        const Geometry g = geometry(win_h, k, dx, dy);
         AreaArgs a;
         a.src = reinterpret_cast<const uint32_t*>(frame);
         a.dst = reinterpret_cast<uint32_t*>(out);
         a.fw = frame_w; a.fh = frame_h; a.ww = win_w; a.wh = win_h;
         a.pitch = out_pitch;
-        a.step = (int)fixed16(1.0 / k);                        // 1024 .. 64 * 65536
-        a.ax = fixed16((0.5 + dx) / k);
-        a.ay = fixed16(((double)win_h + dy - 0.5) / k);
+        a.step = g.step; a.ax = g.ax; a.ay = g.ay;
         a.bg = background;
         const dim3 grid((unsigned)((win_w + kAreaLanes - 1) / kAreaLanes), (unsigned)((win_h + kAreaBandRows - 1) / kAreaBandRows));
         hipStream_t s = static_cast<hipStream_t>(hip_stream);

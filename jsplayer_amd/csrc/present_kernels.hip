@@ -4,7 +4,9 @@
 //                     Manager.fill_bitmap_data's conversion, the row flip, the crop and the resampling in one pass.
 // The resampling rule is this project's own, in integers (include/jsplayer_amd.h, jsp_display_present): 16.16 bitmap coordinates of
 // each output pixel's centre, X = ax + ox * step, Y = ay - oy * step; nearest = the pixel at (X >> 16, Y >> 16); bilinear = four taps
-// around (X - 32768, Y - 32768) with 8-bit weights, every byte of the converted words blended separately.
+// around (X - 32768, Y - 32768) with 8-bit weights, every byte of the converted words blended separately.  Its arithmetic is not
+// written here: fixed16, the geometry and the shared bounds are present_rule.h's, convert, taps, hblend and vblend
+// present_rule_device.h's, where the index kernels (index_present_device.h) take them from too.
 //
 // Shape: a lane owns kPresentRun consecutive pixels of a row (one 16-byte non-temporal store where `out` and its pitch allow, scalar
 // stores otherwise and for the row's remainder), a workgroup is one wave — kPresentSpanX pixels of kPresentBandRows output rows.  A
@@ -14,14 +16,16 @@
 // blockIdx.y alone.  mode and filter are template parameters.  No LDS, no full-size converted frame.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
 #include "../../include/jsplayer_amd.h"
 #include "common.h"
+#include "present_rule_device.h"
 
 namespace {
+
+using namespace jsp::present_rule;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -40,31 +44,6 @@ struct PresentArgs {
     uint32_t bg;
     int vec;               // every row of `dst` starts on a 16-byte boundary
 };
-
-// the four conversions of display_kernels.hip's convert(), bit for bit
-template <int MODE>
-__device__ __forceinline__ uint32_t convert(uint32_t c) {
-    if (MODE == JSP_DISPLAY_CANVAS) return 0xFF000000u | ((c & 0xFFu) << 16) | (c & 0xFF00u) | ((c >> 16) & 0xFFu);   // Manager.hx:379
-    if (MODE == JSP_DISPLAY_CANVAS_RGB15) return 0xFF000000u | (c << 3);                                               // :370
-    if (MODE == JSP_DISPLAY_SETPIXELS) return 0xFF000000u | c;                                                         // :351
-    return c << 11;                                                                                                    // :340
-}
-
-// p0 * (256 - w) + p1 * w for the four bytes of two converted words: bytes 0 and 2 in the halves of .e, bytes 1 and 3 in those of .o
-// (a byte times 256 at most: each sum fits its 16 bits)
-struct HSum { uint32_t e, o; };
-__device__ __forceinline__ HSum hblend(uint32_t p0, uint32_t p1, uint32_t w) {
-    const uint32_t v = 256u - w;
-    return HSum{(p0 & 0x00FF00FFu) * v + (p1 & 0x00FF00FFu) * w, ((p0 >> 8) & 0x00FF00FFu) * v + ((p1 >> 8) & 0x00FF00FFu) * w};
-}
-__device__ __forceinline__ uint32_t vblend(HSum a, HSum b, uint32_t w) {
-    const uint32_t v = 256u - w;
-    const uint32_t b0 = ((a.e & 0xFFFFu) * v + (b.e & 0xFFFFu) * w + 32768u) >> 16;
-    const uint32_t b2 = ((a.e >> 16) * v + (b.e >> 16) * w + 32768u) >> 16;
-    const uint32_t b1 = ((a.o & 0xFFFFu) * v + (b.o & 0xFFFFu) * w + 32768u) >> 16;
-    const uint32_t b3 = ((a.o >> 16) * v + (b.o >> 16) * w + 32768u) >> 16;
-    return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
-}
 
 template <int MODE, int FILTER>
 __global__ __launch_bounds__(kPresentLanes) void display_present_kernel(const PresentArgs a) {
@@ -88,11 +67,10 @@ __global__ __launch_bounds__(kPresentLanes) void display_present_kernel(const Pr
             if (FILTER == JSP_PRESENT_NEAREST) {
                 x0[j] = (int)(X >> 16);
             } else {
-                const int U = (int)X - 32768;                  // (covered: X < 2^30)
-                const int t = U >> 16;                         // -1 .. fw - 1
-                x0[j] = max(t, 0);
-                x1[j] = min(t + 1, a.fw - 1);
-                wx[j] = (uint32_t)(U & 0xFFFF) >> 8;
+                const Taps tx = taps((int)X, a.fw);            // (covered: X < 2^30)
+                x0[j] = tx.t0;
+                x1[j] = tx.t1;
+                wx[j] = tx.w;
             }
         }
     }
@@ -112,14 +90,13 @@ __global__ __launch_bounds__(kPresentLanes) void display_present_kernel(const Pr
                 const uint32_t* row = a.src + (size_t)(Y >> 16) * a.fw;
 #pragma unroll
                 for (int j = 0; j < kPresentRun; ++j) {
-                    const uint32_t c = convert<MODE>(row[x0[j]]);
+                    const uint32_t c = convert(row[x0[j]], MODE);
                     if (in[j]) px[j] = c;
                 }
             } else {
-                const int V = (int)Y - 32768;
-                const int t = V >> 16;
-                const int r0 = max(t, 0), r1 = min(t + 1, a.fh - 1);
-                const uint32_t wy = (uint32_t)(V & 0xFFFF) >> 8;
+                const Taps ty = taps((int)Y, a.fh);
+                const int r0 = ty.t0, r1 = ty.t1;
+                const uint32_t wy = ty.w;
                 HSum na[kPresentRun], nb[kPresentRun];
                 if (r0 == ra) {
 #pragma unroll
@@ -130,7 +107,7 @@ __global__ __launch_bounds__(kPresentLanes) void display_present_kernel(const Pr
                 } else {
                     const uint32_t* row = a.src + (size_t)r0 * a.fw;
 #pragma unroll
-                    for (int j = 0; j < kPresentRun; ++j) na[j] = hblend(convert<MODE>(row[x0[j]]), convert<MODE>(row[x1[j]]), wx[j]);
+                    for (int j = 0; j < kPresentRun; ++j) na[j] = hblend(convert(row[x0[j]], MODE), convert(row[x1[j]], MODE), wx[j]);
                 }
                 if (r1 == r0) {
 #pragma unroll
@@ -144,7 +121,7 @@ __global__ __launch_bounds__(kPresentLanes) void display_present_kernel(const Pr
                 } else {
                     const uint32_t* row = a.src + (size_t)r1 * a.fw;
 #pragma unroll
-                    for (int j = 0; j < kPresentRun; ++j) nb[j] = hblend(convert<MODE>(row[x0[j]]), convert<MODE>(row[x1[j]]), wx[j]);
+                    for (int j = 0; j < kPresentRun; ++j) nb[j] = hblend(convert(row[x0[j]], MODE), convert(row[x1[j]], MODE), wx[j]);
                 }
                 ra = r0;
                 rb = r1;
@@ -173,15 +150,6 @@ void launch_filter(int filter, dim3 grid, hipStream_t s, const PresentArgs& a) {
     else hipLaunchKernelGGL((display_present_kernel<MODE, JSP_PRESENT_BILINEAR>), grid, dim3(kPresentLanes), 0, s, a);
 }
 
-// F(v) = floor(v * 65536 + 0.5) as a 64-bit integer.  A value beyond +-2^62 (a far-away dx or dy) is held there: with ox * step below
-// 2^36 every pixel of such a window lies outside the picture either way, so the window is the one the unbounded integer gives.
-long long fixed16(double v) {
-    const double f = std::floor(v * 65536.0 + 0.5), lim = 4611686018427387904.0;
-    if (f >= lim) return 1ll << 62;
-    if (f <= -lim) return -(1ll << 62);
-    return (long long)f;
-}
-
 }  // namespace
 
 extern "C" {
@@ -191,20 +159,17 @@ int jsp_display_present(const int32_t* frame, int frame_w, int frame_h, int32_t*
     try {
         if (!frame || !out) throw std::runtime_error("null pointer");
         if (frame_w < 1 || frame_w > 16384 || frame_h < 1 || frame_h > 16384) throw std::runtime_error("frame size outside 1..16384");
-        if (win_w < 1 || win_w > 16384 || win_h < 1 || win_h > 16384) throw std::runtime_error("window size outside 1..16384");
+        if (const char* why = window_refusal(win_w, win_h)) throw std::runtime_error(why);
         if (out_pitch < (size_t)win_w) throw std::runtime_error("out_pitch below win_w");
-        if (!std::isfinite(k) || !std::isfinite(dx) || !std::isfinite(dy)) throw std::runtime_error("k, dx, dy must be finite");
-        if (k < 1.0 / 64.0 || k > 64.0) throw std::runtime_error("k outside 1/64..64");
-        if (mode < JSP_DISPLAY_CANVAS || mode > JSP_DISPLAY_SETPIXELS_RGB15) throw std::runtime_error("unknown mode");
+        if (const char* why = view_refusal(k, dx, dy, mode)) throw std::runtime_error(why);
         if (filter != JSP_PRESENT_NEAREST && filter != JSP_PRESENT_BILINEAR) throw std::runtime_error("unknown filter");
+        const Geometry g = geometry(win_h, k, dx, dy);
         PresentArgs a;
         a.src = reinterpret_cast<const uint32_t*>(frame);
         a.dst = reinterpret_cast<uint32_t*>(out);
         a.fw = frame_w; a.fh = frame_h; a.ww = win_w; a.wh = win_h;
         a.pitch = out_pitch;
-        a.step = (int)fixed16(1.0 / k);                        // 1024 .. 64 * 65536
-        a.ax = fixed16((0.5 + dx) / k);
-        a.ay = fixed16(((double)win_h + dy - 0.5) / k);
+        a.step = g.step; a.ax = g.ax; a.ay = g.ay;
         a.bg = background;
         a.vec = ((reinterpret_cast<uintptr_t>(out) & 15) == 0 && (out_pitch & 3) == 0) ? 1 : 0;
         const dim3 grid((unsigned)((win_w + kPresentSpanX - 1) / kPresentSpanX), (unsigned)((win_h + kPresentBandRows - 1) / kPresentBandRows));
