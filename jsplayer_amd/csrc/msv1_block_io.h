@@ -1,6 +1,6 @@
 // What the MSVideo1 block kernels (msv1_kernels.hip, msv1_seek_kernels.hip) share around decode_block (msv1_decode.h): a block's row
 // loads and stores, the look-before-OR of a significance word, the pixels no block covers, the palette prologue, the decode of a
-// code in global memory, the seek index's last-writer walk, and the host's BITS x VEC dispatch.
+// code in global memory, the seek index's block rule (index_block) with its last-writer walk, and the host's BITS x VEC dispatch.
 #pragma once
 #include <type_traits>
 
@@ -123,29 +123,32 @@ __device__ __forceinline__ void decode_at(const uint8_t* __restrict__ stream, ui
     decode_block<BITS>(reinterpret_cast<const uint8_t*>(cw), avail, s_pal, px);
 }
 
-// The 16 pixels frame f of a seek index makes of block `blk`, which it codes: its chunk (frame_chunk[], chunks[]) gives the table
+// ---- the seek index (Msv1IndexSrc, msv1_seek.h): what its kernels — show, play, thumbnails, present, tensor — share ----------------
+// The 16 pixels frame f of the index makes of block `blk`, which it codes: its chunk (frame_chunk[], chunks[]) gives the table
 // entry and the stream.
 template <int BITS>
-__device__ __forceinline__ void index_decode(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk, size_t pitch,
-                                             int f, int blk, const uint32_t* s_pal, uint32_t (&px)[16]) {
-    const Msv1IndexChunk ch = chunks[frame_chunk[f]];
+__device__ __forceinline__ void index_decode(const Msv1IndexSrc& s, int f, int blk, const uint32_t* s_pal, uint32_t (&px)[16]) {
+    const Msv1IndexChunk ch = s.chunks[s.frame_chunk[f]];
     const int lf = f - (int)ch.first;
-    const uint32_t o = *(cgu32*)(ch.desc + (size_t)lf * pitch + blk);
+    const uint32_t o = *(cgu32*)(ch.desc + (size_t)lf * s.pitch + blk);
     decode_at<BITS>(ch.stream, o, ch.frames[lf].stream_end, s_pal, px);
 }
 
 constexpr int INDEX_SCAN = 4;   // bitmap words a lane has in flight per step of its walk down (msv1_seek_kernels.hip's SCAN is this)
 
-// The bitmap word of block `blk` that holds the last frame <= t coding it, masked to the frames <= t (its highest set bit is that
-// frame: 32 * w + 31 - clz; w is set), or 0 when nothing up to t coded the block.  Word t / 32 first, then the words below it,
-// INDEX_SCAN in flight per step.  Shared by the show, play, thumbnail and present kernels.
-__device__ __forceinline__ uint32_t index_last_writer(const uint32_t* __restrict__ bitmap, int nblocks, int blk, int t, int& w) {
+// The frame that the non-zero masked bitmap word `m`, word `w` of its block, names: its highest set bit.
+__device__ __forceinline__ int index_word_frame(int w, uint32_t m) { return 32 * w + 31 - __builtin_clz(m); }
+
+// The bitmap word of block `blk` that holds the last frame <= t coding it, masked to the frames <= t (index_word_frame(w, m) is that
+// frame; w is set), or 0 when nothing up to t coded the block.  Word t / 32 first, then the words below it, INDEX_SCAN in flight
+// per step.
+__device__ __forceinline__ uint32_t index_last_writer(const Msv1IndexSrc& s, int blk, int t, int& w) {
     w = t >> 5;
-    uint32_t m = *(cgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
+    uint32_t m = *(cgu32*)(s.bitmap + (size_t)w * (size_t)s.nblocks + blk) & (0xFFFFFFFFu >> (31 - (t & 31)));
     while (m == 0u && w > 0) {
         uint32_t e[INDEX_SCAN];
 #pragma unroll
-        for (int k = 0; k < INDEX_SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(cgu32*)(bitmap + (size_t)(w - 1 - k) * (size_t)nblocks + blk) : 0u;
+        for (int k = 0; k < INDEX_SCAN; ++k) e[k] = w - 1 - k >= 0 ? *(cgu32*)(s.bitmap + (size_t)(w - 1 - k) * (size_t)s.nblocks + blk) : 0u;
         int step = INDEX_SCAN;
 #pragma unroll
         for (int k = INDEX_SCAN - 1; k >= 0; --k)
@@ -153,6 +156,31 @@ __device__ __forceinline__ uint32_t index_last_writer(const uint32_t* __restrict
         w -= step;
     }
     return m;
+}
+
+// THE BLOCK RULE of a seek index.  Block `blk` (block column bx, block row by) of the picture of index frame t is what the last
+// frame <= t that coded it makes of it, decoded from its code; else the block of the picture before the index; else nothing: px[]
+// is zeros then, and the result false (the block is not defined — Show and Play leave the destination alone, the kernels that
+// have no destination picture use the zeros).  before_vec: the block of `before` is read 16 bytes a row (a constant where the caller
+// has one: the branch folds away).
+template <int BITS>
+__device__ __forceinline__ bool index_block(const Msv1IndexSrc& s, int t, int blk, int bx, int by, bool before_vec, const uint32_t* s_pal,
+                                            uint32_t (&px)[16]) {
+    int w;
+    const uint32_t m = index_last_writer(s, blk, t, w);
+    if (m != 0u) {
+        index_decode<BITS>(s, index_word_frame(w, m), blk, s_pal, px);
+        return true;
+    }
+    if (s.before != nullptr) {
+        const uint32_t* p = s.before + (size_t)by * 4u * (size_t)s.X + (size_t)bx * 4u;
+        if (before_vec) load_block<true>(p, s.X, px);
+        else load_block<false>(p, s.X, px);
+        return true;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) px[i] = 0u;
+    return false;
 }
 
 // Host: f(std::integral_constant<int, BITS>{}, std::bool_constant<VEC>{}) for the kernel instantiation that `bits` (16, else 8) and

@@ -21,26 +21,26 @@ struct jsp_index {
         int first = 0, count = 0;
     };
     std::vector<std::unique_ptr<Chunk>> chunks;
-    DeviceBuffer d_chunks, d_frame_chunk, d_bitmap, d_palette, d_before;
-    bool has_before = false;
+    DeviceBuffer d_chunks, d_frame_chunk, d_bitmap, d_palette, d_before;   // (d_before: nothing when there is no picture before the index)
+    Msv1IndexSrc src{};                    // what the index kernels read of all that: filled when the build ends (index_src)
     std::vector<int> significance;         // per frame: jsp_find_change's verdict (1 / 0)
     std::vector<uint8_t> reported;         // per frame: what jsp_seek of frames 0..t reports as *significant_changes
     std::vector<uint8_t> block_changes;    // nframes rows of nby flags: the per-row state after frame t
     int first_adopted = 0;                 // the first frame that adopts its destination (nframes: none)
     int32_t* prev_caller = nullptr;        // the codec's previous frame at build time (what a show before first_adopted leaves)
     int32_t* prev_dev = nullptr;
-    PinnedBuffer h_thumb_frames;           // jsp_index_thumbs / jsp_index_present: the call's frame list on its way to ...
-    DeviceBuffer d_thumb_frames;           // ... the array the kernel reads (both grown on demand)
+    PinnedBuffer h_frame_list;             // jsp_index_thumbs / _present / _tensor: the call's frame list on its way to ...
+    DeviceBuffer d_frame_list;             // ... the array the kernel reads (both grown on demand)
     PinnedBuffer h_play_dsts;              // jsp_index_play: the call's destinations on their way to ...
     DeviceBuffer d_play_dsts;              // ... the array the kernel reads (both grown on demand; nothing until the first call)
     uint64_t device_bytes() const {
-        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_thumb_frames.cap + d_play_dsts.cap;
+        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_frame_list.cap + d_play_dsts.cap;
         for (const auto& c : chunks) n += c->stream.cap + c->desc.cap + c->frames.cap;
         return n;
     }
     uint64_t host_bytes() const {
         return sizeof(*this) + chunks.size() * sizeof(Chunk) + significance.size() * sizeof(int) + reported.size() + block_changes.size() +
-               h_thumb_frames.cap + h_play_dsts.cap;
+               h_frame_list.cap + h_play_dsts.cap;
     }
 };
 
@@ -91,12 +91,13 @@ bool nothing_in_flight(const jsp_codec* c, const char* who) {
 bool dst_not_previous(const jsp_codec* c, const int32_t* dst, const char* who) {
     return dst != c->prev_caller || refuse(who, "dst is the current previous frame");
 }
-bool dst_on_device(const int32_t* dst, const char* who) {   // (after c->activate())
+bool on_device(const void* p, const char* who, const char* what) {   // (after c->activate())
     hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, dst) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged)) return true;
+    if (hipPointerGetAttributes(&attr, p) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged)) return true;
     (void)hipGetLastError();
-    return refuse(who, "dst must be a device frame buffer");
+    return refuse(who, what);
 }
+bool dst_on_device(const int32_t* dst, const char* who) { return on_device(dst, who, "dst must be a device frame buffer"); }
 bool device_pointers(const jsp_codec* c, const char* who) { return c->ptr_mode != 2 || refuse(who, "codec is in host-pointer mode"); }
 
 // A call that leaves the codec where a sequential decode into `dst` would: the worker's frames finished, device pointers from now
@@ -200,6 +201,26 @@ void judge_chunk(jsp_codec* c, const jsp_staged* st, const Msv1SeekView& v, int 
     msv1_launch_change_scan(v, d_first + head + nf, nwalk, d_first + head, stop_at_hit ? d_first : nullptr, before, c->stream);
     JSP_HIP(hipGetLastError());
     JSP_HIP(hipMemcpyAsync(v.h_signif, v.d_signif, sizeof(uint32_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+}
+
+// What the index kernels read of a built index (Msv1IndexSrc, msv1_seek.h), with the clamps a picture without a block needs.
+Msv1IndexSrc index_src(const jsp_index& idx) {
+    const Msv1Geometry& geo = idx.geo;
+    Msv1IndexSrc s{};
+    s.chunks = idx.d_chunks.as<const Msv1IndexChunk>();
+    s.frame_chunk = idx.d_frame_chunk.as<const uint32_t>();
+    s.palette = idx.d_palette.as<const int32_t>();
+    s.bitmap = idx.d_bitmap.as<const uint32_t>();
+    s.before = idx.d_before.as<const uint32_t>();
+    s.pitch = (size_t)std::max(geo.nblocks, 1);
+    s.nblocks = std::max(geo.nblocks, 0);
+    s.nbx = std::max(geo.nbx, 0);
+    s.nby = std::max(geo.nby, 0);
+    s.X = geo.X;
+    s.Y = geo.Y;
+    s.bits = geo.bits;
+    s.before_vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(s.before) & 15);
+    return s;
 }
 
 }  // namespace
@@ -400,7 +421,6 @@ extern "C" jsp_index* jsp_index_build(jsp_codec* c, int nframes, const uint8_t* 
         d_run.reserve(pic_bytes);
         int32_t* run = static_cast<int32_t*>(d_run.p);
         if (c->prev_dev) {
-            idx->has_before = true;
             idx->d_before.reserve(pic_bytes);
             JSP_HIP(hipMemcpyAsync(idx->d_before.p, c->prev_dev, sizeof(int32_t) * npix, hipMemcpyDeviceToDevice, c->stream));
             JSP_HIP(hipMemcpyAsync(run, c->prev_dev, sizeof(int32_t) * npix, hipMemcpyDeviceToDevice, c->stream));
@@ -491,7 +511,7 @@ extern "C" jsp_index* jsp_index_build(jsp_codec* c, int nframes, const uint8_t* 
             std::copy(rows_now.begin(), rows_now.end(), idx->block_changes.begin() + (size_t)t * (size_t)nby);
         }
 
-        // ---- what the show kernel reads: per-chunk pointers, the chunk of every frame, the palette ---------------------------------
+        // ---- what the index kernels read: per-chunk pointers, the chunk of every frame, and the record that names it all -------------
         std::vector<Msv1IndexChunk> table;
         std::vector<uint32_t> frame_chunk((size_t)nframes);
         for (size_t k = 0; k < idx->chunks.size(); ++k) {
@@ -504,6 +524,7 @@ extern "C" jsp_index* jsp_index_build(jsp_codec* c, int nframes, const uint8_t* 
         idx->d_frame_chunk.reserve(sizeof(uint32_t) * frame_chunk.size());
         JSP_HIP(hipMemcpy(idx->d_chunks.p, table.data(), sizeof(Msv1IndexChunk) * table.size(), hipMemcpyHostToDevice));
         JSP_HIP(hipMemcpy(idx->d_frame_chunk.p, frame_chunk.data(), sizeof(uint32_t) * frame_chunk.size(), hipMemcpyHostToDevice));
+        idx->src = index_src(*idx);
         msv1_restore_state(c, saved);
         return idx.release();
     } catch (const std::exception& e) {
@@ -541,9 +562,7 @@ extern "C" int jsp_index_show(jsp_codec* c, jsp_index* idx, int t, int32_t* dst,
         if (!dst_on_device(dst, "index_show") || !device_pointers(c, "index_show")) return JSP_ERROR_OCCURED;
         const bool adopted = t >= idx->first_adopted;   // jsp_seek of frames 0..t writes dst only then
         if (adopted) {
-            msv1_launch_index_show(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
-                                   static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p), t, dst,
-                                   idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, c->stream);
+            msv1_launch_index_show(idx->src, t, dst, c->stream);
             JSP_HIP(hipGetLastError());
             JSP_HIP(hipStreamSynchronize(c->stream));
         }
@@ -598,11 +617,8 @@ extern "C" int jsp_index_play(jsp_codec* c, jsp_index* idx, int first, int n, in
             std::fill(h, h + first_written, nullptr);
             std::copy(dsts + first_written, dsts + n, h + first_written);
             JSP_HIP(hipMemcpyAsync(idx->d_play_dsts.p, h, sizeof(int32_t*) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-            const int segs = c->index_play_segments > 0 ? c->index_play_segments : msv1_index_play_auto_segments(idx->geo, n);
-            msv1_launch_index_play(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
-                                   static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p), first, n, stride, segs,
-                                   static_cast<int32_t* const*>(idx->d_play_dsts.p), aligned16,
-                                   idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, c->stream);
+            const int segs = c->index_play_segments > 0 ? c->index_play_segments : msv1_index_play_auto_segments(idx->src, n);
+            msv1_launch_index_play(idx->src, first, n, stride, segs, idx->d_play_dsts.as<int32_t*>(), aligned16, c->stream);
             JSP_HIP(hipGetLastError());
             JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned destination list is free for the next call)
         }
@@ -619,9 +635,8 @@ extern "C" int jsp_index_play(jsp_codec* c, jsp_index* idx, int first, int n, in
     }
 }
 
-// ---- thumbnails: the preview that follows the pointer along the seek bar (Main.on_mouse_move, Main.hx:1147-1215), a filmstrip of a
-// key interval — n frames of the index, each reduced scale x scale pixels to one, in ONE launch of msv1_index_thumbs_kernel.  The
-// full-size pictures never exist, and the codec is only lent: its stream carries the launch, nothing of its state is read or written.
+// ---- the calls the codec is only lent to — jsp_index_thumbs, jsp_index_present, jsp_index_tensor: its stream carries the launch,
+// nothing of its state is read or written, and no full-size picture exists anywhere. ---------------------------------------------------
 namespace {
 // The thumbnail of an index at `scale`: false (error set) for a scale other than 4 / 8 / 16 or a picture too small for one pixel.
 bool thumb_size(const jsp_index* idx, int scale, const char* who, int& tw, int& th) {
@@ -629,6 +644,33 @@ bool thumb_size(const jsp_index* idx, int scale, const char* who, int& tw, int& 
     tw = std::max(idx->geo.nbx, 0) * 4 / scale;
     th = std::max(idx->geo.nby, 0) * 4 / scale;
     return (tw > 0 && th > 0) || refuse(who, "the picture is too small for a thumbnail at this scale");
+}
+
+// What those calls do before their launch, in the order of their refusals: the index is this codec's; `first`, the call's own checks
+// that come before the frame numbers (n is one of them); every frame number lies inside the index; `then`, the call's other checks;
+// nothing is in flight; c->activate(); `out` is device memory; the frame list goes to the device on the codec's stream.  The device
+// list, or null: refused and the error set (`first` and `then` return false with theirs).
+template <class First, class Then>
+const int32_t* lent_frame_list(jsp_codec* c, jsp_index* idx, const char* who, int n, const int* frames, const void* out, First&& first, Then&& then) {
+    if (idx->codec_serial != c->serial) return refuse(who, "the index was built by another codec"), nullptr;
+    if (!first()) return nullptr;
+    for (int k = 0; k < n; ++k)
+        if (frames[k] < 0 || frames[k] >= idx->nframes) return refuse(who, "a frame number is outside the index"), nullptr;
+    if (!then() || !nothing_in_flight(c, who)) return nullptr;
+    c->activate();
+    if (!on_device(out, who, "out must be a device buffer")) return nullptr;
+    idx->h_frame_list.reserve(sizeof(int32_t) * (size_t)n);
+    idx->d_frame_list.reserve(sizeof(int32_t) * (size_t)n);
+    std::copy(frames, frames + n, idx->h_frame_list.as<int32_t>());
+    JSP_HIP(hipMemcpyAsync(idx->d_frame_list.p, idx->h_frame_list.p, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    return idx->d_frame_list.as<const int32_t>();
+}
+
+// ... and after it: the launch went in, and the pinned list is free for the next call.
+int launched(jsp_codec* c) {
+    JSP_HIP(hipGetLastError());
+    JSP_HIP(hipStreamSynchronize(c->stream));
+    return JSP_ZERO_STATE;
 }
 }  // namespace
 
@@ -641,117 +683,78 @@ extern "C" int jsp_index_thumb_size(const jsp_index* idx, int scale, int* width,
     return JSP_ZERO_STATE;
 }
 
+// Thumbnails: the preview that follows the pointer along the seek bar (Main.on_mouse_move, Main.hx:1147-1215), a filmstrip of a key
+// interval — n frames of the index, each reduced scale x scale pixels to one, in ONE launch of msv1_index_thumbs_kernel.
 extern "C" int jsp_index_thumbs(jsp_codec* c, jsp_index* idx, int n, const int* frames, int scale, int cols, int32_t* out, size_t out_pixels) {
+    const char* who = "index_thumbs";
     if (!c || !idx || !frames || !out) return fail("index_thumbs: null argument");
-    if (!is_msv1(c, "index_thumbs")) return JSP_ERROR_OCCURED;
-    if (idx->codec_serial != c->serial) return fail("index_thumbs: the index was built by another codec");
-    if (n < 1 || n > 4096) return fail("index_thumbs: n is outside 1..4096");
-    for (int k = 0; k < n; ++k)
-        if (frames[k] < 0 || frames[k] >= idx->nframes) return fail("index_thumbs: a frame number is outside the index");
-    int tw = 0, th = 0;
-    if (!thumb_size(idx, scale, "index_thumbs", tw, th)) return JSP_ERROR_OCCURED;
-    if (cols < 1) return fail("index_thumbs: cols must be at least 1");
-    const uint64_t sheet = (uint64_t)cols * (uint64_t)tw * (uint64_t)((n + (int64_t)cols - 1) / cols) * (uint64_t)th;
-    if ((uint64_t)out_pixels < sheet) return fail("index_thumbs: out_pixels is smaller than the sheet");
-    if (!nothing_in_flight(c, "index_thumbs")) return JSP_ERROR_OCCURED;
+    if (!is_msv1(c, who)) return JSP_ERROR_OCCURED;
     try {
-        c->activate();
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, out) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
-            (void)hipGetLastError();
-            return fail("index_thumbs: out must be a device buffer");
-        }
-        idx->h_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
-        idx->d_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
-        std::copy(frames, frames + n, static_cast<int32_t*>(idx->h_thumb_frames.p));
-        JSP_HIP(hipMemcpyAsync(idx->d_thumb_frames.p, idx->h_thumb_frames.p, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        msv1_launch_index_thumbs(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
-                                 static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p),
-                                 static_cast<const int32_t*>(idx->d_thumb_frames.p), n, scale, cols, out,
-                                 idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, c->stream);
-        JSP_HIP(hipGetLastError());
-        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned list is free for the next call)
-        return JSP_ZERO_STATE;
+        const int32_t* d_frames = lent_frame_list(
+            c, idx, who, n, frames, out, [&] { return (n >= 1 && n <= 4096) || refuse(who, "n is outside 1..4096"); },
+            [&] {
+                int tw = 0, th = 0;
+                if (!thumb_size(idx, scale, who, tw, th)) return false;
+                if (cols < 1) return refuse(who, "cols must be at least 1");
+                const uint64_t sheet = (uint64_t)cols * (uint64_t)tw * (uint64_t)((n + (int64_t)cols - 1) / cols) * (uint64_t)th;
+                return (uint64_t)out_pixels >= sheet || refuse(who, "out_pixels is smaller than the sheet");
+            });
+        if (!d_frames) return JSP_ERROR_OCCURED;
+        msv1_launch_index_thumbs(idx->src, d_frames, n, scale, cols, out, c->stream);
+        return launched(c);
     } catch (const std::exception& e) {
         set_error("%s", e.what());
         return JSP_ERROR_OCCURED;
     }
 }
 
-// ---- windows: the hover preview at the size the UI wants, a scrub at 200 % with the view scrolled, a contact sheet — the windows
+// Windows: the hover preview at the size the UI wants, a scrub at 200 % with the view scrolled, a contact sheet — the windows
 // jsp_display_present / jsp_display_present_area would show of n frames of the index, on one sheet, in ONE launch of
-// msv1_index_present_kernel.  The full-size pictures never exist and no frame buffer is written; the codec is only lent, as for the
-// thumbnails, and the frame list travels the thumbnails' way.
+// msv1_index_present_kernel.  No frame buffer is written.
 extern "C" int jsp_index_present(jsp_codec* c, jsp_index* idx, int n, const int* frames, int32_t* out, size_t out_ints, int win_w, int win_h,
                                  size_t out_pitch, int cols, double k, double dx, double dy, int mode, int filter, uint32_t background) {
+    const char* who = "index_present";
     if (!c || !idx || !frames || !out) return fail("index_present: null argument");
     if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
-    if (idx->codec_serial != c->serial) return fail("index_present: the index was built by another codec");
-    if (const char* why = index_present_refusal(n, out_ints, win_w, win_h, out_pitch, cols, k, dx, dy, mode, filter)) return fail("index_present: %s", why);
-    for (int i = 0; i < n; ++i)
-        if (frames[i] < 0 || frames[i] >= idx->nframes) return fail("index_present: a frame number is outside the index");
-    if (idx->geo.X < 1 || idx->geo.Y < 1) return fail("index_present: the index has no picture");
-    if (!nothing_in_flight(c, "index_present")) return JSP_ERROR_OCCURED;
     try {
-        c->activate();
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, out) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
-            (void)hipGetLastError();
-            return fail("index_present: out must be a device buffer");
-        }
-        idx->h_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
-        idx->d_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
-        std::copy(frames, frames + n, static_cast<int32_t*>(idx->h_thumb_frames.p));
-        JSP_HIP(hipMemcpyAsync(idx->d_thumb_frames.p, idx->h_thumb_frames.p, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        const int32_t* d_frames = lent_frame_list(
+            c, idx, who, n, frames, out,
+            [&] {
+                const char* why = index_present_refusal(n, out_ints, win_w, win_h, out_pitch, cols, k, dx, dy, mode, filter);
+                return !why || refuse(who, why);
+            },
+            [&] { return (idx->geo.X >= 1 && idx->geo.Y >= 1) || refuse(who, "the index has no picture"); });
+        if (!d_frames) return JSP_ERROR_OCCURED;
         const IndexPresentArgs a = index_present_args(out, n, idx->geo.X, idx->geo.Y, win_w, win_h, out_pitch, cols, k, dx, dy, filter, background, 4);
-        msv1_launch_index_present(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
-                                  static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p),
-                                  static_cast<const int32_t*>(idx->d_thumb_frames.p), n,
-                                  idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, a, mode, filter, c->stream);
-        JSP_HIP(hipGetLastError());
-        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned list is free for the next call)
-        return JSP_ZERO_STATE;
+        msv1_launch_index_present(idx->src, d_frames, n, a, mode, filter, c->stream);
+        return launched(c);
     } catch (const std::exception& e) {
         set_error("%s", e.what());
         return JSP_ERROR_OCCURED;
     }
 }
 
-// ---- tensors: the same windows as a model's input batch — N x 3 x H x W or N x H x W x 3, float32 / float16 / bfloat16 / uint8, scaled and
-// biased per channel — in ONE launch of msv1_index_tensor_kernel: Present's kernel with another last step.  No sheet is written; the
-// codec is only lent and the frame list travels as for Present.
+// Tensors: the same windows as a model's input batch — N x 3 x H x W or N x H x W x 3, float32 / float16 / bfloat16 / uint8, scaled and
+// biased per channel — in ONE launch of msv1_index_tensor_kernel: Present's kernel with another last step.  No sheet is written.
 extern "C" int jsp_index_tensor(jsp_codec* c, jsp_index* idx, int n, const int* frames, void* out, size_t out_bytes, int win_w, int win_h, double k,
                                 double dx, double dy, int mode, int filter, uint32_t background, int dtype, int layout, const float* scale,
                                 const float* bias) {
+    const char* who = "index_tensor";
     if (!c || !idx || !frames || !out) return fail("index_tensor: null argument");
     if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
-    if (idx->codec_serial != c->serial) return fail("index_tensor: the index was built by another codec");
-    if (const char* why = index_tensor_refusal(n, out, out_bytes, win_w, win_h, k, dx, dy, mode, filter, dtype, layout, scale, bias))
-        return fail("index_tensor: %s", why);
-    for (int i = 0; i < n; ++i)
-        if (frames[i] < 0 || frames[i] >= idx->nframes) return fail("index_tensor: a frame number is outside the index");
-    if (idx->geo.X < 1 || idx->geo.Y < 1) return fail("index_tensor: the index has no picture");
-    if (!nothing_in_flight(c, "index_tensor")) return JSP_ERROR_OCCURED;
     try {
-        c->activate();
-        hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, out) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
-            (void)hipGetLastError();
-            return fail("index_tensor: out must be a device buffer");
-        }
-        idx->h_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
-        idx->d_thumb_frames.reserve(sizeof(int32_t) * (size_t)n);
-        std::copy(frames, frames + n, static_cast<int32_t*>(idx->h_thumb_frames.p));
-        JSP_HIP(hipMemcpyAsync(idx->d_thumb_frames.p, idx->h_thumb_frames.p, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        const int32_t* d_frames = lent_frame_list(
+            c, idx, who, n, frames, out,
+            [&] {
+                const char* why = index_tensor_refusal(n, out, out_bytes, win_w, win_h, k, dx, dy, mode, filter, dtype, layout, scale, bias);
+                return !why || refuse(who, why);
+            },
+            [&] { return (idx->geo.X >= 1 && idx->geo.Y >= 1) || refuse(who, "the index has no picture"); });
+        if (!d_frames) return JSP_ERROR_OCCURED;
         const IndexPresentArgs a = index_present_args(nullptr, n, idx->geo.X, idx->geo.Y, win_w, win_h, (size_t)win_w, 1, k, dx, dy, filter, background, 4);
         const IndexTensorArgs t = index_tensor_args(out, win_w, dtype, layout, scale, bias);
-        msv1_launch_index_tensor(idx->geo, static_cast<const Msv1IndexChunk*>(idx->d_chunks.p), static_cast<const uint32_t*>(idx->d_frame_chunk.p),
-                                 static_cast<const int32_t*>(idx->d_palette.p), static_cast<const uint32_t*>(idx->d_bitmap.p),
-                                 static_cast<const int32_t*>(idx->d_thumb_frames.p), n,
-                                 idx->has_before ? static_cast<const int32_t*>(idx->d_before.p) : nullptr, a, t, mode, filter, c->stream);
-        JSP_HIP(hipGetLastError());
-        JSP_HIP(hipStreamSynchronize(c->stream));   // (the pinned list is free for the next call)
-        return JSP_ZERO_STATE;
+        msv1_launch_index_tensor(idx->src, d_frames, n, a, t, mode, filter, c->stream);
+        return launched(c);
     } catch (const std::exception& e) {
         set_error("%s", e.what());
         return JSP_ERROR_OCCURED;

@@ -60,7 +60,7 @@ bool msv1_block_changes_now(jsp_codec* c, std::vector<uint8_t>& out);
 // The batch's stream buffer, block tables and frame records change hands (the batch keeps none of them; its next staging allocates
 // afresh).  False: not a batch of the MSVideo1 staging.
 bool msv1_take_batch(jsp_staged* st, DeviceBuffer& stream, DeviceBuffer& desc, DeviceBuffer& frames);
-// What the show kernel reads of one staged chunk of an index.
+// What the index kernels read of one staged chunk of an index.
 struct Msv1IndexChunk {
     const uint8_t* stream;
     const uint32_t* desc;            // the chunk's frame f at f * pitch (pitch = nblocks)
@@ -71,33 +71,41 @@ struct Msv1IndexChunk {
 // ONE launch of msv1_coded_bitmap_kernel over the chunk `v` = index frames [a, a + v.nframes): bitmap (word-major, nblocks words per
 // 32 frames, zeroed before the first chunk), d_rows (nby words per 32 frames, zeroed) and d_stop (one word per frame, all ones before).
 void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, uint32_t* d_rows, uint32_t* d_stop, hipStream_t stream);
+// What every kernel of a seek index reads, and nothing a kernel writes: filled once, at the end of jsp_index_build (index_src,
+// msv1_seek.cpp — the one place with the clamps that keep a picture of fewer than 4 pixels a side harmless), and passed to the
+// kernels by value.
+struct Msv1IndexSrc {
+    const Msv1IndexChunk* chunks;
+    const uint32_t* frame_chunk;     // the chunk of every frame
+    const int32_t* palette;          // 8-bit: 256 entries
+    const uint32_t* bitmap;          // word-major: bit k of word w * nblocks + blk says that frame 32 w + k codes block blk
+    const uint32_t* before;          // the picture before the index, or null
+    size_t pitch;                    // table entries per frame: nblocks, 1 at least
+    int nblocks, nbx, nby;           // none below 0 (nbx is only divided by for a block below nblocks, so where it is 1 at least)
+    int X, Y, bits;
+    int before_vec;                  // blocks of `before` may be read 16 bytes a row
+};
 // ONE launch of msv1_index_show_kernel: frame t of the index into dst.
-void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                            const uint32_t* d_bitmap, int t, int32_t* dst, const int32_t* before, hipStream_t stream);
+void msv1_launch_index_show(const Msv1IndexSrc& src, int t, int32_t* dst, hipStream_t stream);
 // ONE launch of msv1_index_play_kernel: index frames first + k * stride, k < n, each into d_dsts[k] (a device array; a null entry is
 // walked but not written) exactly as msv1_launch_index_show writes it.  The run is split into `segs` (clamped to 1..n) contiguous
 // segments of destinations along grid.y, each composing its own first frame; the pictures do not depend on the split.
 // dsts_aligned16: every non-null destination is 16-byte aligned (else the scalar instantiation).
-void msv1_launch_index_play(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                            const uint32_t* d_bitmap, int first, int n, int stride, int segs, int32_t* const* d_dsts, bool dsts_aligned16,
-                            const int32_t* before, hipStream_t stream);
+void msv1_launch_index_play(const Msv1IndexSrc& src, int first, int n, int stride, int segs, int32_t* const* d_dsts, bool dsts_aligned16,
+                            hipStream_t stream);
 // Segments for a run of n frames when the caller leaves it to the library (option "msv1_index_play_segments" = "auto").
-int msv1_index_play_auto_segments(const Msv1Geometry& geo, int n);
+int msv1_index_play_auto_segments(const Msv1IndexSrc& src, int n);
 // ONE launch of msv1_index_thumbs_kernel: the pictures of index frames d_frames[0..n) (a device array), each reduced scale x scale
 // pixels to one (scale 4, 8 or 16; box mean, rounded half up), into the sheet `out`: thumbnails of (4 nbx / scale) x (4 nby / scale)
 // pixels, `cols` to a sheet row, row pitch cols thumbnail widths.  A block nothing up to its frame coded comes from `before`, else is 0.
-void msv1_launch_index_thumbs(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                              const uint32_t* d_bitmap, const int32_t* d_frames, int n, int scale, int cols, int32_t* out, const int32_t* before,
-                              hipStream_t stream);
+void msv1_launch_index_thumbs(const Msv1IndexSrc& src, const int32_t* d_frames, int n, int scale, int cols, int32_t* out, hipStream_t stream);
 // ONE launch of msv1_index_present_kernel (msv1_index_present_kernels.hip): the windows `a` describes of the pictures of index frames
 // d_frames[0..n) (a device array) — the pictures msv1_launch_index_show writes into a destination that held zeros, remainder pixels
 // included — converted by `mode` and resampled by `filter` (0, 1 or JSP_PRESENT_AREA) into the cells of the sheet a.out.
-void msv1_launch_index_present(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                               const uint32_t* d_bitmap, const int32_t* d_frames, int n, const int32_t* before, const IndexPresentArgs& a, int mode,
-                               int filter, hipStream_t stream);
+void msv1_launch_index_present(const Msv1IndexSrc& src, const int32_t* d_frames, int n, const IndexPresentArgs& a, int mode, int filter,
+                               hipStream_t stream);
 // The same windows as elements of the dense tensor `t` describes (msv1_index_tensor_kernel): ONE launch; `a` has one column of cells.
-void msv1_launch_index_tensor(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                              const uint32_t* d_bitmap, const int32_t* d_frames, int n, const int32_t* before, const IndexPresentArgs& a,
-                              const IndexTensorArgs& t, int mode, int filter, hipStream_t stream);
+void msv1_launch_index_tensor(const Msv1IndexSrc& src, const int32_t* d_frames, int n, const IndexPresentArgs& a, const IndexTensorArgs& t,
+                              int mode, int filter, hipStream_t stream);
 
 }  // namespace jsp

@@ -214,59 +214,43 @@ __global__ __launch_bounds__(WG) void msv1_coded_bitmap_kernel(const uint32_t* _
     }
 }
 
-// (index_last_writer, which the show, play and thumbnail kernels share with msv1_index_present_kernel: msv1_block_io.h)
+// The index kernels below read the index as one record (Msv1IndexSrc, by value) and compose a block by one rule (index_block,
+// msv1_block_io.h): the last frame <= t that coded it, else `before`, else nothing.  What a kernel writes is an argument of its own.
 
-// Show frame t: one work-item per block, as msv1_seek_kernel.  The lane masks bitmap word t / 32 to the frames <= t and walks the words
-// downwards (SCAN in flight per step) to the first non-zero one: its highest set bit is the last frame <= t that coded the block.  That
-// frame's chunk (frame_chunk[], chunks[]) gives its table entry and stream, and the code is decoded as the seek kernel decodes it.  No
-// writer: the block comes from `before` (the picture before the index; null: `dst` is left as it is).  Work-items past the last block
-// copy the pixels no block covers from `before`.
+// Show frame t: one work-item per block, as msv1_seek_kernel, storing the block index_block composes (an undefined block leaves `dst`
+// as it is).  Work-items past the last block copy the pixels no block covers from `before`.
 template <int BITS, bool VEC>
-__global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk,
-                                                             const int32_t* __restrict__ palette, const uint32_t* __restrict__ bitmap, size_t pitch, int t,
-                                                             uint32_t* __restrict__ dst, const uint32_t* __restrict__ before, int nblocks, int nbx, int X,
-                                                             int cx, int cy, long nrem) {
+__global__ __launch_bounds__(WG) void msv1_index_show_kernel(const Msv1IndexSrc s, int t, uint32_t* __restrict__ dst, int cx, int cy, long nrem) {
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    load_palette<BITS>(s_pal, palette);
+    load_palette<BITS>(s_pal, s.palette);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
-    if (gid >= nblocks) {   // a pixel no block covers, as in msv1_seek_kernel
-        const long r = gid - nblocks;
-        if (r >= nrem || before == nullptr) return;
-        const size_t i = uncovered_pixel(r, X, cx, cy);
-        *(gu32*)(dst + i) = *(cgu32*)(before + i);
+    if (gid >= s.nblocks) {   // a pixel no block covers, as in msv1_seek_kernel
+        const long r = gid - s.nblocks;
+        if (r >= nrem || s.before == nullptr) return;
+        const size_t i = uncovered_pixel(r, s.X, cx, cy);
+        *(gu32*)(dst + i) = *(cgu32*)(s.before + i);
         return;
     }
     const int blk = (int)gid;
-    const int by = blk / nbx;
-    const int bx = blk - by * nbx;
-    const size_t di = (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
-    int w;
-    const uint32_t m = index_last_writer(bitmap, nblocks, blk, t, w);
+    const int by = blk / s.nbx;
+    const int bx = blk - by * s.nbx;
     uint32_t px[16];
-    if (m == 0u) {   // nothing up to t coded the block
-        if (before != nullptr) {
-            load_block<VEC>(before + di, X, px);
-            store_block<VEC>(dst + di, X, px);
-        }
-        return;
-    }
-    index_decode<BITS>(chunks, frame_chunk, pitch, 32 * w + 31 - __builtin_clz(m), blk, s_pal, px);
-    store_block<VEC>(dst + di, X, px);
+    if (index_block<BITS>(s, t, blk, bx, by, VEC, s_pal, px)) store_block<VEC>(dst + (size_t)by * 4u * (size_t)s.X + (size_t)bx * 4u, s.X, px);
 }
 
 // index_last_writer with a lower bound: the bitmap word of block `blk` that holds the last frame in (tp, t] coding it, masked to those
-// frames (highest set bit = that frame; w is set), or 0 when nothing in the span coded the block.  The top word is masked to the frames
-// <= t, the bottom word (that of frame tp + 1) to the frames > tp, and the walk down (SCAN words in flight per step) stops at the bottom
-// word.  (cw, cv) is the top word the lane fetched last and (pw, pv) the one before it: consecutive spans of a run fetch a word once
-// while the run's frames stay in it, and a span of stride <= 32 — two words at most — finds its bottom word in (pw, pv).
-__device__ __forceinline__ uint32_t index_last_writer_span(const uint32_t* __restrict__ bitmap, int nblocks, int blk, int tp, int t, int& w,
-                                                           int& cw, uint32_t& cv, int& pw, uint32_t& pv) {
+// frames (index_word_frame(w, m) is that frame; w is set), or 0 when nothing in the span coded the block.  The top word is masked to the
+// frames <= t, the bottom word (that of frame tp + 1) to the frames > tp, and the walk down (SCAN words in flight per step) stops at the
+// bottom word.  (cw, cv) is the top word the lane fetched last and (pw, pv) the one before it: consecutive spans of a run fetch a word
+// once while the run's frames stay in it, and a span of stride <= 32 — two words at most — finds its bottom word in (pw, pv).
+__device__ __forceinline__ uint32_t index_last_writer_span(const Msv1IndexSrc& s, int blk, int tp, int t, int& w, int& cw, uint32_t& cv, int& pw,
+                                                           uint32_t& pv) {
     const int lo = tp + 1, wb = lo >> 5;
     const uint32_t mask_lo = 0xFFFFFFFFu << (lo & 31);
     w = t >> 5;
     if (w != cw) {
         pw = cw; pv = cv;
-        cw = w; cv = *(cgu32*)(bitmap + (size_t)w * (size_t)nblocks + blk);
+        cw = w; cv = *(cgu32*)(s.bitmap + (size_t)w * (size_t)s.nblocks + blk);
     }
     uint32_t m = cv & (0xFFFFFFFFu >> (31 - (t & 31)));
     if (w == wb) return m & mask_lo;
@@ -275,7 +259,7 @@ __device__ __forceinline__ uint32_t index_last_writer_span(const uint32_t* __res
 #pragma unroll
         for (int k = 0; k < SCAN; ++k) {
             const int i = w - 1 - k;
-            e[k] = i < wb ? 0u : i == pw ? pv : *(cgu32*)(bitmap + (size_t)i * (size_t)nblocks + blk);
+            e[k] = i < wb ? 0u : i == pw ? pv : *(cgu32*)(s.bitmap + (size_t)i * (size_t)s.nblocks + blk);
             if (i == wb) e[k] &= mask_lo;
         }
         int step = SCAN;
@@ -289,29 +273,26 @@ __device__ __forceinline__ uint32_t index_last_writer_span(const uint32_t* __res
 
 // Play (jsp_index_play): frames t_k = first + k * stride, k < n, each into dsts[k] exactly as msv1_index_show_kernel(t_k) writes it — ONE
 // launch.  One work-item per block as there, and per SEGMENT of the run (blockIdx.y: destinations [y * seg, (y + 1) * seg)).  The lane
-// composes its segment's first frame as the show kernel does and keeps the 16 pixels in registers; `have` says whether the block is
-// defined yet (no writer so far and no `before`: Show leaves such a block alone, and so does every store here).  For each further
+// composes its segment's first frame as the show kernel does (index_block) and keeps the 16 pixels in registers; `have` says whether
+// the block is defined yet (Show leaves an undefined block alone, and so does every store here).  For each further
 // frame it asks for the last writer in (t_{k-1}, t_k] (index_last_writer_span): a coded block overwrites the whole block, so only the
 // last writer of the gap is decoded, and the registers stay when there is none.  A null dsts[k] (a frame before the index's first
 // adopting one, where Show writes nothing) is walked but not stored.  k is wave-uniform: all lanes of a wave store to the same
 // destination in the same iteration, with the show kernel's row stores.  Work-items past the last block copy the pixels no block covers
 // from `before` into every non-null destination of the segment.
 template <int BITS, bool VEC>
-__global__ __launch_bounds__(WG) void msv1_index_play_kernel(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk,
-                                                             const int32_t* __restrict__ palette, const uint32_t* __restrict__ bitmap, size_t pitch,
-                                                             int first, int n, int stride, int seg, uint32_t* const* __restrict__ dsts,
-                                                             const uint32_t* __restrict__ before, int nblocks, int nbx, int X, int cx, int cy,
-                                                             long nrem) {
+__global__ __launch_bounds__(WG) void msv1_index_play_kernel(const Msv1IndexSrc s, int first, int n, int stride, int seg,
+                                                             uint32_t* const* __restrict__ dsts, int cx, int cy, long nrem) {
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    load_palette<BITS>(s_pal, palette);
+    load_palette<BITS>(s_pal, s.palette);
     const int k0 = (int)blockIdx.y * seg;
     const int k1 = min(n, k0 + seg);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
-    if (gid >= nblocks) {   // a pixel no block covers, as in msv1_seek_kernel
-        const long r = gid - nblocks;
-        if (r >= nrem || before == nullptr) return;
-        const size_t i = uncovered_pixel(r, X, cx, cy);
-        const uint32_t v = *(cgu32*)(before + i);
+    if (gid >= s.nblocks) {   // a pixel no block covers, as in msv1_seek_kernel
+        const long r = gid - s.nblocks;
+        if (r >= nrem || s.before == nullptr) return;
+        const size_t i = uncovered_pixel(r, s.X, cx, cy);
+        const uint32_t v = *(cgu32*)(s.before + i);
         for (int k = k0; k < k1; ++k) {
             uint32_t* d = dsts[k];
             if (d != nullptr) *(gu32*)(d + i) = v;
@@ -319,34 +300,24 @@ __global__ __launch_bounds__(WG) void msv1_index_play_kernel(const Msv1IndexChun
         return;
     }
     const int blk = (int)gid;
-    const int by = blk / nbx;
-    const int bx = blk - by * nbx;
-    const size_t di = (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
+    const int by = blk / s.nbx;
+    const int bx = blk - by * s.nbx;
+    const size_t di = (size_t)by * 4u * (size_t)s.X + (size_t)bx * 4u;
     int t = first + k0 * stride;
-    int w;
-    uint32_t m = index_last_writer(bitmap, nblocks, blk, t, w);
     uint32_t px[16];
-    bool have = true;
-    if (m != 0u) {
-        index_decode<BITS>(chunks, frame_chunk, pitch, 32 * w + 31 - __builtin_clz(m), blk, s_pal, px);
-    } else if (before != nullptr) {
-        load_block<VEC>(before + di, X, px);
-    } else {   // nothing up to t_k0 coded the block and there is no picture before the range
-        have = false;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) px[i] = 0u;
-    }
+    bool have = index_block<BITS>(s, t, blk, bx, by, VEC, s_pal, px);
     int cw = -1, pw = -1;
     uint32_t cv = 0u, pv = 0u;
     for (int k = k0;;) {
         uint32_t* d = dsts[k];
-        if (have && d != nullptr) store_block<VEC>(d + di, X, px);
+        if (have && d != nullptr) store_block<VEC>(d + di, s.X, px);
         if (++k >= k1) break;
         const int tp = t;
         t += stride;
-        m = index_last_writer_span(bitmap, nblocks, blk, tp, t, w, cw, cv, pw, pv);
+        int w;
+        const uint32_t m = index_last_writer_span(s, blk, tp, t, w, cw, cv, pw, pv);
         if (m != 0u) {
-            index_decode<BITS>(chunks, frame_chunk, pitch, 32 * w + 31 - __builtin_clz(m), blk, s_pal, px);
+            index_decode<BITS>(s, index_word_frame(w, m), blk, s_pal, px);
             have = true;
         }
     }
@@ -354,9 +325,9 @@ __global__ __launch_bounds__(WG) void msv1_index_play_kernel(const Msv1IndexChun
 
 // Thumbnails (jsp_index_thumbs): the pictures of n frames of the index, each reduced S x S pixels to one (box mean, rounded half up),
 // into one sheet — ONE launch, no full-size picture anywhere.  blockIdx.y is the thumbnail, frames[blockIdx.y] its frame; a lane per
-// 4x4 block and thumbnail finds the block's last writer <= t as the show kernel does (index_last_writer), decodes that one code (or
-// loads the block from `before`; neither: zeros) and sums its 16 pixels, R and B together under 0x00FF00FF, G apart: at S = 16 a field
-// ends at most at 256 * 255 + 128 < 2^16, so the 16-bit fields never carry into each other.
+// 4x4 block and thumbnail composes the block as the show kernel does (index_block; an undefined block is zeros) and sums its 16
+// pixels, R and B together under 0x00FF00FF, G apart: at S = 16 a field ends at most at 256 * 255 + 128 < 2^16, so the 16-bit fields
+// never carry into each other.
 //   S = 4:  the lane's block is the output pixel; lanes in block raster order, one dword store each (a wave writes 256 contiguous bytes
 //           of a thumbnail row, or the end of one row and the start of the next).
 //   S = 8 / 16: G = S / 4; the G x G blocks of one output pixel are G * G consecutive lanes (lane & (G - 1) the block column, the next
@@ -367,16 +338,13 @@ __global__ __launch_bounds__(WG) void msv1_index_play_kernel(const Msv1IndexChun
 // picture; the trailing block column / row that fills no output pixel and the X % 4, Y % 4 remainders are never read.  A group is
 // aligned to G * G lanes and lives or returns as one, so the shuffles only meet live lanes.
 template <int BITS, int S>
-__global__ __launch_bounds__(WG) void msv1_index_thumbs_kernel(const Msv1IndexChunk* __restrict__ chunks, const uint32_t* __restrict__ frame_chunk,
-                                                               const int32_t* __restrict__ palette, const uint32_t* __restrict__ bitmap, size_t pitch,
-                                                               const int32_t* __restrict__ frames, uint32_t* __restrict__ out,
-                                                               const uint32_t* __restrict__ before, int nblocks, int nbx, int X, int tw, int th,
-                                                               int cols, int before_vec) {
+__global__ __launch_bounds__(WG) void msv1_index_thumbs_kernel(const Msv1IndexSrc s, const int32_t* __restrict__ frames, uint32_t* __restrict__ out,
+                                                               int tw, int th, int cols) {
     constexpr int G = S / 4, GG = G * G;                            // blocks per output pixel: a side, all
     constexpr int LG = S == 4 ? 0 : S == 8 ? 1 : 2;                 // log2(G)
     constexpr uint32_t SH = 4 + 2 * LG, HALF = (uint32_t)(S * S) / 2u;   // log2(S * S), the rounding term
     __shared__ uint32_t s_pal[BITS == 8 ? 256 : 1];
-    load_palette<BITS>(s_pal, palette);
+    load_palette<BITS>(s_pal, s.palette);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
     const long q = gid >> (2 * LG);                                 // output pixel of the thumbnail, raster order
     if (q >= (long)tw * th) return;
@@ -385,22 +353,9 @@ __global__ __launch_bounds__(WG) void msv1_index_thumbs_kernel(const Msv1IndexCh
     const int px_ = (int)(q - (long)py * tw);
     const int by = py * G + (sub >> LG);
     const int bx = px_ * G + (sub & (G - 1));
-    const int blk = by * nbx + bx;
     const int k = (int)blockIdx.y;
-    const int t = frames[k];
-    int w;
-    const uint32_t m = index_last_writer(bitmap, nblocks, blk, t, w);
     uint32_t px[16];
-    if (m != 0u) {
-        index_decode<BITS>(chunks, frame_chunk, pitch, 32 * w + 31 - __builtin_clz(m), blk, s_pal, px);
-    } else if (before != nullptr) {   // nothing up to t coded the block: the picture before the index
-        const uint32_t* p = before + (size_t)by * 4u * (size_t)X + (size_t)bx * 4u;
-        if (before_vec) load_block<true>(p, X, px);
-        else load_block<false>(p, X, px);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) px[i] = 0u;
-    }
+    index_block<BITS>(s, frames[k], by * s.nbx + bx, bx, by, s.before_vec != 0, s_pal, px);
     uint32_t rb = 0, g = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -421,8 +376,10 @@ __global__ __launch_bounds__(WG) void msv1_index_thumbs_kernel(const Msv1IndexCh
 
 // The seek and show kernels' work: one work-item per block, then one per pixel no block covers (nrem of them: the columns from cx on
 // in the block rows, the rows from cy on), and whether rows of `dst` and `src` may move 16 bytes at a time.  False: nothing to do.
+// (geo: a batch's Msv1Geometry or an index's Msv1IndexSrc)
 struct PictureGrid { int cx, cy; long nrem; dim3 grid; bool vec; };
-bool picture_grid(const Msv1Geometry& geo, const void* dst, const void* src, PictureGrid& g) {
+template <class Geo>
+bool picture_grid(const Geo& geo, const void* dst, const void* src, PictureGrid& g) {
     if (geo.X <= 0 || geo.Y <= 0) return false;
     g.cx = geo.nbx * 4;
     g.cy = geo.nby * 4;
@@ -434,11 +391,16 @@ bool picture_grid(const Msv1Geometry& geo, const void* dst, const void* src, Pic
     return true;
 }
 
-// Segments of the walk list: enough work-items for ~8 waves per SIMD (a 1080p frame alone gives ~2), at least 16 entries each
+// How many times over a launch of one work-item per block must run (its segments along grid.y) to put ~8 waves on every SIMD: a 1080p
+// picture alone gives ~2.
+long segments_to_fill(int nblocks) {
+    const long waves_one = std::max(1L, ((long)nblocks + 63) / 64);
+    return std::max(1L, (8L * 1024L + waves_one - 1) / waves_one);
+}
+
+// Segments of the walk list: segments_to_fill, at least 16 entries each
 dim3 scan_grid(const Msv1Geometry& geo, int nwalk, int& seg) {
-    const long waves_one = ((long)geo.nblocks + 63) / 64;
-    long nseg = std::max(1L, (8L * 1024L + waves_one - 1) / waves_one);
-    nseg = std::min(nseg, std::max(1L, ((long)nwalk + 15) / 16));
+    long nseg = std::min(segments_to_fill(geo.nblocks), std::max(1L, ((long)nwalk + 15) / 16));
     nseg = std::min(nseg, 65535L);
     seg = (int)(((long)nwalk + nseg - 1) / nseg);
     nseg = ((long)nwalk + seg - 1) / seg;
@@ -485,56 +447,54 @@ void msv1_launch_coded_bitmap(const Msv1SeekView& v, int a, uint32_t* d_bitmap, 
                        std::max(geo.nbx, 1), geo.nby);
 }
 
-void msv1_launch_index_show(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                            const uint32_t* d_bitmap, int t, int32_t* dst, const int32_t* before, hipStream_t stream) {
+void msv1_launch_index_show(const Msv1IndexSrc& src, int t, int32_t* dst, hipStream_t stream) {
     PictureGrid g;
-    if (!picture_grid(geo, dst, before, g)) return;
-    const size_t pitch = (size_t)std::max(geo.nblocks, 1);
-    dispatch_bits_vec(geo.bits, g.vec, [&](auto B, auto V) {
-        hipLaunchKernelGGL((msv1_index_show_kernel<decltype(B)::value, decltype(V)::value>), g.grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk,
-                           d_palette, d_bitmap, pitch, t, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t*>(before), geo.nblocks,
-                           std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem);
+    if (!picture_grid(src, dst, src.before, g)) return;
+    dispatch_bits_vec(src.bits, g.vec, [&](auto B, auto V) {
+        hipLaunchKernelGGL((msv1_index_show_kernel<decltype(B)::value, decltype(V)::value>), g.grid, dim3(WG), 0, stream, src, t,
+                           reinterpret_cast<uint32_t*>(dst), g.cx, g.cy, g.nrem);
     });
 }
 
-int msv1_index_play_auto_segments(const Msv1Geometry& geo, int n) {
-    // the rule of scan_grid: enough work-items for ~8 waves per SIMD (a 1080p picture alone gives ~2), never more segments than frames
-    const long waves_one = std::max(1L, ((long)geo.nblocks + 63) / 64);
-    const long nseg = std::max(1L, (8L * 1024L + waves_one - 1) / waves_one);
-    return (int)std::min(nseg, (long)std::max(n, 1));
+int msv1_index_play_auto_segments(const Msv1IndexSrc& src, int n) {   // (never more segments than frames)
+    return (int)std::min(segments_to_fill(src.nblocks), (long)std::max(n, 1));
 }
 
-void msv1_launch_index_play(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                            const uint32_t* d_bitmap, int first, int n, int stride, int segs, int32_t* const* d_dsts, bool dsts_aligned16,
-                            const int32_t* before, hipStream_t stream) {
+void msv1_launch_index_play(const Msv1IndexSrc& src, int first, int n, int stride, int segs, int32_t* const* d_dsts, bool dsts_aligned16,
+                            hipStream_t stream) {
     PictureGrid g;
-    if (n <= 0 || !picture_grid(geo, nullptr, before, g)) return;
+    if (n <= 0 || !picture_grid(src, nullptr, src.before, g)) return;
     const bool vec = g.vec && dsts_aligned16;
     const int seg = (n + std::min(std::max(segs, 1), n) - 1) / std::min(std::max(segs, 1), n);   // destinations per segment
     const dim3 grid(g.grid.x, (unsigned)((n + seg - 1) / seg));
-    const size_t pitch = (size_t)std::max(geo.nblocks, 1);
-    dispatch_bits_vec(geo.bits, vec, [&](auto B, auto V) {
-        hipLaunchKernelGGL((msv1_index_play_kernel<decltype(B)::value, decltype(V)::value>), grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk,
-                           d_palette, d_bitmap, pitch, first, n, stride, seg, reinterpret_cast<uint32_t* const*>(d_dsts),
-                           reinterpret_cast<const uint32_t*>(before), geo.nblocks, std::max(geo.nbx, 1), geo.X, g.cx, g.cy, g.nrem);
+    dispatch_bits_vec(src.bits, vec, [&](auto B, auto V) {
+        hipLaunchKernelGGL((msv1_index_play_kernel<decltype(B)::value, decltype(V)::value>), grid, dim3(WG), 0, stream, src, first, n, stride, seg,
+                           reinterpret_cast<uint32_t* const*>(d_dsts), g.cx, g.cy, g.nrem);
     });
 }
 
-void msv1_launch_index_thumbs(const Msv1Geometry& geo, const Msv1IndexChunk* d_chunks, const uint32_t* d_frame_chunk, const int32_t* d_palette,
-                              const uint32_t* d_bitmap, const int32_t* d_frames, int n, int scale, int cols, int32_t* out, const int32_t* before,
-                              hipStream_t stream) {
-    const int tw = geo.nbx * 4 / scale, th = geo.nby * 4 / scale;
+// f(std::integral_constant<int, BITS>{}, std::integral_constant<int, S>{}) for the thumbnail kernel that `bits` (16, else 8) and
+// `scale` (4, 8 or 16; any other: nothing) select.
+template <class F>
+void dispatch_bits_scale(int bits, int scale, F&& f) {
+    auto with_bits = [&](auto B) {
+        if (scale == 4) f(B, std::integral_constant<int, 4>{});
+        else if (scale == 8) f(B, std::integral_constant<int, 8>{});
+        else if (scale == 16) f(B, std::integral_constant<int, 16>{});
+    };
+    if (bits == 16) with_bits(std::integral_constant<int, 16>{});
+    else with_bits(std::integral_constant<int, 8>{});
+}
+
+void msv1_launch_index_thumbs(const Msv1IndexSrc& src, const int32_t* d_frames, int n, int scale, int cols, int32_t* out, hipStream_t stream) {
+    const int tw = src.nbx * 4 / scale, th = src.nby * 4 / scale;
     if (n <= 0 || cols <= 0 || tw <= 0 || th <= 0) return;
     const long lanes = (long)tw * th * (scale / 4) * (scale / 4);
     const dim3 grid((unsigned)((lanes + WG - 1) / WG), (unsigned)n);
-    const size_t pitch = (size_t)std::max(geo.nblocks, 1);
-    const int before_vec = (geo.X & 3) == 0 && !(reinterpret_cast<uintptr_t>(before) & 15);
-#define JSP_THUMBS(BITS, S) hipLaunchKernelGGL((msv1_index_thumbs_kernel<BITS, S>), grid, dim3(WG), 0, stream, d_chunks, d_frame_chunk, d_palette, d_bitmap, \
-                                               pitch, d_frames, reinterpret_cast<uint32_t*>(out), reinterpret_cast<const uint32_t*>(before),            \
-                                               geo.nblocks, geo.nbx, geo.X, tw, th, cols, before_vec)
-    if (geo.bits == 16) { if (scale == 4) JSP_THUMBS(16, 4); else if (scale == 8) JSP_THUMBS(16, 8); else if (scale == 16) JSP_THUMBS(16, 16); }
-    else { if (scale == 4) JSP_THUMBS(8, 4); else if (scale == 8) JSP_THUMBS(8, 8); else if (scale == 16) JSP_THUMBS(8, 16); }
-#undef JSP_THUMBS
+    dispatch_bits_scale(src.bits, scale, [&](auto B, auto S) {
+        hipLaunchKernelGGL((msv1_index_thumbs_kernel<decltype(B)::value, decltype(S)::value>), grid, dim3(WG), 0, stream, src, d_frames,
+                           reinterpret_cast<uint32_t*>(out), tw, th, cols);
+    });
 }
 
 }  // namespace jsp
