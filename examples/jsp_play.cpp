@@ -32,6 +32,11 @@
 //                                jsp_sp_index_show), then the last frame and every frame down
 //                                to 0, one jsp_index_show each (Main.on_prevframe, Manager.hx:191-196); prints "<index> <key|inter>
 //                                <changed> <crc32>" per frame — sorted, the plain run's frames, significance and CRCs
+//   jsp_play clip.avi --activity [FIRST[:COUNT]]
+//                                ONE seek index over the clip of either codec, built as for --step-back, then its activity map for frames
+//                                FIRST .. FIRST + COUNT - 1 (default: the whole clip), ONE jsp_index_activity / jsp_sp_index_activity call
+//                                per 4096 frames: prints "<frame> <changed pixels> <x,y,w,h of its non-zero 16x16 cells, display
+//                                coordinates, or ->" per frame and "map <cols>x<rows>x<frames> <crc32 of the map's uint16 words>"
 //   jsp_play clip.avi --filmstrip N[:scale]
 //                                ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build), then ONE
 //                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
@@ -431,6 +436,7 @@ int main(int argc, char** argv) {
     long seek_to = -1;                                        // --seek N: frame N first, through jsp_seek
     bool skip_stills = false;                                 // --skip-stills: from frame 0, skip to each significant change (jsp_find_change)
     bool step_back = false;                                   // --step-back: a seek index over the clip, shown from the last frame down to 0
+    long act_first = -1, act_count = -1;                      // --activity [FIRST[:COUNT]]: the activity map of a seek index over the clip
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
     long play_first = -1, play_count = -1, play_stride = 1;   // --play-index FIRST[:COUNT[:STRIDE]]: frames played out of a ScreenPressor seek index
     long run_first = -1, run_count = -1, run_stride = 1;      // --index-run FIRST[:COUNT[:STRIDE]]: frames played out of an MSVideo1 seek index
@@ -455,6 +461,15 @@ int main(int argc, char** argv) {
         else if (o == "--seek" && a + 1 < argc) seek_to = std::atol(argv[++a]);
         else if (o == "--skip-stills") skip_stills = true;
         else if (o == "--step-back") step_back = true;
+        else if (o == "--activity") {
+            act_first = 0;
+            if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') {
+                const std::string v = argv[++a];
+                const size_t colon = v.find(':');
+                act_first = std::atol(v.substr(0, colon).c_str());
+                if (colon != std::string::npos) act_count = std::atol(v.substr(colon + 1).c_str());
+            }
+        }
         else if (o == "--filmstrip" && a + 1 < argc) {
             const std::string v = argv[++a];
             const size_t colon = v.find(':');
@@ -522,6 +537,7 @@ int main(int argc, char** argv) {
     if (seek_to >= 0 && (pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--seek goes with the plain per-frame run\n"); return 2; }
     if (skip_stills && (seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--skip-stills goes alone\n"); return 2; }
     if (step_back && (skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--step-back goes alone\n"); return 2; }
+    if (act_first >= 0 && (run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--activity goes alone\n"); return 2; }
     if (strip > 0 && (step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--filmstrip goes alone\n"); return 2; }
     if (play_first >= 0 && (strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--play-index goes alone\n"); return 2; }
     if (play_first >= 0 && clip.kind != JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--play-index: ScreenPressor only (an MSVideo1 index adopts: --seek and the plain run play on from any frame)\n"); return 2; }
@@ -807,6 +823,69 @@ int main(int argc, char** argv) {
                 std::printf("%zu %s %d %08x\n", t, keys[t] ? "key" : "inter", sig[t], crc);
             }
         }
+        jsp_index_destroy(idx);
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        return rc;
+    }
+    if (act_first >= 0) {   // where and when the picture changes: one index build, then ONE jsp_index_activity / jsp_sp_index_activity per 4096 frames
+        const size_t n = clip.frames.size();
+        std::vector<const uint8_t*> srcs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> keys;
+        for (size_t i = 0; i < n; ++i) {
+            srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+            lens.push_back(clip.frames[i].second);
+            keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        const bool sp = clip.kind == JSP_CODEC_SCREENPRESSOR;   // the same two calls on the index of either codec
+        jsp_index* idx = n && !sp ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        jsp_sp_index* sidx = n && sp ? jsp_sp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        if (!idx && !sidx) { std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_build" : "jsp_index_build", n ? jsp_last_error() : "no frames"); rc = 1; }
+        const char* const call = sp ? "jsp_sp_index_activity" : "jsp_index_activity";
+        int cols = 0, rows = 0;
+        if (rc == 0 && (sp ? jsp_sp_index_activity_size(sidx, &cols, &rows) : jsp_index_activity_size(idx, &cols, &rows)) != JSP_ZERO_STATE) {
+            std::fprintf(stderr, "%s_size: %s\n", call, jsp_last_error());
+            rc = 1;
+        }
+        const long count = act_count >= 0 ? act_count : (long)n - act_first;
+        if (rc == 0 && (count < 1 || act_first + count > (long)n)) { std::fprintf(stderr, "--activity: frames %ld .. %ld are not all in the clip (%zu frames)\n", act_first, act_first + count - 1, n); rc = 1; }
+        const size_t cell = (size_t)cols * (size_t)rows;
+        jsp_pool* sheet = nullptr;   // one "frame" that holds the map: cell ints a row, a row per two frames of the run
+        if (rc == 0 && !(sheet = jsp_pool_create(0, (int)cell, (int)((count + 1) / 2), 1))) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
+        if (rc == 0) {
+            std::vector<int32_t> words(cell * (size_t)((count + 1) / 2));
+            uint16_t* out = reinterpret_cast<uint16_t*>(jsp_pool_buffer(sheet, 0));
+            for (long k = 0; rc == 0 && k < count; k += 4096) {
+                const int m = (int)std::min<long>(4096, count - k);
+                if ((sp ? jsp_sp_index_activity(dec, sidx, (int)(act_first + k), m, out + (size_t)k * cell, (size_t)(count - k) * cell)
+                        : jsp_index_activity(dec, idx, (int)(act_first + k), m, out + (size_t)k * cell, (size_t)(count - k) * cell)) != JSP_ZERO_STATE) {
+                    std::fprintf(stderr, "%s: %s\n", call, jsp_last_error());
+                    rc = 1;
+                }
+            }
+            if (rc == 0 && jsp_download(jsp_pool_buffer(sheet, 0), words.data(), words.size()) != 0) { std::fprintf(stderr, "jsp_download: %s\n", jsp_last_error()); rc = 1; }
+            const uint16_t* map = reinterpret_cast<const uint16_t*>(words.data());
+            for (long k = 0; rc == 0 && k < count; ++k) {   // per frame: changed pixels and the box of its non-zero cells, display coordinates (top row first)
+                long total = 0;
+                int q0 = cols, q1 = -1, r0 = rows, r1 = -1;
+                for (int r = 0; r < rows; ++r)
+                    for (int q = 0; q < cols; ++q) {
+                        const uint16_t v = map[((size_t)k * (size_t)rows + (size_t)r) * (size_t)cols + (size_t)q];
+                        if (!v) continue;
+                        total += v;
+                        q0 = std::min(q0, q); q1 = std::max(q1, q); r0 = std::min(r0, r); r1 = std::max(r1, r);
+                    }
+                if (q1 < 0) std::printf("%ld 0 -\n", act_first + k);
+                else {
+                    const int x0 = q0 * 16, x1 = std::min((q1 + 1) * 16, clip.X), y0 = r0 * 16, y1 = std::min((r1 + 1) * 16, clip.Y);
+                    std::printf("%ld %ld %d,%d,%d,%d\n", act_first + k, total, x0, clip.Y - y1, x1 - x0, y1 - y0);
+                }
+            }
+            if (rc == 0) std::printf("map %dx%dx%ld %08x\n", cols, rows, count, crc32(reinterpret_cast<const uint8_t*>(map), (size_t)count * cell * 2));
+        }
+        if (sheet) jsp_pool_destroy(sheet);
+        jsp_sp_index_destroy(sidx);
         jsp_index_destroy(idx);
         jsp_pool_destroy(pool);
         jsp_codec_destroy(dec);

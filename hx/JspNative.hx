@@ -66,6 +66,9 @@ extern class JspNative {
     @:native("jsp_index_play")         static function indexPlay(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, first:Int, n:Int, stride:Int,
                                                                  dsts:RawPointer<RawPointer<cpp.Int32>>, adoptK:Int,
                                                                  dataPnts:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
+    @:native("jsp_index_activity_size") static function indexActivitySize(idx:RawPointer<JspIndex>, cols:RawPointer<Int>, rows:RawPointer<Int>):Int;
+    @:native("jsp_index_activity")     static function indexActivity(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, first:Int, n:Int,
+                                                                     out:RawPointer<cpp.UInt16>, outElems:SizeT):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)
@@ -85,6 +88,9 @@ extern class JspNative {
                                                                         dtype:Int, layout:Int, scale:RawConstPointer<cpp.Float32>, bias:RawConstPointer<cpp.Float32>):Int;
     @:native("jsp_sp_index_play")         static function spIndexPlay(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, first:Int, n:Int, stride:Int,
                                                                       dsts:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
+    @:native("jsp_sp_index_activity_size") static function spIndexActivitySize(idx:RawPointer<JspSpIndex>, cols:RawPointer<Int>, rows:RawPointer<Int>):Int;
+    @:native("jsp_sp_index_activity")     static function spIndexActivity(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, first:Int, n:Int,
+                                                                          out:RawPointer<cpp.UInt16>, outElems:SizeT):Int;
     @:native("jsp_sp_index_significance") static function spIndexSignificance(idx:RawPointer<JspSpIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_sp_index_info")         static function spIndexInfo(idx:RawPointer<JspSpIndex>, nframes:RawPointer<Int>, deviceBytes:RawPointer<cpp.UInt64>,
                                                                       hostBytes:RawPointer<cpp.UInt64>):Int;

@@ -192,6 +192,9 @@ int jsp_set_stream(jsp_codec* c, void* hip_stream);
 /*   "msv1_index_play_segments" = "auto" (default) | "1".."64" : MSVideo1 only, jsp_index_play.  The run's destinations are split into this many
  *       contiguous segments along the launch grid (never more than frames in the run), each composing its own first frame; auto:
  *       enough segments for about 8 waves per SIMD.  Results do not depend on it. */
+/*   "msv1_index_activity_segments" = "auto" (default) | "1".."64" : MSVideo1 only, jsp_index_activity.  The run's frames are split into this
+ *       many contiguous segments along the launch grid (never more than frames in the run), each composing the picture before its own
+ *       first frame; auto: as "msv1_index_play_segments".  Results do not depend on it. */
 /*   "async_depth" = "1".."16" (default "4") : any codec.  Frames that may be in flight between jsp_decompress_*_async and
  *       jsp_wait. */
 int jsp_set_option(jsp_codec* c, const char* key, const char* value);
@@ -644,6 +647,39 @@ int jsp_sp_index_tensor(jsp_codec* c, jsp_sp_index* idx, int n, const int* frame
  *       the index, an asynchronous frame in flight, a host-pointer buffer, a buffer that is the codec's current previous frame, the same
  *       pointer twice in `dsts`. */
 int jsp_sp_index_play(jsp_codec* c, jsp_sp_index* idx, int first, int n, int stride, int32_t* const* dsts, int* significant_changes);
+
+/* ---- activity map of an index, either codec: where and when a screen recording changes — an activity strip along the seek bar, "skip
+ * idle" judged on the part of the picture in view, the rectangle a frame changed to scroll the view to, the frames worth giving to a
+ * model — as changed pixels per frame and 16x16 cell, without a picture written or compared anywhere ---------------------------------------
+ * Activity: THE PICTURE P(t) of frame t, 0 <= t < nframes, is the one jsp_index_present / jsp_sp_index_present define: not restated.
+ *       P(-1), MSVideo1: the index's copy of the picture before the range, else all zeros.  P(-1), ScreenPressor: all zeros (its index
+ *       starts at a coded key frame and holds nothing before it).  An MSVideo1 block that no frame <= t has coded and that has no picture
+ *       before the range is zeros in P(t), as for Thumbs and Present: a first writer that writes zeros changes nothing.
+ *   GRID  *cols = ceil(X / 16), *rows = ceil(Y / 16) (jsp_index_activity_size / jsp_sp_index_activity_size).  Cell (r, q) covers stored
+ *       rows 16 r .. 16 r + 15 and columns 16 q .. 16 q + 15, clipped to the picture.  Rows are in the frame buffer's own order: grid row
+ *       0 is frame rows 0 .. 15, as Thumbs keeps it.  A cell is the ScreenPressor block and 4 x 4 MSVideo1 blocks.
+ *   EQUIVALENCE  out[(k * rows + r) * cols + q] = the number of pixels of cell (r, q) whose whole 32-bit word differs between
+ *       P(first + k) and P(first + k - 1), for k = 0 .. n-1: 0 .. 256.  The X % 4 / Y % 4 remainder pixels of an MSVideo1 picture are
+ *       the same in every P(t) and so never count.  Exactly n * rows * cols elements are written, every one of them; nothing else is.
+ *       Coarser grids, totals and boxes are sums the caller takes: the call has one cell size, so every cell has one owner.
+ *   ONE kernel launch whatever n (msv1_index_activity_kernel / sp_index_activity_kernel), behind a memset of `out` on the same stream:
+ *       the walk of jsp_index_play / jsp_sp_index_play with a compare-and-count where Play has a store; a set bit of the index's bitmap
+ *       is not a change (MSVideo1 codes a block again with the pixels it had; a ScreenPressor rectangle is the bounding box of a change
+ *       and its literalised motion rewrites pixels that stay), so the pixels are compared.  Option "msv1_index_activity_segments"
+ *       splits an MSVideo1 run along the grid, as "msv1_index_play_segments" does; the result does not depend on it.  Runs on the
+ *       codec's stream and returns synchronised.  THE CODEC IS ONLY LENT, as for Thumbs / Present: its state, previous frame, per-row
+ *       flags and every frame buffer stay untouched.  No full-size picture is written anywhere; the index grows by nothing the size of a
+ *       picture (a ScreenPressor index that never played gets Play's 16-byte record and key-frame bit per frame).
+ *   BOUNDS  n 1..4096; first >= 0; first + n <= nframes (computed in 64 bits); out_elems >= n * rows * cols; `out` is a device pointer
+ *       aligned to 2 bytes.
+ *   ERRORS, each before anything is queued, with nothing changed and nothing written (jsp_last_error() starts with "index_activity:",
+ *       but for the wrong codec kind's "index: MSVideo1 only" / "sp_index: ScreenPressor only"): a null argument, n or first outside
+ *       their bounds, out_elems too small, a misaligned or host-pointer `out`, an index built by another codec, the wrong codec kind, an
+ *       asynchronous frame in flight. */
+int jsp_index_activity_size(const jsp_index* idx, int* cols, int* rows);
+int jsp_index_activity(jsp_codec* c, jsp_index* idx, int first, int n, uint16_t* out, size_t out_elems);
+int jsp_sp_index_activity_size(const jsp_sp_index* idx, int* cols, int* rows);
+int jsp_sp_index_activity(jsp_codec* c, jsp_sp_index* idx, int first, int n, uint16_t* out, size_t out_elems);
 
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 

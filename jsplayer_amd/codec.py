@@ -556,10 +556,62 @@ class _IndexTensor:
         return out.reshape(-1)[:count].reshape(shape)
 
 
-class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor):
+ACTIVITY_MAX_RUN = 4096   # frames one jsp_index_activity / jsp_sp_index_activity call takes
+
+
+class _IndexActivity:
+    """ActivitySize / Activity of a seek index, MSVideo1 or ScreenPressor: the two C calls have one contract (jsp_index_activity).  A
+    subclass names its pair of C functions in `_ACTIVITY_CALLS` and has `_open(who)` and `frames`."""
+
+    _ACTIVITY_CALLS = ("", "")   # (activity_size, activity): exports of the library, without the "jsp_" in front
+
+    def ActivitySize(self) -> tuple:
+        """(cols, rows) of the activity grid: ceil(X / 16), ceil(Y / 16) cells of 16 x 16 pixels, the last column / row clipped."""
+        size_call, _ = self._ACTIVITY_CALLS
+        self._open(size_call)
+        cols, rows = C.c_int(0), C.c_int(0)
+        if getattr(self._lib, "jsp_" + size_call)(self._h, C.byref(cols), C.byref(rows)) != 0:
+            raise CodecError(N.last_error())
+        return cols.value, rows.value
+
+    def Activity(self, first: int = 0, n: Optional[int] = None, out=None):
+        """How many pixels of each 16 x 16 cell each of the frames first .. first + n - 1 (n None: to the end of the index) changed:
+        element [k, r, q] counts the pixels of cell (r, q) that differ between the pictures of frames first + k and first + k - 1
+        (the picture before frame 0: the one before the index, else zeros) — 0 .. 256.  Grid rows are in the frame's own bottom-up
+        order, as a thumbnail's.  ONE launch per 4096 frames, no picture written, the codec not touched.  Returns an int16 device
+        tensor of shape (n, rows, cols) — no value exceeds 256, so the bits are the C call's uint16_t — `out` when it is given (that
+        shape and dtype, contiguous) or a new one."""
+        import torch
+        size_call, call = self._ACTIVITY_CALLS
+        codec = self._open(call)
+        first = int(first)
+        n = self.frames - first if n is None else int(n)
+        cols, rows = self.ActivitySize()
+        shape = (max(n, 0), rows, cols)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int16, device=f"cuda:{codec._device}")
+        elif not hasattr(out, "data_ptr") or out.dtype != torch.int16 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise CodecError(f"{call}: out must be a contiguous int16 tensor of shape {shape}")
+        fn = getattr(self._lib, "jsp_" + call)
+        cell = rows * cols
+        k = 0
+        while True:   # (a run the C call refuses — empty, outside the index — goes to it once, for its message)
+            m = min(n - k, ACTIVITY_MAX_RUN)
+            if fn(codec._h, self._h, first + k, m, C.c_void_p(out.data_ptr() + 2 * k * cell), (out.numel() - k * cell)) != 0:
+                raise CodecError(N.last_error())
+            k += m
+            if k >= n:
+                break
+        if hasattr(self, "_info"):
+            self._info()   # (a ScreenPressor index that never played gets Play's per-frame table at the first call)
+        return out
+
+
+class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch, Play(first, dsts, stride) one launch for
     a run of frames, each into a buffer of its own (jsp_index_play), Present(frames, ...) one launch for the windows of any
-    frames (jsp_index_present), Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_index_tensor).
+    frames (jsp_index_present), Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_index_tensor),
+    Activity(first, n) one launch for the changed pixels per frame and 16x16 cell of a run (jsp_index_activity; _IndexActivity).
     `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
@@ -567,6 +619,7 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor):
     _THUMB_CALLS = ("index_thumb_size", "index_thumbs")
     _PRESENT_CALL = "index_present"
     _TENSOR_CALL = "index_tensor"
+    _ACTIVITY_CALLS = ("index_activity_size", "index_activity")
 
     def __init__(self, codec: _NativeCodec, handle: int, prev_at_build):
         self._codec, self._h = codec, handle
@@ -704,12 +757,13 @@ class ScreenPressor(_NativeCodec):
         return SpScrubIndex(self, h)
 
 
-class SpScrubIndex(_IndexThumbs, _IndexPresent, _IndexTensor):
+class SpScrubIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     """A ScreenPressor range resident in HBM (jsp_sp_index_build, via ScreenPressor.BuildScrubIndex): Show(t) is one launch,
     Play(first, dsts, stride) one launch for a run of frames played forward from any frame (jsp_sp_index_play),
     Thumbs(frames) one launch for any number of downscaled frames (jsp_sp_index_thumbs; _IndexThumbs has the two methods),
     Present(frames, ...) one launch for their windows of any size (jsp_sp_index_present; _IndexPresent),
-    Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_sp_index_tensor; _IndexTensor).
+    Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_sp_index_tensor; _IndexTensor),
+    Activity(first, n) one launch for the changed pixels per frame and 16x16 block of a run (jsp_sp_index_activity; _IndexActivity).
     `significance` = the verdict the sequential run records for every frame, `frames`, `device_bytes`, `host_bytes`.  close() (or
     the context manager) frees it; safe after the codec is gone."""
 
@@ -717,6 +771,7 @@ class SpScrubIndex(_IndexThumbs, _IndexPresent, _IndexTensor):
     _THUMB_CALLS = ("sp_index_thumb_size", "sp_index_thumbs")
     _PRESENT_CALL = "sp_index_present"
     _TENSOR_CALL = "sp_index_tensor"
+    _ACTIVITY_CALLS = ("sp_index_activity_size", "sp_index_activity")
 
     def _present_mode(self) -> int:   # 16-bpp frames hold 5-bit components (Manager.hx:121), as Manager.present chooses it
         return 1 if getattr(self._codec, "bpp", 0) == 16 else 0   # DISPLAY_CANVAS_RGB15 / DISPLAY_CANVAS

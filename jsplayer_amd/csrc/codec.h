@@ -91,6 +91,7 @@ struct jsp_codec {
     std::unique_ptr<jsp_staged> seek_scratch;   // jsp_seek's staged range (kept: its buffers serve the next seek)
     int seek_chunk_frames = 0;            // option "msv1_seek_chunk_frames": frames staged per chunk of a seek (0 = auto)
     int index_play_segments = 0;          // option "msv1_index_play_segments": segments of a jsp_index_play run (0 = auto)
+    int index_activity_segments = 0;      // option "msv1_index_activity_segments": segments of a jsp_index_activity run (0 = auto)
     jsp::DeviceBuffer find_dev;           // jsp_find_change: first-hit word, judged rows and walk list of a chunk (device) ...
     jsp::PinnedBuffer find_host;          // ... and where the host builds them
 

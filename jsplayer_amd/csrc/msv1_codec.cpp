@@ -786,6 +786,14 @@ struct Msv1Codec : jsp_codec {
             index_play_segments = (int)v;
             return 0;
         }
+        if (std::strcmp(key, "msv1_index_activity_segments") == 0) {   // jsp_index_activity: segments of the run along grid.y ("auto": as Play's)
+            if (std::strcmp(value, "auto") == 0) { index_activity_segments = 0; return 0; }
+            char* end = nullptr;
+            const long v = std::strtol(value, &end, 10);
+            if (end == value || *end || v < 1 || v > 64) return -1;
+            index_activity_segments = (int)v;
+            return 0;
+        }
         if (std::strcmp(key, "msv1_scrub_tables") == 0) {   // tests: a replay must rebuild every block table it reads
             opt_scrub_tables = std::strcmp(value, "1") == 0;
             return 0;

@@ -761,6 +761,42 @@ extern "C" int jsp_index_tensor(jsp_codec* c, jsp_index* idx, int n, const int* 
     }
 }
 
+// ---- activity: how many pixels of every 16x16 cell each frame of a run changed — the seek bar's activity strip, "skip idle" judged
+// on the part of the picture in view, the rectangle to scroll to — in ONE launch of msv1_index_activity_kernel.  The first call that
+// looks across frames instead of at one; the codec is only lent, as for Thumbs, and no picture is written.
+extern "C" int jsp_index_activity_size(const jsp_index* idx, int* cols, int* rows) {
+    if (!idx || !cols || !rows) return fail("index_activity: null argument");
+    *cols = (std::max(idx->geo.X, 0) + 15) / 16;
+    *rows = (std::max(idx->geo.Y, 0) + 15) / 16;
+    return JSP_ZERO_STATE;
+}
+
+extern "C" int jsp_index_activity(jsp_codec* c, jsp_index* idx, int first, int n, uint16_t* out, size_t out_elems) {
+    const char* who = "index_activity";
+    if (!c || !idx || !out) return fail("index_activity: null argument");
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_activity: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("index_activity: n is outside 1..4096");
+    if (first < 0 || (int64_t)first + (int64_t)n > (int64_t)idx->nframes) return fail("index_activity: the run is outside the index");
+    const int cols = (std::max(idx->geo.X, 0) + 15) / 16, rows = (std::max(idx->geo.Y, 0) + 15) / 16;
+    const uint64_t elems = (uint64_t)n * (uint64_t)rows * (uint64_t)cols;
+    if ((uint64_t)out_elems < elems) return fail("index_activity: out_elems is smaller than the map");
+    if (reinterpret_cast<uintptr_t>(out) & 1) return fail("index_activity: out is not aligned to 2 bytes");
+    if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        if (!on_device(out, who, "out must be a device buffer")) return JSP_ERROR_OCCURED;
+        if (elems == 0) return JSP_ZERO_STATE;   // (an index without a picture)
+        JSP_HIP(hipMemsetAsync(out, 0, elems * sizeof(uint16_t), c->stream));   // (the kernel stores the non-zero counts only)
+        const int segs = c->index_activity_segments > 0 ? c->index_activity_segments : msv1_index_play_auto_segments(idx->src, n);
+        msv1_launch_index_activity(idx->src, first, n, segs, out, cols, rows, c->stream);
+        return launched(c);
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
 extern "C" int jsp_index_significance(const jsp_index* idx, int* out) {
     if (!idx || !out) return fail("index_significance: null argument");
     std::copy(idx->significance.begin(), idx->significance.end(), out);

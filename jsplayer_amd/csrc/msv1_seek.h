@@ -107,5 +107,11 @@ void msv1_launch_index_present(const Msv1IndexSrc& src, const int32_t* d_frames,
 // The same windows as elements of the dense tensor `t` describes (msv1_index_tensor_kernel): ONE launch; `a` has one column of cells.
 void msv1_launch_index_tensor(const Msv1IndexSrc& src, const int32_t* d_frames, int n, const IndexPresentArgs& a, const IndexTensorArgs& t,
                               int mode, int filter, hipStream_t stream);
+// ONE launch of msv1_index_activity_kernel (msv1_index_activity_kernels.hip): out[(k * rows + r) * cols + q], k < n, = the pixels of
+// the 16x16 cell (r, q) of the cols x rows grid (ceil(X / 16) x ceil(Y / 16)) that differ between the pictures of index frames
+// first + k and first + k - 1 (the picture before frame 0: `before`, else zeros).  Only non-zero counts are stored: the caller zeroes
+// `out` first.  The run is split into `segs` (clamped to 1..n) contiguous segments along grid.y, each composing the picture before its
+// own first frame; the counts do not depend on the split.
+void msv1_launch_index_activity(const Msv1IndexSrc& src, int first, int n, int segs, uint16_t* out, int cols, int rows, hipStream_t stream);
 
 }  // namespace jsp

@@ -10,6 +10,7 @@
 
 #include "codec.h"
 #include "sp.h"
+#include "sp_index_activity.h"
 
 using namespace jsp;
 using namespace jsp::sp;
@@ -481,6 +482,31 @@ extern "C" int jsp_sp_index_tensor(jsp_codec* c, jsp_sp_index* idx, int n, const
     }
 }
 
+namespace {
+// The per-frame table of the kernels that walk forward (Play, Activity) — an IndexPlayFrame per frame, then the key-frame mask — made by
+// the first call that needs it, once.
+void play_frames(jsp_sp_index* idx, hipStream_t stream) {
+    if (idx->d_play_frames.p) return;
+    const size_t nwords = ((size_t)idx->nframes + 31) / 32;
+    const size_t bytes = idx->play_mask_offset() + nwords * sizeof(uint32_t);
+    PinnedBuffer pin;
+    pin.reserve(bytes);
+    auto* recs = static_cast<IndexPlayFrame*>(pin.p);
+    auto* mask = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(pin.p) + idx->play_mask_offset());
+    std::fill(mask, mask + nwords, 0u);
+    for (int f = 0; f < idx->nframes; ++f) {
+        recs[f] = IndexPlayFrame{idx->key_of[(size_t)f], (uint32_t)idx->key_slot[(size_t)f], idx->slot_base[(size_t)f]};
+        if (idx->key_of[(size_t)f] == f) mask[f >> 5] |= 1u << (f & 31);
+    }
+    DeviceBuffer d;
+    exact(d, bytes);
+    JSP_HIP(hipMemcpyAsync(d.p, pin.p, bytes, hipMemcpyHostToDevice, stream));
+    JSP_HIP(hipStreamSynchronize(stream));   // (the pinned copy goes away here)
+    std::swap(idx->d_play_frames.p, d.p);
+    std::swap(idx->d_play_frames.cap, d.cap);
+}
+}  // namespace
+
 // ---- playback: a run of frames of the index, carried forward in registers from the first one, in ONE launch of sp_index_play_kernel.
 // Everything Show does to the codec, per destination: the buffers are written behind its back, so it forgets their last columns.
 extern "C" int jsp_sp_index_play(jsp_codec* c, jsp_sp_index* idx, int first, int n, int stride, int32_t* const* dsts, int* significant_changes) {
@@ -509,25 +535,7 @@ extern "C" int jsp_sp_index_play(jsp_codec* c, jsp_sp_index* idx, int first, int
         for (int k = 0; k < n; ++k)
             if (!on_device(dsts[k])) return fail("sp_index_play: every buffer of dsts must be a device frame buffer");
         hipStream_t stream = c->stream;
-        const size_t nwords = ((size_t)idx->nframes + 31) / 32;
-        if (!idx->d_play_frames.p) {   // the first Play of this index: the per-frame table, once
-            const size_t bytes = idx->play_mask_offset() + nwords * sizeof(uint32_t);
-            PinnedBuffer pin;
-            pin.reserve(bytes);
-            auto* recs = static_cast<IndexPlayFrame*>(pin.p);
-            auto* mask = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(pin.p) + idx->play_mask_offset());
-            std::fill(mask, mask + nwords, 0u);
-            for (int f = 0; f < idx->nframes; ++f) {
-                recs[f] = IndexPlayFrame{idx->key_of[(size_t)f], (uint32_t)idx->key_slot[(size_t)f], idx->slot_base[(size_t)f]};
-                if (idx->key_of[(size_t)f] == f) mask[f >> 5] |= 1u << (f & 31);
-            }
-            DeviceBuffer d;
-            exact(d, bytes);
-            JSP_HIP(hipMemcpyAsync(d.p, pin.p, bytes, hipMemcpyHostToDevice, stream));
-            JSP_HIP(hipStreamSynchronize(stream));   // (the pinned copy goes away here)
-            std::swap(idx->d_play_frames.p, d.p);
-            std::swap(idx->d_play_frames.cap, d.cap);
-        }
+        play_frames(idx, stream);
         idx->h_play_dsts.reserve(sizeof(int32_t*) * (size_t)n);
         idx->d_play_dsts.reserve(sizeof(int32_t*) * (size_t)n);
         std::copy(dsts, dsts + n, static_cast<int32_t**>(idx->h_play_dsts.p));
@@ -543,6 +551,46 @@ extern "C" int jsp_sp_index_play(jsp_codec* c, jsp_sp_index* idx, int first, int
             lender->forget_buffer(dsts[k]);       // (written behind the codec's back: their last columns are asked for again)
             if (significant_changes) significant_changes[k] = idx->significance[(size_t)first + (size_t)k * (size_t)stride];
         }
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- activity: how many pixels of every 16x16 block each frame of a run changed (jsp_index_activity's contract), in ONE launch of
+// sp_index_activity_kernel: Play's walk with a compare-and-count where Play has a store.  No picture is written, so the codec is lent
+// its stream and nothing else (no forget_buffer); the per-frame table is Play's.
+extern "C" int jsp_sp_index_activity_size(const jsp_sp_index* idx, int* cols, int* rows) {
+    if (!idx || !cols || !rows) return fail("index_activity: null argument");
+    *cols = idx->geo.nbx;
+    *rows = idx->geo.nby;
+    return JSP_ZERO_STATE;
+}
+
+extern "C" int jsp_sp_index_activity(jsp_codec* c, jsp_sp_index* idx, int first, int n, uint16_t* out, size_t out_elems) {
+    if (!c || !idx || !out) return fail("index_activity: null argument");
+    if (c->kind != JSP_CODEC_SCREENPRESSOR || !dynamic_cast<IndexLender*>(c)) return fail("sp_index: ScreenPressor only");
+    if (idx->codec_serial != c->serial) return fail("index_activity: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("index_activity: n is outside 1..4096");
+    if (first < 0 || (int64_t)first + (int64_t)n > (int64_t)idx->nframes) return fail("index_activity: the run is outside the index");
+    const uint64_t elems = (uint64_t)n * (uint64_t)idx->geo.nby * (uint64_t)idx->geo.nbx;
+    if ((uint64_t)out_elems < elems) return fail("index_activity: out_elems is smaller than the map");
+    if (reinterpret_cast<uintptr_t>(out) & 1) return fail("index_activity: out is not aligned to 2 bytes");
+    if (c->next_ticket != c->oldest_ticket) return fail("index_activity: an asynchronous frame is in flight (jsp_wait for it first)");
+    try {
+        c->activate();
+        if (!on_device(out)) return fail("index_activity: out must be a device buffer");
+        hipStream_t stream = c->stream;
+        play_frames(idx, stream);
+        JSP_HIP(hipMemsetAsync(out, 0, elems * sizeof(uint16_t), stream));   // (the kernel stores the non-zero counts only)
+        launch_index_activity(idx->geo, out, first, n, static_cast<const int32_t*>(idx->d_keys.p), idx->pic_stride,
+                              static_cast<const IndexPlayFrame*>(idx->d_play_frames.p),
+                              reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(idx->d_play_frames.p) + idx->play_mask_offset()),
+                              static_cast<const PBlock*>(idx->d_blocks.p), static_cast<const uint32_t*>(idx->d_payload.p),
+                              static_cast<const uint32_t*>(idx->d_bitmap.p), stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(stream));
         return JSP_ZERO_STATE;
     } catch (const std::exception& e) {
         set_error("%s", e.what());

@@ -16,7 +16,8 @@ attached (`Manager.attach_index`: a range kept resident by the decoder's `BuildI
 shown — ScreenPressor's, `ADOPTS` false — serves the frame and leaves the decode position where it is); `next_frame` / `prev_frame` / `next_key` /
 `prev_key` are the navigation of Manager.hx:184-208 over `seek`; `play_from_index` plays a run of frames out of such a non-adopting
 index, one `Play` launch per batch of free buffers; `preview` / `filmstrip` are the seek bar's small pictures, one
-`Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex).  `View` is the zoom / scroll / fit state of Main
+`Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex); `activity` / `change_totals` / `change_box` /
+`next_change` say where and when the picture changes, from the index's `Activity` map (changed pixels per frame and 16x16 cell).  `View` is the zoom / scroll / fit state of Main
 (Main.hx:288-319, 1186-1278) and `Manager.present` draws the window it shows of a frame buffer, one launch.  Timers, bitmaps and audio
 of the reference's Manager are not rebuilt.
 """
@@ -182,6 +183,73 @@ class Manager:
         BuildScrubIndex) shows pictures without moving the decoder: a frame inside it is served before the decode position is
         touched, and decoding continues later from where the decoder really stands."""
         self.index, self.index_first = index, int(first)
+        self._activity = None   # (the map belongs to the index it was computed from)
+
+    _activity = None
+
+    # -- where and when the picture changes: the attached index's activity map (jsp_index_activity / jsp_sp_index_activity) ----------
+    def activity(self):
+        """The activity map of the whole attached index: [frame of the index, grid row, grid column] -> pixels of that 16 x 16 cell
+        the frame changed, grid rows in the frame's own bottom-up order (the index's `Activity`: one launch per 4096 frames, no
+        picture written, the decoder not touched).  Computed once per attach_index and kept where the index puts it (on the device);
+        attach_index drops it.  No index attached, or an index object without `Activity`: ValueError."""
+        if self.index is None:
+            raise ValueError("no seek index attached")
+        if not hasattr(self.index, "Activity"):
+            raise ValueError("the attached seek index has no activity map")
+        if self._activity is None:
+            self._activity = self.index.Activity()
+        return self._activity
+
+    @staticmethod
+    def _frame_sums(cells) -> np.ndarray:
+        """Per frame, the sum of the cells of a [frames, rows, cols] part of the map, on the host (int64)."""
+        if isinstance(cells, np.ndarray):
+            return cells.astype(np.int64).sum(axis=(1, 2))
+        import torch
+        return cells.to(torch.int64).sum(dim=(1, 2)).cpu().numpy()
+
+    def change_totals(self) -> List[int]:
+        """Changed pixels per frame of the attached index (entry k: clip frame index_first + k): the seek bar's activity strip."""
+        return [int(v) for v in self._frame_sums(self.activity())]
+
+    def change_box(self, i: int):
+        """(x, y, w, h) of what clip frame `i` changed, in display coordinates (top row first; the map is in stored bottom-up
+        order, so display row = H - 1 - stored row), clipped to the picture: the union of the frame's non-zero 16 x 16 cells — CELL
+        granularity, a superset of the changed pixels.  None for a frame that changes nothing.  `i` outside the index: ValueError."""
+        if not self._in_index(i):
+            raise ValueError(f"frame {i} is not in an attached seek index")
+        cells = self.activity()[i - self.index_first]
+        cells = cells if isinstance(cells, np.ndarray) else cells.cpu().numpy()
+        rs, qs = np.nonzero(cells)
+        if rs.size == 0:
+            return None
+        W, H = self.vi.X, self.vi.Y
+        x0, x1 = int(qs.min()) * 16, min((int(qs.max()) + 1) * 16, W)
+        y0, y1 = int(rs.min()) * 16, min((int(rs.max()) + 1) * 16, H)   # stored rows y0 .. y1 - 1
+        return x0, H - y1, x1 - x0, y1 - y0
+
+    def next_change(self, frames: Sequence[bytes], rect=None, min_pixels: int = 1, key_flags: Optional[Sequence[bool]] = None):
+        """Show the first frame after `frame_of_interest`, inside the attached index, that changes at least `min_pixels` pixels of
+        `rect` = (x, y, w, h) in display coordinates (top row first; None: the whole picture) — "skip idle" for the part of the
+        picture in view.  Whole 16 x 16 cells are summed: every cell `rect` intersects counts in full, so a SUPERSET of `rect` is
+        judged.  The frame is shown through seek(), exactly as skip_stills shows a known change, and its DecodedFrame returned;
+        None, and nothing shown, when no such frame is left in the index (or `rect` lies outside the picture)."""
+        act = self.activity()
+        W, H = self.vi.X, self.vi.Y
+        if rect is None:
+            rect = (0, 0, W, H)
+        x, y, w, h = (int(v) for v in rect)
+        x0, x1 = max(x, 0), min(x + w, W)
+        s0, s1 = max(H - (y + h), 0), min(H - y, H)          # stored rows s0 .. s1 - 1
+        k0 = max(self.frame_of_interest + 1 - self.index_first, 0)
+        if x0 >= x1 or s0 >= s1 or k0 >= self.index.frames:
+            return None
+        sums = self._frame_sums(act[k0:, s0 // 16:(s1 + 15) // 16, x0 // 16:(x1 + 15) // 16])
+        hits = np.nonzero(sums >= int(min_pixels))[0]
+        if hits.size == 0:
+            return None
+        return self.seek(frames, self.index_first + k0 + int(hits[0]), key_flags)
 
     def _index_adopts(self) -> bool:
         return bool(getattr(self.index, "ADOPTS", True))
