@@ -37,6 +37,13 @@
 //                                FIRST .. FIRST + COUNT - 1 (default: the whole clip), ONE jsp_index_activity / jsp_sp_index_activity call
 //                                per 4096 frames: prints "<frame> <changed pixels> <x,y,w,h of its non-zero 16x16 cells, display
 //                                coordinates, or ->" per frame and "map <cols>x<rows>x<frames> <crc32 of the map's uint16 words>"
+//   jsp_play clip.avi --cut FIRST[:COUNT] OUT.avi
+//                                MSVideo1: the clip from frame FIRST on (COUNT frames; default: to the end) as an AVI file of its own.
+//                                ONE seek index from the nearest key frame <= FIRST up to FIRST, ONE jsp_index_key_frame call (a key frame
+//                                that decodes to frame FIRST's picture, made of the codes the clip holds; a FIRST that is a key frame
+//                                is copied), the frames after it copied.  Then OUT.avi is played back through the ordinary decode loop:
+//                                prints "<frame of the clip> <crc32 from OUT.avi> <crc32 from the clip>" per frame (the CRC-32 of the
+//                                pixels that blocks cover) and exits with 1 on any difference
 //   jsp_play clip.avi --filmstrip N[:scale]
 //                                ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build), then ONE
 //                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
@@ -102,6 +109,7 @@ uint32_t crc32(const uint8_t* p, size_t n) {
 
 struct Clip {
     int X = 0, Y = 0, bpp = 32, kind = JSP_CODEC_SCREENPRESSOR;
+    uint32_t usec = 66667;                           // avih: microseconds per frame
     std::vector<uint8_t> palette;
     std::vector<std::pair<size_t, size_t>> frames;   // offset, padded size inside `bytes`
     std::vector<uint8_t> index_key;                  // idx1 key flags of the video chunks, in file order (empty: no index)
@@ -130,6 +138,7 @@ void walk(Clip& c, size_t lo, size_t hi, bool in_movi, uint8_t (&fourcc)[4], boo
             const bool movi = !std::memcmp(d + body, "movi", 4);
             walk(c, body + 4, std::min(body + size, hi), in_movi || movi, fourcc, video_stream, have_video);
         } else if (!std::memcmp(tag, "avih", 4)) {
+            c.usec = le32(d + body);
             c.X = (int)le32(d + body + 32);
             c.Y = (int)le32(d + body + 36);
         } else if (!std::memcmp(tag, "strh", 4)) {
@@ -174,6 +183,84 @@ bool load(const char* path, Clip& c) {
 bool frame_is_key(const Clip& c, jsp_codec* dec, size_t i) {
     if (!c.index_key.empty()) return c.index_key[i] != 0;
     return i == 0 || jsp_is_key_frame(dec, c.bytes.data() + c.frames[i].first, c.frames[i].second);
+}
+
+// ---- --cut ---------------------------------------------------------------------------------------------------------------------
+void put16(std::vector<uint8_t>& v, uint32_t x) { v.push_back((uint8_t)x); v.push_back((uint8_t)(x >> 8)); }
+void put32(std::vector<uint8_t>& v, uint32_t x) { put16(v, x); put16(v, x >> 16); }
+void put_chunk(std::vector<uint8_t>& v, const char* tag, const uint8_t* p, size_t n) {
+    v.insert(v.end(), tag, tag + 4);
+    put32(v, (uint32_t)n);
+    v.insert(v.end(), p, p + n);
+    if (n & 1) v.push_back(0);
+}
+// A minimal AVI file with the video stream of `c` (its size, depth, palette and frame time; fourcc CRAM) and these frames:
+// hdrl(avih, strl(strh, strf)), movi(00dc ...), idx1 with the key flags.
+std::vector<uint8_t> avi_file(const Clip& c, const std::vector<std::pair<const uint8_t*, size_t>>& frames, const std::vector<uint8_t>& keys) {
+    const uint32_t n = (uint32_t)frames.size();
+    std::vector<uint8_t> avih, strh, strf, strl, hdrl, movi, idx1, body, file;
+    for (uint32_t x : {c.usec, 0u, 0u, 0x10u, n, 0u, 1u, 0u, (uint32_t)c.X, (uint32_t)c.Y, 0u, 0u, 0u, 0u}) put32(avih, x);
+    strh.insert(strh.end(), {'v', 'i', 'd', 's', 'C', 'R', 'A', 'M'});
+    put32(strh, 0); put16(strh, 0); put16(strh, 0); put32(strh, 0);
+    put32(strh, c.usec); put32(strh, 1000000);                       // scale / rate: frames per second = rate / scale
+    for (uint32_t x : {0u, n, 0u, 0xFFFFFFFFu, 0u}) put32(strh, x);
+    for (uint32_t x : {0u, 0u, (uint32_t)c.X, (uint32_t)c.Y}) put16(strh, x);
+    const bool pal = c.bpp == 8;
+    put32(strf, 40); put32(strf, (uint32_t)c.X); put32(strf, (uint32_t)c.Y); put16(strf, 1); put16(strf, (uint32_t)c.bpp);
+    strf.insert(strf.end(), {'C', 'R', 'A', 'M'});
+    for (uint32_t x : {0u, 0u, 0u, pal ? (uint32_t)c.palette.size() / 4 : 0u, 0u}) put32(strf, x);
+    if (pal) strf.insert(strf.end(), c.palette.begin(), c.palette.end());
+    strl.insert(strl.end(), {'s', 't', 'r', 'l'});
+    put_chunk(strl, "strh", strh.data(), strh.size());
+    put_chunk(strl, "strf", strf.data(), strf.size());
+    hdrl.insert(hdrl.end(), {'h', 'd', 'r', 'l'});
+    put_chunk(hdrl, "avih", avih.data(), avih.size());
+    put_chunk(hdrl, "LIST", strl.data(), strl.size());
+    movi.insert(movi.end(), {'m', 'o', 'v', 'i'});
+    for (uint32_t i = 0; i < n; ++i) {
+        idx1.insert(idx1.end(), {'0', '0', 'd', 'c'});
+        put32(idx1, keys[i] ? 0x10u : 0u); put32(idx1, (uint32_t)movi.size()); put32(idx1, (uint32_t)frames[i].second);
+        put_chunk(movi, "00dc", frames[i].first, frames[i].second);
+    }
+    body.insert(body.end(), {'A', 'V', 'I', ' '});
+    put_chunk(body, "LIST", hdrl.data(), hdrl.size());
+    put_chunk(body, "LIST", movi.data(), movi.size());
+    put_chunk(body, "idx1", idx1.data(), idx1.size());
+    file.insert(file.end(), {'R', 'I', 'F', 'F'});
+    put32(file, (uint32_t)body.size());
+    file.insert(file.end(), body.begin(), body.end());
+    return file;
+}
+
+// The ordinary decode loop over frames 0 .. upto - 1 of `clip` on a codec and two frame buffers of its own (DecompressI for a key
+// frame, DecompressP else, never into the previous frame): per frame the CRC-32 of the pixels of the picture shown that 4x4 blocks
+// cover (the X % 4 / Y % 4 remainder pixels are in no MSVideo1 frame).  False: an error, printed.
+bool covered_crcs(const Clip& clip, size_t upto, std::vector<uint32_t>& crcs) {
+    jsp_codec* dec = jsp_codec_create(clip.kind, clip.X, clip.Y, clip.bpp, clip.palette.empty() ? nullptr : clip.palette.data(), (int)clip.palette.size(), 0);
+    jsp_pool* pool = dec ? jsp_pool_create(0, clip.X, clip.Y, 2) : nullptr;
+    bool ok = dec && pool;
+    if (!ok) std::fprintf(stderr, "jsp_codec_create / jsp_pool_create: %s\n", jsp_last_error());
+    if (ok) jsp_preinit(dec, kInsignificantLines);
+    const size_t npx = (size_t)clip.X * clip.Y, cw = (size_t)(clip.X / 4) * 4, chh = (size_t)(clip.Y / 4) * 4;
+    std::vector<int32_t> host(npx), cov(cw * chh);
+    crcs.clear();
+    for (size_t i = 0; ok && i < upto; ++i) {
+        const uint8_t* src = clip.bytes.data() + clip.frames[i].first;
+        const size_t len = clip.frames[i].second;
+        int32_t* dst = jsp_pool_buffer(pool, jsp_previous_frame(dec) == jsp_pool_buffer(pool, 0) ? 1 : 0);
+        int32_t* shown = nullptr;
+        int signif = 0;
+        if (frame_is_key(clip, dec, i)) ok = jsp_decompress_i(dec, src, len, dst) == JSP_ZERO_STATE;
+        else ok = jsp_decompress_p(dec, src, len, dst, &shown, &signif) == 0;
+        if (!ok) { std::fprintf(stderr, "frame %zu: %s\n", i, jsp_last_error()); break; }
+        shown = jsp_previous_frame(dec);
+        if (shown && jsp_download(shown, host.data(), npx) != 0) { std::fprintf(stderr, "jsp_download: %s\n", jsp_last_error()); ok = false; break; }
+        for (size_t y = 0; shown && y < chh; ++y) std::memcpy(cov.data() + y * cw, host.data() + y * (size_t)clip.X, cw * 4);
+        crcs.push_back(shown ? crc32(reinterpret_cast<const uint8_t*>(cov.data()), cov.size() * 4) : 0u);
+    }
+    if (pool) jsp_pool_destroy(pool);
+    if (dec) jsp_codec_destroy(dec);
+    return ok;
 }
 }  // namespace
 
@@ -437,6 +524,8 @@ int main(int argc, char** argv) {
     bool skip_stills = false;                                 // --skip-stills: from frame 0, skip to each significant change (jsp_find_change)
     bool step_back = false;                                   // --step-back: a seek index over the clip, shown from the last frame down to 0
     long act_first = -1, act_count = -1;                      // --activity [FIRST[:COUNT]]: the activity map of a seek index over the clip
+    long cut_first = -1, cut_count = -1;                      // --cut FIRST[:COUNT] OUT.avi: the clip from frame FIRST on as a file of its own
+    std::string cut_path;
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
     long play_first = -1, play_count = -1, play_stride = 1;   // --play-index FIRST[:COUNT[:STRIDE]]: frames played out of a ScreenPressor seek index
     long run_first = -1, run_count = -1, run_stride = 1;      // --index-run FIRST[:COUNT[:STRIDE]]: frames played out of an MSVideo1 seek index
@@ -469,6 +558,14 @@ int main(int argc, char** argv) {
                 act_first = std::atol(v.substr(0, colon).c_str());
                 if (colon != std::string::npos) act_count = std::atol(v.substr(colon + 1).c_str());
             }
+        }
+        else if (o == "--cut" && a + 2 < argc) {
+            const std::string v = argv[++a];
+            const size_t colon = v.find(':');
+            cut_first = std::atol(v.substr(0, colon).c_str());
+            if (colon != std::string::npos) cut_count = std::atol(v.substr(colon + 1).c_str());
+            cut_path = argv[++a];
+            if (cut_first < 0 || (colon != std::string::npos && cut_count < 1)) { std::fprintf(stderr, "--cut FIRST[:COUNT] OUT.avi: FIRST >= 0, COUNT >= 1\n"); return 2; }
         }
         else if (o == "--filmstrip" && a + 1 < argc) {
             const std::string v = argv[++a];
@@ -538,6 +635,8 @@ int main(int argc, char** argv) {
     if (skip_stills && (seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--skip-stills goes alone\n"); return 2; }
     if (step_back && (skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--step-back goes alone\n"); return 2; }
     if (act_first >= 0 && (run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--activity goes alone\n"); return 2; }
+    if (cut_first >= 0 && (act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--cut goes alone\n"); return 2; }
+    if (cut_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--cut: MSVideo1 only (a ScreenPressor key frame needs the entropy encoder)\n"); return 2; }
     if (strip > 0 && (step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--filmstrip goes alone\n"); return 2; }
     if (play_first >= 0 && (strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--play-index goes alone\n"); return 2; }
     if (play_first >= 0 && clip.kind != JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--play-index: ScreenPressor only (an MSVideo1 index adopts: --seek and the plain run play on from any frame)\n"); return 2; }
@@ -889,6 +988,59 @@ int main(int argc, char** argv) {
         jsp_index_destroy(idx);
         jsp_pool_destroy(pool);
         jsp_codec_destroy(dec);
+        return rc;
+    }
+    if (cut_first >= 0) {   // a clip that starts at any frame: one index build from the key frame before, ONE jsp_index_key_frame, the file, its playback
+        const size_t n = clip.frames.size();
+        const long count = cut_count >= 0 ? cut_count : (long)n - cut_first;
+        if (count < 1 || cut_first + count > (long)n) { std::fprintf(stderr, "--cut: frames %ld .. %ld are not all in the clip (%zu frames)\n", cut_first, cut_first + count - 1, n); rc = 1; }
+        std::vector<uint8_t> key_frame;
+        if (rc == 0 && !frame_is_key(clip, dec, (size_t)cut_first)) {
+            size_t k = (size_t)cut_first;
+            while (k > 0 && !frame_is_key(clip, dec, k)) --k;   // the nearest key frame <= FIRST (frame 0 is one)
+            std::vector<const uint8_t*> srcs;
+            std::vector<size_t> lens;
+            std::vector<uint8_t> keys;
+            for (size_t i = k; i <= (size_t)cut_first; ++i) {
+                srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+                lens.push_back(clip.frames[i].second);
+                keys.push_back(i == k || frame_is_key(clip, dec, i) ? 1 : 0);
+            }
+            jsp_index* idx = jsp_index_build(dec, (int)srcs.size(), srcs.data(), lens.data(), keys.data(), kInsignificantLines);
+            size_t bound = 0, len = 0;
+            if (!idx) { std::fprintf(stderr, "jsp_index_build: %s\n", jsp_last_error()); rc = 1; }
+            if (rc == 0 && jsp_index_key_frame_bound(idx, &bound) != JSP_ZERO_STATE) { std::fprintf(stderr, "jsp_index_key_frame_bound: %s\n", jsp_last_error()); rc = 1; }
+            key_frame.resize(bound);
+            if (rc == 0 && jsp_index_key_frame(dec, idx, (int)((size_t)cut_first - k), key_frame.data(), bound, &len) != JSP_ZERO_STATE) {
+                std::fprintf(stderr, "jsp_index_key_frame: %s\n", jsp_last_error());
+                rc = 1;
+            }
+            key_frame.resize(len);
+            jsp_index_destroy(idx);
+        }
+        std::vector<std::pair<const uint8_t*, size_t>> out_frames;
+        std::vector<uint8_t> out_keys;
+        for (long i = cut_first; rc == 0 && i < cut_first + count; ++i) {   // the frames after the first: the clip's own, with their flags
+            if (i == cut_first && !key_frame.empty()) out_frames.emplace_back(key_frame.data(), key_frame.size());
+            else out_frames.emplace_back(clip.bytes.data() + clip.frames[(size_t)i].first, clip.frames[(size_t)i].second);
+            out_keys.push_back(i == cut_first || frame_is_key(clip, dec, (size_t)i) ? 1 : 0);
+        }
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        if (rc != 0) return rc;
+        const std::vector<uint8_t> file = avi_file(clip, out_frames, out_keys);
+        FILE* f = std::fopen(cut_path.c_str(), "wb");
+        if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size()) { std::fprintf(stderr, "cannot write %s\n", cut_path.c_str()); if (f) std::fclose(f); return 1; }
+        std::fclose(f);
+        // OUT.avi played back through the ordinary decode loop, beside the clip's own frames
+        Clip cut;
+        if (!load(cut_path.c_str(), cut) || cut.frames.size() != (size_t)count) { std::fprintf(stderr, "cannot read %s back\n", cut_path.c_str()); return 1; }
+        std::vector<uint32_t> got, want;
+        if (!covered_crcs(cut, cut.frames.size(), got) || !covered_crcs(clip, (size_t)(cut_first + count), want)) return 1;
+        for (long k = 0; k < count; ++k) {
+            std::printf("%ld %08x %08x\n", cut_first + k, got[(size_t)k], want[(size_t)(cut_first + k)]);
+            if (got[(size_t)k] != want[(size_t)(cut_first + k)]) rc = 1;
+        }
         return rc;
     }
     if (strip > 0) {   // the seek bar's preview pictures: one index build, then ONE jsp_index_thumbs / jsp_sp_index_thumbs for all of them

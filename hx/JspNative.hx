@@ -69,6 +69,9 @@ extern class JspNative {
     @:native("jsp_index_activity_size") static function indexActivitySize(idx:RawPointer<JspIndex>, cols:RawPointer<Int>, rows:RawPointer<Int>):Int;
     @:native("jsp_index_activity")     static function indexActivity(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, first:Int, n:Int,
                                                                      out:RawPointer<cpp.UInt16>, outElems:SizeT):Int;
+    @:native("jsp_index_key_frame_bound") static function indexKeyFrameBound(idx:RawPointer<JspIndex>, bytes:RawPointer<SizeT>):Int;
+    @:native("jsp_index_key_frame")    static function indexKeyFrame(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, t:Int, out:RawPointer<UInt8>,
+                                                                     cap:SizeT, len:RawPointer<SizeT>):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)

@@ -681,6 +681,38 @@ int jsp_index_activity(jsp_codec* c, jsp_index* idx, int first, int n, uint16_t*
 int jsp_sp_index_activity_size(const jsp_sp_index* idx, int* cols, int* rows);
 int jsp_sp_index_activity(jsp_codec* c, jsp_sp_index* idx, int first, int n, uint16_t* out, size_t out_elems);
 
+/* ---- a key frame for any frame of an MSVideo1 index: cut a clip at frame t.  A clip has to start on a key frame, and t is almost never
+ * one.  The picture of frame t is, block by block, what the last frame <= t that coded the block made of it, and that frame's code for
+ * the block lies in the index's resident stream bytes: the key frame is those codes, concatenated in block order.  No pixel is
+ * decoded, nothing is re-quantised, and every byte of the result is a byte of a code the range already contained -------------------------
+ * KeyFrame: let e be the end of the writer's frame data (16-bit: rounded down to a whole word).  The code at offset o is WHOLE when
+ *       (1) its two-byte code word lies below e, (2) the bytes that settle its length lie below e — for a 16-bit code whose second byte
+ *       is below 0x80 that is the colour word at o + 2 — and (3) o + L <= e, L being 2 / 6 / 18 bytes (16-bit: 1-, 2-, 8-colour code)
+ *       or 2 / 4 / 10 bytes (8-bit).  KeyFrame(t) = for blocks 0 .. nblocks-1 in table order, which is stream order, the L bytes of the
+ *       whole code of the block's last writer <= t.  No skip codes, no end marker, nothing after the last block.
+ *   PROMISED for the bytes written: jsp_is_key_frame says yes; decoded as a key frame they give the picture of frame t on every pixel a
+ *       block covers (the X % 4 / Y % 4 remainder pixels are in no MSVideo1 frame and stay the caller's); the range's frames t + 1 ...
+ *       decoded on top give the pictures the range gives.  NOT promised: that significance verdicts, per-row flags or data_pnt of the
+ *       cut clip equal the original's — the new key frame codes every block.
+ *   REFUSED, as an error with nothing written: a block that no frame <= t of the index codes (it shows the picture before the range, or
+ *       nothing: its pixels came from no code the index holds) — the text names the first such block; a block whose last writer's code
+ *       is not whole (the end of a damaged frame cuts it off; what the reference paints there need not be expressible) — the text names
+ *       the block and the frame.  One rule for both depths; nothing is re-encoded.
+ *   `out` is HOST memory: these are file bytes.  *len is set to the frame's length whenever the frame can be cut, also when `cap` is
+ *       smaller — that is then an error with nothing written: size `out` by jsp_index_key_frame_bound (nblocks * 18 for 16-bit,
+ *       nblocks * 10 for 8-bit) or ask twice (`out` may be null when cap is 0).  *len is 0 after every other error.
+ *   TWO kernel launches (msv1_index_keyframe_sizes_kernel: per block the writer and the code's length, a scan inside each workgroup of
+ *       1024 blocks, a total per workgroup; msv1_index_keyframe_gather_kernel: the totals before its own summed, the codes copied) — no
+ *       workgroup waits for another.  The bytes are assembled in device scratch of the index (8 bytes per block, 4 per workgroup, the
+ *       frame at its bound; allocated by the first call, counted by jsp_index_info) and reach `out` in one copy only after the status
+ *       says that the frame can be cut.  Runs on the codec's stream and returns synchronised.  THE CODEC IS ONLY LENT: its state and
+ *       every frame buffer stay untouched.
+ *   ERRORS, each before anything is queued (jsp_last_error() starts with "index_key_frame:", but for the wrong codec kind's "index:
+ *       MSVideo1 only"): a null argument, the wrong codec kind, an index built by another codec, t outside the index, a picture without
+ *       a 4x4 block, an asynchronous frame in flight. */
+int jsp_index_key_frame_bound(const jsp_index* idx, size_t* bytes);
+int jsp_index_key_frame(jsp_codec* c, jsp_index* idx, int t, uint8_t* out, size_t cap, size_t* len);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

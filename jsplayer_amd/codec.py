@@ -611,7 +611,8 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch, Play(first, dsts, stride) one launch for
     a run of frames, each into a buffer of its own (jsp_index_play), Present(frames, ...) one launch for the windows of any
     frames (jsp_index_present), Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_index_tensor),
-    Activity(first, n) one launch for the changed pixels per frame and 16x16 cell of a run (jsp_index_activity; _IndexActivity).
+    Activity(first, n) one launch for the changed pixels per frame and 16x16 cell of a run (jsp_index_activity; _IndexActivity),
+    KeyFrame(t) two launches for a key frame that decodes to frame t's picture, made of the codes the range holds (jsp_index_key_frame).
     `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
@@ -685,6 +686,29 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
             data = None if not outs[k] else d if outs[k] == addrs[k] else self._prev_at_build
             results.append(PFrameResult(data, bool(signif[k])))
         return results
+
+    def KeyFrameBound(self) -> int:
+        """The most bytes KeyFrame returns: 18 per 4x4 block of a 16-bit picture, 10 per block of an 8-bit one."""
+        self._open("index_key_frame_bound")
+        n = C.c_size_t(0)
+        if self._lib.jsp_index_key_frame_bound(self._h, C.byref(n)) != 0:
+            raise CodecError(N.last_error())
+        return n.value
+
+    def KeyFrame(self, t: int) -> bytes:
+        """A key frame that decodes to the picture of frame t: for every block the code of its last writer <= t, in block order —
+        bytes the range already contained, nothing decoded or re-quantised (jsp_index_key_frame: two launches, the codec not
+        touched).  IsKeyFrame of it is true; the range's frames t + 1 ... decoded on top give the pictures the range gives.
+        CodecError, naming the block, when a block has no writer <= t in the index or its last writer's code is cut off."""
+        codec = self._open("index_key_frame")
+        buf = (C.c_uint8 * max(self.KeyFrameBound(), 1))()
+        n = C.c_size_t(0)
+        if self._lib.jsp_index_key_frame(codec._h, self._h, int(t), buf, len(buf), C.byref(n)) != 0:
+            raise CodecError(N.last_error())
+        dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first call adds the scratch the frame is assembled in)
+        self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
+        self.device_bytes, self.host_bytes = dev.value, host.value
+        return bytes(memoryview(buf)[:n.value])
 
     def _open(self, who: str) -> _NativeCodec:
         if not self._h:

@@ -33,14 +33,17 @@ struct jsp_index {
     DeviceBuffer d_frame_list;             // ... the array the kernel reads (both grown on demand)
     PinnedBuffer h_play_dsts;              // jsp_index_play: the call's destinations on their way to ...
     DeviceBuffer d_play_dsts;              // ... the array the kernel reads (both grown on demand; nothing until the first call)
+    DeviceBuffer d_key_frame;              // jsp_index_key_frame: status, workgroup totals, block records, the frame at its bound ...
+    PinnedBuffer h_key_frame;              // ... and where the status, the length and a refused block's record arrive (both: first call)
     uint64_t device_bytes() const {
-        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_frame_list.cap + d_play_dsts.cap;
+        uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_frame_list.cap + d_play_dsts.cap +
+                     d_key_frame.cap;
         for (const auto& c : chunks) n += c->stream.cap + c->desc.cap + c->frames.cap;
         return n;
     }
     uint64_t host_bytes() const {
         return sizeof(*this) + chunks.size() * sizeof(Chunk) + significance.size() * sizeof(int) + reported.size() + block_changes.size() +
-               h_frame_list.cap + h_play_dsts.cap;
+               h_frame_list.cap + h_play_dsts.cap + h_key_frame.cap;
     }
 };
 
@@ -791,6 +794,68 @@ extern "C" int jsp_index_activity(jsp_codec* c, jsp_index* idx, int first, int n
         const int segs = c->index_activity_segments > 0 ? c->index_activity_segments : msv1_index_play_auto_segments(idx->src, n);
         msv1_launch_index_activity(idx->src, first, n, segs, out, cols, rows, c->stream);
         return launched(c);
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- a key frame for any frame: the clip from frame t on has to start on a key frame, and t is almost never one.  The picture of
+// frame t is, block by block, what the last frame <= t that coded the block made of it, and that frame's code lies in the resident
+// stream bytes: the key frame is those codes in block order — file bytes the file already contained, no pixel decoded (the rule:
+// msv1_index_keyframe_kernels.hip).  TWO launches; the first call that produces a stream, and into HOST memory.  The codec is only lent.
+extern "C" int jsp_index_key_frame_bound(const jsp_index* idx, size_t* bytes) {
+    if (!idx || !bytes) return fail("index_key_frame: null argument");
+    *bytes = (size_t)std::max(idx->geo.nblocks, 0) * (idx->geo.bits == 16 ? 18u : 10u);
+    return JSP_ZERO_STATE;
+}
+
+extern "C" int jsp_index_key_frame(jsp_codec* c, jsp_index* idx, int t, uint8_t* out, size_t cap, size_t* len) {
+    const char* who = "index_key_frame";
+    if (len) *len = 0;
+    if (!c || !idx || !len || (!out && cap)) return fail("index_key_frame: null argument");
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_key_frame: the index was built by another codec");
+    if (t < 0 || t >= idx->nframes) return fail("index_key_frame: t is outside the index");
+    const Msv1IndexSrc& src = idx->src;
+    if (src.nblocks < 1) return fail("index_key_frame: the picture has no 4x4 block");
+    if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        // the scratch: [status, length][a total per workgroup][two words per block][the frame at its bound], 16-byte aligned parts
+        const auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+        const size_t totals_at = 16, records_at = totals_at + up16(sizeof(uint32_t) * (size_t)msv1_keyframe_workgroups(src.nblocks));
+        const size_t out_at = records_at + up16(2 * sizeof(uint32_t) * (size_t)src.nblocks);
+        const size_t bound = (size_t)src.nblocks * (src.bits == 16 ? 18u : 10u);
+        idx->d_key_frame.reserve(out_at + bound);
+        idx->h_key_frame.reserve(4 * sizeof(uint32_t));
+        uint8_t* d = idx->d_key_frame.as<uint8_t>();
+        const Msv1KeyFrameScratch k{reinterpret_cast<uint32_t*>(d), reinterpret_cast<uint32_t*>(d + totals_at),
+                                    reinterpret_cast<uint32_t*>(d + records_at), d + out_at};
+        uint32_t* h = idx->h_key_frame.as<uint32_t>();
+        JSP_HIP(hipMemsetAsync(k.status, 0xFF, 2 * sizeof(uint32_t), c->stream));
+        msv1_launch_index_keyframe(src, t, k, c->stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipMemcpyAsync(h, k.status, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        JSP_HIP(hipStreamSynchronize(c->stream));
+        if (h[0] != 0xFFFFFFFFu) {   // not cuttable: the first block that says so, and for a code cut off its writer
+            const uint32_t blk = h[0] >> 1;
+            if ((h[0] & 1u) == MSV1_KEYFRAME_NO_WRITER) {
+                set_error("index_key_frame: block %u has no writer up to frame %d in the index (it shows the picture before the range)", blk, t);
+            } else {
+                JSP_HIP(hipMemcpyAsync(h + 2, k.records + 2 * (size_t)blk, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                JSP_HIP(hipStreamSynchronize(c->stream));
+                set_error("index_key_frame: the code of block %u in frame %u, its last writer, is cut off by the end of the frame's data", blk, h[2]);
+            }
+            return JSP_ERROR_OCCURED;
+        }
+        const size_t total = h[1];
+        if (total > bound) throw std::runtime_error("index_key_frame: the frame is longer than its bound");
+        *len = total;
+        if (cap < total) return fail("index_key_frame: cap is smaller than the frame (*len has its length)");
+        JSP_HIP(hipMemcpyAsync(out, k.out, total, hipMemcpyDeviceToHost, c->stream));
+        JSP_HIP(hipStreamSynchronize(c->stream));
+        return JSP_ZERO_STATE;
     } catch (const std::exception& e) {
         set_error("%s", e.what());
         return JSP_ERROR_OCCURED;

@@ -113,5 +113,21 @@ void msv1_launch_index_tensor(const Msv1IndexSrc& src, const int32_t* d_frames, 
 // `out` first.  The run is split into `segs` (clamped to 1..n) contiguous segments along grid.y, each composing the picture before its
 // own first frame; the counts do not depend on the split.
 void msv1_launch_index_activity(const Msv1IndexSrc& src, int first, int n, int segs, uint16_t* out, int cols, int rows, hipStream_t stream);
+// The device scratch of jsp_index_key_frame (the index owns it; every part 16-byte aligned).
+struct Msv1KeyFrameScratch {
+    uint32_t* status;                // [0]: all ones, else the first block that cannot be cut (block << 1 | kind); [1]: the frame's length
+    uint32_t* totals;                // per workgroup of MSV1_KEYFRAME_WG_BLOCKS blocks: the bytes of its codes
+    uint32_t* records;               // per block: writer frame, (offset within its workgroup's bytes << 8 | code length, 0 with a status)
+    uint8_t* out;                    // the key frame, room for its bound (18 / 10 bytes a block)
+};
+constexpr int MSV1_KEYFRAME_WG_BLOCKS = 1024;      // consecutive blocks a workgroup of the two kernels owns
+constexpr uint32_t MSV1_KEYFRAME_NO_WRITER = 0u;   // kinds of status: no frame <= t of the index codes the block ...
+constexpr uint32_t MSV1_KEYFRAME_CUT = 1u;         // ... the end of its last writer's data cuts the code off
+inline int msv1_keyframe_workgroups(int nblocks) { return (nblocks + MSV1_KEYFRAME_WG_BLOCKS - 1) / MSV1_KEYFRAME_WG_BLOCKS; }
+// TWO launches (msv1_index_keyframe_kernels.hip, which states the rule): msv1_index_keyframe_sizes_kernel, then
+// msv1_index_keyframe_gather_kernel — the codes of the last writers <= t of all blocks, in block order, into k.out, the length into
+// k.status[1]; k.status[0] (all ones from the caller) names the first block without a writer or with a code cut off, and k.out is
+// then not a key frame.  Nothing for an index without a block.
+void msv1_launch_index_keyframe(const Msv1IndexSrc& src, int t, const Msv1KeyFrameScratch& k, hipStream_t stream);
 
 }  // namespace jsp

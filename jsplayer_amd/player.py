@@ -17,7 +17,8 @@ shown — ScreenPressor's, `ADOPTS` false — serves the frame and leaves the de
 `prev_key` are the navigation of Manager.hx:184-208 over `seek`; `play_from_index` plays a run of frames out of such a non-adopting
 index, one `Play` launch per batch of free buffers; `preview` / `filmstrip` are the seek bar's small pictures, one
 `Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex); `activity` / `change_totals` / `change_box` /
-`next_change` say where and when the picture changes, from the index's `Activity` map (changed pixels per frame and 16x16 cell).  `View` is the zoom / scroll / fit state of Main
+`next_change` say where and when the picture changes, from the index's `Activity` map (changed pixels per frame and 16x16 cell);
+`cut` / `write_cut` give the clip from any frame on as frames and flags / as an AVI file, its first frame the index's `KeyFrame`.  `View` is the zoom / scroll / fit state of Main
 (Main.hx:288-319, 1186-1278) and `Manager.present` draws the window it shows of a frame buffer, one launch.  Timers, bitmaps and audio
 of the reference's Manager are not rebuilt.
 """
@@ -250,6 +251,45 @@ class Manager:
         if hits.size == 0:
             return None
         return self.seek(frames, self.index_first + k0 + int(hits[0]), key_flags)
+
+    # -- a clip that starts at any frame: the attached index's KeyFrame (jsp_index_key_frame) ------------------------------------------
+    def cut(self, frames: Sequence[bytes], first: int, last: Optional[int] = None, key_flags: Optional[Sequence[bool]] = None):
+        """Clip frames first .. last (None: to the end), as a clip of its own: (list of frame bytes, key flags).  A clip has to start
+        on a key frame.  Where frame `first` is one — by `key_flags`, else frame 0 or the decoder's IsKeyFrame — it is taken as it
+        is and no index is needed.  Else the attached index must contain `first`, and the first frame of the result is
+        index.KeyFrame(first - index_first): a key frame that decodes to the picture of frame `first`, made of the codes the index
+        holds (a frame the index cannot cut raises its CodecError).  The frames after it are the caller's own objects and keep
+        their flags; the first flag is True.  Nothing is decoded and neither decoder nor buffers change.  ValueError: `first`
+        outside the clip or last < first; at an inter frame, no index attached, `first` outside it, or an index object without
+        `KeyFrame` (ScreenPressor's)."""
+        first = int(first)
+        last = len(frames) - 1 if last is None else int(last)
+        if not 0 <= first < len(frames):
+            raise ValueError(f"cut: frame {first} is not in the clip")
+        if last < first:
+            raise ValueError(f"cut: last ({last}) is before first ({first})")
+        last = min(last, len(frames) - 1)
+        tail = list(frames[first + 1:last + 1])
+        flags = [True] + [bool(key_flags[i]) if key_flags is not None else bool(self.decoder.IsKeyFrame(frames[i]))
+                          for i in range(first + 1, last + 1)]
+        if self._key_at(frames, first, key_flags):
+            return [frames[first]] + tail, flags
+        if self.index is None:
+            raise ValueError(f"cut: frame {first} is not a key frame and no seek index is attached")
+        if not self._in_index(first):
+            raise ValueError(f"cut: frame {first} is not a key frame and not in the attached seek index")
+        if not hasattr(self.index, "KeyFrame"):
+            raise ValueError("cut: the attached seek index cannot make a key frame")
+        return [self.index.KeyFrame(first - self.index_first)] + tail, flags
+
+    def write_cut(self, frames: Sequence[bytes], first: int, last: Optional[int] = None, key_flags: Optional[Sequence[bool]] = None,
+                  fps: float = 15.0) -> bytes:
+        """`cut` as an AVI file (avi.write_avi) with this Manager's stream: width, height, bit depth and palette of its VideoInfo,
+        fourcc CRAM for MSVideo1 and SCPR for ScreenPressor."""
+        from .avi import write_avi
+        out, flags = self.cut(frames, first, last, key_flags)
+        fourcc = b"SCPR" if self.vi.codec == CODEC_SCREENPRESSOR else b"CRAM"
+        return write_avi(self.vi.X, self.vi.Y, out, fourcc=fourcc, bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
 
     def _index_adopts(self) -> bool:
         return bool(getattr(self.index, "ADOPTS", True))

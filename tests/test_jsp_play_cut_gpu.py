@@ -1,0 +1,79 @@
+"""examples/jsp_play clip.avi --cut FIRST[:COUNT] OUT.avi on MSVideo1 clips: OUT.avi holds COUNT frames, the first flagged key and equal
+to SeekIndex.KeyFrame of that frame over an index from the key frame before it, the others the clip's own; every CRC pair the example
+prints — OUT.avi played back through the ordinary decode loop beside the clip's own frames — is equal; a frame that cannot be cut
+exits with 1, the library's text and no file."""
+import os
+import subprocess
+
+import pytest
+
+from jsplayer_amd import avi
+from jsplayer_amd import streamgen as sg
+from msv1_range_clips import long_clip, make_gpu
+
+pytestmark = pytest.mark.gpu
+
+W, H = 64, 32
+FIRST, COUNT = 40, 20
+
+
+def exe_path():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "examples", "jsp_play")
+    if not os.path.exists(exe):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(root, "examples")])
+    return exe
+
+
+def run(path, extra):
+    res = subprocess.run([exe_path(), str(path), "--cut"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    return res.returncode, [l.split() for l in res.stdout.decode().splitlines()], res.stderr.decode()
+
+
+def clip_of(bits):
+    if bits == 8:      # end markers, repaints, all-skip frames; key frames 0 and 70: frame 40's writers go back to frame 0
+        frames, keys, pal, _ = long_clip(8, W, H, seed=5, n=96)
+        return frames, keys, pal
+    frames, keys, _ = sg.msv1_clip(97, W, H, 64, p_mix=sg.msv1_p_mix(0.9, 6.0), key_every=16)
+    return frames, keys, None
+
+
+@pytest.mark.parametrize("bits", [16, 8])
+def test_jsp_play_cut_writes_a_clip_that_plays_back_as_the_original(tmp_path, bits):
+    frames, keys, pal = clip_of(bits)
+    assert not keys[FIRST]
+    path, out = tmp_path / "clip.avi", tmp_path / "out.avi"
+    path.write_bytes(avi.write_avi(W, H, frames, fourcc=b"CRAM", bpp=bits, fps=15.0, palette=pal, key_flags=keys))
+    rc, lines, err = run(path, [f"{FIRST}:{COUNT}", str(out)])
+    assert rc == 0, err
+    assert [l[0] for l in lines] == [str(FIRST + k) for k in range(COUNT)]
+    assert all(len(l) == 3 and l[1] == l[2] for l in lines), lines
+    assert len({l[1] for l in lines}) > 1                      # (the pictures do change over the run)
+    vi, got, got_keys = avi.read_avi_indexed(out.read_bytes())
+    assert (vi.X, vi.Y, vi.bpp, vi.nframes) == (W, H, bits, COUNT) and (vi.palette or None) == pal
+    assert len(got) == COUNT and got_keys[0] and list(got_keys[1:]) == [bool(k) for k in keys[FIRST + 1:FIRST + COUNT]]
+    assert [bytes(f) for f in got[1:]] == [bytes(f) for f in frames[FIRST + 1:FIRST + COUNT]]
+    k = max(i for i in range(FIRST + 1) if keys[i])
+    dec = make_gpu(bits, W, H, pal)
+    with dec.BuildIndex(frames[k:FIRST + 1], keys[k:FIRST + 1]) as idx:
+        assert bytes(got[0]) == idx.KeyFrame(FIRST - k) != bytes(frames[FIRST])
+    dec.StopAndClean()
+    # at a key frame the frame is copied; to the end of the clip without a count
+    key = max(i for i in range(len(frames)) if keys[i])
+    rc, lines, err = run(path, [str(key), str(out)])
+    assert rc == 0 and len(lines) == len(frames) - key and all(l[1] == l[2] for l in lines), err
+    _, got, got_keys = avi.read_avi_indexed(out.read_bytes())
+    assert bytes(got[0]) == bytes(frames[key]) and got_keys[0]
+    for extra in ([f"{len(frames) - 1}:2", str(out)], [str(len(frames)), str(out)], ["5:0", str(out)], ["5", str(out), "--step-back"], ["5"]):
+        rc, lines, err = run(path, extra)                      # past the end; an empty run; it goes alone; no file name
+        assert rc != 0 and not lines, extra
+
+
+def test_jsp_play_cut_refuses_where_the_library_does(tmp_path):
+    """16-bit long_clip: the truncated frame 31 cuts codes off, and nothing codes those blocks again before key 70."""
+    frames, keys, _, _ = long_clip(16, W, H, seed=5, n=96)
+    path, out = tmp_path / "clip.avi", tmp_path / "out.avi"
+    path.write_bytes(avi.write_avi(W, H, frames, fourcc=b"CRAM", bpp=16, fps=15.0, key_flags=keys))
+    rc, lines, err = run(path, [f"{FIRST}:{COUNT}", str(out)])
+    assert rc == 1 and not lines and "index_key_frame:" in err and "cut off" in err and "frame 31" in err, err
+    assert not out.exists()
