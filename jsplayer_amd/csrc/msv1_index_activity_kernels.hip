@@ -35,7 +35,10 @@ __global__ __launch_bounds__(WG) void msv1_index_activity_kernel(const Msv1Index
     load_palette<BITS>(s_pal, s.palette);
     const long gid = (long)blockIdx.x * WG + threadIdx.x;
     const long q = gid >> 4;                                        // cell of the grid, raster order
-    if (q >= (long)cols * rows) return;                             // (a whole group of 16 lanes)
+    // The tail of the last workgroup: q is the same for the 16 lanes of a group, so whole groups leave — up to 15 of the workgroup's
+    // 16, one to three of a wave's four while the rest of the wave goes on.  The shuffles below stay inside a group (xor 1..8).
+    // (After load_palette: every lane of the workgroup loads its palette entry and reaches the barrier behind it.)
+    if (q >= (long)cols * rows) return;
     const int sub = (int)(gid & 15);
     const int r = (int)(q / cols);
     const int qx = (int)(q - (long)r * cols);

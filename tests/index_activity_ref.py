@@ -6,9 +6,11 @@ tests of its own.
   * msv1_pictures — THE PICTURE P(t) of an MSVideo1 index from the oracle's sequential run (msv1_range_clips.truth_run): the
     oracle's picture where the index has one, zeros in a block nothing has coded yet when there is no picture before the range.
   * msv1_model — msv1_index_activity_kernel's walk over a plan of msv1_range_clips (which frame codes which block): a lane per 4x4
-    block, 16 lanes to a cell with the lanes of an edge cell that have no block alive, the bitmap words masked to the segment's
-    frames and ORed over the cell, the segment that composes the picture before its own first frame, the `have` flag (a block
-    nothing has coded and nothing lies under is zeros).  As in msv1_index_play_ref the model is about WHICH code a lane decodes
+    block enumerated as the launch enumerates them — lane gid of ceil(cells * 16 / 256) workgroups of 256 belongs to cell
+    q = gid >> 4 of the grid in raster order (r = q // cols, qx = q - r * cols) and is its lane sub = gid & 15, a group with
+    q >= cols * rows owns nothing — with the lanes of an edge cell that have no block alive, the bitmap words masked to the
+    segment's frames and ORed over the cell, the segment that composes the picture before its own first frame, the `have` flag
+    (a block nothing has coded and nothing lies under is zeros).  As in msv1_index_play_ref the model is about WHICH code a lane decodes
     and what it compares it with, not about the decode: a block's pixels as frame f codes them are the oracle's after frame f.
   * sp_model — sp_index_activity_kernel's walk over what sp_index_ref.Composer keeps (key pictures; per inter frame a literal
     image and the mask of its rectangles): the events bitmap | keymask of the run's frames word by word, literals compared and
@@ -16,13 +18,15 @@ tests of its own.
 
 `wrong=` selects a deliberately broken walk that the tests must catch:
   msv1_model: "bit_is_16" (a set bit counts as 16 changed pixels), "no_recompose" (a segment after the first starts from the picture
-              before the index instead of composing the picture before its first frame);
+              before the index instead of composing the picture before its first frame), "cols_is_4" (r = q // 4, qx = q % 4: right
+              on a grid of four columns only), "one_workgroup" (lanes from 256 on own nothing: right up to 16 cells only);
   sp_model:   "rect_area" (every pixel under a rectangle counts), "key_ignored" (a key frame inside the run is not an event)."""
 import numpy as np
 
 from msv1_index_play_ref import _top_bit, bitmap_words, index_last_writer, segment_length, to_blocks
 
 CELL = 16
+WG, GROUP = 256, 16   # msv1_index_activity_kernel: lanes of a workgroup, lanes of a cell
 
 
 def grid(w, h):
@@ -85,6 +89,8 @@ def msv1_model(coded, block_pics, w, h, first, n, segs=1, before=None, wrong=Non
     nb = nbx * nby
     cols, rows = grid(w, h)
     out = np.zeros((n, rows, cols), dtype=np.uint16)
+    flat = out.reshape(-1)
+    nwg = (cols * rows * GROUP + WG - 1) // WG
     under = to_blocks(before, w, h).astype(np.int32) if before is not None and nb else None
     seg = segment_length(n, segs)
     for k0 in range(0, n, seg):
@@ -101,31 +107,38 @@ def msv1_model(coded, block_pics, w, h, first, n, segs=1, before=None, wrong=Non
                 px[b] = block_pics[int(32 * wd[b] + _top_bit(m[b:b + 1])[0])][b]
                 have[b] = True
         px[~have] = 0
-        for r in range(rows):
-            for q in range(cols):
-                lanes = []   # the cell's 16 lanes: (block, live)
-                for sub in range(16):
-                    by, bx = r * 4 + (sub >> 2), q * 4 + (sub & 3)
-                    live = by < nby and bx < nbx
-                    lanes.append((by * nbx + bx if live else 0, live))
-                for wd in range(t0 >> 5, (t1 >> 5) + 1):
-                    lo, hi = max(t0, 32 * wd), min(t1, 32 * wd + 31)
-                    rng = (0xFFFFFFFF << (lo & 31)) & (0xFFFFFFFF >> (31 - (hi & 31))) & 0xFFFFFFFF
-                    mine = [int(bm[wd, b]) & rng if live else 0 for b, live in lanes]
-                    union = 0
-                    for v in mine:
-                        union |= v
-                    while union:
-                        bit = (union & -union).bit_length() - 1
-                        union &= union - 1
-                        f, cnt = 32 * wd + bit, 0
-                        for (b, live), v in zip(lanes, mine):
-                            if (v >> bit) & 1:
-                                nx = block_pics[f][b]
-                                cnt += 16 if wrong == "bit_is_16" else int(np.count_nonzero(nx != px[b]))
-                                px[b] = nx
-                        if cnt:
-                            out[f - first, r, q] = cnt
+        for g0 in range(0, nwg * WG, GROUP):
+            lanes, r, qx = [], 0, 0   # the group's lanes that go on: (block, live); all 16 or none — q, r, qx are the same for the 16
+            for gid in range(g0, g0 + GROUP):
+                q, sub = gid >> 4, gid & 15
+                if q >= cols * rows or (wrong == "one_workgroup" and gid >= WG):
+                    continue   # (a tail group leaves)
+                r, qx = (q // 4, q % 4) if wrong == "cols_is_4" else (q // cols, q - (q // cols) * cols)
+                by, bx = r * 4 + (sub >> 2), qx * 4 + (sub & 3)
+                live = by < nby and bx < nbx
+                lanes.append((by * nbx + bx if live else 0, live))
+            if not lanes:
+                continue
+            assert len(lanes) == GROUP
+            for wd in range(t0 >> 5, (t1 >> 5) + 1):
+                lo, hi = max(t0, 32 * wd), min(t1, 32 * wd + 31)
+                rng = (0xFFFFFFFF << (lo & 31)) & (0xFFFFFFFF >> (31 - (hi & 31))) & 0xFFFFFFFF
+                mine = [int(bm[wd, b]) & rng if live else 0 for b, live in lanes]
+                union = 0
+                for v in mine:
+                    union |= v
+                while union:
+                    bit = (union & -union).bit_length() - 1
+                    union &= union - 1
+                    f, cnt = 32 * wd + bit, 0
+                    for (b, live), v in zip(lanes, mine):
+                        if (v >> bit) & 1:
+                            nx = block_pics[f][b]
+                            cnt += 16 if wrong == "bit_is_16" else int(np.count_nonzero(nx != px[b]))
+                            px[b] = nx
+                    at = ((f - first) * rows + r) * cols + qx   # the first lane's store, a flat element as the kernel addresses it
+                    if cnt and at < flat.size:                  # (a wrong r can point behind the map: the model drops that store)
+                        flat[at] = cnt
     return out
 
 

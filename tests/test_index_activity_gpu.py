@@ -32,7 +32,7 @@ class Case:
     """A codec brought to frame `start` of a clip frame by frame, its index over the `count` frames from there on, and the map of
     the whole index by the definition."""
 
-    def __init__(self, bits, w, h, pal, frames, keys, coded, lines=36, start=0, count=None):
+    def __init__(self, bits, w, h, pal, frames, keys, coded, lines=36, start=0, count=None, chunk=None):
         count = len(frames) - start if count is None else count
         self.bits, self.w, self.h, self.n = bits, w, h, count
         self.frames, self.keys = frames, keys
@@ -41,7 +41,7 @@ class Case:
         pics = [t[0] for t in truth]
         self.p_before, self.p = ar.msv1_pictures(pics[start:], coded[start:start + count], w, h, pics[start - 1] if start > 0 else None)
         self.want = ar.activity(self.p, self.p_before, w, h)
-        self.gpu = make_gpu(bits, w, h, pal, lines)
+        self.gpu = make_gpu(bits, w, h, pal, lines, chunk)   # (chunk: the msv1_seek_chunk_frames option — an index of several chunks)
         self.pool = [dev_buf(w * h) for _ in range(3)]
         sequential(self.gpu, frames, keys, start, self.pool)
         self.idx = self.gpu.BuildIndex(frames[start:start + count], keys[start:start + count])
