@@ -11,7 +11,8 @@ with no writer <= t, or whose last writer's code is not whole, makes t uncuttabl
   * codes_of — one frame: per block (offset, length) of its whole code, "cut" for a code the frame's end cuts off, None for a block
     the frame does not code.  The control flow is msv1_range_clips.coded_blocks' (a block is coded exactly where that says so:
     test_index_keyframe_ref_cpu.py asserts it), with the offsets kept.
-  * key_frame — the bytes, or ("none" | "cut", block) with the FIRST block that refuses."""
+  * key_frame — the bytes, or ("none" | "cut", block) with the FIRST block that refuses;
+  * cut_writer — the frame a ("cut", block) refusal names: the block's last writer <= t."""
 
 
 def codes_of(bits, nbx, nby, src, have_prev=True):
@@ -88,3 +89,8 @@ def key_frame(bits, nbx, nby, frames, t, codes=None):
         o, length = codes[f][blk]
         out += bytes(frames[f])[o:o + length]
     return bytes(out)
+
+
+def cut_writer(codes, t, blk):
+    """The frame whose code of `blk` is cut off when key_frame says ("cut", blk) at t: the last frame <= t that codes the block."""
+    return next(f for f in range(t, -1, -1) if codes[f][blk] is not None)

@@ -15,6 +15,7 @@ import index_activity_ref as ar
 import msv1_activity_geometry_clips as gc
 from jsplayer_amd import _native as N
 from msv1_range_clips import long_clip, make_gpu, make_plan, palette
+import test_index_activity_gpu as base
 from test_index_activity_gpu import MSV1_N, Case
 
 pytestmark = pytest.mark.gpu
@@ -81,7 +82,7 @@ def test_a_picture_without_a_block_has_a_map_of_zeros(size, cells):
     """No 4x4 block fits: the grid still has its cells, no lane of the launch has a block, and the map is the zeros the host wrote."""
     import torch
     w, h = size
-    gpu = make_gpu(16, w, h)
+    gpu = make_gpu(16, w, h, parse=base.PARSE)
     idx = gpu.BuildIndex([b"\x01\x02\x03\x04", b""], [True, False])
     assert idx.ActivitySize() == cells
     n, cell = 2, cells[0] * cells[1]
@@ -138,3 +139,19 @@ def test_the_codec_goes_on_as_a_twin_that_never_asked():
     a.check(0, 5)
     a.close()
     twin.close()
+
+
+class TestOnGpuParse:
+    """Every test of this file once more with the block tables of the on-GPU parse, the codec's default (base.Case reads base.PARSE).
+    The tests above keep the host parser and their names."""
+
+    @pytest.fixture(autouse=True)
+    def parse_mode(self):
+        base.PARSE = "gpu"
+        yield base.PARSE
+        base.PARSE = "host"
+
+
+for _name, _test in list(globals().items()):
+    if _name.startswith("test_"):
+        setattr(TestOnGpuParse, _name, staticmethod(_test))

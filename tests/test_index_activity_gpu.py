@@ -16,6 +16,7 @@ from msv1_range_clips import POISON, Idle, dev_buf, long_clip, make_gpu, make_pl
 pytestmark = pytest.mark.gpu
 
 MSV1_N = 72   # words 0, 1, 2 of the bitmap: a run crosses two word boundaries; the key frame at 70 repaints the picture as it is
+PARSE = "host"   # the msv1_parse of every codec built here; TestOnGpuParse (the end of this file) runs every test with "gpu" too
 
 
 def sequential(gpu, frames, keys, hi, pool):
@@ -41,12 +42,12 @@ class Case:
         pics = [t[0] for t in truth]
         self.p_before, self.p = ar.msv1_pictures(pics[start:], coded[start:start + count], w, h, pics[start - 1] if start > 0 else None)
         self.want = ar.activity(self.p, self.p_before, w, h)
-        self.gpu = make_gpu(bits, w, h, pal, lines, chunk)   # (chunk: the msv1_seek_chunk_frames option — an index of several chunks)
+        self.gpu = make_gpu(bits, w, h, pal, lines, chunk, PARSE)   # (chunk: the msv1_seek_chunk_frames option — an index of several chunks)
         self.pool = [dev_buf(w * h) for _ in range(3)]
         sequential(self.gpu, frames, keys, start, self.pool)
         self.idx = self.gpu.BuildIndex(frames[start:start + count], keys[start:start + count])
         assert self.idx.frames == count
-        self.where = f"{bits}-bit {w}x{h} start={start}"
+        self.where = f"{bits}-bit {w}x{h} start={start} ({PARSE} parse)"
 
     def check(self, first, n, what=""):
         got = self.idx.Activity(first, n)
@@ -167,3 +168,20 @@ def test_nothing_else_is_written_and_the_codec_is_only_lent():
         a.check(0, 5)
     a.close()
     twin.close()
+
+
+class TestOnGpuParse:
+    """Every test of this file once more with the block tables of the on-GPU parse, the codec's default (Case reads PARSE).  The
+    tests above keep the host parser and their names."""
+
+    @pytest.fixture(autouse=True)
+    def parse_mode(self):
+        global PARSE
+        PARSE = "gpu"
+        yield PARSE
+        PARSE = "host"
+
+
+for _name, _test in list(globals().items()):
+    if _name.startswith("test_"):
+        setattr(TestOnGpuParse, _name, staticmethod(_test))

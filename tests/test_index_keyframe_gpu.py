@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 MSV1_N = 72      # frames of the index's range: bitmap words 0, 1, 2
 FILL = 0xA5      # what `out` holds before a call
 WG_BLOCKS = 1024   # MSV1_KEYFRAME_WG_BLOCKS (msv1_seek.h): consecutive blocks a workgroup of the two kernels owns
+PARSE = "host"     # the msv1_parse of every codec built here; TestOnGpuParse (the end of this file) runs every test with "gpu" too
 
 
 def sequential(gpu, frames, keys, hi, pool):
@@ -43,14 +44,14 @@ class Case:
         self.nbx, self.nby = w // 4, h // 4
         self.range, self.range_keys = frames[start:start + count], keys[start:start + count]
         self.codes = [kr.codes_of(bits, self.nbx, self.nby, f) for f in self.range]
-        self.gpu = make_gpu(bits, w, h, pal, lines, chunk)
+        self.gpu = make_gpu(bits, w, h, pal, lines, chunk, PARSE)
         self.pool = [dev_buf(w * h) for _ in range(3)]
         sequential(self.gpu, frames, keys, start, self.pool)
         self.idx = self.gpu.BuildIndex(self.range, self.range_keys)
         assert self.idx.frames == count
         self.bound = self.idx.KeyFrameBound()
         assert self.bound == self.nbx * self.nby * (18 if bits == 16 else 10)
-        self.where = f"{bits}-bit {w}x{h} start={start} chunk={chunk}"
+        self.where = f"{bits}-bit {w}x{h} start={start} chunk={chunk} ({PARSE} parse)"
 
     def want(self, t):
         return kr.key_frame(self.bits, self.nbx, self.nby, self.range, t, self.codes)
@@ -80,6 +81,8 @@ class Case:
             assert rc != 0 and n == 0, where
             assert err.startswith("index_key_frame:") and f"block {blk} " in err, (where, err)
             assert ("no writer" in err) == (kind == "none") and ("cut off" in err) == (kind == "cut"), (where, err)
+            if kind == "cut":   # ... and names the frame whose code it is: the block's last writer
+                assert f"block {blk} in frame {kr.cut_writer(self.codes, t, blk)}," in err, (where, err)
             assert np.all(out == FILL), where + ": written on a refusal"
             with pytest.raises(CodecError, match=f"block {blk} "):
                 self.idx.KeyFrame(t)
@@ -187,7 +190,7 @@ def test_cap_and_bound(bits):
 
 
 def test_a_picture_without_a_block_is_refused_before_any_launch():
-    gpu = make_gpu(16, 3, 8)
+    gpu = make_gpu(16, 3, 8, parse=PARSE)
     idx = gpu.BuildIndex([b"\x01\x02\x03\x04", b""], [True, False])
     assert idx.KeyFrameBound() == 0
     out = np.full(16, FILL, dtype=np.uint8)
@@ -210,7 +213,7 @@ def test_round_trip_through_the_gpu_codec(bits):
     shown = dev_buf(w * h)
     for t in (cuttable[0], cuttable[len(cuttable) // 2], cuttable[-1]):
         kf = c.idx.KeyFrame(t)
-        fresh = make_gpu(bits, w, h, pal, plan["lines"])
+        fresh = make_gpu(bits, w, h, pal, plan["lines"], parse=PARSE)
         assert fresh.IsKeyFrame(kf)
         pool = [dev_buf(w * h) for _ in range(2)]
         assert fresh.DecompressI(kf, pool[0]) == 0
@@ -229,3 +232,21 @@ def test_round_trip_through_the_gpu_codec(bits):
                 f"{c.where}: frame {t + k} on top of KeyFrame({t})"
         fresh.StopAndClean()
     c.close()
+
+
+class TestOnGpuParse:
+    """Every test of this file once more with the block tables of the on-GPU parse — the codec's default, under which frames too
+    short to code every block still get their table from the host parser: one index then mixes both sources.  (The tests above keep
+    the host parser and their names.)"""
+
+    @pytest.fixture(autouse=True)
+    def parse_mode(self):
+        global PARSE
+        PARSE = "gpu"
+        yield PARSE
+        PARSE = "host"
+
+
+for _name, _test in list(globals().items()):
+    if _name.startswith("test_"):
+        setattr(TestOnGpuParse, _name, staticmethod(_test))

@@ -40,6 +40,17 @@ def clip_of(bits):
 
 @pytest.mark.parametrize("bits", [16, 8])
 def test_jsp_play_cut_writes_a_clip_that_plays_back_as_the_original(tmp_path, bits):
+    cut_and_play_back(tmp_path, bits, "host")
+
+
+@pytest.mark.parametrize("bits", [16, 8])
+def test_jsp_play_cut_is_the_key_frame_of_an_index_parsed_on_the_gpu(tmp_path, bits):
+    cut_and_play_back(tmp_path, bits, "gpu")
+
+
+def cut_and_play_back(tmp_path, bits, parse_mode):
+    """parse_mode: the msv1_parse of the codec whose KeyFrame the file's first frame is held to — the block tables of the host parser,
+    or of the on-GPU parse (the example itself runs with the library's default)."""
     frames, keys, pal = clip_of(bits)
     assert not keys[FIRST]
     path, out = tmp_path / "clip.avi", tmp_path / "out.avi"
@@ -54,7 +65,7 @@ def test_jsp_play_cut_writes_a_clip_that_plays_back_as_the_original(tmp_path, bi
     assert len(got) == COUNT and got_keys[0] and list(got_keys[1:]) == [bool(k) for k in keys[FIRST + 1:FIRST + COUNT]]
     assert [bytes(f) for f in got[1:]] == [bytes(f) for f in frames[FIRST + 1:FIRST + COUNT]]
     k = max(i for i in range(FIRST + 1) if keys[i])
-    dec = make_gpu(bits, W, H, pal)
+    dec = make_gpu(bits, W, H, pal, parse=parse_mode)
     with dec.BuildIndex(frames[k:FIRST + 1], keys[k:FIRST + 1]) as idx:
         assert bytes(got[0]) == idx.KeyFrame(FIRST - k) != bytes(frames[FIRST])
     dec.StopAndClean()
