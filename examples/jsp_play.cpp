@@ -44,6 +44,15 @@
 //                                is copied), the frames after it copied.  Then OUT.avi is played back through the ordinary decode loop:
 //                                prints "<frame of the clip> <crc32 from OUT.avi> <crc32 from the clip>" per frame (the CRC-32 of the
 //                                pixels that blocks cover) and exits with 1 on any difference
+//   jsp_play clip.avi --thin FIRST[:COUNT[:STRIDE]] OUT.avi
+//                                MSVideo1: frames FIRST, FIRST + STRIDE, ... of the clip (COUNT of them; default: as many as the clip
+//                                holds; STRIDE default 8) as an AVI file of its own — a time-lapse.  ONE seek index from the nearest key
+//                                frame <= FIRST up to the last frame kept; the first frame as for --cut; a later frame that is a key
+//                                frame of the clip, or that follows the one before it directly, is copied; every other one is an inter
+//                                frame that spans its gap, made of the codes the clip holds and skips, all of them from ONE
+//                                jsp_index_delta_frames call.  Then OUT.avi is played back through the ordinary decode loop: prints
+//                                "<frame of the clip> <crc32 from OUT.avi> <crc32 from the clip>" per frame kept and exits with 1 on any
+//                                difference
 //   jsp_play clip.avi --filmstrip N[:scale]
 //                                ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build), then ONE
 //                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
@@ -526,6 +535,8 @@ int main(int argc, char** argv) {
     long act_first = -1, act_count = -1;                      // --activity [FIRST[:COUNT]]: the activity map of a seek index over the clip
     long cut_first = -1, cut_count = -1;                      // --cut FIRST[:COUNT] OUT.avi: the clip from frame FIRST on as a file of its own
     std::string cut_path;
+    long thin_first = -1, thin_count = -1, thin_stride = 8;   // --thin FIRST[:COUNT[:STRIDE]] OUT.avi: every STRIDE-th frame as a file of its own
+    std::string thin_path;
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
     long play_first = -1, play_count = -1, play_stride = 1;   // --play-index FIRST[:COUNT[:STRIDE]]: frames played out of a ScreenPressor seek index
     long run_first = -1, run_count = -1, run_stride = 1;      // --index-run FIRST[:COUNT[:STRIDE]]: frames played out of an MSVideo1 seek index
@@ -566,6 +577,18 @@ int main(int argc, char** argv) {
             if (colon != std::string::npos) cut_count = std::atol(v.substr(colon + 1).c_str());
             cut_path = argv[++a];
             if (cut_first < 0 || (colon != std::string::npos && cut_count < 1)) { std::fprintf(stderr, "--cut FIRST[:COUNT] OUT.avi: FIRST >= 0, COUNT >= 1\n"); return 2; }
+        }
+        else if (o == "--thin" && a + 2 < argc) {
+            const std::string v = argv[++a];
+            const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            thin_first = std::atol(v.substr(0, c1).c_str());
+            if (c1 != std::string::npos) thin_count = std::atol(v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1).c_str());
+            if (c2 != std::string::npos) thin_stride = std::atol(v.substr(c2 + 1).c_str());
+            thin_path = argv[++a];
+            if (thin_first < 0 || (c1 != std::string::npos && thin_count < 1) || thin_stride < 1) {
+                std::fprintf(stderr, "--thin FIRST[:COUNT[:STRIDE]] OUT.avi: FIRST >= 0, COUNT >= 1, STRIDE >= 1\n");
+                return 2;
+            }
         }
         else if (o == "--filmstrip" && a + 1 < argc) {
             const std::string v = argv[++a];
@@ -637,6 +660,8 @@ int main(int argc, char** argv) {
     if (act_first >= 0 && (run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--activity goes alone\n"); return 2; }
     if (cut_first >= 0 && (act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--cut goes alone\n"); return 2; }
     if (cut_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--cut: MSVideo1 only (a ScreenPressor key frame needs the entropy encoder)\n"); return 2; }
+    if (thin_first >= 0 && (cut_first >= 0 || act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--thin goes alone\n"); return 2; }
+    if (thin_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--thin: MSVideo1 only (a ScreenPressor frame needs the entropy encoder)\n"); return 2; }
     if (strip > 0 && (step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--filmstrip goes alone\n"); return 2; }
     if (play_first >= 0 && (strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--play-index goes alone\n"); return 2; }
     if (play_first >= 0 && clip.kind != JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--play-index: ScreenPressor only (an MSVideo1 index adopts: --seek and the plain run play on from any frame)\n"); return 2; }
@@ -1040,6 +1065,97 @@ int main(int argc, char** argv) {
         for (long k = 0; k < count; ++k) {
             std::printf("%ld %08x %08x\n", cut_first + k, got[(size_t)k], want[(size_t)(cut_first + k)]);
             if (got[(size_t)k] != want[(size_t)(cut_first + k)]) rc = 1;
+        }
+        return rc;
+    }
+    if (thin_first >= 0) {   // a time-lapse: one index build from the key frame before, ONE jsp_index_delta_frames for every gap, the file, its playback
+        const size_t n = clip.frames.size();
+        std::vector<size_t> keep;
+        for (long i = thin_first; i < (long)n && (thin_count < 0 || (long)keep.size() < thin_count); i += thin_stride) keep.push_back((size_t)i);
+        if (keep.empty() || (thin_count >= 0 && (long)keep.size() < thin_count)) {
+            std::fprintf(stderr, "--thin: frames %ld, %ld, ... (%ld of them) are not all in the clip (%zu frames)\n", thin_first, thin_first + thin_stride, thin_count, n);
+            rc = 1;
+        }
+        std::vector<uint8_t> key_frame, deltas;
+        std::vector<size_t> gaps, delta_lens;                   // entries of `keep` that are inter frames over a gap, and their lengths
+        for (size_t j = 1; rc == 0 && j < keep.size(); ++j)
+            if (keep[j] != keep[j - 1] + 1 && !frame_is_key(clip, dec, keep[j])) gaps.push_back(j);
+        const bool need_key = rc == 0 && !frame_is_key(clip, dec, keep[0]);
+        if (rc == 0 && (need_key || !gaps.empty())) {
+            size_t k = keep[0];
+            while (k > 0 && !frame_is_key(clip, dec, k)) --k;   // the nearest key frame <= FIRST (frame 0 is one)
+            std::vector<const uint8_t*> srcs;
+            std::vector<size_t> lens;
+            std::vector<uint8_t> keys;
+            for (size_t i = k; i <= keep.back(); ++i) {
+                srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+                lens.push_back(clip.frames[i].second);
+                keys.push_back(i == k || frame_is_key(clip, dec, i) ? 1 : 0);
+            }
+            jsp_index* idx = jsp_index_build(dec, (int)srcs.size(), srcs.data(), lens.data(), keys.data(), kInsignificantLines);
+            if (!idx) { std::fprintf(stderr, "jsp_index_build: %s\n", jsp_last_error()); rc = 1; }
+            if (rc == 0 && need_key) {
+                size_t bound = 0, len = 0;
+                if (jsp_index_key_frame_bound(idx, &bound) != JSP_ZERO_STATE) { std::fprintf(stderr, "jsp_index_key_frame_bound: %s\n", jsp_last_error()); rc = 1; }
+                key_frame.resize(bound);
+                if (rc == 0 && jsp_index_key_frame(dec, idx, (int)(keep[0] - k), key_frame.data(), bound, &len) != JSP_ZERO_STATE) {
+                    std::fprintf(stderr, "jsp_index_key_frame: %s\n", jsp_last_error());
+                    rc = 1;
+                }
+                key_frame.resize(len);
+            }
+            for (size_t g0 = 0; rc == 0 && g0 < gaps.size(); g0 += 4096) {   // (a call takes 4096 pairs)
+                const size_t m = std::min<size_t>(4096, gaps.size() - g0);
+                std::vector<int> from(m), to(m);
+                for (size_t i = 0; i < m; ++i) {
+                    from[i] = (int)(keep[gaps[g0 + i] - 1] - k);
+                    to[i] = (int)(keep[gaps[g0 + i]] - k);
+                }
+                std::vector<size_t> ls(m);
+                size_t total = 0;
+                // asked twice: the lengths (cap 0 is a refusal that still sets them), then the bytes
+                if (jsp_index_delta_frames(dec, idx, (int)m, from.data(), to.data(), nullptr, 0, ls.data(), &total) == JSP_ZERO_STATE || total == 0) {
+                    std::fprintf(stderr, "jsp_index_delta_frames: %s\n", jsp_last_error());
+                    rc = 1;
+                    break;
+                }
+                const size_t at = deltas.size();
+                deltas.resize(at + total);
+                if (jsp_index_delta_frames(dec, idx, (int)m, from.data(), to.data(), deltas.data() + at, total, ls.data(), &total) != JSP_ZERO_STATE) {
+                    std::fprintf(stderr, "jsp_index_delta_frames: %s\n", jsp_last_error());
+                    rc = 1;
+                }
+                delta_lens.insert(delta_lens.end(), ls.begin(), ls.end());
+            }
+            jsp_index_destroy(idx);
+        }
+        std::vector<std::pair<const uint8_t*, size_t>> out_frames;
+        std::vector<uint8_t> out_keys;
+        size_t g = 0, at = 0;
+        for (size_t j = 0; rc == 0 && j < keep.size(); ++j) {
+            const bool was_key = frame_is_key(clip, dec, keep[j]);
+            if (j == 0 && need_key) out_frames.emplace_back(key_frame.data(), key_frame.size());
+            else if (g < gaps.size() && gaps[g] == j) {
+                out_frames.emplace_back(deltas.data() + at, delta_lens[g]);
+                at += delta_lens[g++];
+            } else out_frames.emplace_back(clip.bytes.data() + clip.frames[keep[j]].first, clip.frames[keep[j]].second);
+            out_keys.push_back(j == 0 || was_key || jsp_is_key_frame(dec, out_frames.back().first, out_frames.back().second) ? 1 : 0);
+        }
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        if (rc != 0) return rc;
+        const std::vector<uint8_t> file = avi_file(clip, out_frames, out_keys);
+        FILE* f = std::fopen(thin_path.c_str(), "wb");
+        if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size()) { std::fprintf(stderr, "cannot write %s\n", thin_path.c_str()); if (f) std::fclose(f); return 1; }
+        std::fclose(f);
+        // OUT.avi played back through the ordinary decode loop, beside the clip's own frames FIRST + k * STRIDE
+        Clip thinned;
+        if (!load(thin_path.c_str(), thinned) || thinned.frames.size() != keep.size()) { std::fprintf(stderr, "cannot read %s back\n", thin_path.c_str()); return 1; }
+        std::vector<uint32_t> got, want;
+        if (!covered_crcs(thinned, thinned.frames.size(), got) || !covered_crcs(clip, keep.back() + 1, want)) return 1;
+        for (size_t j = 0; j < keep.size(); ++j) {
+            std::printf("%zu %08x %08x\n", keep[j], got[j], want[keep[j]]);
+            if (got[j] != want[keep[j]]) rc = 1;
         }
         return rc;
     }

@@ -72,6 +72,10 @@ extern class JspNative {
     @:native("jsp_index_key_frame_bound") static function indexKeyFrameBound(idx:RawPointer<JspIndex>, bytes:RawPointer<SizeT>):Int;
     @:native("jsp_index_key_frame")    static function indexKeyFrame(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, t:Int, out:RawPointer<UInt8>,
                                                                      cap:SizeT, len:RawPointer<SizeT>):Int;
+    @:native("jsp_index_delta_bound")  static function indexDeltaBound(idx:RawPointer<JspIndex>, bytes:RawPointer<SizeT>):Int;
+    @:native("jsp_index_delta_frames") static function indexDeltaFrames(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, n:Int, from:RawConstPointer<Int>,
+                                                                        to:RawConstPointer<Int>, out:RawPointer<UInt8>, cap:SizeT,
+                                                                        lens:RawPointer<SizeT>, total:RawPointer<SizeT>):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)

@@ -195,6 +195,9 @@ int jsp_set_stream(jsp_codec* c, void* hip_stream);
 /*   "msv1_index_activity_segments" = "auto" (default) | "1".."64" : MSVideo1 only, jsp_index_activity.  The run's frames are split into this
  *       many contiguous segments along the launch grid (never more than frames in the run), each composing the picture before its own
  *       first frame; auto: as "msv1_index_play_segments".  Results do not depend on it. */
+/*   "msv1_index_delta_slice" = "auto" (default) | "1".."4096" : MSVideo1 only, jsp_index_delta_frames.  The call's pairs run in slices of
+ *       this many, which bounds the scratch the index owns (auto: as many pairs as 64 MiB of scratch hold, one at least).  Results do
+ *       not depend on it. */
 /*   "async_depth" = "1".."16" (default "4") : any codec.  Frames that may be in flight between jsp_decompress_*_async and
  *       jsp_wait. */
 int jsp_set_option(jsp_codec* c, const char* key, const char* value);
@@ -712,6 +715,44 @@ int jsp_sp_index_activity(jsp_codec* c, jsp_sp_index* idx, int first, int n, uin
  *       a 4x4 block, an asynchronous frame in flight. */
 int jsp_index_key_frame_bound(const jsp_index* idx, size_t* bytes);
 int jsp_index_key_frame(jsp_codec* c, jsp_index* idx, int t, uint8_t* out, size_t cap, size_t* len);
+
+/* ---- inter frames that span a gap of an MSVideo1 index: thin a clip.  A x8 time-lapse, "the same recording without its idle frames",
+ * "frames 100, 164, 228, ..." each need frames that exist in no file.  An inter frame that takes the picture of frame a to the picture
+ * of frame b is, block by block, the code of the block's last writer in (a, b] or a skip: again no pixel is decoded, nothing is
+ * re-quantised, and every code byte is one the range contained ------------------------------------------------------------------------
+ * Delta: WHOLE is KeyFrame's definition above.  Block i is WRITTEN in (a, b] when some frame f with a < f <= b codes it; a = -1 means
+ *       "from before the range".  Delta(a, b), -1 <= a < b < nframes = for blocks i = 0 .. nblocks-1 in table order:
+ *         - i is written: the L bytes of the whole code of its last writer <= b;
+ *         - i is not written and is a RUN HEAD (i = 0, or block i - 1 is written, or i % 1023 = 0): one skip word, bytes (count & 0xFF,
+ *           0x84 + (count >> 8)), count = the consecutive unwritten blocks from i on, stopping before the next written block, before
+ *           the next multiple of 1023 above i, and at nblocks: 1 <= count <= 1023;
+ *         - otherwise: nothing.
+ *       A skip word never crosses a block number that is a multiple of 1023 (the format's 10-bit count).  The frame always covers all
+ *       nblocks blocks.  A gap that writes nothing gives ceil(nblocks / 1023) skip words (shorter than the 16-bit decoder's early-out
+ *       threshold, which it takes); a gap that writes every block gives no skip word and is, from a = -1, byte for byte KeyFrame(b).
+ *   PROMISED: decoded as an inter frame on top of the picture of frame a (a = -1: the picture before the range, where one is defined)
+ *       the bytes give the picture of frame b on every pixel a block covers; jsp_is_key_frame is true exactly when every block is
+ *       written; len(Delta(a, b)) <= len(KeyFrame(b)) whenever both exist.  NOT promised: significance verdicts, per-row flags and
+ *       data_pnt of the thinned clip — the exclusions of KeyFrame.
+ *   REFUSED, as an error with nothing written: a written block whose last writer's code is not whole; the text names the pair, the
+ *       block and the writer frame — of the FIRST refusing (pair, block) in that order.  A block without a writer is skipped, never
+ *       refused.
+ *   n pairs (from[j], to[j]], n in 1 .. 4096, independent of each other; frame j = Delta(from[j], to[j]); the frames lie back to back in
+ *       `out`, HOST memory.  lens[j] and *total are set whenever every pair can be cut, also when `cap` is smaller than *total — that
+ *       is then an error with nothing written (`out` may be null when cap is 0); they are zeros after every other error.  Size `out` by
+ *       n * jsp_index_delta_bound (per frame nblocks * 18 for 16-bit, nblocks * 10 for 8-bit) or ask twice.
+ *   TWO kernel launches for a slice of pairs, grid.y = the pair, in the shape of KeyFrame's (msv1_index_delta_sizes_kernel,
+ *       msv1_index_delta_gather_kernel) — no workgroup waits for another.  A call runs in slices of pairs so that the scratch the index
+ *       owns stays bounded (per pair 8 bytes per block, 8 per workgroup, the frame at its bound; allocated by the first call, counted
+ *       by jsp_index_info): a sizes launch per slice first, so that statuses and lengths of ALL pairs are known before the first byte
+ *       reaches `out`, then sizes and gather per slice (a single slice: the gather alone).  Option "msv1_index_delta_slice" sets the
+ *       pairs per slice; the bytes do not depend on it.  Runs on the codec's stream and returns synchronised.  THE CODEC IS ONLY LENT.
+ *   ERRORS, each before anything is queued (jsp_last_error() starts with "index_delta:", but for the wrong codec kind's "index:
+ *       MSVideo1 only"), in this order: a null argument, the wrong codec kind, an index built by another codec, n outside 1 .. 4096, the
+ *       first bad pair (from < -1, to <= from, to >= nframes), a picture without a 4x4 block, an asynchronous frame in flight. */
+int jsp_index_delta_bound(const jsp_index* idx, size_t* bytes);
+int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap, size_t* lens,
+                           size_t* total);
 
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 

@@ -128,6 +128,9 @@ SIGNATURES = {
     "jsp_sp_index_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "jsp_index_key_frame_bound": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "jsp_index_key_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "jsp_index_delta_bound": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "jsp_index_delta_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "jsp_display_convert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "jsp_view_matrix": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -557,6 +557,7 @@ class _IndexTensor:
 
 
 ACTIVITY_MAX_RUN = 4096   # frames one jsp_index_activity / jsp_sp_index_activity call takes
+DELTA_ASK_TWICE = 64 << 20   # SeekIndex.DeltaFrames: above this many bytes of n frames at their bound, the lengths are asked for first
 
 
 class _IndexActivity:
@@ -612,7 +613,8 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     a run of frames, each into a buffer of its own (jsp_index_play), Present(frames, ...) one launch for the windows of any
     frames (jsp_index_present), Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_index_tensor),
     Activity(first, n) one launch for the changed pixels per frame and 16x16 cell of a run (jsp_index_activity; _IndexActivity),
-    KeyFrame(t) two launches for a key frame that decodes to frame t's picture, made of the codes the range holds (jsp_index_key_frame).
+    KeyFrame(t) two launches for a key frame that decodes to frame t's picture, made of the codes the range holds (jsp_index_key_frame),
+    DeltaFrames(pairs) inter frames that each span a gap (a, b] of the range, made of the same codes and skips (jsp_index_delta_frames).
     `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
@@ -709,6 +711,44 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
         self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
         self.device_bytes, self.host_bytes = dev.value, host.value
         return bytes(memoryview(buf)[:n.value])
+
+    def DeltaBound(self) -> int:
+        """The most bytes one frame of DeltaFrames has: 18 per 4x4 block of a 16-bit picture, 10 per block of an 8-bit one."""
+        self._open("index_delta_bound")
+        n = C.c_size_t(0)
+        if self._lib.jsp_index_delta_bound(self._h, C.byref(n)) != 0:
+            raise CodecError(N.last_error())
+        return n.value
+
+    def DeltaFrames(self, pairs) -> list:
+        """One inter frame per pair (a, b), -1 <= a < b < frames: decoded on top of the picture of frame a (-1: the picture before the
+        range) it gives the picture of frame b — for every block the code of its last writer in (a, b], else a skip; bytes the range
+        already contained, nothing decoded or re-quantised (jsp_index_delta_frames: two launches per slice of pairs, the codec not
+        touched).  IsKeyFrame of a frame is true exactly when its gap writes every block.  CodecError, naming the pair, the block and
+        the writer frame, when a written block's last code is cut off; nothing is returned then."""
+        codec = self._open("index_delta")
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        n = len(pairs)
+        frm = (C.c_int * max(n, 1))(*[a for a, _ in pairs])
+        to = (C.c_int * max(n, 1))(*[b for _, b in pairs])
+        lens = (C.c_size_t * max(n, 1))()
+        total = C.c_size_t(0)
+        cap = max(n, 1) * self.DeltaBound()
+        if cap > DELTA_ASK_TWICE:   # many large frames: the lengths first (cap 0 is the refusal that still sets them), then the bytes
+            if self._lib.jsp_index_delta_frames(codec._h, self._h, n, frm, to, None, 0, lens, C.byref(total)) == 0 or total.value == 0:
+                raise CodecError(N.last_error())
+            cap = total.value
+        buf = (C.c_uint8 * max(cap, 1))()
+        if self._lib.jsp_index_delta_frames(codec._h, self._h, n, frm, to, buf, len(buf), lens, C.byref(total)) != 0:
+            raise CodecError(N.last_error())
+        dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first call adds the scratch the frames are assembled in)
+        self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
+        self.device_bytes, self.host_bytes = dev.value, host.value
+        view, out, at = memoryview(buf), [], 0
+        for j in range(n):
+            out.append(bytes(view[at:at + lens[j]]))
+            at += lens[j]
+        return out
 
     def _open(self, who: str) -> _NativeCodec:
         if not self._h:

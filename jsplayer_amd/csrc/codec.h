@@ -92,6 +92,7 @@ struct jsp_codec {
     int seek_chunk_frames = 0;            // option "msv1_seek_chunk_frames": frames staged per chunk of a seek (0 = auto)
     int index_play_segments = 0;          // option "msv1_index_play_segments": segments of a jsp_index_play run (0 = auto)
     int index_activity_segments = 0;      // option "msv1_index_activity_segments": segments of a jsp_index_activity run (0 = auto)
+    int index_delta_slice = 0;            // option "msv1_index_delta_slice": pairs per slice of a jsp_index_delta_frames call (0 = auto)
     jsp::DeviceBuffer find_dev;           // jsp_find_change: first-hit word, judged rows and walk list of a chunk (device) ...
     jsp::PinnedBuffer find_host;          // ... and where the host builds them
 

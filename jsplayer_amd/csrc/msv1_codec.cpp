@@ -794,6 +794,14 @@ struct Msv1Codec : jsp_codec {
             index_activity_segments = (int)v;
             return 0;
         }
+        if (std::strcmp(key, "msv1_index_delta_slice") == 0) {   // jsp_index_delta_frames: pairs per slice ("auto": by a byte budget of scratch)
+            if (std::strcmp(value, "auto") == 0) { index_delta_slice = 0; return 0; }
+            char* end = nullptr;
+            const long v = std::strtol(value, &end, 10);
+            if (end == value || *end || v < 1 || v > 4096) return -1;
+            index_delta_slice = (int)v;
+            return 0;
+        }
         if (std::strcmp(key, "msv1_scrub_tables") == 0) {   // tests: a replay must rebuild every block table it reads
             opt_scrub_tables = std::strcmp(value, "1") == 0;
             return 0;

@@ -24,28 +24,15 @@
 // into the LDS array: LDS and global positions then agree modulo 16.  The image leaves in 16-byte pieces, whole pieces as one 16-byte
 // store; the first and the last piece, where the image covers only a part, 16 bits at a time (base is even, nothing more).  The last
 // workgroup writes the frame's length next to the status word.
-#include "msv1_block_io.h"
+#include "msv1_index_codes.h"
 
 namespace jsp {
 namespace {
 
-constexpr int WG = 256;
+constexpr int WG = INDEX_CODES_WG;
 constexpr int KF_LANE_BLOCKS = 4;
 constexpr int KF_WG_BLOCKS = MSV1_KEYFRAME_WG_BLOCKS;   // (msv1_seek.h: the host sizes totals[] by it)
 static_assert(KF_WG_BLOCKS == WG * KF_LANE_BLOCKS, "a lane owns KF_LANE_BLOCKS consecutive blocks");
-
-typedef const __attribute__((address_space(1))) uint16_t cgu16;
-typedef __attribute__((address_space(1))) uint16_t gu16;
-
-// The writer frame's chunk, and within it the offset of the code of block `blk` and the end of the frame's data.
-__device__ __forceinline__ Msv1IndexChunk keyframe_code(const Msv1IndexSrc& s, int f, int blk, int bits, uint32_t& o, uint32_t& e) {
-    const Msv1IndexChunk ch = s.chunks[s.frame_chunk[f]];
-    const int lf = f - (int)ch.first;
-    o = *(cgu32*)(ch.desc + (size_t)lf * s.pitch + blk);
-    const uint32_t end = ch.frames[lf].stream_end;
-    e = bits == 16 ? (end & ~1u) : end;
-    return ch;
-}
 
 template <int BITS>
 __global__ __launch_bounds__(WG) void msv1_index_keyframe_sizes_kernel(const Msv1IndexSrc s, int t, Msv1KeyFrameScratch k) {
@@ -65,51 +52,21 @@ __global__ __launch_bounds__(WG) void msv1_index_keyframe_sizes_kernel(const Msv
         if (m != 0u) {
             const int f = index_word_frame(w, m);
             uint32_t o, e;
-            const Msv1IndexChunk ch = keyframe_code(s, f, blk, BITS, o, e);
+            const Msv1IndexChunk ch = index_code_at(s, f, blk, BITS, o, e);
             frame[i] = (uint32_t)f;
-            kind = MSV1_KEYFRAME_CUT;
-            // (o + 4 cannot wrap: o and e are offsets into one allocation; o <= e - 2 is established first)
-            if (e >= 2u && o <= e - 2u) {
-                const uint32_t b = (uint32_t)*(cgu16*)(ch.stream + o) >> 8;
-                uint32_t L = 2u;
-                bool settled = true;
-                if (BITS == 16) {
-                    if (b < 0x80u) {
-                        settled = e >= 4u && o <= e - 4u;
-                        if (settled) L = (*(cgu16*)(ch.stream + o + 2u) & 0x8000u) ? 18u : 6u;
-                    }
-                } else {
-                    L = b < 0x80u ? 4u : (b >= 0x90u ? 10u : 2u);
-                }
-                if (settled && e >= L && o <= e - L) {
-                    len[i] = L;
-                    kind = 0xFFFFFFFFu;
-                }
-            }
+            len[i] = index_whole_length<BITS>(ch, o, e);
+            kind = len[i] != 0u ? 0xFFFFFFFFu : MSV1_KEYFRAME_CUT;
         }
         if (kind != 0xFFFFFFFFu) worst = min(worst, ((uint32_t)blk << 1) | kind);
     }
     if (worst != 0xFFFFFFFFu) atomicMin(k.status, worst);
 
-    // exclusive scan of the lengths over the workgroup: inclusive over the wave's lanes by shuffles, the waves' sums through LDS
+    // exclusive scan of the lengths over the workgroup
     uint32_t mine = 0u;
 #pragma unroll
     for (int i = 0; i < KF_LANE_BLOCKS; ++i) mine += len[i];
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t off = incl - mine, total = 0u;
-#pragma unroll
-    for (int v = 0; v < WG / 64; ++v) {
-        if (v < wave) off += s_wave[v];
-        total += s_wave[v];
-    }
+    uint32_t total;
+    uint32_t off = index_wg_scan(mine, s_wave, total);
 #pragma unroll
     for (int i = 0; i < KF_LANE_BLOCKS; ++i) {
         const int blk = blk0 + i;
@@ -127,18 +84,7 @@ __global__ __launch_bounds__(WG) void msv1_index_keyframe_gather_kernel(const Ms
     constexpr int IMAGE = KF_WG_BLOCKS * (BITS == 16 ? 18 : 10);                 // bytes of a workgroup's output at its bound
     __shared__ __attribute__((aligned(16))) uint16_t s_img[(IMAGE + 16) / 2];   // (+ 16: the image starts base % 16 bytes in)
     __shared__ uint32_t s_wave[WG / 64];
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-
-    // base: the bytes of the workgroups before this one
-    uint32_t sum = 0u;
-    for (int g = (int)threadIdx.x; g < (int)blockIdx.x; g += WG) sum += *(cgu32*)(k.totals + g);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) sum += (uint32_t)__shfl_xor((int)sum, d);
-    if (lane == 0) s_wave[wave] = sum;
-    __syncthreads();
-    size_t base = 0;
-#pragma unroll
-    for (int v = 0; v < WG / 64; ++v) base += s_wave[v];
+    const size_t base = index_wg_bytes_before(k.totals, (int)blockIdx.x, s_wave);   // the bytes of the workgroups before this one
     const uint32_t total = *(cgu32*)(k.totals + blockIdx.x);
     const uint32_t lo = (uint32_t)(base & 15), hi = lo + total;                  // the image is s_img bytes [lo, hi)
 
@@ -151,20 +97,12 @@ __global__ __launch_bounds__(WG) void msv1_index_keyframe_gather_kernel(const Ms
         const uint32_t L = ol & 0xFFu, at = lo + (ol >> 8);
         if (L == 0u || at + L > hi) continue;                                   // (a block with a status; the second test never holds)
         uint32_t o, e;
-        const Msv1IndexChunk ch = keyframe_code(s, (int)f, blk, BITS, o, e);
+        const Msv1IndexChunk ch = index_code_at(s, (int)f, blk, BITS, o, e);
         for (uint32_t b = 0; b < L; b += 2u) s_img[(at + b) >> 1] = *(cgu16*)(ch.stream + o + b);
     }
     __syncthreads();
 
-    uint8_t* dst = k.out + (base - lo);                                         // 16-byte aligned; piece c is dst[16 c, 16 c + 16)
-    for (uint32_t c = threadIdx.x; 16u * c < hi; c += WG) {
-        const uint32_t p0 = 16u * c;
-        if (p0 >= lo && p0 + 16u <= hi) {
-            *(gu32x4*)(dst + p0) = *reinterpret_cast<const u32x4*>(&s_img[p0 >> 1]);
-        } else {
-            for (uint32_t p = max(p0, lo); p < min(p0 + 16u, hi); p += 2u) *(gu16*)(dst + p) = s_img[p >> 1];
-        }
-    }
+    index_image_store(k.out + (base - lo), s_img, lo, hi);                       // (16-byte aligned; piece c is bytes [16 c, 16 c + 16))
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *(gu32*)(k.status + 1) = (uint32_t)base + total;
 }
 

@@ -35,15 +35,17 @@ struct jsp_index {
     DeviceBuffer d_play_dsts;              // ... the array the kernel reads (both grown on demand; nothing until the first call)
     DeviceBuffer d_key_frame;              // jsp_index_key_frame: status, workgroup totals, block records, the frame at its bound ...
     PinnedBuffer h_key_frame;              // ... and where the status, the length and a refused block's record arrive (both: first call)
+    DeviceBuffer d_delta;                  // jsp_index_delta_frames: one slice of pairs — their list, statuses, totals, records, frames ...
+    PinnedBuffer h_delta;                  // ... and the host's side of the list, the statuses and the totals (both: first call)
     uint64_t device_bytes() const {
         uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_frame_list.cap + d_play_dsts.cap +
-                     d_key_frame.cap;
+                     d_key_frame.cap + d_delta.cap;
         for (const auto& c : chunks) n += c->stream.cap + c->desc.cap + c->frames.cap;
         return n;
     }
     uint64_t host_bytes() const {
         return sizeof(*this) + chunks.size() * sizeof(Chunk) + significance.size() * sizeof(int) + reported.size() + block_changes.size() +
-               h_frame_list.cap + h_play_dsts.cap + h_key_frame.cap;
+               h_frame_list.cap + h_play_dsts.cap + h_key_frame.cap + h_delta.cap;
     }
 };
 
@@ -857,6 +859,135 @@ extern "C" int jsp_index_key_frame(jsp_codec* c, jsp_index* idx, int t, uint8_t*
         JSP_HIP(hipStreamSynchronize(c->stream));
         return JSP_ZERO_STATE;
     } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- inter frames that span a gap: a clip thinned to every s-th frame, or without its idle frames, needs frames that exist in no
+// file.  The inter frame from the picture of frame a to the picture of frame b is, block by block, the code of the block's last
+// writer in (a, b] or a skip (the rule: msv1_index_delta_kernels.hip).  n pairs a call, in slices of pairs so that the scratch stays
+// bounded: a sizes launch per slice first — statuses and lengths of ALL pairs are known before a byte reaches `out` — then a sizes
+// and a gather launch per slice (one slice: its records are still there, the gather alone).  Into HOST memory; the codec is only lent.
+namespace {
+constexpr uint64_t kDeltaSliceBudget = 64ull << 20;   // option "msv1_index_delta_slice" = "auto": the pairs whose scratch this holds
+
+// The parts of d_delta for slices of S pairs, each 16-byte aligned; h_delta has the first four at the same offsets.
+struct DeltaLayout {
+    size_t pairs_at, bases_at, status_at, totals_at, first_at, records_at, out_at, bytes;
+};
+DeltaLayout delta_layout(size_t S, size_t nblocks, size_t nwg, size_t bound) {
+    const auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    DeltaLayout l{};
+    l.pairs_at = 0;
+    l.bases_at = l.pairs_at + up16(2 * sizeof(int32_t) * S);
+    l.status_at = l.bases_at + up16(sizeof(uint64_t) * S);
+    l.totals_at = l.status_at + up16(sizeof(uint32_t) * S);
+    l.first_at = l.totals_at + up16(sizeof(uint32_t) * S * nwg);
+    l.records_at = l.first_at + up16(sizeof(uint32_t) * S * nwg);
+    l.out_at = l.records_at + up16(2 * sizeof(uint32_t) * S * nblocks);
+    l.bytes = l.out_at + S * bound;
+    return l;
+}
+}  // namespace
+
+extern "C" int jsp_index_delta_bound(const jsp_index* idx, size_t* bytes) {
+    if (!idx || !bytes) return fail("index_delta: null argument");
+    *bytes = (size_t)std::max(idx->geo.nblocks, 0) * (idx->geo.bits == 16 ? 18u : 10u);
+    return JSP_ZERO_STATE;
+}
+
+extern "C" int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap, size_t* lens,
+                                      size_t* total) {
+    const char* who = "index_delta";
+    if (total) *total = 0;
+    if (lens && n >= 1 && n <= 4096) std::fill(lens, lens + n, (size_t)0);
+    if (!c || !idx || !from || !to || !lens || !total || (!out && cap)) return fail("index_delta: null argument");
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_delta: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("index_delta: n is outside 1..4096");
+    for (int j = 0; j < n; ++j)
+        if (from[j] < -1 || to[j] <= from[j] || to[j] >= idx->nframes) {
+            set_error("index_delta: pair %d (%d, %d] is not a gap of the index (-1 <= from < to < %d frames)", j, from[j], to[j], idx->nframes);
+            return JSP_ERROR_OCCURED;
+        }
+    const Msv1IndexSrc& src = idx->src;
+    if (src.nblocks < 1) return fail("index_delta: the picture has no 4x4 block");
+    if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        const size_t nblocks = (size_t)src.nblocks, nwg = (size_t)msv1_keyframe_workgroups(src.nblocks);
+        const size_t bound = nblocks * (src.bits == 16 ? 18u : 10u);
+        size_t S = (size_t)c->index_delta_slice;
+        if (S == 0) S = std::clamp<uint64_t>(kDeltaSliceBudget / delta_layout(1, nblocks, nwg, bound).bytes, 1, 4096);
+        S = std::min(S, (size_t)n);
+        const DeltaLayout l = delta_layout(S, nblocks, nwg, bound);
+        idx->d_delta.reserve(l.bytes);
+        idx->h_delta.reserve(l.first_at + 16);
+        uint8_t* d = idx->d_delta.as<uint8_t>();
+        uint8_t* h = idx->h_delta.as<uint8_t>();
+        const Msv1DeltaScratch k{reinterpret_cast<const int32_t*>(d + l.pairs_at), reinterpret_cast<const uint64_t*>(d + l.bases_at),
+                                 reinterpret_cast<uint32_t*>(d + l.status_at),     reinterpret_cast<uint32_t*>(d + l.totals_at),
+                                 reinterpret_cast<uint32_t*>(d + l.first_at),      reinterpret_cast<uint32_t*>(d + l.records_at),
+                                 d + l.out_at};
+        std::vector<size_t> length((size_t)n, 0);
+        // pairs [j0, j0 + m) and where their frames start go to the device, then the sizes launch (not when the records are there)
+        const auto sizes = [&](size_t j0, size_t m, bool launch) {
+            int32_t* hp = reinterpret_cast<int32_t*>(h + l.pairs_at);
+            uint64_t* hb = reinterpret_cast<uint64_t*>(h + l.bases_at);
+            uint64_t at = 0;
+            for (size_t i = 0; i < m; ++i) {
+                hp[2 * i] = from[j0 + i];
+                hp[2 * i + 1] = to[j0 + i];
+                hb[i] = at;
+                at += length[j0 + i];
+            }
+            JSP_HIP(hipMemcpyAsync(d, h, l.status_at, hipMemcpyHostToDevice, c->stream));
+            if (!launch) return;
+            JSP_HIP(hipMemsetAsync(k.status, 0xFF, sizeof(uint32_t) * m, c->stream));
+            msv1_launch_index_delta_sizes(src, (int)m, k, c->stream);
+            JSP_HIP(hipGetLastError());
+        };
+        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
+            const size_t m = std::min(S, (size_t)n - j0);
+            sizes(j0, m, true);
+            JSP_HIP(hipMemcpyAsync(h + l.status_at, d + l.status_at, l.first_at - l.status_at, hipMemcpyDeviceToHost, c->stream));
+            JSP_HIP(hipStreamSynchronize(c->stream));
+            const uint32_t* status = reinterpret_cast<const uint32_t*>(h + l.status_at);
+            const uint32_t* totals = reinterpret_cast<const uint32_t*>(h + l.totals_at);
+            for (size_t i = 0; i < m; ++i) {
+                if (status[i] != 0xFFFFFFFFu) {   // not cuttable: the first pair, and its first block, that says so, and the block's writer
+                    uint32_t* writer = reinterpret_cast<uint32_t*>(h + l.first_at);
+                    JSP_HIP(hipMemcpyAsync(writer, k.records + 2 * (i * nblocks + status[i]), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                    JSP_HIP(hipStreamSynchronize(c->stream));
+                    set_error("index_delta: pair %d (%d, %d]: the code of block %u in frame %u, its last writer, is cut off by the end of the frame's data",
+                              (int)(j0 + i), from[j0 + i], to[j0 + i], status[i], *writer);
+                    return JSP_ERROR_OCCURED;
+                }
+                for (size_t g = 0; g < nwg; ++g) length[j0 + i] += totals[i * nwg + g];
+                if (length[j0 + i] > bound) throw std::runtime_error("index_delta: a frame is longer than its bound");
+            }
+        }
+        size_t sum = 0;
+        for (int j = 0; j < n; ++j) sum += (lens[j] = length[(size_t)j]);
+        *total = sum;
+        if (cap < sum) return fail("index_delta: cap is smaller than the frames (*total has their length, lens[] each frame's)");
+        size_t at = 0;
+        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
+            const size_t m = std::min(S, (size_t)n - j0);
+            sizes(j0, m, S < (size_t)n);
+            msv1_launch_index_delta_gather(src, (int)m, k, c->stream);
+            JSP_HIP(hipGetLastError());
+            size_t bytes = 0;
+            for (size_t i = 0; i < m; ++i) bytes += length[j0 + i];
+            JSP_HIP(hipMemcpyAsync(out + at, k.out, bytes, hipMemcpyDeviceToHost, c->stream));
+            JSP_HIP(hipStreamSynchronize(c->stream));
+            at += bytes;
+        }
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        std::fill(lens, lens + n, (size_t)0);
+        *total = 0;
         set_error("%s", e.what());
         return JSP_ERROR_OCCURED;
     }

@@ -130,4 +130,25 @@ inline int msv1_keyframe_workgroups(int nblocks) { return (nblocks + MSV1_KEYFRA
 // then not a key frame.  Nothing for an index without a block.
 void msv1_launch_index_keyframe(const Msv1IndexSrc& src, int t, const Msv1KeyFrameScratch& k, hipStream_t stream);
 
+// The device scratch of jsp_index_delta_frames for one slice of pairs (the index owns it; every part 16-byte aligned).  nwg =
+// msv1_keyframe_workgroups(nblocks): the two kernels keep the key frame's shape, a workgroup owns MSV1_KEYFRAME_WG_BLOCKS blocks.
+struct Msv1DeltaScratch {
+    const int32_t* pairs;            // per pair: from (-1: before the range), to
+    const uint64_t* bases;           // per pair: where its frame starts in `out` (even; read by the gather only)
+    uint32_t* status;                // per pair: all ones, else the first written block whose last writer's code is cut off
+    uint32_t* totals;                // per pair and workgroup (pair * nwg + g): the bytes of its codes and skip words
+    uint32_t* first_written;         // per pair and workgroup: its first written block, MSV1_DELTA_NONE when it has none
+    uint32_t* records;               // per pair and block ((pair * nblocks + blk) * 2): writer frame, (offset within its workgroup's
+                                     // bytes << 8 | L); L = code length, MSV1_DELTA_SKIP for a run head, 0 for nothing (or a status)
+    uint8_t* out;                    // the slice's frames back to back, room for npairs * the bound
+};
+constexpr uint32_t MSV1_DELTA_NONE = 0xFFFFFFFFu;
+constexpr uint32_t MSV1_DELTA_SKIP = 1u;           // (odd: no code has this length)
+constexpr int MSV1_DELTA_RUN = 1023;               // a skip word's count is 10 bits: no skip word crosses a multiple of this
+// ONE launch each (msv1_index_delta_kernels.hip, which states the rule), grid.y = the pair.  Sizes: status (all ones from the
+// caller), totals, first_written and records of npairs pairs.  Gather, after a sizes launch over the same pairs with no status
+// raised and with bases[] = the running sums of the pairs' lengths: the frames into d.out.  Nothing for an index without a block.
+void msv1_launch_index_delta_sizes(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, hipStream_t stream);
+void msv1_launch_index_delta_gather(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, hipStream_t stream);
+
 }  // namespace jsp

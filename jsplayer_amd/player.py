@@ -18,7 +18,8 @@ shown — ScreenPressor's, `ADOPTS` false — serves the frame and leaves the de
 index, one `Play` launch per batch of free buffers; `preview` / `filmstrip` are the seek bar's small pictures, one
 `Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex); `activity` / `change_totals` / `change_box` /
 `next_change` say where and when the picture changes, from the index's `Activity` map (changed pixels per frame and 16x16 cell);
-`cut` / `write_cut` give the clip from any frame on as frames and flags / as an AVI file, its first frame the index's `KeyFrame`.  `View` is the zoom / scroll / fit state of Main
+`cut` / `write_cut` give the clip from any frame on as frames and flags / as an AVI file, its first frame the index's `KeyFrame`;
+`thin` / `write_thin` the clip made of any ascending list of frames, the gaps spanned by the index's `DeltaFrames`.  `View` is the zoom / scroll / fit state of Main
 (Main.hx:288-319, 1186-1278) and `Manager.present` draws the window it shows of a frame buffer, one launch.  Timers, bitmaps and audio
 of the reference's Manager are not rebuilt.
 """
@@ -288,6 +289,60 @@ class Manager:
         fourcc CRAM for MSVideo1 and SCPR for ScreenPressor."""
         from .avi import write_avi
         out, flags = self.cut(frames, first, last, key_flags)
+        fourcc = b"SCPR" if self.vi.codec == CODEC_SCREENPRESSOR else b"CRAM"
+        return write_avi(self.vi.X, self.vi.Y, out, fourcc=fourcc, bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
+
+    # -- a clip thinned to the frames worth keeping: the attached index's DeltaFrames (jsp_index_delta_frames) -----------------------------
+    def thin(self, frames: Sequence[bytes], keep: Sequence[int], key_flags: Optional[Sequence[bool]] = None):
+        """The clip's frames `keep` (strictly ascending frame numbers) as a clip of its own: (list of frame bytes, key flags) — a
+        time-lapse (every s-th frame), a recording without its idle frames (`change_totals`), any list.  Entry 0 follows `cut`: the
+        frame itself where it is a key frame, else index.KeyFrame.  A later entry that is a key frame of the clip is copied; one
+        that follows its predecessor directly (keep[k] == keep[k - 1] + 1) is the caller's own object; every other one is
+        index.DeltaFrames' inter frame from the picture of keep[k - 1] to the picture of keep[k], all of them from ONE call.
+        Flags: True for entry 0 and the copied key frames, else the decoder's IsKeyFrame of the bytes.  Nothing is decoded and
+        neither decoder nor buffers change; a gap the index cannot span raises its CodecError.  ValueError: `keep` empty, not
+        strictly ascending or outside the clip; where the index is needed, none attached, a frame outside it, or an index object
+        without `KeyFrame` / `DeltaFrames` (ScreenPressor's)."""
+        keep = [int(k) for k in keep]
+        if not keep:
+            raise ValueError("thin: keep is empty")
+        for k in keep:
+            if not 0 <= k < len(frames):
+                raise ValueError(f"thin: frame {k} is not in the clip")
+        for prev, k in zip(keep, keep[1:]):
+            if k <= prev:
+                raise ValueError(f"thin: keep is not strictly ascending ({k} after {prev})")
+        is_key = [self._key_at(frames, k, key_flags) for k in keep]
+        gaps = [j for j in range(1, len(keep)) if not is_key[j] and keep[j] != keep[j - 1] + 1]
+        need_key = not is_key[0]
+        if need_key or gaps:
+            if self.index is None:
+                raise ValueError("thin: no seek index is attached")
+            wanted = ([keep[0]] if need_key else []) + [keep[j] for j in gaps]
+            for k in wanted:
+                if not self._in_index(k):
+                    raise ValueError(f"thin: frame {k} is not in the attached seek index")
+            for j in gaps:   # (the gap may start on the frame before the index: its picture is the one before the range)
+                if keep[j - 1] < self.index_first - 1:
+                    raise ValueError(f"thin: frame {keep[j - 1]} is not in the attached seek index")
+            if need_key and not hasattr(self.index, "KeyFrame"):
+                raise ValueError("thin: the attached seek index cannot make a key frame")
+            if gaps and not hasattr(self.index, "DeltaFrames"):
+                raise ValueError("thin: the attached seek index cannot span a gap")
+        out = [frames[k] for k in keep]
+        if need_key:
+            out[0] = self.index.KeyFrame(keep[0] - self.index_first)
+        if gaps:
+            made = self.index.DeltaFrames([(keep[j - 1] - self.index_first, keep[j] - self.index_first) for j in gaps])
+            for j, data in zip(gaps, made):
+                out[j] = data
+        flags = [True] + [True if is_key[j] else bool(self.decoder.IsKeyFrame(out[j])) for j in range(1, len(keep))]
+        return out, flags
+
+    def write_thin(self, frames: Sequence[bytes], keep: Sequence[int], key_flags: Optional[Sequence[bool]] = None, fps: float = 15.0) -> bytes:
+        """`thin` as an AVI file (avi.write_avi) with this Manager's stream, as `write_cut` writes `cut`."""
+        from .avi import write_avi
+        out, flags = self.thin(frames, keep, key_flags)
         fourcc = b"SCPR" if self.vi.codec == CODEC_SCREENPRESSOR else b"CRAM"
         return write_avi(self.vi.X, self.vi.Y, out, fourcc=fourcc, bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
 
