@@ -53,6 +53,10 @@
 //                                jsp_index_delta_frames call.  Then OUT.avi is played back through the ordinary decode loop: prints
 //                                "<frame of the clip> <crc32 from OUT.avi> <crc32 from the clip>" per frame kept and exits with 1 on any
 //                                difference
+//   jsp_play clip.avi --thin-tight FIRST[:COUNT[:STRIDE]] OUT.avi
+//                                --thin with jsp_index_tight_frames in place of jsp_index_delta_frames: a block that a gap codes but
+//                                whose pixels it does not change is dropped from the gap's frame.  The same playback, CRC check and
+//                                exit status; OUT.avi is never longer than --thin's
 //   jsp_play clip.avi --filmstrip N[:scale]
 //                                ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build), then ONE
 //                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
@@ -535,6 +539,7 @@ int main(int argc, char** argv) {
     long act_first = -1, act_count = -1;                      // --activity [FIRST[:COUNT]]: the activity map of a seek index over the clip
     long cut_first = -1, cut_count = -1;                      // --cut FIRST[:COUNT] OUT.avi: the clip from frame FIRST on as a file of its own
     std::string cut_path;
+    bool thin_tight = false;   // --thin-tight: --thin with jsp_index_tight_frames
     long thin_first = -1, thin_count = -1, thin_stride = 8;   // --thin FIRST[:COUNT[:STRIDE]] OUT.avi: every STRIDE-th frame as a file of its own
     std::string thin_path;
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
@@ -578,7 +583,8 @@ int main(int argc, char** argv) {
             cut_path = argv[++a];
             if (cut_first < 0 || (colon != std::string::npos && cut_count < 1)) { std::fprintf(stderr, "--cut FIRST[:COUNT] OUT.avi: FIRST >= 0, COUNT >= 1\n"); return 2; }
         }
-        else if (o == "--thin" && a + 2 < argc) {
+        else if ((o == "--thin" || o == "--thin-tight") && a + 2 < argc) {
+            thin_tight = o == "--thin-tight";
             const std::string v = argv[++a];
             const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
             thin_first = std::atol(v.substr(0, c1).c_str());
@@ -586,7 +592,7 @@ int main(int argc, char** argv) {
             if (c2 != std::string::npos) thin_stride = std::atol(v.substr(c2 + 1).c_str());
             thin_path = argv[++a];
             if (thin_first < 0 || (c1 != std::string::npos && thin_count < 1) || thin_stride < 1) {
-                std::fprintf(stderr, "--thin FIRST[:COUNT[:STRIDE]] OUT.avi: FIRST >= 0, COUNT >= 1, STRIDE >= 1\n");
+                std::fprintf(stderr, "%s FIRST[:COUNT[:STRIDE]] OUT.avi: FIRST >= 0, COUNT >= 1, STRIDE >= 1\n", o.c_str());
                 return 2;
             }
         }
@@ -1068,7 +1074,7 @@ int main(int argc, char** argv) {
         }
         return rc;
     }
-    if (thin_first >= 0) {   // a time-lapse: one index build from the key frame before, ONE jsp_index_delta_frames for every gap, the file, its playback
+    if (thin_first >= 0) {   // a time-lapse: one index build from the key frame before, ONE jsp_index_delta_frames (--thin-tight: jsp_index_tight_frames) for every gap, the file, its playback
         const size_t n = clip.frames.size();
         std::vector<size_t> keep;
         for (long i = thin_first; i < (long)n && (thin_count < 0 || (long)keep.size() < thin_count); i += thin_stride) keep.push_back((size_t)i);
@@ -1076,6 +1082,8 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--thin: frames %ld, %ld, ... (%ld of them) are not all in the clip (%zu frames)\n", thin_first, thin_first + thin_stride, thin_count, n);
             rc = 1;
         }
+        const auto gap_frames = thin_tight ? jsp_index_tight_frames : jsp_index_delta_frames;
+        const char* gap_name = thin_tight ? "jsp_index_tight_frames" : "jsp_index_delta_frames";
         std::vector<uint8_t> key_frame, deltas;
         std::vector<size_t> gaps, delta_lens;                   // entries of `keep` that are inter frames over a gap, and their lengths
         for (size_t j = 1; rc == 0 && j < keep.size(); ++j)
@@ -1114,15 +1122,15 @@ int main(int argc, char** argv) {
                 std::vector<size_t> ls(m);
                 size_t total = 0;
                 // asked twice: the lengths (cap 0 is a refusal that still sets them), then the bytes
-                if (jsp_index_delta_frames(dec, idx, (int)m, from.data(), to.data(), nullptr, 0, ls.data(), &total) == JSP_ZERO_STATE || total == 0) {
-                    std::fprintf(stderr, "jsp_index_delta_frames: %s\n", jsp_last_error());
+                if (gap_frames(dec, idx, (int)m, from.data(), to.data(), nullptr, 0, ls.data(), &total) == JSP_ZERO_STATE || total == 0) {
+                    std::fprintf(stderr, "%s: %s\n", gap_name, jsp_last_error());
                     rc = 1;
                     break;
                 }
                 const size_t at = deltas.size();
                 deltas.resize(at + total);
-                if (jsp_index_delta_frames(dec, idx, (int)m, from.data(), to.data(), deltas.data() + at, total, ls.data(), &total) != JSP_ZERO_STATE) {
-                    std::fprintf(stderr, "jsp_index_delta_frames: %s\n", jsp_last_error());
+                if (gap_frames(dec, idx, (int)m, from.data(), to.data(), deltas.data() + at, total, ls.data(), &total) != JSP_ZERO_STATE) {
+                    std::fprintf(stderr, "%s: %s\n", gap_name, jsp_last_error());
                     rc = 1;
                 }
                 delta_lens.insert(delta_lens.end(), ls.begin(), ls.end());

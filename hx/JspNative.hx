@@ -76,6 +76,9 @@ extern class JspNative {
     @:native("jsp_index_delta_frames") static function indexDeltaFrames(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, n:Int, from:RawConstPointer<Int>,
                                                                         to:RawConstPointer<Int>, out:RawPointer<UInt8>, cap:SizeT,
                                                                         lens:RawPointer<SizeT>, total:RawPointer<SizeT>):Int;
+    @:native("jsp_index_tight_frames") static function indexTightFrames(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, n:Int, from:RawConstPointer<Int>,
+                                                                        to:RawConstPointer<Int>, out:RawPointer<UInt8>, cap:SizeT,
+                                                                        lens:RawPointer<SizeT>, total:RawPointer<SizeT>):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)

@@ -754,6 +754,34 @@ int jsp_index_delta_bound(const jsp_index* idx, size_t* bytes);
 int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap, size_t* lens,
                            size_t* total);
 
+/* ---- the same inter frames, tight: a block that the gap codes but whose pixels it does not change is dropped.  A gap that spans a key
+ * frame of the clip writes every block, a picture that returns to an earlier state (a blinking cursor, A -> B -> A) is coded again in
+ * full, an encoder may recode a block with what it already shows: Delta carries all of those, Tight carries none --------------------
+ * Tight: WHOLE, WRITTEN, RUN HEAD, the skip word and the 1023 rule are Delta's.  P(t)[i] is the 16 frame-buffer words that the last
+ *       frame <= t coding block i makes of it (a code that a frame's end cuts off is decoded as the decoder decodes it), else the block
+ *       of the picture before the range; P(a)[i] is DEFINED when one of the two exists (for a = -1 only the picture before the range
+ *       can define it).  Block i is KEPT in (a, b] when it is written in (a, b] and either P(a)[i] is not defined or P(b)[i] differs
+ *       from P(a)[i] in at least one of the 16 words; every other block — unwritten, or written but unchanged — is DROPPED.  Pixels are
+ *       compared as the 32-bit words a frame buffer holds: two 8-bit palette indices of one colour are equal, and so are different
+ *       code bytes that decode alike.  Tight(a, b) is Delta's rule with "written" replaced by "kept" everywhere: in the codes, in the
+ *       run-head test (is block i - 1 kept?) and in the counts.
+ *   PROMISED: decoded as an inter frame on top of the picture of frame a the bytes give the picture of frame b on every pixel a block
+ *       covers; jsp_is_key_frame is true exactly when every block is kept; len(Tight(a, b)) <= len(Delta(a, b)) whenever both exist
+ *       (a dropped block removes L >= 2 bytes and adds at most one skip word); Tight(a, b) == Delta(a, b) when nothing is dropped, in
+ *       particular for a = -1 on a range with no picture before it; a gap across which no pixel of any block changed gives exactly
+ *       ceil(nblocks / 1023) skip words.  NOT promised: the exclusions of KeyFrame and Delta.
+ *   REFUSED, as an error with nothing written: a KEPT block whose last writer's code is not whole; the text is Delta's with the prefix
+ *       "index_tight:" and names the FIRST refusing (pair, block) in that order.  A dropped block never refuses, even when its
+ *       writer's code is cut off: its pixels were defined and equal, and none of its bytes are used.
+ *   Everything else is jsp_index_delta_frames', word for word: n pairs in 1 .. 4096, `out` in HOST memory, lens[] and *total set when
+ *       only `cap` is short, zeros and nothing written after every other error, jsp_index_delta_bound, the index's scratch (shared
+ *       with Delta's), option "msv1_index_delta_slice" (the bytes do not depend on it), synchronised on return, THE CODEC ONLY LENT.
+ *       Two launches per slice as well: the sizes launch is msv1_index_delta_sizes_kernel's TIGHT form, which decodes both ends of the
+ *       gap of every written block and compares them; the gather launch is Delta's.
+ *   ERRORS: Delta's, in Delta's order, jsp_last_error() starting with "index_tight:". */
+int jsp_index_tight_frames(jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap, size_t* lens,
+                           size_t* total);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

@@ -614,7 +614,8 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     frames (jsp_index_present), Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_index_tensor),
     Activity(first, n) one launch for the changed pixels per frame and 16x16 cell of a run (jsp_index_activity; _IndexActivity),
     KeyFrame(t) two launches for a key frame that decodes to frame t's picture, made of the codes the range holds (jsp_index_key_frame),
-    DeltaFrames(pairs) inter frames that each span a gap (a, b] of the range, made of the same codes and skips (jsp_index_delta_frames).
+    DeltaFrames(pairs) inter frames that each span a gap (a, b] of the range, made of the same codes and skips (jsp_index_delta_frames);
+    with tight=True without the blocks whose pixels the gap did not change (jsp_index_tight_frames).
     `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
@@ -720,13 +721,17 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
             raise CodecError(N.last_error())
         return n.value
 
-    def DeltaFrames(self, pairs) -> list:
+    def DeltaFrames(self, pairs, tight: bool = False) -> list:
         """One inter frame per pair (a, b), -1 <= a < b < frames: decoded on top of the picture of frame a (-1: the picture before the
         range) it gives the picture of frame b — for every block the code of its last writer in (a, b], else a skip; bytes the range
         already contained, nothing decoded or re-quantised (jsp_index_delta_frames: two launches per slice of pairs, the codec not
         touched).  IsKeyFrame of a frame is true exactly when its gap writes every block.  CodecError, naming the pair, the block and
-        the writer frame, when a written block's last code is cut off; nothing is returned then."""
-        codec = self._open("index_delta")
+        the writer frame, when a written block's last code is cut off; nothing is returned then.
+        tight: a block the gap codes but whose 16 pixels are the same before and after it is dropped as well (jsp_index_tight_frames:
+        the sizes launch decodes both ends of the gap and compares them) — frames never longer than without it, the same pictures;
+        "written" above then reads "kept", and a dropped block's cut code refuses nothing."""
+        codec = self._open("index_tight" if tight else "index_delta")
+        call = self._lib.jsp_index_tight_frames if tight else self._lib.jsp_index_delta_frames
         pairs = [(int(a), int(b)) for a, b in pairs]
         n = len(pairs)
         frm = (C.c_int * max(n, 1))(*[a for a, _ in pairs])
@@ -735,11 +740,11 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
         total = C.c_size_t(0)
         cap = max(n, 1) * self.DeltaBound()
         if cap > DELTA_ASK_TWICE:   # many large frames: the lengths first (cap 0 is the refusal that still sets them), then the bytes
-            if self._lib.jsp_index_delta_frames(codec._h, self._h, n, frm, to, None, 0, lens, C.byref(total)) == 0 or total.value == 0:
+            if call(codec._h, self._h, n, frm, to, None, 0, lens, C.byref(total)) == 0 or total.value == 0:
                 raise CodecError(N.last_error())
             cap = total.value
         buf = (C.c_uint8 * max(cap, 1))()
-        if self._lib.jsp_index_delta_frames(codec._h, self._h, n, frm, to, buf, len(buf), lens, C.byref(total)) != 0:
+        if call(codec._h, self._h, n, frm, to, buf, len(buf), lens, C.byref(total)) != 0:
             raise CodecError(N.last_error())
         dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first call adds the scratch the frames are assembled in)
         self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))

@@ -27,6 +27,16 @@
 // LDS image and leave in 16-byte pieces, as in the key frame's gather.  The count of a run head: the next written block from an LDS
 // bitmask of the workgroup's records, beyond the workgroup from first_written of the next two workgroups (1022 blocks ahead never
 // reach further), clipped by the multiple of 1023 and by nblocks.
+//
+// THE TIGHT RULE (jsp_index_tight_frames; the sizes kernel's TIGHT form, the gather kernel as it is).  P(t)[i] is index_block's: the
+// 16 frame-buffer words that the last frame <= t coding block i makes of it (a code that the frame's end cuts off decoded by
+// decode_at's rule), else the block of the picture before the index; P(a)[i] is DEFINED when one of the two exists (a = -1: only the
+// picture before the index can define it).  Block i is KEPT in (a, b] when it is written in (a, b] and P(a)[i] is not defined or
+// differs from P(b)[i] in at least one of the 16 words; every other block is DROPPED.  Tight(a, b) is Delta(a, b) with "written"
+// replaced by "kept" everywhere — codes, run heads (is block i - 1 kept?), counts — and only a KEPT block whose last writer's code is
+// not whole refuses: no byte of a dropped block is used.  Words are compared as a frame buffer holds them: two palette indices of
+// one colour are equal, and so are different code bytes that decode alike.  The sizes kernel takes a lane's blocks one after the
+// other, 2 x 16 pixel registers at a time; records, totals and first_written then say "kept" where they said "written".
 #include "msv1_index_codes.h"
 
 namespace jsp {
@@ -47,8 +57,33 @@ __device__ __forceinline__ bool delta_written(const Msv1IndexSrc& s, int blk, in
     return f > a;
 }
 
+// THE TIGHT RULE's test of block `blk`, written in (a, b] by frame f: false (dropped) when P(a) is defined and equals P(b).
 template <int BITS>
+__device__ __forceinline__ bool tight_kept(const Msv1IndexSrc& s, int blk, int a, int f, const uint32_t* s_pal) {
+    uint32_t pa[16], pb[16];
+    int w;
+    const uint32_t m = a >= 0 ? index_last_writer(s, blk, a, w) : 0u;
+    if (m != 0u) {
+        index_decode<BITS>(s, index_word_frame(w, m), blk, s_pal, pa);
+    } else if (s.before != nullptr) {
+        const uint32_t* p = s.before + (size_t)(blk / s.nbx) * 4u * (size_t)s.X + (size_t)(blk % s.nbx) * 4u;
+        if (s.before_vec) load_block<true>(p, s.X, pa);
+        else load_block<false>(p, s.X, pa);
+    } else {
+        return true;
+    }
+    index_decode<BITS>(s, f, blk, s_pal, pb);
+    uint32_t diff = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) diff |= pa[k] ^ pb[k];
+    return diff != 0u;
+}
+
+// TIGHT = false is jsp_index_delta_frames' kernel; TIGHT = true applies THE TIGHT RULE: `written` below then reads "kept".
+template <int BITS, bool TIGHT>
 __global__ __launch_bounds__(WG) void msv1_index_delta_sizes_kernel(const Msv1IndexSrc s, Msv1DeltaScratch d) {
+    __shared__ uint32_t s_pal[TIGHT && BITS == 8 ? 256 : 1];
+    if (TIGHT) load_palette<BITS>(s_pal, s.palette);
     __shared__ uint32_t s_wave[WG / 64];
     __shared__ uint32_t s_first[WG / 64];
     __shared__ uint8_t s_last[WG];                       // per lane: its last block is written
@@ -67,6 +102,7 @@ __global__ __launch_bounds__(WG) void msv1_index_delta_sizes_kernel(const Msv1In
         if (blk >= s.nblocks) continue;
         int f;
         if (!delta_written(s, blk, a, b, f)) continue;
+        if (TIGHT && !tight_kept<BITS>(s, blk, a, f, s_pal)) continue;
         written[i] = true;
         first = min(first, (uint32_t)blk);
         uint32_t o, e;
@@ -82,7 +118,7 @@ __global__ __launch_bounds__(WG) void msv1_index_delta_sizes_kernel(const Msv1In
     bool before = true;                                  // (block 0 is a run head: as if a written block stood before it)
     if (threadIdx.x == 0 && blk0 > 0 && blk0 < s.nblocks) {
         int f;
-        before = delta_written(s, blk0 - 1, a, b, f);
+        before = delta_written(s, blk0 - 1, a, b, f) && (!TIGHT || tight_kept<BITS>(s, blk0 - 1, a, f, s_pal));
     }
     __syncthreads();
     if (threadIdx.x > 0) before = s_last[threadIdx.x - 1] != 0;
@@ -181,11 +217,17 @@ __global__ __launch_bounds__(WG) void msv1_index_delta_gather_kernel(const Msv1I
 
 }  // namespace
 
-void msv1_launch_index_delta_sizes(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, hipStream_t stream) {
+void msv1_launch_index_delta_sizes(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, bool tight, hipStream_t stream) {
     if (src.nblocks <= 0 || npairs <= 0) return;
     const dim3 grid((unsigned)msv1_keyframe_workgroups(src.nblocks), (unsigned)npairs);
-    if (src.bits == 16) hipLaunchKernelGGL(msv1_index_delta_sizes_kernel<16>, grid, dim3(WG), 0, stream, src, d);
-    else hipLaunchKernelGGL(msv1_index_delta_sizes_kernel<8>, grid, dim3(WG), 0, stream, src, d);
+    if (tight) {
+        if (src.bits == 16) hipLaunchKernelGGL((msv1_index_delta_sizes_kernel<16, true>), grid, dim3(WG), 0, stream, src, d);
+        else hipLaunchKernelGGL((msv1_index_delta_sizes_kernel<8, true>), grid, dim3(WG), 0, stream, src, d);
+    } else if (src.bits == 16) {
+        hipLaunchKernelGGL((msv1_index_delta_sizes_kernel<16, false>), grid, dim3(WG), 0, stream, src, d);
+    } else {
+        hipLaunchKernelGGL((msv1_index_delta_sizes_kernel<8, false>), grid, dim3(WG), 0, stream, src, d);
+    }
 }
 
 void msv1_launch_index_delta_gather(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, hipStream_t stream) {

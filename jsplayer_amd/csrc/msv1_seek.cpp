@@ -897,22 +897,24 @@ extern "C" int jsp_index_delta_bound(const jsp_index* idx, size_t* bytes) {
     return JSP_ZERO_STATE;
 }
 
-extern "C" int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap, size_t* lens,
-                                      size_t* total) {
-    const char* who = "index_delta";
+namespace {
+// jsp_index_delta_frames (who = "index_delta") and jsp_index_tight_frames ("index_tight", tight): one routine, the rule of the sizes
+// launch apart.
+int index_gap_frames(const char* who, bool tight, jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap,
+                     size_t* lens, size_t* total) {
     if (total) *total = 0;
     if (lens && n >= 1 && n <= 4096) std::fill(lens, lens + n, (size_t)0);
-    if (!c || !idx || !from || !to || !lens || !total || (!out && cap)) return fail("index_delta: null argument");
+    if (!c || !idx || !from || !to || !lens || !total || (!out && cap)) return fail("%s: null argument", who);
     if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
-    if (idx->codec_serial != c->serial) return fail("index_delta: the index was built by another codec");
-    if (n < 1 || n > 4096) return fail("index_delta: n is outside 1..4096");
+    if (idx->codec_serial != c->serial) return fail("%s: the index was built by another codec", who);
+    if (n < 1 || n > 4096) return fail("%s: n is outside 1..4096", who);
     for (int j = 0; j < n; ++j)
         if (from[j] < -1 || to[j] <= from[j] || to[j] >= idx->nframes) {
-            set_error("index_delta: pair %d (%d, %d] is not a gap of the index (-1 <= from < to < %d frames)", j, from[j], to[j], idx->nframes);
+            set_error("%s: pair %d (%d, %d] is not a gap of the index (-1 <= from < to < %d frames)", who, j, from[j], to[j], idx->nframes);
             return JSP_ERROR_OCCURED;
         }
     const Msv1IndexSrc& src = idx->src;
-    if (src.nblocks < 1) return fail("index_delta: the picture has no 4x4 block");
+    if (src.nblocks < 1) return fail("%s: the picture has no 4x4 block", who);
     if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
     try {
         c->activate();
@@ -945,7 +947,7 @@ extern "C" int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const
             JSP_HIP(hipMemcpyAsync(d, h, l.status_at, hipMemcpyHostToDevice, c->stream));
             if (!launch) return;
             JSP_HIP(hipMemsetAsync(k.status, 0xFF, sizeof(uint32_t) * m, c->stream));
-            msv1_launch_index_delta_sizes(src, (int)m, k, c->stream);
+            msv1_launch_index_delta_sizes(src, (int)m, k, tight, c->stream);
             JSP_HIP(hipGetLastError());
         };
         for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
@@ -960,18 +962,18 @@ extern "C" int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const
                     uint32_t* writer = reinterpret_cast<uint32_t*>(h + l.first_at);
                     JSP_HIP(hipMemcpyAsync(writer, k.records + 2 * (i * nblocks + status[i]), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
                     JSP_HIP(hipStreamSynchronize(c->stream));
-                    set_error("index_delta: pair %d (%d, %d]: the code of block %u in frame %u, its last writer, is cut off by the end of the frame's data",
-                              (int)(j0 + i), from[j0 + i], to[j0 + i], status[i], *writer);
+                    set_error("%s: pair %d (%d, %d]: the code of block %u in frame %u, its last writer, is cut off by the end of the frame's data",
+                              who, (int)(j0 + i), from[j0 + i], to[j0 + i], status[i], *writer);
                     return JSP_ERROR_OCCURED;
                 }
                 for (size_t g = 0; g < nwg; ++g) length[j0 + i] += totals[i * nwg + g];
-                if (length[j0 + i] > bound) throw std::runtime_error("index_delta: a frame is longer than its bound");
+                if (length[j0 + i] > bound) throw std::runtime_error(std::string(who) + ": a frame is longer than its bound");
             }
         }
         size_t sum = 0;
         for (int j = 0; j < n; ++j) sum += (lens[j] = length[(size_t)j]);
         *total = sum;
-        if (cap < sum) return fail("index_delta: cap is smaller than the frames (*total has their length, lens[] each frame's)");
+        if (cap < sum) return fail("%s: cap is smaller than the frames (*total has their length, lens[] each frame's)", who);
         size_t at = 0;
         for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
             const size_t m = std::min(S, (size_t)n - j0);
@@ -991,6 +993,18 @@ extern "C" int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const
         set_error("%s", e.what());
         return JSP_ERROR_OCCURED;
     }
+}
+}  // namespace
+
+extern "C" int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap, size_t* lens,
+                                      size_t* total) {
+    return index_gap_frames("index_delta", false, c, idx, n, from, to, out, cap, lens, total);
+}
+
+// The same frames with the blocks dropped whose pixels the gap did not change (THE TIGHT RULE: msv1_index_delta_kernels.hip).
+extern "C" int jsp_index_tight_frames(jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap, size_t* lens,
+                                      size_t* total) {
+    return index_gap_frames("index_tight", true, c, idx, n, from, to, out, cap, lens, total);
 }
 
 extern "C" int jsp_index_significance(const jsp_index* idx, int* out) {

@@ -148,7 +148,9 @@ constexpr int MSV1_DELTA_RUN = 1023;               // a skip word's count is 10 
 // ONE launch each (msv1_index_delta_kernels.hip, which states the rule), grid.y = the pair.  Sizes: status (all ones from the
 // caller), totals, first_written and records of npairs pairs.  Gather, after a sizes launch over the same pairs with no status
 // raised and with bases[] = the running sums of the pairs' lengths: the frames into d.out.  Nothing for an index without a block.
-void msv1_launch_index_delta_sizes(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, hipStream_t stream);
+// tight (jsp_index_tight_frames): the sizes launch decodes both ends of the gap of every written block and keeps the block only
+// where a pixel changed; "written" in the scratch then reads "kept", and the gather launch is the same.
+void msv1_launch_index_delta_sizes(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, bool tight, hipStream_t stream);
 void msv1_launch_index_delta_gather(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, hipStream_t stream);
 
 }  // namespace jsp

@@ -82,6 +82,16 @@ def _differ(a, b, start: int) -> bool:
     return frames_differ(a, b, start, a.numel())
 
 
+def _takes_tight(method) -> bool:
+    """Whether an index object's DeltaFrames has the keyword `tight` (or takes any keyword)."""
+    import inspect
+    try:
+        params = inspect.signature(method).parameters.values()
+    except (TypeError, ValueError):
+        return False
+    return any(p.name == "tight" or p.kind is p.VAR_KEYWORD for p in params)
+
+
 class View:
     """What Main keeps about the part of the picture a window shows: `zoom_index` into ZOOM_FACTORS ("Fit", "100%", "200%",
     Main.hx:170-171) and the two view positions in 0..1.  The slider drawing (calc_slider_handles) is not rebuilt."""
@@ -293,7 +303,7 @@ class Manager:
         return write_avi(self.vi.X, self.vi.Y, out, fourcc=fourcc, bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
 
     # -- a clip thinned to the frames worth keeping: the attached index's DeltaFrames (jsp_index_delta_frames) -----------------------------
-    def thin(self, frames: Sequence[bytes], keep: Sequence[int], key_flags: Optional[Sequence[bool]] = None):
+    def thin(self, frames: Sequence[bytes], keep: Sequence[int], key_flags: Optional[Sequence[bool]] = None, tight: bool = False):
         """The clip's frames `keep` (strictly ascending frame numbers) as a clip of its own: (list of frame bytes, key flags) — a
         time-lapse (every s-th frame), a recording without its idle frames (`change_totals`), any list.  Entry 0 follows `cut`: the
         frame itself where it is a key frame, else index.KeyFrame.  A later entry that is a key frame of the clip is copied; one
@@ -302,7 +312,9 @@ class Manager:
         Flags: True for entry 0 and the copied key frames, else the decoder's IsKeyFrame of the bytes.  Nothing is decoded and
         neither decoder nor buffers change; a gap the index cannot span raises its CodecError.  ValueError: `keep` empty, not
         strictly ascending or outside the clip; where the index is needed, none attached, a frame outside it, or an index object
-        without `KeyFrame` / `DeltaFrames` (ScreenPressor's)."""
+        without `KeyFrame` / `DeltaFrames` (ScreenPressor's).  tight: the one DeltaFrames call is made with tight=True (blocks whose
+        pixels a gap did not change are dropped from its frames); everything else is the same.  ValueError as well when the index's
+        DeltaFrames takes no `tight`."""
         keep = [int(k) for k in keep]
         if not keep:
             raise ValueError("thin: keep is empty")
@@ -329,20 +341,24 @@ class Manager:
                 raise ValueError("thin: the attached seek index cannot make a key frame")
             if gaps and not hasattr(self.index, "DeltaFrames"):
                 raise ValueError("thin: the attached seek index cannot span a gap")
+            if gaps and tight and not _takes_tight(self.index.DeltaFrames):
+                raise ValueError("thin: the attached seek index cannot span a gap tightly")
         out = [frames[k] for k in keep]
         if need_key:
             out[0] = self.index.KeyFrame(keep[0] - self.index_first)
         if gaps:
-            made = self.index.DeltaFrames([(keep[j - 1] - self.index_first, keep[j] - self.index_first) for j in gaps])
+            pairs = [(keep[j - 1] - self.index_first, keep[j] - self.index_first) for j in gaps]
+            made = self.index.DeltaFrames(pairs, tight=True) if tight else self.index.DeltaFrames(pairs)
             for j, data in zip(gaps, made):
                 out[j] = data
         flags = [True] + [True if is_key[j] else bool(self.decoder.IsKeyFrame(out[j])) for j in range(1, len(keep))]
         return out, flags
 
-    def write_thin(self, frames: Sequence[bytes], keep: Sequence[int], key_flags: Optional[Sequence[bool]] = None, fps: float = 15.0) -> bytes:
+    def write_thin(self, frames: Sequence[bytes], keep: Sequence[int], key_flags: Optional[Sequence[bool]] = None, fps: float = 15.0,
+                   tight: bool = False) -> bytes:
         """`thin` as an AVI file (avi.write_avi) with this Manager's stream, as `write_cut` writes `cut`."""
         from .avi import write_avi
-        out, flags = self.thin(frames, keep, key_flags)
+        out, flags = self.thin(frames, keep, key_flags, tight=tight)
         fourcc = b"SCPR" if self.vi.codec == CODEC_SCREENPRESSOR else b"CRAM"
         return write_avi(self.vi.X, self.vi.Y, out, fourcc=fourcc, bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
 
