@@ -57,6 +57,15 @@
 //                                --thin with jsp_index_tight_frames in place of jsp_index_delta_frames: a block that a gap codes but
 //                                whose pixels it does not change is dropped from the gap's frame.  The same playback, CRC check and
 //                                exit status; OUT.avi is never longer than --thin's
+//   jsp_play clip.avi --crop X:Y:W:H[:tight] FIRST[:COUNT[:STRIDE]] OUT.avi
+//                                MSVideo1: the part X:Y:W:H of the picture (display coordinates, top row first) of the frames --thin
+//                                would keep, as an AVI file of its own.  The rectangle is widened to whole 4x4 blocks and clipped to
+//                                the block grid; prints "crop blocks <bx> <by> <bw> <bh> display <x> <y> <w> <h>", the rectangle used.
+//                                ONE seek index from the nearest key frame <= FIRST; the first frame is a key pair, every other one the
+//                                gap pair from the frame kept before it (":tight": JSP_CROP_TIGHT), jsp_index_crop_frames calls of at
+//                                most 4096 pairs.  Then OUT.avi is played back through a decoder of its own size: prints "<frame of
+//                                the clip> <crc32 from OUT.avi> <crc32 of that part of the clip's picture>" per frame kept and exits
+//                                with 1 on any difference
 //   jsp_play clip.avi --filmstrip N[:scale]
 //                                ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build), then ONE
 //                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
@@ -247,14 +256,15 @@ std::vector<uint8_t> avi_file(const Clip& c, const std::vector<std::pair<const u
 
 // The ordinary decode loop over frames 0 .. upto - 1 of `clip` on a codec and two frame buffers of its own (DecompressI for a key
 // frame, DecompressP else, never into the previous frame): per frame the CRC-32 of the pixels of the picture shown that 4x4 blocks
-// cover (the X % 4 / Y % 4 remainder pixels are in no MSVideo1 frame).  False: an error, printed.
-bool covered_crcs(const Clip& clip, size_t upto, std::vector<uint32_t>& crcs) {
+// cover (the X % 4 / Y % 4 remainder pixels are in no MSVideo1 frame) — or, with rw > 0, of the pixels of stored rows ry .. ry + rh - 1,
+// columns rx .. rx + rw - 1 (inside the covered part).  False: an error, printed.
+bool covered_crcs(const Clip& clip, size_t upto, std::vector<uint32_t>& crcs, size_t rx = 0, size_t ry = 0, size_t rw = 0, size_t rh = 0) {
     jsp_codec* dec = jsp_codec_create(clip.kind, clip.X, clip.Y, clip.bpp, clip.palette.empty() ? nullptr : clip.palette.data(), (int)clip.palette.size(), 0);
     jsp_pool* pool = dec ? jsp_pool_create(0, clip.X, clip.Y, 2) : nullptr;
     bool ok = dec && pool;
     if (!ok) std::fprintf(stderr, "jsp_codec_create / jsp_pool_create: %s\n", jsp_last_error());
     if (ok) jsp_preinit(dec, kInsignificantLines);
-    const size_t npx = (size_t)clip.X * clip.Y, cw = (size_t)(clip.X / 4) * 4, chh = (size_t)(clip.Y / 4) * 4;
+    const size_t npx = (size_t)clip.X * clip.Y, cw = rw ? rw : (size_t)(clip.X / 4) * 4, chh = rw ? rh : (size_t)(clip.Y / 4) * 4;
     std::vector<int32_t> host(npx), cov(cw * chh);
     crcs.clear();
     for (size_t i = 0; ok && i < upto; ++i) {
@@ -268,7 +278,7 @@ bool covered_crcs(const Clip& clip, size_t upto, std::vector<uint32_t>& crcs) {
         if (!ok) { std::fprintf(stderr, "frame %zu: %s\n", i, jsp_last_error()); break; }
         shown = jsp_previous_frame(dec);
         if (shown && jsp_download(shown, host.data(), npx) != 0) { std::fprintf(stderr, "jsp_download: %s\n", jsp_last_error()); ok = false; break; }
-        for (size_t y = 0; shown && y < chh; ++y) std::memcpy(cov.data() + y * cw, host.data() + y * (size_t)clip.X, cw * 4);
+        for (size_t y = 0; shown && y < chh; ++y) std::memcpy(cov.data() + y * cw, host.data() + (ry + y) * (size_t)clip.X + rx, cw * 4);
         crcs.push_back(shown ? crc32(reinterpret_cast<const uint8_t*>(cov.data()), cov.size() * 4) : 0u);
     }
     if (pool) jsp_pool_destroy(pool);
@@ -542,6 +552,8 @@ int main(int argc, char** argv) {
     bool thin_tight = false;   // --thin-tight: --thin with jsp_index_tight_frames
     long thin_first = -1, thin_count = -1, thin_stride = 8;   // --thin FIRST[:COUNT[:STRIDE]] OUT.avi: every STRIDE-th frame as a file of its own
     std::string thin_path;
+    bool crop = false, crop_tight = false;   // --crop X:Y:W:H[:tight] FIRST[:COUNT[:STRIDE]] OUT.avi: --thin's frames, a part of the picture
+    long crop_rect[4] = {0, 0, 0, 0};
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
     long play_first = -1, play_count = -1, play_stride = 1;   // --play-index FIRST[:COUNT[:STRIDE]]: frames played out of a ScreenPressor seek index
     long run_first = -1, run_count = -1, run_stride = 1;      // --index-run FIRST[:COUNT[:STRIDE]]: frames played out of an MSVideo1 seek index
@@ -583,8 +595,25 @@ int main(int argc, char** argv) {
             cut_path = argv[++a];
             if (cut_first < 0 || (colon != std::string::npos && cut_count < 1)) { std::fprintf(stderr, "--cut FIRST[:COUNT] OUT.avi: FIRST >= 0, COUNT >= 1\n"); return 2; }
         }
-        else if ((o == "--thin" || o == "--thin-tight") && a + 2 < argc) {
+        else if ((o == "--thin" || o == "--thin-tight" || o == "--crop") && a + (o == "--crop" ? 3 : 2) < argc) {
             thin_tight = o == "--thin-tight";
+            if (o == "--crop") {
+                crop = true;
+                const std::string r = argv[++a];
+                int got = 0;                                   // parts taken; 99: a part that is no number, or text behind ":tight"
+                for (size_t at = 0; at <= r.size() && got < 99; at = std::min(r.find(':', at), r.size()) + 1) {
+                    const std::string part = r.substr(at, std::min(r.find(':', at), r.size()) - at);
+                    char* end = nullptr;
+                    if (got < 4) {
+                        crop_rect[got] = std::strtol(part.c_str(), &end, 10);
+                        got = part.empty() || *end ? 99 : got + 1;
+                    } else if (got == 4 && part == "tight") {
+                        crop_tight = true;
+                        got = 5;
+                    } else got = 99;
+                }
+                if (got < 4 || got > 5 || crop_rect[2] < 1 || crop_rect[3] < 1) { std::fprintf(stderr, "--crop X:Y:W:H[:tight] FIRST[:COUNT[:STRIDE]] OUT.avi: W >= 1, H >= 1\n"); return 2; }
+            }
             const std::string v = argv[++a];
             const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
             thin_first = std::atol(v.substr(0, c1).c_str());
@@ -667,6 +696,7 @@ int main(int argc, char** argv) {
     if (cut_first >= 0 && (act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--cut goes alone\n"); return 2; }
     if (cut_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--cut: MSVideo1 only (a ScreenPressor key frame needs the entropy encoder)\n"); return 2; }
     if (thin_first >= 0 && (cut_first >= 0 || act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--thin goes alone\n"); return 2; }
+    if (crop && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--crop: MSVideo1 only (ScreenPressor codes are entropy-coded in context)\n"); return 2; }
     if (thin_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--thin: MSVideo1 only (a ScreenPressor frame needs the entropy encoder)\n"); return 2; }
     if (strip > 0 && (step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--filmstrip goes alone\n"); return 2; }
     if (play_first >= 0 && (strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--play-index goes alone\n"); return 2; }
@@ -1071,6 +1101,92 @@ int main(int argc, char** argv) {
         for (long k = 0; k < count; ++k) {
             std::printf("%ld %08x %08x\n", cut_first + k, got[(size_t)k], want[(size_t)(cut_first + k)]);
             if (got[(size_t)k] != want[(size_t)(cut_first + k)]) rc = 1;
+        }
+        return rc;
+    }
+    if (thin_first >= 0 && crop) {   // a part of the picture: one index build from the key frame before, jsp_index_crop_frames for a key pair and every gap, the file, its playback
+        const size_t n = clip.frames.size();
+        std::vector<size_t> keep;
+        for (long i = thin_first; i < (long)n && (thin_count < 0 || (long)keep.size() < thin_count); i += thin_stride) keep.push_back((size_t)i);
+        if (keep.empty() || (thin_count >= 0 && (long)keep.size() < thin_count)) {
+            std::fprintf(stderr, "--crop: frames %ld, %ld, ... (%ld of them) are not all in the clip (%zu frames)\n", thin_first, thin_first + thin_stride, thin_count, n);
+            rc = 1;
+        }
+        // the smallest block rectangle that contains the display rectangle, clipped to the block grid; stored row = Y - 1 - display row
+        const long nbx = clip.X / 4, nby = clip.Y / 4;
+        const long x0 = std::max(crop_rect[0], 0l), x1 = std::min(crop_rect[0] + crop_rect[2], 4 * nbx);
+        const long s0 = std::max(clip.Y - (crop_rect[1] + crop_rect[3]), 0l), s1 = std::min(clip.Y - crop_rect[1], 4 * nby);
+        if (rc == 0 && (x0 >= x1 || s0 >= s1)) { std::fprintf(stderr, "--crop: nothing of the rectangle lies in the picture's blocks\n"); rc = 1; }
+        const int bx = (int)(x0 / 4), by = (int)(s0 / 4), bw = (int)((x1 + 3) / 4) - bx, bh = (int)((s1 + 3) / 4) - by;
+        if (rc == 0) std::printf("crop blocks %d %d %d %d display %d %ld %d %d\n", bx, by, bw, bh, 4 * bx, clip.Y - 4l * (by + bh), 4 * bw, 4 * bh);
+        std::vector<uint8_t> made;
+        std::vector<size_t> made_lens;
+        std::vector<int> made_keys;
+        if (rc == 0) {
+            size_t k = keep[0];
+            while (k > 0 && !frame_is_key(clip, dec, k)) --k;   // the nearest key frame <= FIRST (frame 0 is one)
+            std::vector<const uint8_t*> srcs;
+            std::vector<size_t> lens;
+            std::vector<uint8_t> keys;
+            for (size_t i = k; i <= keep.back(); ++i) {
+                srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+                lens.push_back(clip.frames[i].second);
+                keys.push_back(i == k || frame_is_key(clip, dec, i) ? 1 : 0);
+            }
+            jsp_index* idx = jsp_index_build(dec, (int)srcs.size(), srcs.data(), lens.data(), keys.data(), kInsignificantLines);
+            if (!idx) { std::fprintf(stderr, "jsp_index_build: %s\n", jsp_last_error()); rc = 1; }
+            for (size_t g0 = 0; rc == 0 && g0 < keep.size(); g0 += 4096) {   // (a call takes 4096 pairs)
+                const size_t m = std::min<size_t>(4096, keep.size() - g0);
+                std::vector<int> from(m), to(m), ks(m);
+                for (size_t i = 0; i < m; ++i) {
+                    from[i] = g0 + i == 0 ? JSP_CROP_KEY : (int)(keep[g0 + i - 1] - k);
+                    to[i] = (int)(keep[g0 + i] - k);
+                }
+                std::vector<size_t> ls(m);
+                size_t total = 0;
+                const int flags = crop_tight ? JSP_CROP_TIGHT : 0;
+                // asked twice: the lengths (cap 0 is a refusal that still sets them), then the bytes
+                if (jsp_index_crop_frames(dec, idx, bx, by, bw, bh, (int)m, from.data(), to.data(), flags, nullptr, 0, ls.data(), ks.data(), &total) == JSP_ZERO_STATE || total == 0) {
+                    std::fprintf(stderr, "jsp_index_crop_frames: %s\n", jsp_last_error());
+                    rc = 1;
+                    break;
+                }
+                const size_t at = made.size();
+                made.resize(at + total);
+                if (jsp_index_crop_frames(dec, idx, bx, by, bw, bh, (int)m, from.data(), to.data(), flags, made.data() + at, total, ls.data(), ks.data(), &total) != JSP_ZERO_STATE) {
+                    std::fprintf(stderr, "jsp_index_crop_frames: %s\n", jsp_last_error());
+                    rc = 1;
+                }
+                made_lens.insert(made_lens.end(), ls.begin(), ls.end());
+                made_keys.insert(made_keys.end(), ks.begin(), ks.end());
+            }
+            if (idx) jsp_index_destroy(idx);
+        }
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        if (rc != 0) return rc;
+        std::vector<std::pair<const uint8_t*, size_t>> out_frames;
+        std::vector<uint8_t> out_keys;
+        size_t at = 0;
+        for (size_t j = 0; j < keep.size(); ++j) {
+            out_frames.emplace_back(made.data() + at, made_lens[j]);
+            out_keys.push_back(j == 0 || made_keys[j] ? 1 : 0);
+            at += made_lens[j];
+        }
+        Clip header;                                            // the clip's stream at the rectangle's size
+        header.X = 4 * bw, header.Y = 4 * bh, header.bpp = clip.bpp, header.kind = clip.kind, header.usec = clip.usec, header.palette = clip.palette;
+        const std::vector<uint8_t> file = avi_file(header, out_frames, out_keys);
+        FILE* f = std::fopen(thin_path.c_str(), "wb");
+        if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size()) { std::fprintf(stderr, "cannot write %s\n", thin_path.c_str()); if (f) std::fclose(f); return 1; }
+        std::fclose(f);
+        // OUT.avi played back through the ordinary decode loop of a decoder of ITS size, beside that part of the clip's own pictures
+        Clip cropped;
+        if (!load(thin_path.c_str(), cropped) || cropped.frames.size() != keep.size() || cropped.X != 4 * bw || cropped.Y != 4 * bh) { std::fprintf(stderr, "cannot read %s back\n", thin_path.c_str()); return 1; }
+        std::vector<uint32_t> got, want;
+        if (!covered_crcs(cropped, cropped.frames.size(), got) || !covered_crcs(clip, keep.back() + 1, want, 4 * (size_t)bx, 4 * (size_t)by, 4 * (size_t)bw, 4 * (size_t)bh)) return 1;
+        for (size_t j = 0; j < keep.size(); ++j) {
+            std::printf("%zu %08x %08x\n", keep[j], got[j], want[keep[j]]);
+            if (got[j] != want[keep[j]]) rc = 1;
         }
         return rc;
     }

@@ -79,6 +79,14 @@ extern class JspNative {
     @:native("jsp_index_tight_frames") static function indexTightFrames(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, n:Int, from:RawConstPointer<Int>,
                                                                         to:RawConstPointer<Int>, out:RawPointer<UInt8>, cap:SizeT,
                                                                         lens:RawPointer<SizeT>, total:RawPointer<SizeT>):Int;
+    // the frames of a block rectangle (bx, by, bw, bh; table order): from = CROP_KEY makes a key pair, flags = CROP_TIGHT the tight rule; keys may be null
+    static inline var CROP_KEY:Int = -2;
+    static inline var CROP_TIGHT:Int = 1;
+    @:native("jsp_index_crop_bound")   static function indexCropBound(idx:RawPointer<JspIndex>, bw:Int, bh:Int, bytes:RawPointer<SizeT>):Int;
+    @:native("jsp_index_crop_frames")  static function indexCropFrames(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, bx:Int, by:Int, bw:Int, bh:Int,
+                                                                       n:Int, from:RawConstPointer<Int>, to:RawConstPointer<Int>, flags:Int,
+                                                                       out:RawPointer<UInt8>, cap:SizeT, lens:RawPointer<SizeT>, keys:RawPointer<Int>,
+                                                                       total:RawPointer<SizeT>):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)

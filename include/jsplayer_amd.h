@@ -782,6 +782,45 @@ int jsp_index_delta_frames(jsp_codec* c, jsp_index* idx, int n, const int* from,
 int jsp_index_tight_frames(jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap, size_t* lens,
                            size_t* total);
 
+/* CROP A CLIP: the frames of a block rectangle of an MSVideo1 index — the spatial counterpart of the key-frame cut and of Delta /
+ * Tight, by the same means.  An MSVideo1 code carries no position (colours and a mask; 8 bits: indices into the palette, which the
+ * cropped clip keeps), so the clip of a block-aligned rectangle is a gather of codes the index holds: no pixel decoded, nothing
+ * re-quantised.
+ *   THE RECTANGLE is (bx, by, bw, bh) in 4x4 blocks in TABLE order: block row 0 is stored rows 0 .. 3 of a frame buffer, the bottom of
+ *       the picture as displayed.  bw, bh >= 1, 0 <= bx, bx + bw <= nbx, 0 <= by, by + bh <= nby.  nb = bw * bh; block j < nb of the
+ *       rectangle is source block src(j) = (by + j / bw) * nbx + bx + j % bw.  The cropped clip is 4 bw x 4 bh pixels, with the
+ *       source's bit depth and palette.
+ *   THE RULE (stated in msv1_index_crop_kernels.hip): WHOLE, WRITTEN, RUN HEAD, the skip word, the 1023 rule and KEPT of
+ *       jsp_index_key_frame / _delta_frames / _tight_frames, applied to the virtual index whose block j is source block src(j),
+ *       everything in j-numbering: a run head is j = 0, block j - 1 OF THE RECTANGLE written (kept), or j % 1023 = 0; counts stop at
+ *       the next multiple of 1023 in j and at nb.  A pair is
+ *         a GAP pair (from, to], -1 <= from < to < nframes: Delta, or with JSP_CROP_TIGHT in `flags` Tight, of the virtual index.  A cut
+ *           code of a written (tight: kept) block refuses; a block without a writer is skipped;
+ *         a KEY pair, from == JSP_CROP_KEY, 0 <= to < nframes: the whole code of the last writer <= to of every src(j), no skip words.
+ *           A block of the rectangle with no writer <= to refuses ("no writer"), a cut code refuses ("cut").  JSP_CROP_TIGHT does not
+ *           touch key pairs.
+ *       Blocks outside the rectangle never matter: a rectangle can be cut where jsp_index_key_frame of the whole picture refuses.
+ *   PROMISED: a fresh decoder of 4 bw x 4 bh pixels fed a key pair's frame as a key frame, then gap pairs' frames chained
+ *       to[k - 1] == from[k] as inter frames, holds after each the stored rows 4 by .. 4 by + 4 bh - 1, columns 4 bx .. 4 bx + 4 bw - 1
+ *       of the source picture of frame to[k].  With the rectangle equal to the whole block grid the bytes are those of
+ *       jsp_index_delta_frames / _tight_frames, and a key pair's those of jsp_index_key_frame(to).  Every frame is at most
+ *       jsp_index_crop_bound's bytes (nb * 18; 8 bits: nb * 10).  keys[j] (may be null) = frame j codes every block of the rectangle:
+ *       jsp_is_key_frame of it.  NOT promised: the exclusions of KeyFrame.
+ *   REFUSED, as an error with nothing written: the text starts with "index_crop:" and names the FIRST refusing (pair, block) in that
+ *       order — the pair, the block in the rectangle's numbering and in the picture's, the kind, and for "cut" the writer frame.
+ *   Everything else is jsp_index_delta_frames', word for word: n pairs in 1 .. 4096, `out` in HOST memory, frames back to back, lens[],
+ *       keys[] and *total set when only `cap` is short, zeros and nothing written after every other error, a scratch of the index's
+ *       own that jsp_index_info counts, option "msv1_index_delta_slice" (the bytes do not depend on it), synchronised on return, THE
+ *       CODEC ONLY LENT.  Two launches per slice: msv1_index_crop_sizes_kernel, msv1_index_crop_gather_kernel.
+ *   ERRORS before anything is queued, in this order: a null argument; not an MSVideo1 codec ("index: MSVideo1 only"); an index of
+ *       another codec; a rectangle outside the block grid (also: a picture without a block); n outside 1 .. 4096; unknown flag bits;
+ *       the first bad pair; an asynchronous frame in flight. */
+#define JSP_CROP_KEY   (-2)
+#define JSP_CROP_TIGHT 1
+int jsp_index_crop_bound(const jsp_index* idx, int bw, int bh, size_t* bytes);
+int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to, int flags,
+                          uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

@@ -755,6 +755,57 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
             at += lens[j]
         return out
 
+    KEY = -2            # JSP_CROP_KEY: a pair's `a` that makes it a key pair of CropFrames
+    _CROP_TIGHT = 1     # JSP_CROP_TIGHT
+
+    def CropBound(self, bw: int, bh: int) -> int:
+        """The most bytes one frame of CropFrames has for a rectangle of bw x bh blocks: 18 per block at 16 bits, 10 at 8."""
+        self._open("index_crop_bound")
+        n = C.c_size_t(0)
+        if self._lib.jsp_index_crop_bound(self._h, int(bw), int(bh), C.byref(n)) != 0:
+            raise CodecError(N.last_error())
+        return n.value
+
+    def CropFrames(self, rect, pairs, tight: bool = False):
+        """The frames of the block rectangle rect = (bx, by, bw, bh) — 4x4 blocks in table order, block row 0 the BOTTOM of the picture
+        as displayed — one per pair: (list of bytes, list of bool).  A pair (SeekIndex.KEY, t) is the key frame of the rectangle at
+        frame t; a pair (a, b), -1 <= a < b < frames, the inter frame over the gap as DeltaFrames makes it (tight: as
+        DeltaFrames(tight=True); key pairs are not touched), both of the virtual index whose block j is block j of the rectangle
+        (jsp_index_crop_frames: two launches per slice of pairs, the codec not touched).  A decoder of 4 bw x 4 bh pixels fed a key
+        pair's frame and then chained gap pairs' frames shows that part of the source's pictures.  The flag of a frame says that it
+        codes every block of the rectangle: IsKeyFrame of it.  CodecError, naming the pair, the block (in the rectangle and in the
+        picture), the kind and for a cut code the writer frame; nothing is returned then."""
+        codec = self._open("index_crop")
+        bx, by, bw, bh = (int(v) for v in rect)
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        n = len(pairs)
+        frm = (C.c_int * max(n, 1))(*[a for a, _ in pairs])
+        to = (C.c_int * max(n, 1))(*[b for _, b in pairs])
+        lens = (C.c_size_t * max(n, 1))()
+        keys = (C.c_int * max(n, 1))()
+        total = C.c_size_t(0)
+        flags = self._CROP_TIGHT if tight else 0
+        call = self._lib.jsp_index_crop_frames
+        # (a rectangle the block grid does not hold gives no bound to size a buffer by: the call then refuses in its own order)
+        bound = C.c_size_t(0)
+        self._lib.jsp_index_crop_bound(self._h, bw, bh, C.byref(bound))
+        cap = n * bound.value if 1 <= n <= 4096 else 0
+        if cap > DELTA_ASK_TWICE:   # many large frames: the lengths first (cap 0 is the refusal that still sets them), then the bytes
+            if call(codec._h, self._h, bx, by, bw, bh, n, frm, to, flags, None, 0, lens, keys, C.byref(total)) == 0 or total.value == 0:
+                raise CodecError(N.last_error())
+            cap = total.value
+        buf = (C.c_uint8 * max(cap, 1))()
+        if call(codec._h, self._h, bx, by, bw, bh, n, frm, to, flags, buf, len(buf), lens, keys, C.byref(total)) != 0:
+            raise CodecError(N.last_error())
+        dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first call adds the scratch the frames are assembled in)
+        self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
+        self.device_bytes, self.host_bytes = dev.value, host.value
+        view, out, at = memoryview(buf), [], 0
+        for j in range(n):
+            out.append(bytes(view[at:at + lens[j]]))
+            at += lens[j]
+        return out, [bool(keys[j]) for j in range(n)]
+
     def _open(self, who: str) -> _NativeCodec:
         if not self._h:
             raise CodecError(f"{who}: the index is closed")

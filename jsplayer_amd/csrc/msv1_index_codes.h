@@ -1,7 +1,8 @@
-// What the two stream-producing calls of an MSVideo1 seek index share — the key frame (msv1_index_keyframe_kernels.hip, which states
-// when a code is WHOLE) and the inter frame over a gap (msv1_index_delta_kernels.hip): where a writer's code lies and how long it
-// is, the workgroup's exclusive scan of byte counts, the sum of the workgroup totals before one's own, and the way an LDS image of
-// a workgroup's output leaves in 16-byte pieces.  Workgroups of INDEX_CODES_WG lanes.
+// What the stream-producing calls of an MSVideo1 seek index share — the key frame (msv1_index_keyframe_kernels.hip, which states
+// when a code is WHOLE), the inter frame over a gap (msv1_index_delta_kernels.hip, which states WRITTEN and KEPT) and the frames of
+// a block rectangle (msv1_index_crop_kernels.hip): where a writer's code lies and how long it is, whether a gap writes or keeps a
+// block, the workgroup's exclusive scan of byte counts, the sum of the workgroup totals before one's own, and the way an LDS image
+// of a workgroup's output leaves in 16-byte pieces.  Workgroups of INDEX_CODES_WG lanes.
 #pragma once
 #include "msv1_block_io.h"
 
@@ -40,6 +41,38 @@ __device__ __forceinline__ uint32_t index_whole_length(const Msv1IndexChunk& ch,
         L = b < 0x80u ? 4u : (b >= 0x90u ? 10u : 2u);
     }
     return settled && e >= L && o <= e - L ? L : 0u;
+}
+
+// Whether block `blk` is written in (a, b], and then by which frame.
+__device__ __forceinline__ bool delta_written(const Msv1IndexSrc& s, int blk, int a, int b, int& f) {
+    int w;
+    const uint32_t m = index_last_writer(s, blk, b, w);
+    if (m == 0u) return false;
+    f = index_word_frame(w, m);
+    return f > a;
+}
+
+// THE TIGHT RULE's (msv1_index_delta_kernels.hip) test of block `blk`, written in (a, b] by frame f: false (dropped) when P(a) is
+// defined and equals P(b).
+template <int BITS>
+__device__ __forceinline__ bool tight_kept(const Msv1IndexSrc& s, int blk, int a, int f, const uint32_t* s_pal) {
+    uint32_t pa[16], pb[16];
+    int w;
+    const uint32_t m = a >= 0 ? index_last_writer(s, blk, a, w) : 0u;
+    if (m != 0u) {
+        index_decode<BITS>(s, index_word_frame(w, m), blk, s_pal, pa);
+    } else if (s.before != nullptr) {
+        const uint32_t* p = s.before + (size_t)(blk / s.nbx) * 4u * (size_t)s.X + (size_t)(blk % s.nbx) * 4u;
+        if (s.before_vec) load_block<true>(p, s.X, pa);
+        else load_block<false>(p, s.X, pa);
+    } else {
+        return true;
+    }
+    index_decode<BITS>(s, f, blk, s_pal, pb);
+    uint32_t diff = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) diff |= pa[k] ^ pb[k];
+    return diff != 0u;
 }
 
 // Exclusive scan of `mine` over the workgroup's lanes: inclusive over the wave's lanes by shuffles, the waves' sums through LDS

@@ -48,37 +48,6 @@ constexpr int DL_WG_BLOCKS = MSV1_KEYFRAME_WG_BLOCKS;   // (msv1_seek.h: the hos
 static_assert(DL_WG_BLOCKS == WG * DL_LANE_BLOCKS, "a lane owns DL_LANE_BLOCKS consecutive blocks");
 static_assert(2 * DL_WG_BLOCKS >= MSV1_DELTA_RUN, "a count's look-ahead ends within the next two workgroups");
 
-// Whether block `blk` is written in (a, b], and then by which frame.
-__device__ __forceinline__ bool delta_written(const Msv1IndexSrc& s, int blk, int a, int b, int& f) {
-    int w;
-    const uint32_t m = index_last_writer(s, blk, b, w);
-    if (m == 0u) return false;
-    f = index_word_frame(w, m);
-    return f > a;
-}
-
-// THE TIGHT RULE's test of block `blk`, written in (a, b] by frame f: false (dropped) when P(a) is defined and equals P(b).
-template <int BITS>
-__device__ __forceinline__ bool tight_kept(const Msv1IndexSrc& s, int blk, int a, int f, const uint32_t* s_pal) {
-    uint32_t pa[16], pb[16];
-    int w;
-    const uint32_t m = a >= 0 ? index_last_writer(s, blk, a, w) : 0u;
-    if (m != 0u) {
-        index_decode<BITS>(s, index_word_frame(w, m), blk, s_pal, pa);
-    } else if (s.before != nullptr) {
-        const uint32_t* p = s.before + (size_t)(blk / s.nbx) * 4u * (size_t)s.X + (size_t)(blk % s.nbx) * 4u;
-        if (s.before_vec) load_block<true>(p, s.X, pa);
-        else load_block<false>(p, s.X, pa);
-    } else {
-        return true;
-    }
-    index_decode<BITS>(s, f, blk, s_pal, pb);
-    uint32_t diff = 0u;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) diff |= pa[k] ^ pb[k];
-    return diff != 0u;
-}
-
 // TIGHT = false is jsp_index_delta_frames' kernel; TIGHT = true applies THE TIGHT RULE: `written` below then reads "kept".
 template <int BITS, bool TIGHT>
 __global__ __launch_bounds__(WG) void msv1_index_delta_sizes_kernel(const Msv1IndexSrc s, Msv1DeltaScratch d) {

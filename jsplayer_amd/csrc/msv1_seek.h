@@ -153,4 +153,31 @@ constexpr int MSV1_DELTA_RUN = 1023;               // a skip word's count is 10 
 void msv1_launch_index_delta_sizes(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, bool tight, hipStream_t stream);
 void msv1_launch_index_delta_gather(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, hipStream_t stream);
 
+// A block rectangle of the picture, in table order (block row 0 = stored rows 0 .. 3), checked against the block grid by the host
+// (crop_rect_ok, msv1_index_crop_layout.h): bw, bh >= 1, bx + bw <= nbx, by + bh <= nby; nb = bw * bh.  Block j < nb of the
+// rectangle is source block (by + j / bw) * nbx + bx + j % bw.
+struct Msv1CropRect {
+    int bx, by, bw, bh, nb;
+};
+constexpr int MSV1_CROP_KEY = -2;                  // a pair's `from` that says "key pair" (JSP_CROP_KEY)
+// The device scratch of jsp_index_crop_frames for one slice of pairs (the index owns it; every part 16-byte aligned): the delta
+// call's with everything in the rectangle's numbering — nwg = msv1_keyframe_workgroups(nb), records of nb blocks a pair — and
+// the workgroups' code counts.
+struct Msv1CropScratch {
+    const int32_t* pairs;            // per pair: from (-1: before the range; MSV1_CROP_KEY: a key pair), to
+    const uint64_t* bases;           // per pair: where its frame starts in `out` (even; read by the gather only)
+    uint32_t* status;                // per pair: all ones, else the first block of the rectangle that refuses (j << 1 | kind,
+                                     // MSV1_KEYFRAME_NO_WRITER — key pairs only — or MSV1_KEYFRAME_CUT)
+    uint32_t* totals;                // per pair and workgroup (pair * nwg + g): the bytes of its codes and skip words
+    uint32_t* first_written;         // per pair and workgroup: its first written block j, MSV1_DELTA_NONE when it has none
+    uint32_t* counts;                // per pair and workgroup: the blocks that got a code
+    uint32_t* records;               // per pair and block ((pair * nb + j) * 2): as Msv1DeltaScratch's
+    uint8_t* out;                    // the slice's frames back to back, room for npairs * the bound
+};
+// ONE launch each (msv1_index_crop_kernels.hip, which states the rule), grid.y = the pair, in the shape of the two delta launches.
+// tight: THE TIGHT RULE for the gap pairs; key pairs are not touched by it.  Nothing for a rectangle without a block.
+void msv1_launch_index_crop_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, bool tight,
+                                  hipStream_t stream);
+void msv1_launch_index_crop_gather(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, hipStream_t stream);
+
 }  // namespace jsp

@@ -19,7 +19,8 @@ index, one `Play` launch per batch of free buffers; `preview` / `filmstrip` are 
 `Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex); `activity` / `change_totals` / `change_box` /
 `next_change` say where and when the picture changes, from the index's `Activity` map (changed pixels per frame and 16x16 cell);
 `cut` / `write_cut` give the clip from any frame on as frames and flags / as an AVI file, its first frame the index's `KeyFrame`;
-`thin` / `write_thin` the clip made of any ascending list of frames, the gaps spanned by the index's `DeltaFrames`.  `View` is the zoom / scroll / fit state of Main
+`thin` / `write_thin` the clip made of any ascending list of frames, the gaps spanned by the index's `DeltaFrames`.  `crop_rect` / `crop` / `write_crop`
+the same list of frames for a part of the picture, from the index's `CropFrames`.  `View` is the zoom / scroll / fit state of Main
 (Main.hx:288-319, 1186-1278) and `Manager.present` draws the window it shows of a frame buffer, one launch.  Timers, bitmaps and audio
 of the reference's Manager are not rebuilt.
 """
@@ -361,6 +362,70 @@ class Manager:
         out, flags = self.thin(frames, keep, key_flags, tight=tight)
         fourcc = b"SCPR" if self.vi.codec == CODEC_SCREENPRESSOR else b"CRAM"
         return write_avi(self.vi.X, self.vi.Y, out, fourcc=fourcc, bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
+
+    # -- a clip of a part of the picture: the attached index's CropFrames (jsp_index_crop_frames) ------------------------------------------
+    def crop_rect(self, rect):
+        """The block rectangle for the display rectangle `rect` = (x, y, w, h), top row first, as `change_box` returns it: the
+        smallest rectangle of 4x4 blocks that contains it, clipped to the block grid — ((bx, by, bw, bh), (x, y, w, h)): the block
+        rectangle as CropFrames takes it (table order: block row 0 is the BOTTOM of the picture as displayed, so stored row =
+        H - 1 - display row) and the display rectangle that really results.  ValueError when nothing is left."""
+        x, y, w, h = (int(v) for v in rect)
+        W, H = self.vi.X, self.vi.Y
+        nbx, nby = W // 4, H // 4
+        x0, x1 = max(x, 0), min(x + w, 4 * nbx)
+        s0, s1 = max(H - (y + h), 0), min(H - y, 4 * nby)          # stored rows s0 .. s1 - 1
+        if x0 >= x1 or s0 >= s1:
+            raise ValueError(f"crop: nothing of the rectangle {(x, y, w, h)} lies in the picture's blocks")
+        bx, by = x0 // 4, s0 // 4
+        bw, bh = (x1 + 3) // 4 - bx, (s1 + 3) // 4 - by
+        return (bx, by, bw, bh), (4 * bx, H - 4 * (by + bh), 4 * bw, 4 * bh)
+
+    CROP_CALL = 4096   # pairs in one CropFrames call (jsp_index_crop_frames takes no more)
+
+    def crop(self, frames: Sequence[bytes], rect, keep: Sequence[int], tight: bool = False):
+        """The part `rect` (a display rectangle, see crop_rect) of the clip's frames `keep` (strictly ascending frame numbers, all in
+        the attached index) as a clip of its own: (list of frame bytes, key flags, the display rectangle that results).  Entry 0 is
+        the rectangle's key frame at keep[0], entry k the inter frame from the picture of keep[k - 1] to that of keep[k], all from
+        the index's CropFrames in calls of at most 4096 pairs.  flags[0] is True; a later flag says that the frame codes every
+        block of the rectangle.  tight: blocks whose pixels a gap did not change are dropped.  Nothing is decoded and neither
+        decoder nor buffers change; what the index cannot cut raises its CodecError.  ValueError: `keep` empty, not strictly
+        ascending or outside the clip; no index attached, a frame outside it, an index object without `CropFrames`
+        (ScreenPressor's); nothing left of `rect`."""
+        keep = [int(k) for k in keep]
+        if not keep:
+            raise ValueError("crop: keep is empty")
+        for k in keep:
+            if not 0 <= k < len(frames):
+                raise ValueError(f"crop: frame {k} is not in the clip")
+        for prev, k in zip(keep, keep[1:]):
+            if k <= prev:
+                raise ValueError(f"crop: keep is not strictly ascending ({k} after {prev})")
+        if self.index is None:
+            raise ValueError("crop: no seek index is attached")
+        for k in keep:
+            if not self._in_index(k):
+                raise ValueError(f"crop: frame {k} is not in the attached seek index")
+        if not hasattr(self.index, "CropFrames"):
+            raise ValueError("crop: the attached seek index cannot crop")
+        blocks, shown = self.crop_rect(rect)
+        key = getattr(self.index, "KEY", -2)
+        at = [k - self.index_first for k in keep]
+        pairs = [(key, at[0])] + list(zip(at, at[1:]))
+        out, flags = [], []
+        for j0 in range(0, len(pairs), self.CROP_CALL):
+            part = pairs[j0:j0 + self.CROP_CALL]
+            made, keys = self.index.CropFrames(blocks, part, tight=True) if tight else self.index.CropFrames(blocks, part)
+            out += list(made)
+            flags += [bool(v) for v in keys]
+        flags[0] = True
+        return out, flags, shown
+
+    def write_crop(self, frames: Sequence[bytes], rect, keep: Sequence[int], fps: float = 15.0, tight: bool = False) -> bytes:
+        """`crop` as an AVI file (avi.write_avi) of the rectangle's size, 4 bw x 4 bh, fourcc CRAM, with this Manager's bit depth and
+        palette."""
+        from .avi import write_avi
+        out, flags, (_, _, w, h) = self.crop(frames, rect, keep, tight=tight)
+        return write_avi(w, h, out, fourcc=b"CRAM", bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
 
     def _index_adopts(self) -> bool:
         return bool(getattr(self.index, "ADOPTS", True))
