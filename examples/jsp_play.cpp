@@ -66,6 +66,18 @@
 //                                most 4096 pairs.  Then OUT.avi is played back through a decoder of its own size: prints "<frame of
 //                                the clip> <crc32 from OUT.avi> <crc32 of that part of the clip's picture>" per frame kept and exits
 //                                with 1 on any difference
+//   jsp_play clip.avi --pan WxH[:loose] FIRST[:COUNT[:STRIDE]] OUT.avi
+//                                MSVideo1: a rectangle of W x H pixels (rounded up to whole 4x4 blocks, clipped to the block grid)
+//                                that FOLLOWS what the frames --thin would keep change, as an AVI file of its own.  ONE seek index from
+//                                the nearest key frame <= FIRST and its activity map (jsp_index_activity); per frame kept the box of
+//                                the non-zero cells since the frame kept before; the rectangle moves, on each axis, the least number of
+//                                blocks that brings the box inside (centred on a box wider than itself; it starts centred on the first
+//                                box, or on the picture).  The first frame is a key pair, every other one the pair from the rectangle at
+//                                the frame kept before to the rectangle now, with JSP_CROP_TIGHT (":loose": without — a frame behind a
+//                                move then codes every block); jsp_index_pan_frames calls of at most 4096 pairs.  Prints "pan blocks
+//                                <bw> <bh>", then OUT.avi is played back through a decoder of its own size: "<frame of the clip> <bx>
+//                                <by> <crc32 from OUT.avi> <crc32 of that rectangle of the clip's picture>" per frame kept, origins in
+//                                blocks with block row 0 at the bottom; exits with 1 on any difference
 //   jsp_play clip.avi --filmstrip N[:scale]
 //                                ONE seek index over the clip (MSVideo1: jsp_index_build; ScreenPressor: jsp_sp_index_build), then ONE
 //                                jsp_index_thumbs / jsp_sp_index_thumbs call for N frames spread evenly over it (frame (k * frames) / N for k < N), each reduced scale x scale pixels to one (4, 8 or 16; default
@@ -102,6 +114,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <deque>
@@ -258,7 +271,9 @@ std::vector<uint8_t> avi_file(const Clip& c, const std::vector<std::pair<const u
 // frame, DecompressP else, never into the previous frame): per frame the CRC-32 of the pixels of the picture shown that 4x4 blocks
 // cover (the X % 4 / Y % 4 remainder pixels are in no MSVideo1 frame) — or, with rw > 0, of the pixels of stored rows ry .. ry + rh - 1,
 // columns rx .. rx + rw - 1 (inside the covered part).  False: an error, printed.
-bool covered_crcs(const Clip& clip, size_t upto, std::vector<uint32_t>& crcs, size_t rx = 0, size_t ry = 0, size_t rw = 0, size_t rh = 0) {
+// `at` (with rw > 0): frame i takes (rx, ry) from (*at)[i] where that entry exists.
+bool covered_crcs(const Clip& clip, size_t upto, std::vector<uint32_t>& crcs, size_t rx = 0, size_t ry = 0, size_t rw = 0, size_t rh = 0,
+                  const std::vector<std::pair<size_t, size_t>>* at = nullptr) {
     jsp_codec* dec = jsp_codec_create(clip.kind, clip.X, clip.Y, clip.bpp, clip.palette.empty() ? nullptr : clip.palette.data(), (int)clip.palette.size(), 0);
     jsp_pool* pool = dec ? jsp_pool_create(0, clip.X, clip.Y, 2) : nullptr;
     bool ok = dec && pool;
@@ -278,6 +293,7 @@ bool covered_crcs(const Clip& clip, size_t upto, std::vector<uint32_t>& crcs, si
         if (!ok) { std::fprintf(stderr, "frame %zu: %s\n", i, jsp_last_error()); break; }
         shown = jsp_previous_frame(dec);
         if (shown && jsp_download(shown, host.data(), npx) != 0) { std::fprintf(stderr, "jsp_download: %s\n", jsp_last_error()); ok = false; break; }
+        if (at && i < at->size()) rx = (*at)[i].first, ry = (*at)[i].second;
         for (size_t y = 0; shown && y < chh; ++y) std::memcpy(cov.data() + y * cw, host.data() + (ry + y) * (size_t)clip.X + rx, cw * 4);
         crcs.push_back(shown ? crc32(reinterpret_cast<const uint8_t*>(cov.data()), cov.size() * 4) : 0u);
     }
@@ -554,6 +570,8 @@ int main(int argc, char** argv) {
     std::string thin_path;
     bool crop = false, crop_tight = false;   // --crop X:Y:W:H[:tight] FIRST[:COUNT[:STRIDE]] OUT.avi: --thin's frames, a part of the picture
     long crop_rect[4] = {0, 0, 0, 0};
+    bool pan = false, pan_tight = true;      // --pan WxH[:loose] FIRST[:COUNT[:STRIDE]] OUT.avi: --thin's frames, a rectangle that follows the changes
+    long pan_size[2] = {0, 0};
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
     long play_first = -1, play_count = -1, play_stride = 1;   // --play-index FIRST[:COUNT[:STRIDE]]: frames played out of a ScreenPressor seek index
     long run_first = -1, run_count = -1, run_stride = 1;      // --index-run FIRST[:COUNT[:STRIDE]]: frames played out of an MSVideo1 seek index
@@ -595,8 +613,21 @@ int main(int argc, char** argv) {
             cut_path = argv[++a];
             if (cut_first < 0 || (colon != std::string::npos && cut_count < 1)) { std::fprintf(stderr, "--cut FIRST[:COUNT] OUT.avi: FIRST >= 0, COUNT >= 1\n"); return 2; }
         }
-        else if ((o == "--thin" || o == "--thin-tight" || o == "--crop") && a + (o == "--crop" ? 3 : 2) < argc) {
+        else if ((o == "--thin" || o == "--thin-tight" || o == "--crop" || o == "--pan") && a + (o == "--crop" || o == "--pan" ? 3 : 2) < argc) {
             thin_tight = o == "--thin-tight";
+            if (o == "--pan") {
+                pan = true;
+                std::string r = argv[++a];
+                if (r.size() > 6 && r.compare(r.size() - 6, 6, ":loose") == 0) {
+                    pan_tight = false;
+                    r.resize(r.size() - 6);
+                }
+                char* end = nullptr;
+                pan_size[0] = std::strtol(r.c_str(), &end, 10);
+                const bool wide = end != r.c_str() && *end == 'x' && end[1];
+                if (wide) pan_size[1] = std::strtol(end + 1, &end, 10);
+                if (!wide || *end || pan_size[0] < 1 || pan_size[1] < 1) { std::fprintf(stderr, "--pan WxH[:loose] FIRST[:COUNT[:STRIDE]] OUT.avi: W >= 1, H >= 1\n"); return 2; }
+            }
             if (o == "--crop") {
                 crop = true;
                 const std::string r = argv[++a];
@@ -696,6 +727,8 @@ int main(int argc, char** argv) {
     if (cut_first >= 0 && (act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--cut goes alone\n"); return 2; }
     if (cut_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--cut: MSVideo1 only (a ScreenPressor key frame needs the entropy encoder)\n"); return 2; }
     if (thin_first >= 0 && (cut_first >= 0 || act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--thin goes alone\n"); return 2; }
+    if (pan && crop) { std::fprintf(stderr, "--pan and --crop do not go together\n"); return 2; }
+    if (pan && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--pan: MSVideo1 only (ScreenPressor codes are entropy-coded in context)\n"); return 2; }
     if (crop && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--crop: MSVideo1 only (ScreenPressor codes are entropy-coded in context)\n"); return 2; }
     if (thin_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--thin: MSVideo1 only (a ScreenPressor frame needs the entropy encoder)\n"); return 2; }
     if (strip > 0 && (step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--filmstrip goes alone\n"); return 2; }
@@ -1101,6 +1134,147 @@ int main(int argc, char** argv) {
         for (long k = 0; k < count; ++k) {
             std::printf("%ld %08x %08x\n", cut_first + k, got[(size_t)k], want[(size_t)(cut_first + k)]);
             if (got[(size_t)k] != want[(size_t)(cut_first + k)]) rc = 1;
+        }
+        return rc;
+    }
+    if (thin_first >= 0 && pan) {   // a rectangle that follows the changes: one index build, its activity map, jsp_index_pan_frames, the file, its playback
+        const size_t n = clip.frames.size();
+        std::vector<size_t> keep;
+        for (long i = thin_first; i < (long)n && (thin_count < 0 || (long)keep.size() < thin_count); i += thin_stride) keep.push_back((size_t)i);
+        if (keep.empty() || (thin_count >= 0 && (long)keep.size() < thin_count)) {
+            std::fprintf(stderr, "--pan: frames %ld, %ld, ... (%ld of them) are not all in the clip (%zu frames)\n", thin_first, thin_first + thin_stride, thin_count, n);
+            rc = 1;
+        }
+        const int nbx = clip.X / 4, nby = clip.Y / 4;
+        const int bw = (int)std::min<long>((pan_size[0] + 3) / 4, nbx), bh = (int)std::min<long>((pan_size[1] + 3) / 4, nby);
+        if (rc == 0 && (bw < 1 || bh < 1)) { std::fprintf(stderr, "--pan: the picture has no 4x4 block\n"); rc = 1; }
+        if (rc == 0) std::printf("pan blocks %d %d\n", bw, bh);
+        std::vector<uint8_t> made;
+        std::vector<size_t> made_lens;
+        std::vector<int> made_keys, xs, ys;                    // xs, ys: the rectangle's origin per frame kept, in blocks, table order
+        if (rc == 0) {
+            size_t k = keep[0];
+            while (k > 0 && !frame_is_key(clip, dec, k)) --k;   // the nearest key frame <= FIRST (frame 0 is one)
+            std::vector<const uint8_t*> srcs;
+            std::vector<size_t> lens;
+            std::vector<uint8_t> keys;
+            for (size_t i = k; i <= keep.back(); ++i) {
+                srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+                lens.push_back(clip.frames[i].second);
+                keys.push_back(i == k || frame_is_key(clip, dec, i) ? 1 : 0);
+            }
+            jsp_index* idx = jsp_index_build(dec, (int)srcs.size(), srcs.data(), lens.data(), keys.data(), kInsignificantLines);
+            if (!idx) { std::fprintf(stderr, "jsp_index_build: %s\n", jsp_last_error()); rc = 1; }
+            // the activity map of the frames behind the first one kept: index frames keep[0] - k + 1 .. keep.back() - k
+            int cols = 0, rows = 0;
+            if (rc == 0 && jsp_index_activity_size(idx, &cols, &rows) != JSP_ZERO_STATE) { std::fprintf(stderr, "jsp_index_activity_size: %s\n", jsp_last_error()); rc = 1; }
+            const long first = (long)(keep[0] - k) + 1, count = (long)(keep.back() - keep[0]);
+            const size_t cell = (size_t)cols * (size_t)rows;
+            std::vector<int32_t> words(cell * (size_t)((count + 1) / 2) + 1);
+            jsp_pool* sheet = nullptr;
+            if (rc == 0 && count > 0) {
+                if (!(sheet = jsp_pool_create(0, (int)cell, (int)((count + 1) / 2), 1))) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
+                uint16_t* out = sheet ? reinterpret_cast<uint16_t*>(jsp_pool_buffer(sheet, 0)) : nullptr;
+                for (long q = 0; rc == 0 && q < count; q += 4096) {
+                    const int m = (int)std::min<long>(4096, count - q);
+                    if (jsp_index_activity(dec, idx, (int)(first + q), m, out + (size_t)q * cell, (size_t)(count - q) * cell) != JSP_ZERO_STATE) {
+                        std::fprintf(stderr, "jsp_index_activity: %s\n", jsp_last_error());
+                        rc = 1;
+                    }
+                }
+                if (rc == 0 && jsp_download(jsp_pool_buffer(sheet, 0), words.data(), cell * (size_t)((count + 1) / 2)) != 0) { std::fprintf(stderr, "jsp_download: %s\n", jsp_last_error()); rc = 1; }
+            }
+            if (sheet) jsp_pool_destroy(sheet);
+            // per frame kept behind the first: the box (x0, x1, y0, y1) in blocks of the non-zero cells since the frame kept before; x1 = 0: none
+            const uint16_t* map = reinterpret_cast<const uint16_t*>(words.data());
+            std::vector<std::array<int, 4>> boxes(keep.size(), std::array<int, 4>{0, 0, 0, 0});
+            for (size_t j = 1; rc == 0 && j < keep.size(); ++j) {
+                int q0 = cols, q1 = -1, r0 = rows, r1 = -1;
+                for (size_t f = keep[j - 1] + 1; f <= keep[j]; ++f)
+                    for (int r = 0; r < rows; ++r)
+                        for (int q = 0; q < cols; ++q)
+                            if (map[((f - keep[0] - 1) * (size_t)rows + (size_t)r) * (size_t)cols + (size_t)q]) {
+                                q0 = std::min(q0, q); q1 = std::max(q1, q); r0 = std::min(r0, r); r1 = std::max(r1, r);
+                            }
+                if (q1 >= 0) boxes[j] = {q0 * 4, std::min((q1 + 1) * 4, nbx), r0 * 4, std::min((r1 + 1) * 4, nby)};
+            }
+            const auto floor_half = [](int v) { return v >= 0 ? v / 2 : -((1 - v) / 2); };
+            const auto axis = [&](int p, int len, int b0, int b1, int room) {
+                if (b1 - b0 > len) p = b0 + floor_half(b1 - b0 - len);
+                else if (b0 < p) p = b0;
+                else if (b1 > p + len) p = b1 - len;
+                return std::max(0, std::min(p, room));
+            };
+            std::array<int, 4> start{0, nbx, 0, nby};           // centred on the first box, or on the picture
+            for (size_t j = 1; j < keep.size(); ++j)
+                if (boxes[j][1] > 0) { start = boxes[j]; break; }
+            int x = std::max(0, std::min(start[0] + floor_half(start[1] - start[0] - bw), nbx - bw));
+            int y = std::max(0, std::min(start[2] + floor_half(start[3] - start[2] - bh), nby - bh));
+            for (size_t j = 0; j < keep.size(); ++j) {
+                if (boxes[j][1] > 0) {
+                    x = axis(x, bw, boxes[j][0], boxes[j][1], nbx - bw);
+                    y = axis(y, bh, boxes[j][2], boxes[j][3], nby - bh);
+                }
+                xs.push_back(x);
+                ys.push_back(y);
+            }
+            for (size_t g0 = 0; rc == 0 && g0 < keep.size(); g0 += 4096) {   // (a call takes 4096 pairs)
+                const size_t m = std::min<size_t>(4096, keep.size() - g0);
+                std::vector<int> from(m), to(m), from_xy(2 * m), to_xy(2 * m), ks(m);
+                for (size_t i = 0; i < m; ++i) {
+                    const size_t j = g0 + i, b = j == 0 ? 0 : j - 1;
+                    from[i] = j == 0 ? JSP_CROP_KEY : (int)(keep[j - 1] - k);
+                    to[i] = (int)(keep[j] - k);
+                    from_xy[2 * i] = xs[b], from_xy[2 * i + 1] = ys[b];
+                    to_xy[2 * i] = xs[j], to_xy[2 * i + 1] = ys[j];
+                }
+                std::vector<size_t> ls(m);
+                size_t total = 0;
+                const int flags = pan_tight ? JSP_CROP_TIGHT : 0;
+                // asked twice: the lengths (cap 0 is a refusal that still sets them), then the bytes
+                if (jsp_index_pan_frames(dec, idx, bw, bh, (int)m, from.data(), to.data(), from_xy.data(), to_xy.data(), flags, nullptr, 0, ls.data(), ks.data(), &total) == JSP_ZERO_STATE || total == 0) {
+                    std::fprintf(stderr, "jsp_index_pan_frames: %s\n", jsp_last_error());
+                    rc = 1;
+                    break;
+                }
+                const size_t at = made.size();
+                made.resize(at + total);
+                if (jsp_index_pan_frames(dec, idx, bw, bh, (int)m, from.data(), to.data(), from_xy.data(), to_xy.data(), flags, made.data() + at, total, ls.data(), ks.data(), &total) != JSP_ZERO_STATE) {
+                    std::fprintf(stderr, "jsp_index_pan_frames: %s\n", jsp_last_error());
+                    rc = 1;
+                }
+                made_lens.insert(made_lens.end(), ls.begin(), ls.end());
+                made_keys.insert(made_keys.end(), ks.begin(), ks.end());
+            }
+            if (idx) jsp_index_destroy(idx);
+        }
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        if (rc != 0) return rc;
+        std::vector<std::pair<const uint8_t*, size_t>> out_frames;
+        std::vector<uint8_t> out_keys;
+        size_t at = 0;
+        for (size_t j = 0; j < keep.size(); ++j) {
+            out_frames.emplace_back(made.data() + at, made_lens[j]);
+            out_keys.push_back(j == 0 || made_keys[j] ? 1 : 0);
+            at += made_lens[j];
+        }
+        Clip header;                                            // the clip's stream at the rectangle's size
+        header.X = 4 * bw, header.Y = 4 * bh, header.bpp = clip.bpp, header.kind = clip.kind, header.usec = clip.usec, header.palette = clip.palette;
+        const std::vector<uint8_t> file = avi_file(header, out_frames, out_keys);
+        FILE* f = std::fopen(thin_path.c_str(), "wb");
+        if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size()) { std::fprintf(stderr, "cannot write %s\n", thin_path.c_str()); if (f) std::fclose(f); return 1; }
+        std::fclose(f);
+        // OUT.avi played back through the ordinary decode loop of a decoder of ITS size, beside the rectangle of the clip's own pictures
+        Clip panned;
+        if (!load(thin_path.c_str(), panned) || panned.frames.size() != keep.size() || panned.X != 4 * bw || panned.Y != 4 * bh) { std::fprintf(stderr, "cannot read %s back\n", thin_path.c_str()); return 1; }
+        std::vector<std::pair<size_t, size_t>> origins(keep.back() + 1, {0, 0});
+        for (size_t j = 0; j < keep.size(); ++j) origins[keep[j]] = {4 * (size_t)xs[j], 4 * (size_t)ys[j]};
+        std::vector<uint32_t> got, want;
+        if (!covered_crcs(panned, panned.frames.size(), got) || !covered_crcs(clip, keep.back() + 1, want, 0, 0, 4 * (size_t)bw, 4 * (size_t)bh, &origins)) return 1;
+        for (size_t j = 0; j < keep.size(); ++j) {
+            std::printf("%zu %d %d %08x %08x\n", keep[j], xs[j], ys[j], got[j], want[keep[j]]);
+            if (got[j] != want[keep[j]]) rc = 1;
         }
         return rc;
     }

@@ -87,6 +87,11 @@ extern class JspNative {
                                                                        n:Int, from:RawConstPointer<Int>, to:RawConstPointer<Int>, flags:Int,
                                                                        out:RawPointer<UInt8>, cap:SizeT, lens:RawPointer<SizeT>, keys:RawPointer<Int>,
                                                                        total:RawPointer<SizeT>):Int;
+    // the same for a rectangle of bw x bh blocks that moves: per pair its origin (x, y) at `from` (fromXy, not read for key pairs) and at `to` (toXy)
+    @:native("jsp_index_pan_frames")   static function indexPanFrames(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, bw:Int, bh:Int, n:Int,
+                                                                      from:RawConstPointer<Int>, to:RawConstPointer<Int>, fromXy:RawConstPointer<Int>,
+                                                                      toXy:RawConstPointer<Int>, flags:Int, out:RawPointer<UInt8>, cap:SizeT,
+                                                                      lens:RawPointer<SizeT>, keys:RawPointer<Int>, total:RawPointer<SizeT>):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)

@@ -821,6 +821,40 @@ int jsp_index_crop_bound(const jsp_index* idx, int bw, int bh, size_t* bytes);
 int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to, int flags,
                           uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total);
 
+/* PAN A CROP: the frames of a block rectangle THAT MOVES — a 640x360 clip that follows the action across a 1080p recording, the
+ * rectangle jsp_index_activity names ("the rectangle a frame changed to scroll the view to") joined to jsp_index_crop_frames.  Codes
+ * carry no position, so a moved rectangle stays a gather: the block at position j of the new rectangle is either the same 16 words
+ * as the block that stood at position j of the old one (skipped) or gets the code of its last writer (copied).
+ *   A CALL has one rectangle size (bw, bh) in 4x4 blocks, nb = bw * bh, and n pairs.  Pair k: from[k], to[k], the origin
+ *       A = (from_xy[2k], from_xy[2k+1]) of the rectangle at frame `from` and B = (to_xy[2k], to_xy[2k+1]) at frame `to`, both (bx, by)
+ *       in table order as in crop.  srcA(j), srcB(j): crop's src(j) for the two origins.
+ *   THE RULE (PAN, stated in msv1_index_pan_kernels.hip).  A pair is
+ *         a KEY pair, from == JSP_CROP_KEY: crop's key pair of rectangle B at `to`; from_xy is not read;
+ *         a STILL gap pair, A == B and -1 <= from < to < nframes: crop's gap pair (Delta, or Tight with JSP_CROP_TIGHT);
+ *         a MOVED pair, A != B and -1 <= from <= to, 0 <= to < nframes (from == to only here: a pan across a picture that stands
+ *           still).  Without JSP_CROP_TIGHT: the bytes and refusals of the KEY pair (B, to), keys[k] = 1.  With it: block j is DROPPED
+ *           when P(from)[srcA(j)] and P(to)[srcB(j)] are both defined and equal in all 16 words, else KEPT — "written in the gap"
+ *           plays no part.  A kept block gives the whole code of the last writer <= to of srcB(j); without one it refuses ("no
+ *           writer"), with a cut code it refuses ("cut"); a dropped block never refuses.  Run heads and counts are Tight's, in j.
+ *   PROMISED: a fresh decoder of 4 bw x 4 bh pixels fed a KEY pair's frame as a key frame, then the frames of pairs chained by
+ *       to[k-1] == from[k] and to_xy[k-1] == from_xy[k], holds after each the pixels of rectangle B of the source picture of to[k].  A
+ *       call whose pairs are all KEY or STILL with one origin throughout returns byte for byte what jsp_index_crop_frames returns
+ *       for that rectangle (lens, keys, total and the refusal texts too, apart from the prefix).  A moved tight frame is never longer
+ *       than the KEY pair (B, to).  NOT promised: the exclusions of KeyFrame.
+ *   REFUSED as in crop, the text starting with "index_pan:"; a moved pair reads "(from -> to, moved)", and the picture's block number
+ *       is srcB(j).
+ *   Everything else is jsp_index_crop_frames', word for word: jsp_index_crop_bound(idx, bw, bh) sizes `out` (HOST memory, frames back
+ *       to back), lens[], keys[] (may be null) and *total set when only `cap` is short, zeros and nothing written after every other
+ *       error, slices under "msv1_index_delta_slice" with a sizes launch for all slices first, a scratch of the index's own that
+ *       jsp_index_info counts, synchronised on return, THE CODEC ONLY LENT.  Two launches per slice: msv1_index_pan_sizes_kernel,
+ *       msv1_index_pan_gather_kernel.
+ *   ERRORS before anything is queued, in this order: a null argument (keys may be null; from_xy may be null only when every pair is a
+ *       KEY pair); not an MSVideo1 codec ("index: MSVideo1 only"); an index of another codec; bw or bh outside 1 .. nbx / 1 .. nby
+ *       (also: a picture without a block); n outside 1 .. 4096; unknown flag bits; the first bad pair — its frames by its kind, then B
+ *       outside the grid, then for gap pairs A outside the grid (the text names the pair and which); an asynchronous frame in flight. */
+int jsp_index_pan_frames(jsp_codec* c, jsp_index* idx, int bw, int bh, int n, const int* from, const int* to, const int* from_xy,
+                         const int* to_xy, int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

@@ -806,6 +806,50 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
             at += lens[j]
         return out, [bool(keys[j]) for j in range(n)]
 
+    def PanFrames(self, size, pairs, tight: bool = False):
+        """CropFrames for a rectangle of size = (bw, bh) blocks that MOVES: (list of bytes, list of bool), one frame per pair.  A pair
+        is (a, b, (abx, aby), (bbx, bby)) — the rectangle stands at (abx, aby) in the picture of frame a and at (bbx, bby) in that of
+        frame b, origins in table order as CropFrames' — or (SeekIndex.KEY, t, None, (bx, by)), the key frame of the rectangle there.
+        With equal origins a pair is CropFrames' gap pair; with different ones (a <= b: the picture may stand still) the frame codes
+        every block, or with tight only those where the block that stood at that position of the rectangle before differs from the
+        one that stands there now (jsp_index_pan_frames).  A decoder of 4 bw x 4 bh pixels fed a key pair's frame and then chained
+        pairs' frames shows the rectangle along its path.  CodecError with the C text; nothing is returned then."""
+        codec = self._open("index_pan")
+        bw, bh = (int(v) for v in size)
+        pairs = [(int(a), int(b), None if fa is None else (int(fa[0]), int(fa[1])), (int(tb[0]), int(tb[1]))) for a, b, fa, tb in pairs]
+        n = len(pairs)
+        m = max(n, 1)
+        frm = (C.c_int * m)(*[p[0] for p in pairs])
+        to = (C.c_int * m)(*[p[1] for p in pairs])
+        to_xy = (C.c_int * (2 * m))(*[v for p in pairs for v in p[3]])
+        if all(p[2] is None for p in pairs):
+            from_xy = None
+        else:   # (a key pair's origin at `from` is not read)
+            from_xy = (C.c_int * (2 * m))(*[v for p in pairs for v in (p[2] if p[2] is not None else p[3])])
+        lens = (C.c_size_t * m)()
+        keys = (C.c_int * m)()
+        total = C.c_size_t(0)
+        flags = self._CROP_TIGHT if tight else 0
+        call = self._lib.jsp_index_pan_frames
+        bound = C.c_size_t(0)
+        self._lib.jsp_index_crop_bound(self._h, bw, bh, C.byref(bound))
+        cap = n * bound.value if 1 <= n <= 4096 else 0
+        if cap > DELTA_ASK_TWICE:   # many large frames: the lengths first (cap 0 is the refusal that still sets them), then the bytes
+            if call(codec._h, self._h, bw, bh, n, frm, to, from_xy, to_xy, flags, None, 0, lens, keys, C.byref(total)) == 0 or total.value == 0:
+                raise CodecError(N.last_error())
+            cap = total.value
+        buf = (C.c_uint8 * max(cap, 1))()
+        if call(codec._h, self._h, bw, bh, n, frm, to, from_xy, to_xy, flags, buf, len(buf), lens, keys, C.byref(total)) != 0:
+            raise CodecError(N.last_error())
+        dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first call adds the scratch the frames are assembled in)
+        self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
+        self.device_bytes, self.host_bytes = dev.value, host.value
+        view, out, at = memoryview(buf), [], 0
+        for j in range(n):
+            out.append(bytes(view[at:at + lens[j]]))
+            at += lens[j]
+        return out, [bool(keys[j]) for j in range(n)]
+
     def _open(self, who: str) -> _NativeCodec:
         if not self._h:
             raise CodecError(f"{who}: the index is closed")

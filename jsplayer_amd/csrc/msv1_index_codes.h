@@ -1,8 +1,9 @@
 // What the stream-producing calls of an MSVideo1 seek index share — the key frame (msv1_index_keyframe_kernels.hip, which states
 // when a code is WHOLE), the inter frame over a gap (msv1_index_delta_kernels.hip, which states WRITTEN and KEPT) and the frames of
-// a block rectangle (msv1_index_crop_kernels.hip): where a writer's code lies and how long it is, whether a gap writes or keeps a
-// block, the workgroup's exclusive scan of byte counts, the sum of the workgroup totals before one's own, and the way an LDS image
-// of a workgroup's output leaves in 16-byte pieces.  Workgroups of INDEX_CODES_WG lanes.
+// a block rectangle that stands (msv1_index_crop_kernels.hip) or moves (msv1_index_pan_kernels.hip): where a writer's code lies and how
+// long it is, whether a gap writes or keeps a block, a block of a picture of the index, the workgroup's exclusive scan of byte
+// counts, the sum of the workgroup totals before one's own, and the way an LDS image of a workgroup's output leaves in 16-byte
+// pieces.  Workgroups of INDEX_CODES_WG lanes.
 #pragma once
 #include "msv1_block_io.h"
 
@@ -73,6 +74,31 @@ __device__ __forceinline__ bool tight_kept(const Msv1IndexSrc& s, int blk, int a
 #pragma unroll
     for (int k = 0; k < 16; ++k) diff |= pa[k] ^ pb[k];
     return diff != 0u;
+}
+
+// P(t)[blk] of THE TIGHT RULE, or "not DEFINED", for a block whose last writer <= t is known: the 16 words frame f makes of block
+// `blk`, else (f = -1: no writer) the block of the picture before the range; false, and px untouched, when neither exists.
+template <int BITS>
+__device__ __forceinline__ bool picture_block_of(const Msv1IndexSrc& s, int blk, int f, const uint32_t* s_pal, uint32_t (&px)[16]) {
+    if (f >= 0) {
+        index_decode<BITS>(s, f, blk, s_pal, px);
+        return true;
+    }
+    if (s.before == nullptr) return false;
+    const uint32_t* p = s.before + (size_t)(blk / s.nbx) * 4u * (size_t)s.X + (size_t)(blk % s.nbx) * 4u;
+    if (s.before_vec) load_block<true>(p, s.X, px);
+    else load_block<false>(p, s.X, px);
+    return true;
+}
+
+// The same for a frame t >= -1: the last writer <= t is looked up first (t = -1: only the picture before the range can define it).
+// What tight_kept asks of both ends of a gap for one block, for callers that compare two different blocks
+// (msv1_index_pan_kernels.hip).
+template <int BITS>
+__device__ __forceinline__ bool picture_block(const Msv1IndexSrc& s, int blk, int t, const uint32_t* s_pal, uint32_t (&px)[16]) {
+    int w;
+    const uint32_t m = t >= 0 ? index_last_writer(s, blk, t, w) : 0u;
+    return picture_block_of<BITS>(s, blk, m != 0u ? index_word_frame(w, m) : -1, s_pal, px);
 }
 
 // Exclusive scan of `mine` over the workgroup's lanes: inclusive over the wave's lanes by shuffles, the waves' sums through LDS

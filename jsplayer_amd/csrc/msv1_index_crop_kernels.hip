@@ -157,6 +157,8 @@ __global__ __launch_bounds__(WG) void msv1_index_crop_sizes_kernel(const Msv1Ind
     }
 }
 
+// (msv1_index_pan_gather_kernel, msv1_index_pan_kernels.hip, is a copy of this kernel with the origin read per pair: a fix to one
+// belongs in the other too.)
 template <int BITS>
 __global__ __launch_bounds__(WG) void msv1_index_crop_gather_kernel(const Msv1IndexSrc s, const Msv1CropRect r, Msv1CropScratch d) {
     constexpr int IMAGE = CR_WG_BLOCKS * (BITS == 16 ? 18 : 10);                 // bytes of a workgroup's output at its bound

@@ -8,6 +8,7 @@
 
 #include "codec.h"
 #include "msv1_index_crop_layout.h"
+#include "msv1_index_pan_layout.h"
 #include "msv1_seek.h"
 
 using namespace jsp;
@@ -40,15 +41,17 @@ struct jsp_index {
     PinnedBuffer h_delta;                  // ... and the host's side of the list, the statuses and the totals (both: first call)
     DeviceBuffer d_crop;                   // jsp_index_crop_frames: the same for a slice of pairs of a rectangle (CropLayout) ...
     PinnedBuffer h_crop;                   // ... and the host's side of it (both: first call)
+    DeviceBuffer d_pan;                    // jsp_index_pan_frames: the same with the pairs' origins in front (PanLayout) ...
+    PinnedBuffer h_pan;                    // ... and the host's side of it (both: first call)
     uint64_t device_bytes() const {
         uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_frame_list.cap + d_play_dsts.cap +
-                     d_key_frame.cap + d_delta.cap + d_crop.cap;
+                     d_key_frame.cap + d_delta.cap + d_crop.cap + d_pan.cap;
         for (const auto& c : chunks) n += c->stream.cap + c->desc.cap + c->frames.cap;
         return n;
     }
     uint64_t host_bytes() const {
         return sizeof(*this) + chunks.size() * sizeof(Chunk) + significance.size() * sizeof(int) + reported.size() + block_changes.size() +
-               h_frame_list.cap + h_play_dsts.cap + h_key_frame.cap + h_delta.cap + h_crop.cap;
+               h_frame_list.cap + h_play_dsts.cap + h_key_frame.cap + h_delta.cap + h_crop.cap + h_pan.cap;
     }
 };
 
@@ -1023,6 +1026,8 @@ extern "C" int jsp_index_crop_bound(const jsp_index* idx, int bw, int bh, size_t
     return JSP_ZERO_STATE;
 }
 
+// (jsp_index_pan_frames below repeats this function's slices, refusals and gather loop with an origin per pair; this call is pinned and
+// is not routed through it, so a fix to the slice, refusal or gather logic here belongs there too.)
 extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to,
                                      int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
     const char* who = "index_crop";
@@ -1143,6 +1148,169 @@ extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int b
             size_t bytes = 0;
             for (size_t i = 0; i < m; ++i) bytes += length[j0 + i];
             JSP_HIP(hipMemcpyAsync(out + at, k.out, bytes, hipMemcpyDeviceToHost, c->stream));
+            JSP_HIP(hipStreamSynchronize(c->stream));
+            at += bytes;
+        }
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        zero();
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
+// ---- a clip that pans across the picture: jsp_index_crop_frames with an origin per pair and end of a pair (the rule:
+// msv1_index_pan_kernels.hip).  A moved pair of a call without JSP_CROP_TIGHT goes to the device as the key pair of its rectangle at
+// `to`.  Slices, launches and the contract are jsp_index_crop_frames' — the body is that function's, copied, with the origins added:
+// a fix to the slice, refusal or gather logic belongs in both.  Into HOST memory; the codec is only lent.
+extern "C" int jsp_index_pan_frames(jsp_codec* c, jsp_index* idx, int bw, int bh, int n, const int* from, const int* to, const int* from_xy,
+                                    const int* to_xy, int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
+    const char* who = "index_pan";
+    const bool n_ok = n >= 1 && n <= 4096;
+    const auto zero = [&]() {
+        if (total) *total = 0;
+        if (lens && n_ok) std::fill(lens, lens + n, (size_t)0);
+        if (keys && n_ok) std::fill(keys, keys + n, 0);
+    };
+    zero();
+    if (!c || !idx || !from || !to || !to_xy || !lens || !total || (!out && cap)) return fail("%s: null argument", who);
+    if (!from_xy && n_ok && std::any_of(from, from + n, [](int f) { return f != JSP_CROP_KEY; })) return fail("%s: null argument", who);
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("%s: the index was built by another codec", who);
+    const Msv1IndexSrc& src = idx->src;
+    if (src.nblocks < 1 || !crop_rect_ok(src.nbx, src.nby, 0, 0, bw, bh)) {
+        set_error("%s: the rectangle's size (%d x %d blocks) is outside the block grid (%d x %d blocks)", who, bw, bh,
+                  src.nblocks < 1 ? 0 : src.nbx, src.nblocks < 1 ? 0 : src.nby);
+        return JSP_ERROR_OCCURED;
+    }
+    if (!n_ok) return fail("%s: n is outside 1..4096", who);
+    if (flags & ~JSP_CROP_TIGHT) return fail("%s: unknown flag bits", who);
+    for (int j = 0; j < n; ++j) {
+        const int* a = from_xy ? from_xy + 2 * j : to_xy + 2 * j;   // (null: every pair is a key pair, and a key pair's A is not read)
+        const int* b = to_xy + 2 * j;
+        switch (pan_pair_check(idx->nframes, src.nbx, src.nby, bw, bh, from[j], to[j], JSP_CROP_KEY, a, b)) {
+            case PAN_OK: continue;
+            case PAN_BAD_FRAMES:
+                set_error("%s: pair %d (%d, %d) is neither a gap of the index (-1 <= from < to < %d frames; from <= to where the rectangle "
+                          "moves) nor a key pair (from = %d, 0 <= to)",
+                          who, j, from[j], to[j], idx->nframes, JSP_CROP_KEY);
+                break;
+            case PAN_BAD_TO_ORIGIN:
+                set_error("%s: pair %d (%d, %d): the rectangle at `to` (%d, %d, %d x %d blocks) is outside the block grid (%d x %d blocks)", who, j,
+                          from[j], to[j], b[0], b[1], bw, bh, src.nbx, src.nby);
+                break;
+            case PAN_BAD_FROM_ORIGIN:
+                set_error("%s: pair %d (%d, %d): the rectangle at `from` (%d, %d, %d x %d blocks) is outside the block grid (%d x %d blocks)", who,
+                          j, from[j], to[j], a[0], a[1], bw, bh, src.nbx, src.nby);
+                break;
+        }
+        return JSP_ERROR_OCCURED;
+    }
+    if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
+    const bool tight = (flags & JSP_CROP_TIGHT) != 0;
+    const auto kind_of = [&](size_t p) { return pan_kind(from[p], JSP_CROP_KEY, from_xy ? from_xy + 2 * p : to_xy + 2 * p, to_xy + 2 * p); };
+    try {
+        c->activate();
+        const size_t nb = (size_t)bw * (size_t)bh, nwg = (size_t)msv1_keyframe_workgroups((int)nb);
+        const size_t bound = nb * (src.bits == 16 ? 18u : 10u);
+        size_t S = (size_t)c->index_delta_slice;
+        if (S == 0) S = std::clamp<uint64_t>(kDeltaSliceBudget / pan_layout(1, nb, nwg, bound).bytes, 1, 4096);
+        S = std::min(S, (size_t)n);
+        const PanLayout pl = pan_layout(S, nb, nwg, bound);
+        const CropLayout& l = pl.c;
+        idx->d_pan.reserve(pl.bytes);
+        idx->h_pan.reserve(l.records_at + 16);
+        uint8_t* d = idx->d_pan.as<uint8_t>();
+        uint8_t* h = idx->h_pan.as<uint8_t>();
+        const Msv1PanScratch k{reinterpret_cast<const int32_t*>(d + pl.origins_at),
+                               {reinterpret_cast<const int32_t*>(d + l.pairs_at), reinterpret_cast<const uint64_t*>(d + l.bases_at),
+                                reinterpret_cast<uint32_t*>(d + l.status_at), reinterpret_cast<uint32_t*>(d + l.totals_at),
+                                reinterpret_cast<uint32_t*>(d + l.first_at), reinterpret_cast<uint32_t*>(d + l.counts_at),
+                                reinterpret_cast<uint32_t*>(d + l.records_at), d + l.out_at}};
+        std::vector<size_t> length((size_t)n, 0);
+        std::vector<uint8_t> all_coded((size_t)n, 0);
+        // pairs [j0, j0 + m), their origins and where their frames start go to the device, then the sizes launch (not when the records are there)
+        const auto sizes = [&](size_t j0, size_t m, bool launch) {
+            int32_t* ho = reinterpret_cast<int32_t*>(h + pl.origins_at);
+            int32_t* hp = reinterpret_cast<int32_t*>(h + l.pairs_at);
+            uint64_t* hb = reinterpret_cast<uint64_t*>(h + l.bases_at);
+            uint64_t at = 0;
+            for (size_t i = 0; i < m; ++i) {
+                const size_t p = j0 + i;
+                const PanKind kind = kind_of(p);
+                const int* b = to_xy + 2 * p;
+                const int* a = kind == PAN_KEY ? b : from_xy + 2 * p;
+                ho[4 * i] = a[0];
+                ho[4 * i + 1] = a[1];
+                ho[4 * i + 2] = b[0];
+                ho[4 * i + 3] = b[1];
+                hp[2 * i] = kind == PAN_MOVED && !tight ? JSP_CROP_KEY : from[p];
+                hp[2 * i + 1] = to[p];
+                hb[i] = at;
+                at += length[p];
+            }
+            JSP_HIP(hipMemcpyAsync(d, h, l.status_at, hipMemcpyHostToDevice, c->stream));
+            if (!launch) return;
+            JSP_HIP(hipMemsetAsync(k.c.status, 0xFF, sizeof(uint32_t) * m, c->stream));
+            msv1_launch_index_pan_sizes(src, bw, bh, (int)m, k, tight, c->stream);
+            JSP_HIP(hipGetLastError());
+        };
+        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
+            const size_t m = std::min(S, (size_t)n - j0);
+            sizes(j0, m, true);
+            JSP_HIP(hipMemcpyAsync(h + l.status_at, d + l.status_at, l.first_at - l.status_at, hipMemcpyDeviceToHost, c->stream));
+            JSP_HIP(hipStreamSynchronize(c->stream));
+            const uint32_t* status = reinterpret_cast<const uint32_t*>(h + l.status_at);
+            const uint32_t* totals = reinterpret_cast<const uint32_t*>(h + l.totals_at);
+            const uint32_t* counts = reinterpret_cast<const uint32_t*>(h + l.counts_at);
+            for (size_t i = 0; i < m; ++i) {
+                if (status[i] != 0xFFFFFFFFu) {   // refused: the first pair, and its first block of the rectangle, that says so
+                    const size_t p = j0 + i;
+                    const uint32_t j = status[i] >> 1;
+                    const long long blk = (long long)crop_src_block(src.nbx, to_xy[2 * p], to_xy[2 * p + 1], bw, (int64_t)j);
+                    char what[64];
+                    const PanKind kind = kind_of(p);
+                    if (kind == PAN_KEY) snprintf(what, sizeof(what), "(key, %d)", to[p]);
+                    else if (kind == PAN_STILL) snprintf(what, sizeof(what), "(%d, %d]", from[p], to[p]);
+                    else snprintf(what, sizeof(what), "(%d -> %d, moved)", from[p], to[p]);
+                    if ((status[i] & 1u) == MSV1_KEYFRAME_NO_WRITER) {
+                        set_error("%s: pair %d %s: block %u of the rectangle (block %lld of the picture) has no writer up to frame %d in the index",
+                                  who, (int)p, what, j, blk, to[p]);
+                    } else {
+                        uint32_t* writer = reinterpret_cast<uint32_t*>(h + l.records_at);
+                        JSP_HIP(hipMemcpyAsync(writer, k.c.records + 2 * (i * nb + j), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                        JSP_HIP(hipStreamSynchronize(c->stream));
+                        set_error("%s: pair %d %s: the code of block %u of the rectangle (block %lld of the picture) in frame %u, its last "
+                                  "writer, is cut off by the end of the frame's data",
+                                  who, (int)p, what, j, blk, *writer);
+                    }
+                    return JSP_ERROR_OCCURED;
+                }
+                size_t coded = 0;
+                for (size_t g = 0; g < nwg; ++g) {
+                    length[j0 + i] += totals[i * nwg + g];
+                    coded += counts[i * nwg + g];
+                }
+                all_coded[j0 + i] = coded == nb;
+                if (length[j0 + i] > bound) throw std::runtime_error(std::string(who) + ": a frame is longer than its bound");
+            }
+        }
+        size_t sum = 0;
+        for (int j = 0; j < n; ++j) {
+            sum += (lens[j] = length[(size_t)j]);
+            if (keys) keys[j] = all_coded[(size_t)j];
+        }
+        *total = sum;
+        if (cap < sum) return fail("%s: cap is smaller than the frames (*total has their length, lens[] each frame's)", who);
+        size_t at = 0;
+        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
+            const size_t m = std::min(S, (size_t)n - j0);
+            sizes(j0, m, S < (size_t)n);
+            msv1_launch_index_pan_gather(src, bw, bh, (int)m, k, c->stream);
+            JSP_HIP(hipGetLastError());
+            size_t bytes = 0;
+            for (size_t i = 0; i < m; ++i) bytes += length[j0 + i];
+            JSP_HIP(hipMemcpyAsync(out + at, k.c.out, bytes, hipMemcpyDeviceToHost, c->stream));
             JSP_HIP(hipStreamSynchronize(c->stream));
             at += bytes;
         }

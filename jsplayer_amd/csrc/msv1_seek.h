@@ -180,4 +180,15 @@ void msv1_launch_index_crop_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r
                                   hipStream_t stream);
 void msv1_launch_index_crop_gather(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, hipStream_t stream);
 
+// The device scratch of jsp_index_pan_frames for one slice of pairs: crop's, and beside the pair words the pairs' origins, checked
+// against the block grid by the host (pan_pair_check, msv1_index_pan_layout.h).
+struct Msv1PanScratch {
+    const int32_t* origins;          // per pair: x, y of the rectangle at `from` (a key pair: not read), x, y at `to`, in blocks
+    Msv1CropScratch c;               // c.pairs: a moved pair of a call without the tight flag stands there as the key pair (to)
+};
+// ONE launch each (msv1_index_pan_kernels.hip, which states the rule), grid.y = the pair, in the shape of the two crop launches; the
+// rectangle is bw x bh blocks for every pair.  tight: THE TIGHT RULE for still gap pairs, the two-block compare for moved ones.
+void msv1_launch_index_pan_sizes(const Msv1IndexSrc& src, int bw, int bh, int npairs, const Msv1PanScratch& d, bool tight, hipStream_t stream);
+void msv1_launch_index_pan_gather(const Msv1IndexSrc& src, int bw, int bh, int npairs, const Msv1PanScratch& d, hipStream_t stream);
+
 }  // namespace jsp

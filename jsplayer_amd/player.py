@@ -20,7 +20,8 @@ index, one `Play` launch per batch of free buffers; `preview` / `filmstrip` are 
 `next_change` say where and when the picture changes, from the index's `Activity` map (changed pixels per frame and 16x16 cell);
 `cut` / `write_cut` give the clip from any frame on as frames and flags / as an AVI file, its first frame the index's `KeyFrame`;
 `thin` / `write_thin` the clip made of any ascending list of frames, the gaps spanned by the index's `DeltaFrames`.  `crop_rect` / `crop` / `write_crop`
-the same list of frames for a part of the picture, from the index's `CropFrames`.  `View` is the zoom / scroll / fit state of Main
+the same list of frames for a part of the picture, from the index's `CropFrames`; `follow` / `pan` / `write_pan` for a part that follows what
+changes, from `activity` and the index's `PanFrames`.  `View` is the zoom / scroll / fit state of Main
 (Main.hx:288-319, 1186-1278) and `Manager.present` draws the window it shows of a frame buffer, one launch.  Timers, bitmaps and audio
 of the reference's Manager are not rebuilt.
 """
@@ -426,6 +427,123 @@ class Manager:
         from .avi import write_avi
         out, flags, (_, _, w, h) = self.crop(frames, rect, keep, tight=tight)
         return write_avi(w, h, out, fourcc=b"CRAM", bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
+
+    # -- a clip that follows the action: the activity map joined to the attached index's PanFrames (jsp_index_pan_frames) ------------------
+    def pan_size(self, size):
+        """(bw, bh): `size` = (w, h) display pixels rounded up to 4x4 blocks and clipped to the block grid.  ValueError when nothing is left."""
+        w, h = (int(v) for v in size)
+        nbx, nby = self.vi.X // 4, self.vi.Y // 4
+        bw, bh = min((w + 3) // 4, nbx), min((h + 3) // 4, nby)
+        if bw < 1 or bh < 1:
+            raise ValueError(f"pan: nothing of a rectangle of {(w, h)} pixels lies in the picture's blocks")
+        return bw, bh
+
+    @staticmethod
+    def _follow_axis(p: int, n: int, b0: int, b1: int, room: int) -> int:
+        """Where a span [p, p + n) goes so that [b0, b1) lies inside it: the least move, or centred on a wider box; then within [0, room]."""
+        if b1 - b0 > n:
+            p = b0 + (b1 - b0 - n) // 2
+        elif b0 < p:
+            p = b0
+        elif b1 > p + n:
+            p = b1 - n
+        return max(0, min(p, room))
+
+    def follow(self, size, keep: Sequence[int], start=None):
+        """A path [(frame, bx, by), ...], one entry per frame of `keep` (strictly ascending, all in the attached index), for a rectangle
+        of `size` display pixels (pan_size) that follows what the frames change: plain host arithmetic on activity().  Origins are in
+        blocks in table order (block row 0 the BOTTOM of the picture as displayed), as PanFrames takes them.  For entry k the box is
+        the union of the non-zero 16 x 16 cells of the index frames (keep[k - 1], keep[k]], in blocks, clipped to the grid.  An empty
+        box, or one inside the rectangle, leaves the rectangle where it is; otherwise on each axis it moves the least number of
+        blocks that brings the box inside, or centres on a box wider than itself, and is clamped to the grid.  It starts at `start`
+        = (bx, by), clamped; without one centred on the first non-empty box, or on the picture when there is none.  ValueError as
+        `crop`'s for `keep`, and for an index without an activity map."""
+        keep = [int(k) for k in keep]
+        if not keep:
+            raise ValueError("pan: keep is empty")
+        for prev, k in zip(keep, keep[1:]):
+            if k <= prev:
+                raise ValueError(f"pan: keep is not strictly ascending ({k} after {prev})")
+        for k in keep:
+            if not self._in_index(k):
+                raise ValueError(f"pan: frame {k} is not in the attached seek index")
+        bw, bh = self.pan_size(size)
+        nbx, nby = self.vi.X // 4, self.vi.Y // 4
+        cells = self.activity()
+        cells = cells if isinstance(cells, np.ndarray) else cells.cpu().numpy()
+        busy = cells != 0
+        rows, cols = busy.any(axis=2), busy.any(axis=1)           # [frame, grid row], [frame, grid column]
+        boxes = [None]
+        for prev, k in zip(keep, keep[1:]):
+            a, b = prev - self.index_first + 1, k - self.index_first + 1
+            rs, qs = np.nonzero(rows[a:b].any(axis=0))[0], np.nonzero(cols[a:b].any(axis=0))[0]
+            if rs.size == 0:
+                boxes.append(None)
+            else:   # (x0, x1, y0, y1) in blocks: a cell is 4 x 4 of them
+                boxes.append((int(qs[0]) * 4, min((int(qs[-1]) + 1) * 4, nbx), int(rs[0]) * 4, min((int(rs[-1]) + 1) * 4, nby)))
+        if start is not None:
+            x, y = max(0, min(int(start[0]), nbx - bw)), max(0, min(int(start[1]), nby - bh))
+        else:
+            x0, x1, y0, y1 = next((b for b in boxes if b is not None), (0, nbx, 0, nby))
+            x = max(0, min(x0 + (x1 - x0 - bw) // 2, nbx - bw))
+            y = max(0, min(y0 + (y1 - y0 - bh) // 2, nby - bh))
+        path = []
+        for k, box in zip(keep, boxes):
+            if box is not None:
+                x = self._follow_axis(x, bw, box[0], box[1], nbx - bw)
+                y = self._follow_axis(y, bh, box[2], box[3], nby - bh)
+            path.append((k, x, y))
+        return path
+
+    PAN_CALL = 4096   # pairs in one PanFrames call (jsp_index_pan_frames takes no more)
+
+    def pan(self, frames: Sequence[bytes], size, path, tight: bool = True):
+        """The clip of a rectangle of `size` display pixels (pan_size) along `path` = [(frame, bx, by), ...] as `follow` returns it:
+        (list of frame bytes, key flags, the display rectangles (x, y, w, h) top row first, one per entry).  Entry 0 is the
+        rectangle's key frame at its first position; entry k the frame from the rectangle at path[k - 1] in the picture of that
+        frame to the rectangle at path[k] in the picture of this one — all from the index's PanFrames, in calls of at most 4096
+        pairs.  tight (the default): a frame codes only the blocks that differ from the block that stood at the same place of the
+        rectangle before; else a frame behind a move codes every block.  flags[0] is True; a later flag says that the frame codes
+        every block.  Nothing is decoded and neither decoder nor buffers change; what the index cannot cut raises its CodecError.
+        ValueError: `crop`'s, a path that is not strictly ascending, an origin outside the grid, an index object without `PanFrames`."""
+        path = [(int(k), int(x), int(y)) for k, x, y in path]
+        if not path:
+            raise ValueError("pan: the path is empty")
+        for k, _, _ in path:
+            if not 0 <= k < len(frames):
+                raise ValueError(f"pan: frame {k} is not in the clip")
+        for (prev, _, _), (k, _, _) in zip(path, path[1:]):
+            if k <= prev:
+                raise ValueError(f"pan: the path is not strictly ascending ({k} after {prev})")
+        if self.index is None:
+            raise ValueError("pan: no seek index is attached")
+        for k, _, _ in path:
+            if not self._in_index(k):
+                raise ValueError(f"pan: frame {k} is not in the attached seek index")
+        if not hasattr(self.index, "PanFrames"):
+            raise ValueError("pan: the attached seek index cannot pan")
+        bw, bh = self.pan_size(size)
+        nbx, nby, H = self.vi.X // 4, self.vi.Y // 4, self.vi.Y
+        for k, x, y in path:
+            if not (0 <= x <= nbx - bw and 0 <= y <= nby - bh):
+                raise ValueError(f"pan: the rectangle of frame {k} at block ({x}, {y}) is outside the block grid")
+        key = getattr(self.index, "KEY", -2)
+        at = [(k - self.index_first, (x, y)) for k, x, y in path]
+        pairs = [(key, at[0][0], None, at[0][1])] + [(a, b, A, B) for (a, A), (b, B) in zip(at, at[1:])]
+        out, flags = [], []
+        for j0 in range(0, len(pairs), self.PAN_CALL):
+            made, keys = self.index.PanFrames((bw, bh), pairs[j0:j0 + self.PAN_CALL], tight=bool(tight))
+            out += list(made)
+            flags += [bool(v) for v in keys]
+        flags[0] = True
+        return out, flags, [(4 * x, H - 4 * (y + bh), 4 * bw, 4 * bh) for _, x, y in path]
+
+    def write_pan(self, frames: Sequence[bytes], size, path, fps: float = 15.0, tight: bool = True) -> bytes:
+        """`pan` as an AVI file (avi.write_avi) of the rectangle's size, 4 bw x 4 bh, fourcc CRAM, with this Manager's bit depth and
+        palette, as `write_crop` writes `crop`."""
+        from .avi import write_avi
+        out, flags, shown = self.pan(frames, size, path, tight=tight)
+        return write_avi(shown[0][2], shown[0][3], out, fourcc=b"CRAM", bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
 
     def _index_adopts(self) -> bool:
         return bool(getattr(self.index, "ADOPTS", True))
