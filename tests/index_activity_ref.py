@@ -15,12 +15,23 @@ tests of its own.
   * sp_model — sp_index_activity_kernel's walk over what sp_index_ref.Composer keeps (key pictures; per inter frame a literal
     image and the mask of its rectangles): the events bitmap | keymask of the run's frames word by word, literals compared and
     taken under the rectangle mask, a key frame compared with and reloaded from its picture.
+  * sp_lane_model — the same walk lane by lane, as the launch enumerates workgroups, waves, lanes and chunk positions.
 
 `wrong=` selects a deliberately broken walk that the tests must catch:
   msv1_model: "bit_is_16" (a set bit counts as 16 changed pixels), "no_recompose" (a segment after the first starts from the picture
               before the index instead of composing the picture before its first frame), "cols_is_4" (r = q // 4, qx = q % 4: right
               on a grid of four columns only), "one_workgroup" (lanes from 256 on own nothing: right up to 16 cells only);
-  sp_model:   "rect_area" (every pixel under a rectangle counts), "key_ignored" (a key frame inside the run is not an event)."""
+  sp_model:   "rect_area" (every pixel under a rectangle counts), "key_ignored" (a key frame inside the run is not an event), "stale"
+              (the register takes neither literals nor key pictures), "zeros_counted" (with first = 0 every pixel inside the picture
+              counts at frame 0), "open_end" / "open_start" (the mask of a bitmap word to the run reaches frame last + 1 / first - 1:
+              with `guard` the map comes with the row in front of it and the row behind it, where such a frame would be stored);
+  sp_lane_model: "no_bx_guard" (a wave with bx >= nbx goes on: b names a block of the next row, or none), "chunk_whole" (`inpic` is
+              all four bits whenever x0 < X: a key frame's pixels past the row's end are read from the next row of the picture),
+              "three_ballots" (the fourth pixel of a chunk is never counted).
+Two of them change no count, and the tests say so instead of looking for a wrong map: "open_start" handles frame first - 1 with
+P(first - 1) in the register, so that nothing of it differs and nothing is stored; the lanes of a wave that "no_bx_guard" lets
+go on have x0 >= 16 nbx >= X, own no pixel and count nothing — what the guard keeps away is the read of a block number past the
+tables in the last row of blocks, which sp_lane_model reports in `faults`."""
 import numpy as np
 
 from msv1_index_play_ref import _top_bit, bitmap_words, index_last_writer, segment_length, to_blocks
@@ -143,25 +154,40 @@ def msv1_model(coded, block_pics, w, h, first, n, segs=1, before=None, wrong=Non
 
 
 # ---- ScreenPressor ------------------------------------------------------------------------------------------------------------------
-def sp_model(comp, w, h, first, n, wrong=None):
-    """The kernel's walk over a sp_index_ref.Composer (key_of, key_pic, lit, mask).  (n, rows, cols) uint16."""
-    cols, rows = grid(w, h)
+def _sp_words(comp):
+    """(writers, keymask): per 32 frames the inter frames that code a rectangle anywhere, and the key frames."""
     nframes = len(comp.key_of)
     nwords = (nframes + 31) // 32
-    writers = np.zeros(nwords, dtype=np.uint64)   # frames with a rectangle anywhere (per block in the kernel: an empty block's mask is empty)
-    keymask = np.zeros(nwords, dtype=np.uint64)
+    writers, keymask = [0] * nwords, [0] * nwords
     for f in range(nframes):
         if comp.key_of[f] == f:
-            keymask[f >> 5] |= np.uint64(1 << (f & 31))
+            keymask[f >> 5] |= 1 << (f & 31)
         elif f in comp.mask:
-            writers[f >> 5] |= np.uint64(1 << (f & 31))
+            writers[f >> 5] |= 1 << (f & 31)
+    return writers, keymask
+
+
+def _sp_range(wd, first, last, wrong):
+    """The kernel's `range`: the bits of word wd that are frames of the run."""
+    lo, hi = max(first, 32 * wd), min(last, 32 * wd + 31)
+    if wrong == "open_end":
+        hi = min(last + 1, 32 * wd + 31)
+    if wrong == "open_start" and first > 0:
+        lo = max(first - 1, 32 * wd)
+    return (0xFFFFFFFF << (lo & 31)) & (0xFFFFFFFF >> (31 - (hi & 31))) & 0xFFFFFFFF
+
+
+def sp_model(comp, w, h, first, n, wrong=None, guard=False):
+    """The kernel's walk over a sp_index_ref.Composer (key_of, key_pic, lit, mask).  (n, rows, cols) uint16; guard: (n + 2, rows,
+    cols), the row the kernel would store a frame first - 1 in, the map, the row of a frame first + n — both zero in a right walk."""
+    cols, rows = grid(w, h)
+    writers, keymask = _sp_words(comp)
     last = first + n - 1
     px = comp.picture(first - 1).reshape(h, w).copy() if first > 0 else np.zeros((h, w), dtype=np.uint32)
-    out = np.zeros((n, rows, cols), dtype=np.uint16)
+    out = np.zeros((n + 2, rows, cols), dtype=np.uint16)
     for wd in range(first >> 5, (last >> 5) + 1):
-        lo, hi = max(first, 32 * wd), min(last, 32 * wd + 31)
-        rng = (0xFFFFFFFF << (lo & 31)) & (0xFFFFFFFF >> (31 - (hi & 31))) & 0xFFFFFFFF
-        m, km = int(writers[wd]) & rng, int(keymask[wd]) & rng
+        rng = _sp_range(wd, first, last, wrong)
+        m, km = writers[wd] & rng, keymask[wd] & rng
         if wrong == "key_ignored":
             km = 0
         ev = m | km
@@ -172,10 +198,84 @@ def sp_model(comp, w, h, first, n, wrong=None):
             if (m >> bit) & 1:
                 inside = comp.mask[f]
                 diff = inside.copy() if wrong == "rect_area" else inside & (comp.lit[f] != px)
-                px[inside] = comp.lit[f][inside]
+                if wrong != "stale":
+                    px[inside] = comp.lit[f][inside]
             else:
                 key = comp.key_pic[comp.key_of[f]]
                 diff = key != px
-                px = key.copy()
-            out[f - first] = cell_sums(diff, w, h)
-    return out
+                if wrong == "zeros_counted" and f == 0:
+                    diff = np.ones((h, w), dtype=bool)
+                if wrong != "stale":
+                    px = key.copy()
+            out[f - first + 1] = cell_sums(diff, w, h)
+    return out if guard else out[1:-1]
+
+
+def sp_lane_model(comp, w, h, first, n, wrong=None, guard=False, faults=None):
+    """sp_index_activity_kernel as its launch enumerates it: workgroup (gx, by), wave wv, block bx = 4 gx + wv, a wave with bx >= nbx
+    leaves; lane = (row ly, chunk cx0), `mine`, the `inpic` bits; per event the count is the sum of four ballots, one per chunk
+    position, and it is stored at the flat element (f - first) * nblocks + b.  The lanes start from P(first - 1) (the backward walk
+    has its own model: test_sp_directed_clips_cpu.Walk).  Shape as sp_model.  `faults`: a list that takes what the walk reads outside
+    the tables or the picture, as (what, by, bx, number); such a read gives the model nothing (a wave with such a block stops)."""
+    nbx, nby = grid(w, h)
+    nblocks = nbx * nby
+    vec = w % 4 == 0                              # (the index's key pictures are 16-byte aligned)
+    writers, keymask = _sp_words(comp)
+    nwords = len(writers)
+    block_of = (np.arange(h)[:, None] // CELL) * nbx + np.arange(w)[None, :] // CELL
+    bitmap = np.zeros((nwords, nblocks), dtype=np.int64)
+    for f, mask in comp.mask.items():
+        for b in np.unique(block_of[mask]):
+            bitmap[f >> 5, b] |= 1 << (f & 31)
+    last = first + n - 1
+    before = comp.picture(first - 1).reshape(-1) if first > 0 else np.zeros(w * h, dtype=np.uint32)
+    flat = np.zeros((n + 2) * nblocks, dtype=np.uint16)
+    lane = np.arange(64)
+    ly, cx0 = lane >> 2, (lane & 3) * 4
+    j = np.arange(4)[None, :]
+    for by in range(nby):
+        for gx in range((nbx + 3) // 4):
+            for wv in range(4):
+                bx = 4 * gx + wv
+                if bx >= nbx and wrong != "no_bx_guard":
+                    continue
+                b = by * nbx + bx                 # (without the guard: a block of the next row, or none)
+                if b >= nblocks:
+                    if faults is not None:
+                        faults.append(("block", by, bx, b))
+                    continue
+                y, x0 = by * 16 + ly, bx * 16 + cx0
+                mine = (y < h) & (x0 < w)
+                in_row = (x0[:, None] + j) < w
+                inpic = mine[:, None] & (in_row | vec)
+                at = (y * w + x0)[:, None] + j    # pixel i0 + j
+                px = np.where(inpic, before[np.where(inpic, at, 0)], 0).astype(np.uint32)   # (index_compose: 0 outside the picture)
+                if wrong == "chunk_whole":
+                    inpic = np.repeat(mine[:, None], 4, axis=1)
+                    past = inpic & (at >= w * h)
+                    if past.any() and faults is not None:
+                        faults.append(("pixel", by, bx, int(at[past].min())))
+                    inpic = inpic & ~past
+                safe = np.where(inpic, at, 0)
+                for wd in range(first >> 5, (last >> 5) + 1):
+                    rng = _sp_range(wd, first, last, None)
+                    m, km = int(bitmap[wd, b]) & rng, keymask[wd] & rng
+                    ev = m | km
+                    while ev:
+                        bit = (ev & -ev).bit_length() - 1
+                        ev &= ev - 1
+                        f = 32 * wd + bit
+                        if (m >> bit) & 1:        # (the rectangle is block b's: it ends with the block's part of the row)
+                            inside = inpic & in_row & comp.mask[f].reshape(-1)[safe]
+                            v = comp.lit[f].reshape(-1)[safe]
+                            diff = inside & (v != px)
+                            px = np.where(inside, v, px)
+                        else:
+                            kx = np.where(inpic, comp.key_pic[comp.key_of[f]].reshape(-1)[safe], px)
+                            diff = kx != px
+                            px = kx
+                        cnt = sum(int(diff[:, k].sum()) for k in range(3 if wrong == "three_ballots" else 4))
+                        if cnt:
+                            flat[(f - first + 1) * nblocks + b] = cnt
+    out = flat.reshape(n + 2, nby, nbx)
+    return out if guard else out[1:-1]

@@ -41,10 +41,25 @@ def test_generated_clips(case):
     keys_at = [t for t in range(1, n) if clip.keys[t]]
     runs = [(0, n), (1, 1), (31, 3), (n - 1, 1), (5, n - 9)]
     runs += [(k, min(4, n - k)) for k in keys_at[:3]] + [(k + 1, min(4, n - k - 1)) for k in keys_at[:3] if k + 1 < n]
+    whole = None
     for first, count in runs:
-        check(idx, want, first, count, clip.name)
+        got = check(idx, want, first, count, clip.name)
+        whole = got if (first, count) == (0, n) else whole
     # unchanged frames are all zeros; a set bit is not a change: some rectangle covers pixels that stay
     assert any(not want[t].any() for t in range(1, n))
+    if case is CLIPS[0]:   # (one clip's host-stage records are enough: literalised motion rewrites pixels as they were)
+        comp = ref.Composer(clip)
+        before = np.zeros(w * h, dtype=np.uint32)
+        slack = []             # (frame, block row, block column, the rectangle's pixels there)
+        for t in range(n):
+            if t in comp.mask:
+                stays = ar.cell_sums(comp.mask[t] & (clip.frames[t] == before).reshape(h, w), w, h)
+                area = ar.cell_sums(comp.mask[t], w, h)
+                slack += [(t, r, q, int(area[r, q])) for r, q in zip(*np.nonzero(stays))]
+            before = clip.frames[t]
+        assert slack, f"{clip.name}: every rectangle is all change"
+        for t, r, q, area in slack:
+            assert whole[t, r, q] < area, f"{clip.name} frame {t} block ({r}, {q}): the rectangle's area is not the count"
     assert gpu.PreviousFrame() is None
     idx.close()
     gpu.StopAndClean()
