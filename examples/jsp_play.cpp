@@ -66,6 +66,17 @@
 //                                most 4096 pairs.  Then OUT.avi is played back through a decoder of its own size: prints "<frame of
 //                                the clip> <crc32 from OUT.avi> <crc32 of that part of the clip's picture>" per frame kept and exits
 //                                with 1 on any difference
+//   jsp_play clip.avi --reverse FIRST[:COUNT[:STRIDE]][:tight] OUT.avi
+//   jsp_play clip.avi --boomerang FIRST[:COUNT[:STRIDE]][:tight] OUT.avi
+//                                MSVideo1: the frames --thin would keep, the whole picture, played BACKWARDS (--reverse: last kept
+//                                frame first) or there and back (--boomerang: the last step returns to the first frame kept, so the
+//                                file loops), as an AVI file of its own.  ONE seek index from the nearest key frame <= FIRST; the first
+//                                frame is a key pair, every other one the pair from the frame before it in that order — a step back
+//                                takes, for every block the frames in between coded, the code of its last writer up to the earlier
+//                                frame (":tight": JSP_CROP_TIGHT) — all from ONE jsp_index_path_frames call (at most 4096 frames).
+//                                Prints "reverse blocks ..." / "boomerang blocks ..." as --crop does, then OUT.avi is played back
+//                                through a decoder of its own size: "<frame of the clip> <crc32 from OUT.avi> <crc32 of the clip's
+//                                picture>" per frame written, and exits with 1 on any difference
 //   jsp_play clip.avi --pan WxH[:loose] FIRST[:COUNT[:STRIDE]] OUT.avi
 //                                MSVideo1: a rectangle of W x H pixels (rounded up to whole 4x4 blocks, clipped to the block grid)
 //                                that FOLLOWS what the frames --thin would keep change, as an AVI file of its own.  ONE seek index from
@@ -570,6 +581,7 @@ int main(int argc, char** argv) {
     std::string thin_path;
     bool crop = false, crop_tight = false;   // --crop X:Y:W:H[:tight] FIRST[:COUNT[:STRIDE]] OUT.avi: --thin's frames, a part of the picture
     long crop_rect[4] = {0, 0, 0, 0};
+    int path_mode = 0;                       // --reverse (1) / --boomerang (2) FIRST[:COUNT[:STRIDE]][:tight] OUT.avi: --thin's frames in another order (with crop, crop_tight)
     bool pan = false, pan_tight = true;      // --pan WxH[:loose] FIRST[:COUNT[:STRIDE]] OUT.avi: --thin's frames, a rectangle that follows the changes
     long pan_size[2] = {0, 0};
     int strip = 0, strip_scale = 8;                           // --filmstrip N[:scale]: N evenly spaced thumbnails of a seek index over the clip
@@ -613,8 +625,13 @@ int main(int argc, char** argv) {
             cut_path = argv[++a];
             if (cut_first < 0 || (colon != std::string::npos && cut_count < 1)) { std::fprintf(stderr, "--cut FIRST[:COUNT] OUT.avi: FIRST >= 0, COUNT >= 1\n"); return 2; }
         }
-        else if ((o == "--thin" || o == "--thin-tight" || o == "--crop" || o == "--pan") && a + (o == "--crop" || o == "--pan" ? 3 : 2) < argc) {
+        else if ((o == "--thin" || o == "--thin-tight" || o == "--crop" || o == "--pan" || o == "--reverse" || o == "--boomerang") &&
+                 a + (o == "--crop" || o == "--pan" ? 3 : 2) < argc) {
             thin_tight = o == "--thin-tight";
+            if (o == "--reverse" || o == "--boomerang") {      // the whole picture through the --crop branch, frames in another order
+                crop = true;
+                path_mode = o == "--reverse" ? 1 : 2;
+            }
             if (o == "--pan") {
                 pan = true;
                 std::string r = argv[++a];
@@ -645,7 +662,16 @@ int main(int argc, char** argv) {
                 }
                 if (got < 4 || got > 5 || crop_rect[2] < 1 || crop_rect[3] < 1) { std::fprintf(stderr, "--crop X:Y:W:H[:tight] FIRST[:COUNT[:STRIDE]] OUT.avi: W >= 1, H >= 1\n"); return 2; }
             }
-            const std::string v = argv[++a];
+            std::string v = argv[++a];
+            if (path_mode && v.size() > 6 && v.compare(v.size() - 6, 6, ":tight") == 0) {   // (the frame spec's optional suffix)
+                crop_tight = true;
+                v.resize(v.size() - 6);
+            }
+            if (path_mode && (v.empty() || v.find_first_not_of("0123456789:") != std::string::npos || v.front() == ':' || v.back() == ':' ||
+                              v.find("::") != std::string::npos || std::count(v.begin(), v.end(), ':') > 2)) {
+                std::fprintf(stderr, "%s FIRST[:COUNT[:STRIDE]][:tight] OUT.avi: numbers, and no other suffix\n", o.c_str());
+                return 2;
+            }
             const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
             thin_first = std::atol(v.substr(0, c1).c_str());
             if (c1 != std::string::npos) thin_count = std::atol(v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1).c_str());
@@ -727,9 +753,10 @@ int main(int argc, char** argv) {
     if (cut_first >= 0 && (act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--cut goes alone\n"); return 2; }
     if (cut_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--cut: MSVideo1 only (a ScreenPressor key frame needs the entropy encoder)\n"); return 2; }
     if (thin_first >= 0 && (cut_first >= 0 || act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--thin goes alone\n"); return 2; }
-    if (pan && crop) { std::fprintf(stderr, "--pan and --crop do not go together\n"); return 2; }
+    if (pan && crop) { std::fprintf(stderr, "--pan and %s do not go together\n", path_mode ? "--reverse / --boomerang" : "--crop"); return 2; }
     if (pan && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--pan: MSVideo1 only (ScreenPressor codes are entropy-coded in context)\n"); return 2; }
-    if (crop && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--crop: MSVideo1 only (ScreenPressor codes are entropy-coded in context)\n"); return 2; }
+    const char* crop_opt = path_mode == 1 ? "--reverse" : path_mode == 2 ? "--boomerang" : "--crop";
+    if (crop && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "%s: MSVideo1 only (ScreenPressor codes are entropy-coded in context)\n", crop_opt); return 2; }
     if (thin_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--thin: MSVideo1 only (a ScreenPressor frame needs the entropy encoder)\n"); return 2; }
     if (strip > 0 && (step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--filmstrip goes alone\n"); return 2; }
     if (play_first >= 0 && (strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--play-index goes alone\n"); return 2; }
@@ -1279,20 +1306,30 @@ int main(int argc, char** argv) {
         return rc;
     }
     if (thin_first >= 0 && crop) {   // a part of the picture: one index build from the key frame before, jsp_index_crop_frames for a key pair and every gap, the file, its playback
+        // (--reverse / --boomerang: the whole picture, the frames kept in another order, ONE jsp_index_path_frames call)
         const size_t n = clip.frames.size();
         std::vector<size_t> keep;
         for (long i = thin_first; i < (long)n && (thin_count < 0 || (long)keep.size() < thin_count); i += thin_stride) keep.push_back((size_t)i);
         if (keep.empty() || (thin_count >= 0 && (long)keep.size() < thin_count)) {
-            std::fprintf(stderr, "--crop: frames %ld, %ld, ... (%ld of them) are not all in the clip (%zu frames)\n", thin_first, thin_first + thin_stride, thin_count, n);
+            std::fprintf(stderr, "%s: frames %ld, %ld, ... (%ld of them) are not all in the clip (%zu frames)\n", crop_opt, thin_first, thin_first + thin_stride, thin_count, n);
             rc = 1;
+        }
+        std::vector<size_t> order = keep;                       // the frames written, in the file's order
+        if (path_mode) {
+            std::reverse(order.begin(), order.end());
+            if (path_mode == 2) order.insert(order.begin(), keep.begin(), keep.end() - (keep.empty() ? 0 : 1));
+            crop_rect[0] = crop_rect[1] = 0, crop_rect[2] = clip.X, crop_rect[3] = clip.Y;
+            if (rc == 0 && order.size() > 4096) { std::fprintf(stderr, "%s: more than 4096 frames to write\n", crop_opt); rc = 1; }
         }
         // the smallest block rectangle that contains the display rectangle, clipped to the block grid; stored row = Y - 1 - display row
         const long nbx = clip.X / 4, nby = clip.Y / 4;
         const long x0 = std::max(crop_rect[0], 0l), x1 = std::min(crop_rect[0] + crop_rect[2], 4 * nbx);
         const long s0 = std::max(clip.Y - (crop_rect[1] + crop_rect[3]), 0l), s1 = std::min(clip.Y - crop_rect[1], 4 * nby);
-        if (rc == 0 && (x0 >= x1 || s0 >= s1)) { std::fprintf(stderr, "--crop: nothing of the rectangle lies in the picture's blocks\n"); rc = 1; }
+        if (rc == 0 && (x0 >= x1 || s0 >= s1)) { std::fprintf(stderr, "%s: nothing of the rectangle lies in the picture's blocks\n", crop_opt); rc = 1; }
         const int bx = (int)(x0 / 4), by = (int)(s0 / 4), bw = (int)((x1 + 3) / 4) - bx, bh = (int)((s1 + 3) / 4) - by;
-        if (rc == 0) std::printf("crop blocks %d %d %d %d display %d %ld %d %d\n", bx, by, bw, bh, 4 * bx, clip.Y - 4l * (by + bh), 4 * bw, 4 * bh);
+        if (rc == 0) std::printf("%s blocks %d %d %d %d display %d %ld %d %d\n", crop_opt + 2, bx, by, bw, bh, 4 * bx, clip.Y - 4l * (by + bh), 4 * bw, 4 * bh);
+        const auto frames_call = path_mode ? jsp_index_path_frames : jsp_index_crop_frames;
+        const char* frames_name = path_mode ? "jsp_index_path_frames" : "jsp_index_crop_frames";
         std::vector<uint8_t> made;
         std::vector<size_t> made_lens;
         std::vector<int> made_keys;
@@ -1309,26 +1346,26 @@ int main(int argc, char** argv) {
             }
             jsp_index* idx = jsp_index_build(dec, (int)srcs.size(), srcs.data(), lens.data(), keys.data(), kInsignificantLines);
             if (!idx) { std::fprintf(stderr, "jsp_index_build: %s\n", jsp_last_error()); rc = 1; }
-            for (size_t g0 = 0; rc == 0 && g0 < keep.size(); g0 += 4096) {   // (a call takes 4096 pairs)
-                const size_t m = std::min<size_t>(4096, keep.size() - g0);
+            for (size_t g0 = 0; rc == 0 && g0 < order.size(); g0 += 4096) {   // (a call takes 4096 pairs)
+                const size_t m = std::min<size_t>(4096, order.size() - g0);
                 std::vector<int> from(m), to(m), ks(m);
                 for (size_t i = 0; i < m; ++i) {
-                    from[i] = g0 + i == 0 ? JSP_CROP_KEY : (int)(keep[g0 + i - 1] - k);
-                    to[i] = (int)(keep[g0 + i] - k);
+                    from[i] = g0 + i == 0 ? JSP_CROP_KEY : (int)(order[g0 + i - 1] - k);
+                    to[i] = (int)(order[g0 + i] - k);
                 }
                 std::vector<size_t> ls(m);
                 size_t total = 0;
                 const int flags = crop_tight ? JSP_CROP_TIGHT : 0;
                 // asked twice: the lengths (cap 0 is a refusal that still sets them), then the bytes
-                if (jsp_index_crop_frames(dec, idx, bx, by, bw, bh, (int)m, from.data(), to.data(), flags, nullptr, 0, ls.data(), ks.data(), &total) == JSP_ZERO_STATE || total == 0) {
-                    std::fprintf(stderr, "jsp_index_crop_frames: %s\n", jsp_last_error());
+                if (frames_call(dec, idx, bx, by, bw, bh, (int)m, from.data(), to.data(), flags, nullptr, 0, ls.data(), ks.data(), &total) == JSP_ZERO_STATE || total == 0) {
+                    std::fprintf(stderr, "%s: %s\n", frames_name, jsp_last_error());
                     rc = 1;
                     break;
                 }
                 const size_t at = made.size();
                 made.resize(at + total);
-                if (jsp_index_crop_frames(dec, idx, bx, by, bw, bh, (int)m, from.data(), to.data(), flags, made.data() + at, total, ls.data(), ks.data(), &total) != JSP_ZERO_STATE) {
-                    std::fprintf(stderr, "jsp_index_crop_frames: %s\n", jsp_last_error());
+                if (frames_call(dec, idx, bx, by, bw, bh, (int)m, from.data(), to.data(), flags, made.data() + at, total, ls.data(), ks.data(), &total) != JSP_ZERO_STATE) {
+                    std::fprintf(stderr, "%s: %s\n", frames_name, jsp_last_error());
                     rc = 1;
                 }
                 made_lens.insert(made_lens.end(), ls.begin(), ls.end());
@@ -1342,7 +1379,7 @@ int main(int argc, char** argv) {
         std::vector<std::pair<const uint8_t*, size_t>> out_frames;
         std::vector<uint8_t> out_keys;
         size_t at = 0;
-        for (size_t j = 0; j < keep.size(); ++j) {
+        for (size_t j = 0; j < order.size(); ++j) {
             out_frames.emplace_back(made.data() + at, made_lens[j]);
             out_keys.push_back(j == 0 || made_keys[j] ? 1 : 0);
             at += made_lens[j];
@@ -1355,12 +1392,12 @@ int main(int argc, char** argv) {
         std::fclose(f);
         // OUT.avi played back through the ordinary decode loop of a decoder of ITS size, beside that part of the clip's own pictures
         Clip cropped;
-        if (!load(thin_path.c_str(), cropped) || cropped.frames.size() != keep.size() || cropped.X != 4 * bw || cropped.Y != 4 * bh) { std::fprintf(stderr, "cannot read %s back\n", thin_path.c_str()); return 1; }
+        if (!load(thin_path.c_str(), cropped) || cropped.frames.size() != order.size() || cropped.X != 4 * bw || cropped.Y != 4 * bh) { std::fprintf(stderr, "cannot read %s back\n", thin_path.c_str()); return 1; }
         std::vector<uint32_t> got, want;
         if (!covered_crcs(cropped, cropped.frames.size(), got) || !covered_crcs(clip, keep.back() + 1, want, 4 * (size_t)bx, 4 * (size_t)by, 4 * (size_t)bw, 4 * (size_t)bh)) return 1;
-        for (size_t j = 0; j < keep.size(); ++j) {
-            std::printf("%zu %08x %08x\n", keep[j], got[j], want[keep[j]]);
-            if (got[j] != want[keep[j]]) rc = 1;
+        for (size_t j = 0; j < order.size(); ++j) {
+            std::printf("%zu %08x %08x\n", order[j], got[j], want[order[j]]);
+            if (got[j] != want[order[j]]) rc = 1;
         }
         return rc;
     }

@@ -92,6 +92,11 @@ extern class JspNative {
                                                                       from:RawConstPointer<Int>, to:RawConstPointer<Int>, fromXy:RawConstPointer<Int>,
                                                                       toXy:RawConstPointer<Int>, flags:Int, out:RawPointer<UInt8>, cap:SizeT,
                                                                       lens:RawPointer<SizeT>, keys:RawPointer<Int>, total:RawPointer<SizeT>):Int;
+    // the same for a rectangle that stands, with pairs in either direction: from > to steps back, from == to holds (a reversed clip, a boomerang)
+    @:native("jsp_index_path_frames")  static function indexPathFrames(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, bx:Int, by:Int, bw:Int, bh:Int,
+                                                                       n:Int, from:RawConstPointer<Int>, to:RawConstPointer<Int>, flags:Int,
+                                                                       out:RawPointer<UInt8>, cap:SizeT, lens:RawPointer<SizeT>, keys:RawPointer<Int>,
+                                                                       total:RawPointer<SizeT>):Int;
     @:native("jsp_index_significance") static function indexSignificance(idx:RawPointer<JspIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_index_destroy")      static function indexDestroy(idx:RawPointer<JspIndex>):Void;
     // ScreenPressor seek index: the host entropy stage over a range ONCE, its records resident in HBM, any frame of it shown by ONE launch (the codec is only lent)

@@ -855,6 +855,42 @@ int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, 
 int jsp_index_pan_frames(jsp_codec* c, jsp_index* idx, int bw, int bh, int n, const int* from, const int* to, const int* from_xy,
                          const int* to_xy, int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total);
 
+/* REVERSE A CLIP: the frames of a block rectangle ALONG ANY PATH through an MSVideo1 index — a reversed clip, a boomerang (there and
+ * back, loopable), a freeze frame: the temporal counterpart of crop and pan.  A code carries no position and no reference to the
+ * previous picture, so the inter frame that takes the picture of frame a BACK to the picture of frame b < a is a gather of codes the
+ * index holds, as the step forward is: no pixel decoded, nothing re-quantised.
+ *   THE RECTANGLE, src(j) and the j-numbering are crop's; the whole block grid as the rectangle gives the whole picture.
+ *   THE RULE (PATH, stated in msv1_index_path_kernels.hip).  A pair (from = a, to = b) is
+ *         a KEY pair, a == JSP_CROP_KEY, 0 <= b < nframes: crop's key pair;
+ *         a FORWARD pair, -1 <= a < b < nframes: crop's gap pair (Delta, or Tight with JSP_CROP_TIGHT);
+ *         a HOLD pair, 0 <= a == b < nframes: nothing is touched, the frame is ceil(nb / 1023) skip words;
+ *         a BACK pair, 0 <= b < a < nframes.
+ *       For the three kinds that are not KEY, with lo = min(a, b) and hi = max(a, b): block j is TOUCHED when some frame f,
+ *       lo < f <= hi, codes src(j).  Without JSP_CROP_TIGHT a touched block is KEPT; with it a touched block is DROPPED when
+ *       P(a)[src(j)] and P(b)[src(j)] are both defined and equal in all 16 words, else KEPT.  A kept block gives the whole code of the
+ *       last writer <= b of src(j); without one it refuses ("no writer": only a BACK pair can, and it does even where the picture
+ *       before the range defines P(b) — those pixels come from no code the index holds), with a cut code it refuses ("cut").  Dropped
+ *       and untouched blocks are skipped under Delta's run-head and count rules in j and never refuse.
+ *   PROMISED: a fresh decoder of 4 bw x 4 bh pixels fed a KEY pair's frame as a key frame, then the frames of pairs chained by
+ *       to[k-1] == from[k] in any mix of kinds, holds after each the rectangle of the source picture of to[k].  keys[k] = the frame codes
+ *       all nb blocks: jsp_is_key_frame of it.  A tight frame is never longer than the loose one.  Back(a, b) and Delta(b, a) have
+ *       the same touched set, hence the same skip words when neither is tight.  A call of only KEY and FORWARD pairs returns byte
+ *       for byte what jsp_index_crop_frames returns (lens, keys, total and the refusal texts too, apart from the prefix).  NOT
+ *       promised: the exclusions of KeyFrame, and a step back to before the range (to = -1).
+ *   REFUSED as in crop, the text starting with "index_path:" and naming the FIRST refusing (pair, block) in that order; a BACK pair
+ *       reads "(from -> to, back)".
+ *   Everything else is jsp_index_crop_frames', word for word: jsp_index_crop_bound(idx, bw, bh) sizes `out` (HOST memory, frames back
+ *       to back), lens[], keys[] (may be null) and *total set when only `cap` is short, zeros and nothing written after every other
+ *       error, slices under "msv1_index_delta_slice" with a sizes launch for all slices first, the scratch of the crop call (one of
+ *       the index's own that jsp_index_info counts), synchronised on return, THE CODEC ONLY LENT.  Two launches per slice:
+ *       msv1_index_path_sizes_kernel, msv1_index_crop_gather_kernel.
+ *   ERRORS before anything is queued, in this order: a null argument (keys may be null); not an MSVideo1 codec ("index: MSVideo1
+ *       only"); an index of another codec; a rectangle outside the block grid (also: a picture without a block); n outside 1 .. 4096;
+ *       unknown flag bits; the first bad pair — from < JSP_CROP_KEY, from == -1 with to < 0, `to` outside 0 .. nframes - 1, or
+ *       from >= nframes (the text names the pair and says what a pair may be); an asynchronous frame in flight. */
+int jsp_index_path_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to, int flags,
+                          uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

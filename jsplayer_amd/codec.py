@@ -615,7 +615,8 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     Activity(first, n) one launch for the changed pixels per frame and 16x16 cell of a run (jsp_index_activity; _IndexActivity),
     KeyFrame(t) two launches for a key frame that decodes to frame t's picture, made of the codes the range holds (jsp_index_key_frame),
     DeltaFrames(pairs) inter frames that each span a gap (a, b] of the range, made of the same codes and skips (jsp_index_delta_frames);
-    with tight=True without the blocks whose pixels the gap did not change (jsp_index_tight_frames).
+    with tight=True without the blocks whose pixels the gap did not change (jsp_index_tight_frames).  CropFrames / PanFrames the same
+    for a block rectangle that stands or moves, PathFrames for pairs in either direction — steps back and holds: a reversed clip.
     `significance` = FindChange's verdict
     for every frame, `frames`, `device_bytes`.  close() (or the context manager) frees it; safe after the codec is gone."""
 
@@ -775,7 +776,24 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
         pair's frame and then chained gap pairs' frames shows that part of the source's pictures.  The flag of a frame says that it
         codes every block of the rectangle: IsKeyFrame of it.  CodecError, naming the pair, the block (in the rectangle and in the
         picture), the kind and for a cut code the writer frame; nothing is returned then."""
-        codec = self._open("index_crop")
+        return self._rect_frames("index_crop", self._lib.jsp_index_crop_frames, rect, pairs, tight)
+
+    def PathFrames(self, rect, pairs, tight: bool = False):
+        """CropFrames with pairs in EITHER direction: (list of bytes, list of bool), one frame per pair.  Besides CropFrames' pairs —
+        (SeekIndex.KEY, t) and a step forward (a, b), a < b — a pair may step BACK, (a, b) with 0 <= b < a < frames: the inter frame
+        from the picture of frame a to the picture of the EARLIER frame b, for every block that a frame of (b, a] coded the code of
+        its last writer <= b, a skip elsewhere; or HOLD, (a, a): only skip words.  tight drops the blocks whose pixels are equal in
+        both pictures (jsp_index_path_frames: two launches per slice of pairs, the codec not touched).  rect=None is the whole block
+        grid.  A decoder of 4 bw x 4 bh pixels fed a key pair's frame and then the frames of pairs chained by their ends, in any
+        order of frames, shows that part of the source's pictures along the path: a reversed clip, a boomerang, a freeze frame.
+        CodecError as CropFrames'; a step back to a block that no frame up to b coded refuses ("no writer")."""
+        if rect is None:
+            rect = (0, 0, self._codec.X // 4, self._codec.Y // 4)
+        return self._rect_frames("index_path", self._lib.jsp_index_path_frames, rect, pairs, tight)
+
+    def _rect_frames(self, who: str, call, rect, pairs, tight: bool):
+        """CropFrames and PathFrames: one marshalling of a rectangle, pairs and the tight flag around `call`."""
+        codec = self._open(who)
         bx, by, bw, bh = (int(v) for v in rect)
         pairs = [(int(a), int(b)) for a, b in pairs]
         n = len(pairs)
@@ -785,7 +803,6 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
         keys = (C.c_int * max(n, 1))()
         total = C.c_size_t(0)
         flags = self._CROP_TIGHT if tight else 0
-        call = self._lib.jsp_index_crop_frames
         # (a rectangle the block grid does not hold gives no bound to size a buffer by: the call then refuses in its own order)
         bound = C.c_size_t(0)
         self._lib.jsp_index_crop_bound(self._h, bw, bh, C.byref(bound))

@@ -9,6 +9,7 @@
 #include "codec.h"
 #include "msv1_index_crop_layout.h"
 #include "msv1_index_pan_layout.h"
+#include "msv1_index_path_layout.h"
 #include "msv1_seek.h"
 
 using namespace jsp;
@@ -39,7 +40,7 @@ struct jsp_index {
     PinnedBuffer h_key_frame;              // ... and where the status, the length and a refused block's record arrive (both: first call)
     DeviceBuffer d_delta;                  // jsp_index_delta_frames: one slice of pairs — their list, statuses, totals, records, frames ...
     PinnedBuffer h_delta;                  // ... and the host's side of the list, the statuses and the totals (both: first call)
-    DeviceBuffer d_crop;                   // jsp_index_crop_frames: the same for a slice of pairs of a rectangle (CropLayout) ...
+    DeviceBuffer d_crop;                   // jsp_index_crop_frames, jsp_index_path_frames: the same for a slice of pairs of a rectangle (CropLayout) ...
     PinnedBuffer h_crop;                   // ... and the host's side of it (both: first call)
     DeviceBuffer d_pan;                    // jsp_index_pan_frames: the same with the pairs' origins in front (PanLayout) ...
     PinnedBuffer h_pan;                    // ... and the host's side of it (both: first call)
@@ -1026,11 +1027,13 @@ extern "C" int jsp_index_crop_bound(const jsp_index* idx, int bw, int bh, size_t
     return JSP_ZERO_STATE;
 }
 
-// (jsp_index_pan_frames below repeats this function's slices, refusals and gather loop with an origin per pair; this call is pinned and
-// is not routed through it, so a fix to the slice, refusal or gather logic here belongs there too.)
-extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to,
-                                     int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
-    const char* who = "index_crop";
+// jsp_index_crop_frames (who = "index_crop") and jsp_index_path_frames ("index_path", path): one routine, the check of a pair, the sizes
+// launch and the words that name a pair in a refusal apart.  Both use the index's crop scratch.
+// (jsp_index_pan_frames below repeats this function's slices, refusals and gather loop with an origin per pair; the crop call is pinned
+// and is not routed through it, so a fix to the slice, refusal or gather logic here belongs there too.)
+namespace {
+int index_rect_frames(const char* who, bool path, jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from,
+                      const int* to, int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
     const auto zero = [&]() {
         if (total) *total = 0;
         if (lens && n >= 1 && n <= 4096) std::fill(lens, lens + n, (size_t)0);
@@ -1049,6 +1052,13 @@ extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int b
     if (n < 1 || n > 4096) return fail("%s: n is outside 1..4096", who);
     if (flags & ~JSP_CROP_TIGHT) return fail("%s: unknown flag bits", who);
     for (int j = 0; j < n; ++j) {
+        if (path) {
+            if (path_pair_ok(idx->nframes, from[j], to[j], JSP_CROP_KEY)) continue;
+            set_error("%s: pair %d (%d, %d) is no pair of the index: `to` is one of its %d frames, `from` is one too (a step forward, a "
+                      "hold or a step back), or -1 (before the range), or %d (a key pair)",
+                      who, j, from[j], to[j], idx->nframes, JSP_CROP_KEY);
+            return JSP_ERROR_OCCURED;
+        }
         const bool ok = from[j] == JSP_CROP_KEY ? to[j] >= 0 && to[j] < idx->nframes : from[j] >= -1 && to[j] > from[j] && to[j] < idx->nframes;
         if (!ok) {
             set_error("%s: pair %d (%d, %d) is neither a gap of the index (-1 <= from < to < %d frames) nor a key pair (from = %d, 0 <= to)",
@@ -1091,7 +1101,8 @@ extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int b
             JSP_HIP(hipMemcpyAsync(d, h, l.status_at, hipMemcpyHostToDevice, c->stream));
             if (!launch) return;
             JSP_HIP(hipMemsetAsync(k.status, 0xFF, sizeof(uint32_t) * m, c->stream));
-            msv1_launch_index_crop_sizes(src, r, (int)m, k, tight, c->stream);
+            if (path) msv1_launch_index_path_sizes(src, r, (int)m, k, tight, c->stream);
+            else msv1_launch_index_crop_sizes(src, r, (int)m, k, tight, c->stream);
             JSP_HIP(hipGetLastError());
         };
         for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
@@ -1109,6 +1120,7 @@ extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int b
                     const long long blk = (long long)crop_src_block(src.nbx, bx, by, bw, (int64_t)j);
                     char what[64];
                     if (from[p] == JSP_CROP_KEY) snprintf(what, sizeof(what), "(key, %d)", to[p]);
+                    else if (from[p] > to[p]) snprintf(what, sizeof(what), "(%d -> %d, back)", from[p], to[p]);   // (path only)
                     else snprintf(what, sizeof(what), "(%d, %d]", from[p], to[p]);
                     if ((status[i] & 1u) == MSV1_KEYFRAME_NO_WRITER) {
                         set_error("%s: pair %d %s: block %u of the rectangle (block %lld of the picture) has no writer up to frame %d in the index",
@@ -1157,6 +1169,21 @@ extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int b
         set_error("%s", e.what());
         return JSP_ERROR_OCCURED;
     }
+}
+}  // namespace
+
+extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to,
+                                     int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
+    return index_rect_frames("index_crop", false, c, idx, bx, by, bw, bh, n, from, to, flags, out, cap, lens, keys, total);
+}
+
+// ---- a clip along any path through the index: jsp_index_crop_frames with pairs in either direction — a step back (from > to), a hold
+// (from == to), and crop's key and gap pairs unchanged (the rule: msv1_index_path_kernels.hip).  A step back gathers, for the blocks
+// the frames of (to, from] coded, the code of the last writer <= to: again only codes the index holds.  Slices, scratch, gather launch
+// and the contract are jsp_index_crop_frames'.  Into HOST memory; the codec is only lent.
+extern "C" int jsp_index_path_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to,
+                                     int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
+    return index_rect_frames("index_path", true, c, idx, bx, by, bw, bh, n, from, to, flags, out, cap, lens, keys, total);
 }
 
 // ---- a clip that pans across the picture: jsp_index_crop_frames with an origin per pair and end of a pair (the rule:

@@ -179,6 +179,11 @@ struct Msv1CropScratch {
 void msv1_launch_index_crop_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, bool tight,
                                   hipStream_t stream);
 void msv1_launch_index_crop_gather(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, hipStream_t stream);
+// The sizes launch of jsp_index_path_frames (msv1_index_path_kernels.hip, which states the rule): crop's with pairs in either direction
+// — d.pairs may hold from > to (a step back) and from == to (a hold), checked by the host (path_pair_ok, msv1_index_path_layout.h).
+// It leaves what msv1_launch_index_crop_gather reads; that launch gathers.
+void msv1_launch_index_path_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, bool tight,
+                                  hipStream_t stream);
 
 // The device scratch of jsp_index_pan_frames for one slice of pairs: crop's, and beside the pair words the pairs' origins, checked
 // against the block grid by the host (pan_pair_check, msv1_index_pan_layout.h).

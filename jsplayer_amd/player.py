@@ -545,6 +545,80 @@ class Manager:
         out, flags, shown = self.pan(frames, size, path, tight=tight)
         return write_avi(shown[0][2], shown[0][3], out, fourcc=b"CRAM", bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
 
+    # -- a clip along any path through the index: the attached index's PathFrames (jsp_index_path_frames) ----------------------------------
+    PATH_CALL = 4096   # pairs in one PathFrames call (jsp_index_path_frames takes no more)
+
+    def sequence(self, frames: Sequence[bytes], order: Sequence[int], rect=None, tight: bool = False):
+        """The clip's frames in ANY order as a clip of its own: (list of frame bytes, key flags, the display rectangle that results).
+        `order` is a list of frame numbers of the attached index — repeats allowed, any direction, at most 4096.  Entry 0 is the
+        key frame of the rectangle at order[0]; entry k the inter frame from the picture of order[k - 1] to that of order[k] — a
+        step forward, a step back or, for a repeat, a frame of skip words — all from ONE PathFrames call.  rect: a display
+        rectangle (see crop_rect), None for the whole block grid.  tight: blocks whose pixels are equal in both pictures are
+        dropped.  flags[0] is True; a later flag says that the frame codes every block of the rectangle.  Nothing is decoded and
+        neither decoder nor buffers change; what the index cannot make raises its CodecError.  ValueError: `order` empty, too
+        long or outside the clip; no index attached, a frame outside it, an index object without `PathFrames` (ScreenPressor's);
+        nothing left of `rect`."""
+        order = [int(k) for k in order]
+        if not order:
+            raise ValueError("sequence: order is empty")
+        if len(order) > self.PATH_CALL:
+            raise ValueError(f"sequence: order has more than {self.PATH_CALL} frames")
+        for k in order:
+            if not 0 <= k < len(frames):
+                raise ValueError(f"sequence: frame {k} is not in the clip")
+        if self.index is None:
+            raise ValueError("sequence: no seek index is attached")
+        for k in order:
+            if not self._in_index(k):
+                raise ValueError(f"sequence: frame {k} is not in the attached seek index")
+        if not hasattr(self.index, "PathFrames"):
+            raise ValueError("sequence: the attached seek index cannot step back")
+        W, H = self.vi.X, self.vi.Y
+        blocks, shown = self.crop_rect((0, 0, W, H) if rect is None else rect)
+        key = getattr(self.index, "KEY", -2)
+        at = [k - self.index_first for k in order]
+        pairs = [(key, at[0])] + list(zip(at, at[1:]))
+        made, keys = self.index.PathFrames(blocks, pairs, tight=True) if tight else self.index.PathFrames(blocks, pairs)
+        flags = [bool(v) for v in keys]
+        flags[0] = True
+        return list(made), flags, shown
+
+    @staticmethod
+    def _ascending(who: str, keep: Sequence[int]):
+        keep = [int(k) for k in keep]
+        if not keep:
+            raise ValueError(f"{who}: keep is empty")
+        for prev, k in zip(keep, keep[1:]):
+            if k <= prev:
+                raise ValueError(f"{who}: keep is not strictly ascending ({k} after {prev})")
+        return keep
+
+    def reverse(self, frames: Sequence[bytes], keep: Sequence[int], rect=None, tight: bool = False):
+        """`sequence` of the strictly ascending list `keep` played from its end: keep[-1], ..., keep[0]."""
+        return self.sequence(frames, self._ascending("reverse", keep)[::-1], rect=rect, tight=tight)
+
+    def boomerang(self, frames: Sequence[bytes], keep: Sequence[int], rect=None, tight: bool = False):
+        """`sequence` of the strictly ascending list `keep` there and back: keep[0], ..., keep[-1], ..., keep[0].  The last step
+        returns to keep[0], so the last picture is the first and the file loops."""
+        keep = self._ascending("boomerang", keep)
+        return self.sequence(frames, keep + keep[-2::-1], rect=rect, tight=tight)
+
+    def write_sequence(self, frames: Sequence[bytes], order: Sequence[int], rect=None, fps: float = 15.0, tight: bool = False) -> bytes:
+        """`sequence` as an AVI file (avi.write_avi) of the rectangle's size, 4 bw x 4 bh, fourcc CRAM, with this Manager's bit depth
+        and palette, as `write_crop` writes `crop`."""
+        from .avi import write_avi
+        out, flags, (_, _, w, h) = self.sequence(frames, order, rect=rect, tight=tight)
+        return write_avi(w, h, out, fourcc=b"CRAM", bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
+
+    def write_reverse(self, frames: Sequence[bytes], keep: Sequence[int], rect=None, fps: float = 15.0, tight: bool = False) -> bytes:
+        """`reverse` as an AVI file, as `write_sequence` writes `sequence`."""
+        return self.write_sequence(frames, self._ascending("reverse", keep)[::-1], rect=rect, fps=fps, tight=tight)
+
+    def write_boomerang(self, frames: Sequence[bytes], keep: Sequence[int], rect=None, fps: float = 15.0, tight: bool = False) -> bytes:
+        """`boomerang` as an AVI file, as `write_sequence` writes `sequence`."""
+        keep = self._ascending("boomerang", keep)
+        return self.write_sequence(frames, keep + keep[-2::-1], rect=rect, fps=fps, tight=tight)
+
     def _index_adopts(self) -> bool:
         return bool(getattr(self.index, "ADOPTS", True))
 
