@@ -144,8 +144,9 @@ struct jsp_codec {
     // the frame by itself) than by the batch staging of one frame (parse at staging, a wait, then the decode launch).
     virtual bool sync_through_async() const { return false; }
     // Called (stream idle) before frames are re-run through the synchronous path: undo whatever made the frames in
-    // flight behind the failed one stand still.
-    virtual void async_reset() {}
+    // flight behind the failed one stand still, and whatever stage_async() of the failed frame (`failed`, its staged object) and of
+    // the frames behind it did to the codec's own state beyond prev_dev.
+    virtual void async_reset(jsp_staged* /*failed*/) {}
     // Asynchronous path served by worker threads of the codec's own (ScreenPressor: a coded key frame renews every bit of
     // decoder state, so the host entropy stage of the frames from one coded key frame to the next runs on a thread and a
     // decoder of its own, beside the groups of pictures before it).  worker_submit() returns at once — it hands the frame to

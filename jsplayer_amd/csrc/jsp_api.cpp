@@ -321,8 +321,8 @@ namespace {
 void redo_from(jsp_codec* c, uint64_t from) {
     c->async_flush(nullptr);                             // (frames held for their successors go out as submitted: they find the veto word set and leave their frames alone)
     JSP_HIP(hipStreamSynchronize(c->stream));
-    c->async_reset();
     jsp_async_job& first = c->jobs[from % c->async_depth];
+    c->async_reset(first.st.get());
     c->prev_caller = first.prev_caller_before;
     c->prev_dev = first.prev_dev_before;
     for (uint64_t t = from; t < c->next_ticket; ++t) {

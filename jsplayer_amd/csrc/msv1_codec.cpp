@@ -488,6 +488,10 @@ struct Msv1AsyncStaged : jsp_staged {
     const uint8_t* src_dev = nullptr;         // device-side address of the frame's bytes in pinned host memory
     hipEvent_t uploaded = nullptr;            // (copy-engine form) the frame's bytes are in d_stream
     bool dma = false;
+    // where the codec kept the last fully parsed frame's bytes before this frame was staged (Msv1Codec::async_reset puts it back)
+    bool stale_before = false;
+    const void* full_dev_before = nullptr;
+    size_t full_dev_bytes_before = 0;
     ~Msv1AsyncStaged() override { if (uploaded) (void)hipEventDestroy(uploaded); }
 
     Msv1AsyncInfo* d_info() const {
@@ -653,9 +657,16 @@ struct Msv1Codec : jsp_codec {
     const void* last_full_dev = nullptr;
     size_t last_full_dev_bytes = 0;
     DeviceBuffer d_poison;   // asynchronous path: set by a vetoed decode pass, cleared by async_reset()
-    void async_reset() override {
+    void async_reset(jsp_staged* failed) override {
         held.clear();            // (frames held for their successors are among those about to be re-run: they are never launched)
         if (d_poison.p) JSP_HIP(hipMemsetAsync(d_poison.p, 0, sizeof(uint32_t), stream));
+        // stage_async() named the failed frame (and the frames behind it) as the last fully parsed one; it is not — an end marker, a
+        // short stream.  The host parser that re-runs it must rebuild block_changes from the frame that was, as before the failed one
+        if (auto* st = dynamic_cast<Msv1AsyncStaged*>(failed)) {
+            block_changes_stale = st->stale_before;
+            last_full_dev = st->full_dev_before;
+            last_full_dev_bytes = st->full_dev_bytes_before;
+        }
     }
     // Replays of staged inter-frame batches (Msv1Staged::decode): "msv1_parse_ahead" (default on).
     bool opt_parse_ahead = true;
@@ -906,6 +917,46 @@ struct Msv1Codec : jsp_codec {
         return {st.h_stream.p, st.h_stream.as<const uint8_t>(), nullptr};
     }
 
+    // The bytes of the last fully parsed frame stay in the staged object that brought them up, and two parties may come back for them:
+    // the codec (block_changes_stale: host_parse / msv1_block_changes_now replay last_full_dev) and a frame in flight that the GPU may yet
+    // veto (async_reset puts back full_dev_before).  A staged object whose buffer either of them may still read is not written again:
+    // stage_async() sets the buffer aside first — a swap with d_aside, no copy, no wait.  One spare is enough while the ring is used in
+    // order: with nothing in flight only the codec's pointer counts (async_depth 1: every frame is staged into the object of the frame
+    // before it), and of the frames in flight only the oldest has the frame before it in an object that is free to be staged again.
+    DeviceBuffer d_aside;
+    bool a_rerun_reads(const void* p) const {
+        if (!p) return false;
+        if (block_changes_stale && last_full_dev == p) return true;
+        for (uint64_t t = oldest_ticket; t < next_ticket; ++t) {
+            auto* a = dynamic_cast<const Msv1AsyncStaged*>(jobs[t % (uint64_t)async_depth].st.get());
+            if (a && a->stale_before && a->full_dev_before == p) return true;
+        }
+        return false;
+    }
+    void set_aside_what_a_rerun_reads(Msv1AsyncStaged& st) {
+        if (!a_rerun_reads(st.d_stream.p)) return;
+        if (a_rerun_reads(d_aside.p)) {   // (the spare is spoken for as well: not while the ring is used in order — settle for a host copy)
+            forget_device_bytes(st.d_stream.p);
+            return;
+        }
+        std::swap(d_aside.p, st.d_stream.p);
+        std::swap(d_aside.cap, st.d_stream.cap);
+    }
+    // Nobody keeps a pointer to the bytes in `p` after this: the codec's go to last_full_frame; a frame in flight that is vetoed replays
+    // last_full_frame as it then is (live memory; its flags past an end marker may be older than the reference's)
+    void forget_device_bytes(const void* p) {
+        if (block_changes_stale && last_full_dev == p) {
+            JSP_HIP(hipStreamSynchronize(stream));
+            last_full_frame.resize(last_full_dev_bytes);
+            if (last_full_dev_bytes) JSP_HIP(hipMemcpy(last_full_frame.data(), last_full_dev, last_full_dev_bytes, hipMemcpyDeviceToHost));
+            last_full_dev = nullptr;
+        }
+        for (uint64_t t = oldest_ticket; t < next_ticket; ++t) {
+            auto* a = dynamic_cast<Msv1AsyncStaged*>(jobs[t % (uint64_t)async_depth].st.get());
+            if (a && a->full_dev_before == p) { a->full_dev_before = nullptr; a->full_dev_bytes_before = 0; }
+        }
+    }
+
     jsp_staged* stage_async(const jsp_frame_in& f, jsp_staged* reuse) override {
         activate();
         const bool small_tiles = f.n <= MSV1_SMALL_TILE_FRAME_BYTES;
@@ -919,6 +970,7 @@ struct Msv1Codec : jsp_codec {
         auto* st = dynamic_cast<Msv1AsyncStaged*>(reuse);
         std::unique_ptr<Msv1AsyncStaged> guard;
         if (!st) { st = new Msv1AsyncStaged(); guard.reset(st); }
+        else set_aside_what_a_rerun_reads(*st);
         st->geo = geo;
         st->shared.palette = d_palette.as<const int32_t>();
         st->shared.insignificant_blocks = insignificant_blocks;
@@ -983,7 +1035,11 @@ struct Msv1Codec : jsp_codec {
             else JSP_HIP(hipMemcpyAsync(st->d_stream.p, fb.up, f.n, hipMemcpyHostToDevice, stream));
             JSP_HIP(hipMemcpyAsync(st->d_meta.p, recs, meta_bytes, hipMemcpyHostToDevice, stream));
         }
-        // codec state, as the synchronous path leaves it
+        // codec state, as the synchronous path leaves it — a frame that is fully parsed: should the GPU find that it is not, async_reset()
+        // puts back what is overwritten here before the frame is re-run
+        st->stale_before = block_changes_stale;
+        st->full_dev_before = last_full_dev;
+        st->full_dev_bytes_before = last_full_dev_bytes;
         if (ps.changes) prev_dev = f.dst;
         block_changes_stale = true;
         last_full_dev = st->d_stream.p;

@@ -397,12 +397,14 @@ def scan_segment(nblocks, nwalk):
 
 
 # ---- truth -------------------------------------------------------------------------------------------------------------------
-def truth_run(bits, w, h, pal, frames, keys, lines=36, key_row=36, key_before=None, rows=False, keep=None):
+def truth_run(bits, w, h, pal, frames, keys, lines=36, key_row=36, key_before=None, rows=False, keep=None, start_as=None):
     """Per frame: (picture, significance as the Manager records it[, block_changes bits when rows]) — or None at the frame
-    the reference raises on (the list ends there).  keep: the frames whose picture is kept (None: all; the others get None)."""
+    the reference raises on (the list ends there).  keep: the frames whose picture is kept (None: all; the others get None).
+    start_as: k -> what buffer k of the three holds before it is first decoded into (None: the poison everywhere)."""
     o = OracleMSVideo1(bits, w, h, pal)
     o.Preinit(lines)
-    bufs = [np.full(w * h, POISON, dtype=np.int32) for _ in range(3)]
+    start_as = start_as or (lambda k: np.full(w * h, POISON, dtype=np.int32))
+    bufs = [np.array(start_as(k), dtype=np.int32) for k in range(3)]
     out = []
     for i, (src, key) in enumerate(zip(frames, keys)):
         prev = o.PreviousFrame()
@@ -411,7 +413,7 @@ def truth_run(bits, w, h, pal, frames, keys, lines=36, key_row=36, key_before=No
         if prev is not None:
             np.copyto(dst, prev)
         else:
-            dst.fill(POISON)
+            np.copyto(dst, start_as(next(k for k in range(3) if bufs[k] is dst)))
         if key:
             if o.DecompressI(src, dst) != 0:
                 raise OracleAbort()

@@ -169,7 +169,7 @@ def twin_seek(b, t):
 
 # ---- 1. every run against Show ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("bits", [16, 8])
-@pytest.mark.parametrize("size", [(4, 4), (13, 9), (64, 48), (256, 144)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("size", [(4, 4), (13, 9), (64, 48), (256, 144), (262, 26)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_every_run_matches_show(bits, size):
     w, h = size
     frames, keys, pal = mixed_clip(bits, w, h)

@@ -100,7 +100,7 @@ def test_index_every_t_against_the_oracle(bits, size, chunk):
 
 # ---- index: adopt, then play on -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("chunk", [None, 33], ids=lambda c: f"chunk{c}")
-@pytest.mark.parametrize("size", [(37, 23), (64, 48)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("size", [(37, 23), (64, 48), (262, 26)], ids=lambda s: f"{s[0]}x{s[1]}")
 @pytest.mark.parametrize("bits", [16, 8])
 def test_index_adopt_then_play_on(bits, size, chunk):
     """Show(t, adopt=True), then the next 3 frames through DecompressP / DecompressI: the codec state the show leaves —
@@ -165,7 +165,7 @@ def check_seek(bits, w, h, frames, keys, pal, plan, truth, start, target, chunk=
 
 
 @pytest.mark.parametrize("chunk", [None, 5, 33], ids=lambda c: f"chunk{c}")
-@pytest.mark.parametrize("size", [(13, 9), (37, 23), (64, 48)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("size", [(13, 9), (37, 23), (64, 48), (262, 26)], ids=lambda s: f"{s[0]}x{s[1]}")
 @pytest.mark.parametrize("bits", [16, 8])
 def test_seek_from_the_nearest_key_frame(bits, size, chunk):
     w, h = size
@@ -180,7 +180,7 @@ def test_seek_from_the_nearest_key_frame(bits, size, chunk):
 
 # ---- find change -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("chunk", [None, 7, 33], ids=lambda c: f"chunk{c}")
-@pytest.mark.parametrize("size", [(37, 23), (64, 48)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("size", [(37, 23), (64, 48), (262, 26)], ids=lambda s: f"{s[0]}x{s[1]}")
 @pytest.mark.parametrize("bits", [16, 8])
 def test_find_change_walk(bits, size, chunk):
     """walk(): FindChange from the frame after the one shown to the end, with and without stepping a frame after each landing —
