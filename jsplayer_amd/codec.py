@@ -740,21 +740,7 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
         lens = (C.c_size_t * max(n, 1))()
         total = C.c_size_t(0)
         cap = max(n, 1) * self.DeltaBound()
-        if cap > DELTA_ASK_TWICE:   # many large frames: the lengths first (cap 0 is the refusal that still sets them), then the bytes
-            if call(codec._h, self._h, n, frm, to, None, 0, lens, C.byref(total)) == 0 or total.value == 0:
-                raise CodecError(N.last_error())
-            cap = total.value
-        buf = (C.c_uint8 * max(cap, 1))()
-        if call(codec._h, self._h, n, frm, to, buf, len(buf), lens, C.byref(total)) != 0:
-            raise CodecError(N.last_error())
-        dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first call adds the scratch the frames are assembled in)
-        self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
-        self.device_bytes, self.host_bytes = dev.value, host.value
-        view, out, at = memoryview(buf), [], 0
-        for j in range(n):
-            out.append(bytes(view[at:at + lens[j]]))
-            at += lens[j]
-        return out
+        return self._clip_tail(n, cap, lens, total, lambda out, room: call(codec._h, self._h, n, frm, to, out, room, lens, C.byref(total)))
 
     KEY = -2            # JSP_CROP_KEY: a pair's `a` that makes it a key pair of CropFrames
     _CROP_TIGHT = 1     # JSP_CROP_TIGHT
@@ -807,20 +793,8 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
         bound = C.c_size_t(0)
         self._lib.jsp_index_crop_bound(self._h, bw, bh, C.byref(bound))
         cap = n * bound.value if 1 <= n <= 4096 else 0
-        if cap > DELTA_ASK_TWICE:   # many large frames: the lengths first (cap 0 is the refusal that still sets them), then the bytes
-            if call(codec._h, self._h, bx, by, bw, bh, n, frm, to, flags, None, 0, lens, keys, C.byref(total)) == 0 or total.value == 0:
-                raise CodecError(N.last_error())
-            cap = total.value
-        buf = (C.c_uint8 * max(cap, 1))()
-        if call(codec._h, self._h, bx, by, bw, bh, n, frm, to, flags, buf, len(buf), lens, keys, C.byref(total)) != 0:
-            raise CodecError(N.last_error())
-        dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first call adds the scratch the frames are assembled in)
-        self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
-        self.device_bytes, self.host_bytes = dev.value, host.value
-        view, out, at = memoryview(buf), [], 0
-        for j in range(n):
-            out.append(bytes(view[at:at + lens[j]]))
-            at += lens[j]
+        out = self._clip_tail(n, cap, lens, total, lambda out, room: call(codec._h, self._h, bx, by, bw, bh, n, frm, to, flags, out, room, lens,
+                                                                          keys, C.byref(total)))
         return out, [bool(keys[j]) for j in range(n)]
 
     def PanFrames(self, size, pairs, tight: bool = False):
@@ -851,12 +825,20 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
         bound = C.c_size_t(0)
         self._lib.jsp_index_crop_bound(self._h, bw, bh, C.byref(bound))
         cap = n * bound.value if 1 <= n <= 4096 else 0
+        out = self._clip_tail(n, cap, lens, total, lambda out, room: call(codec._h, self._h, bw, bh, n, frm, to, from_xy, to_xy, flags, out, room,
+                                                                          lens, keys, C.byref(total)))
+        return out, [bool(keys[j]) for j in range(n)]
+
+    def _clip_tail(self, n: int, cap: int, lens, total, call) -> list:
+        """What DeltaFrames, CropFrames, PathFrames and PanFrames do once their arguments are marshalled: call(out, room) is the C call
+        with everything but the buffer bound, filling lens[] and total; cap is the room the caller worked out (it decides which refusal a
+        bad n meets).  The n frames as a list of bytes."""
         if cap > DELTA_ASK_TWICE:   # many large frames: the lengths first (cap 0 is the refusal that still sets them), then the bytes
-            if call(codec._h, self._h, bw, bh, n, frm, to, from_xy, to_xy, flags, None, 0, lens, keys, C.byref(total)) == 0 or total.value == 0:
+            if call(None, 0) == 0 or total.value == 0:
                 raise CodecError(N.last_error())
             cap = total.value
         buf = (C.c_uint8 * max(cap, 1))()
-        if call(codec._h, self._h, bw, bh, n, frm, to, from_xy, to_xy, flags, buf, len(buf), lens, keys, C.byref(total)) != 0:
+        if call(buf, len(buf)) != 0:
             raise CodecError(N.last_error())
         dev, host = C.c_uint64(0), C.c_uint64(0)   # (the first call adds the scratch the frames are assembled in)
         self._lib.jsp_index_info(self._h, None, C.byref(dev), C.byref(host))
@@ -865,7 +847,7 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
         for j in range(n):
             out.append(bytes(view[at:at + lens[j]]))
             at += lens[j]
-        return out, [bool(keys[j]) for j in range(n)]
+        return out
 
     def _open(self, who: str) -> _NativeCodec:
         if not self._h:

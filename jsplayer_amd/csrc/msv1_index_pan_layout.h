@@ -1,9 +1,7 @@
 // Host arithmetic of jsp_index_pan_frames (msv1_seek.cpp) that needs neither HIP nor the codec: the check of a rectangle's origin
-// against the block grid, the kind of a pair and its check, and the parts of the scratch for a slice of pairs with their origins.
-// On top of msv1_index_crop_layout.h.  Plain C++, so that a program of its own can run it under a sanitizer.
+// against the block grid, the kind of a pair and its check; the parts of the scratch: msv1_index_clip_layout.h.  On top of
+// msv1_index_crop_layout.h.  Plain C++, so that a program of its own can run it under a sanitizer.
 #pragma once
-#include <initializer_list>
-
 #include "msv1_index_crop_layout.h"
 
 namespace jsp {
@@ -28,25 +26,6 @@ inline PanBad pan_pair_check(int nframes, int nbx, int nby, int bw, int bh, int 
     if (!pan_origin_ok(nbx, nby, bw, bh, b[0], b[1])) return PAN_BAD_TO_ORIGIN;
     if (kind != PAN_KEY && !pan_origin_ok(nbx, nby, bw, bh, a[0], a[1])) return PAN_BAD_FROM_ORIGIN;
     return PAN_OK;
-}
-
-// The parts of the scratch for slices of S pairs: the pairs' origins (per pair: the x, y at `from`, the x, y at `to`) in front, then
-// crop's parts, moved behind them.  The host's pinned side has the parts before c.records_at at the same offsets.
-struct PanLayout {
-    size_t origins_at;
-    CropLayout c;   // (every offset counts from the start of the scratch)
-    size_t bytes;
-};
-inline PanLayout pan_layout(size_t S, size_t nb, size_t nwg, size_t bound) {
-    PanLayout l{};
-    l.origins_at = 0;
-    const size_t shift = (4 * sizeof(int32_t) * S + 15) & ~(size_t)15;
-    l.c = crop_layout(S, nb, nwg, bound);
-    for (size_t* at : {&l.c.pairs_at, &l.c.bases_at, &l.c.status_at, &l.c.totals_at, &l.c.counts_at, &l.c.first_at, &l.c.records_at, &l.c.out_at,
-                       &l.c.bytes})
-        *at += shift;
-    l.bytes = l.c.bytes;
-    return l;
 }
 
 }  // namespace jsp

@@ -32,27 +32,16 @@
 // set, hence the same skip words when neither is tight.  A call of only KEY and FORWARD pairs returns byte for byte what
 // jsp_index_crop_frames returns.  NOT promised: the exclusions of KeyFrame, and a step back to before the range (to = -1).
 //
-// The shape is the crop sizes kernel's, grid.y = the pair, no workgroup ever waits for another: a lane owns PA_LANE_BLOCKS
-// consecutive blocks OF THE RECTANGLE, a workgroup PA_WG_BLOCKS; the block before a lane's first one is the neighbour lane's last
-// block through LDS, the workgroup's first lane judges src(j0 - 1) by the same rule; bytes and code counts are scanned in one word.
-// What differs is the decision per block, path_kept: the pair's kind is read from (a, b), uniform over the workgroup (the pair is
-// blockIdx.y); a BACK pair walks the writer bitmap twice, for the last writer <= hi and, only for a touched block, the last writer
-// <= b; a tight pair decodes both ends through picture_block_of with the writers it already has.  The records it leaves (writer
-// frame, offset << 8 | length, MSV1_DELTA_SKIP for a run head), the totals, the counts and first_written are what
-// msv1_index_crop_gather_kernel reads: there is no gather kernel here.  Lanes with j >= nb touch nothing, and no lane forms a source
-// block for such a j: the host has checked the rectangle against the block grid, so every src(j), j < nb, lies in [0, nblocks), and
-// every pair against the index, so no walk starts above frame nframes - 1 or below frame 0.
-#include "msv1_index_codes.h"
+// The shape and the kernel's body are the clip skeleton's (msv1_index_clip_device.h), shared with the delta, crop and pan calls; src(j)
+// is crop's.  What this call supplies is the decision per block, PathRule::coded: the pair's kind is read from (a, b), uniform over the
+// workgroup (the pair is blockIdx.y); a BACK pair walks the writer bitmap twice, for the last writer <= hi and, only for a touched
+// block, the last writer <= b; a tight pair decodes both ends through picture_block_of with the writers it already has.  The records
+// it leaves, the totals, the counts and first_written are what msv1_index_crop_gather_kernel reads: there is no gather kernel here.
+// The host has checked every pair against the index, so no walk starts above frame nframes - 1 or below frame 0.
+#include "msv1_index_clip_device.h"
 
 namespace jsp {
 namespace {
-
-constexpr int WG = INDEX_CODES_WG;
-constexpr int PA_LANE_BLOCKS = 4;
-constexpr int PA_WG_BLOCKS = MSV1_KEYFRAME_WG_BLOCKS;   // (msv1_seek.h: the host sizes totals[], first_written[] and counts[] by it)
-static_assert(PA_WG_BLOCKS == WG * PA_LANE_BLOCKS, "a lane owns PA_LANE_BLOCKS consecutive blocks");
-static_assert(2 * PA_WG_BLOCKS >= MSV1_DELTA_RUN, "a count's look-ahead ends within the next two workgroups");
-static_assert(PA_WG_BLOCKS * 18 < (1 << 16) && PA_WG_BLOCKS < (1 << 15), "bytes and codes of a workgroup share one scanned word");
 
 // The last writer <= t of source block `blk`, -1 when there is none (t = -1: none).
 __device__ __forceinline__ int path_last_writer(const Msv1IndexSrc& s, int blk, int t) {
@@ -64,143 +53,50 @@ __device__ __forceinline__ int path_last_writer(const Msv1IndexSrc& s, int blk, 
 
 // Whether source block `blk` is KEPT by the pair (a, b).  f: its last writer <= b, -1 when a kept block has none (it refuses).
 template <int BITS, bool TIGHT>
-__device__ __forceinline__ bool path_kept(const Msv1IndexSrc& s, int blk, int a, int b, const uint32_t* s_pal, int& f) {
-    f = -1;
-    if (a == MSV1_CROP_KEY) {                            // every block of a key pair is kept
-        f = path_last_writer(s, blk, b);
+struct PathRule {
+    static constexpr bool counts = true;
+    int a, b;
+    bool key;
+    __device__ __forceinline__ bool coded(const Msv1IndexSrc& s, int blk, const uint32_t* s_pal, int& f) const {
+        f = -1;
+        if (key) {                                           // every block of a key pair is kept
+            f = path_last_writer(s, blk, b);
+            return true;
+        }
+        const int lo = min(a, b), hi = max(a, b);
+        if (lo == hi) return false;                          // HOLD
+        const int fh = path_last_writer(s, blk, hi);         // (hi > lo >= -1)
+        if (fh <= lo) return false;                          // not touched
+        const bool back = a > b;
+        const int fl = back || TIGHT ? path_last_writer(s, blk, lo) : -1;
+        f = back ? fl : fh;
+        if (TIGHT) {
+            uint32_t pa[16], pb[16];
+            if (picture_block_of<BITS>(s, blk, back ? fh : fl, s_pal, pa) && picture_block_of<BITS>(s, blk, f, s_pal, pb)) {
+                uint32_t diff = 0u;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) diff |= pa[k] ^ pb[k];
+                if (diff == 0u) return false;                // dropped
+            }
+        }
         return true;
     }
-    const int lo = min(a, b), hi = max(a, b);
-    if (lo == hi) return false;                          // HOLD
-    const int fh = path_last_writer(s, blk, hi);         // (hi > lo >= -1)
-    if (fh <= lo) return false;                          // not touched
-    const bool back = a > b;
-    const int fl = back || TIGHT ? path_last_writer(s, blk, lo) : -1;
-    f = back ? fl : fh;
-    if (TIGHT) {
-        uint32_t pa[16], pb[16];
-        if (picture_block_of<BITS>(s, blk, back ? fh : fl, s_pal, pa) && picture_block_of<BITS>(s, blk, f, s_pal, pb)) {
-            uint32_t diff = 0u;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) diff |= pa[k] ^ pb[k];
-            if (diff == 0u) return false;                // dropped
-        }
-    }
-    return true;
-}
+};
 
 // TIGHT = true applies the tight flag to the pairs that are not KEY.
 template <int BITS, bool TIGHT>
-__global__ __launch_bounds__(WG) void msv1_index_path_sizes_kernel(const Msv1IndexSrc s, const Msv1CropRect r, Msv1CropScratch d) {
-    __shared__ uint32_t s_pal[TIGHT && BITS == 8 ? 256 : 1];
-    if (TIGHT) load_palette<BITS>(s_pal, s.palette);
-    __shared__ uint32_t s_wave[WG / 64];
-    __shared__ uint32_t s_first[WG / 64];
-    __shared__ uint8_t s_last[WG];                       // per lane: its last block is kept
-    const int pair = (int)blockIdx.y, nwg = (int)gridDim.x;
-    const int a = d.pairs[2 * pair], b = d.pairs[2 * pair + 1];
-    const bool key = a == MSV1_CROP_KEY;
-    const int j0 = (int)blockIdx.x * PA_WG_BLOCKS + (int)threadIdx.x * PA_LANE_BLOCKS;
-    int col = 0, blk = 0;                                // the column of block j in the rectangle, and src(j)
-    if (j0 < r.nb) {
-        const int row = j0 / r.bw;
-        col = j0 - row * r.bw;
-        blk = (r.by + row) * s.nbx + r.bx + col;
-    }
-    uint32_t frame[PA_LANE_BLOCKS], len[PA_LANE_BLOCKS];
-    bool kept[PA_LANE_BLOCKS];
-    uint32_t worst = 0xFFFFFFFFu, first = MSV1_DELTA_NONE;
-#pragma unroll
-    for (int i = 0; i < PA_LANE_BLOCKS; ++i) {
-        const int j = j0 + i;
-        frame[i] = 0u;
-        len[i] = 0u;
-        kept[i] = false;
-        if (j >= r.nb) continue;
-        if (i > 0) {                                     // src(j) from src(j - 1): the next column, or the first one of the next row
-            ++blk;
-            if (++col == r.bw) {
-                col = 0;
-                blk += s.nbx - r.bw;
-            }
-        }
-        int f;
-        if (!path_kept<BITS, TIGHT>(s, blk, a, b, s_pal, f)) continue;
-        if (f < 0) {                                     // (no code to take: the pair refuses, nothing of it is gathered)
-            worst = min(worst, ((uint32_t)j << 1) | MSV1_KEYFRAME_NO_WRITER);
-            continue;
-        }
-        kept[i] = true;
-        first = min(first, (uint32_t)j);
-        uint32_t o, e;
-        const Msv1IndexChunk ch = index_code_at(s, f, blk, BITS, o, e);
-        frame[i] = (uint32_t)f;
-        len[i] = index_whole_length<BITS>(ch, o, e);
-        if (len[i] == 0u) worst = min(worst, ((uint32_t)j << 1) | MSV1_KEYFRAME_CUT);
-    }
-    if (worst != 0xFFFFFFFFu) atomicMin(d.status + pair, worst);
-
-    // the block before the lane's first one: the neighbour lane's last block; the workgroup's first lane judges src(j0 - 1)
-    s_last[threadIdx.x] = kept[PA_LANE_BLOCKS - 1] ? 1 : 0;
-    bool before = true;                                  // (block 0 is a run head: as if a kept block stood before it)
-    if (threadIdx.x == 0 && !key && j0 > 0 && j0 < r.nb) {   // (a key pair has no run heads: nothing to walk for)
-        const int row = (j0 - 1) / r.bw;
-        int f;
-        before = path_kept<BITS, TIGHT>(s, (r.by + row) * s.nbx + r.bx + (j0 - 1 - row * r.bw), a, b, s_pal, f) && f >= 0;
-    }
-    __syncthreads();
-    if (threadIdx.x > 0) before = s_last[threadIdx.x - 1] != 0;
-#pragma unroll
-    for (int i = 0; i < PA_LANE_BLOCKS; ++i) {
-        const int j = j0 + i;
-        if (j < r.nb && !key && !kept[i] && (before || j % MSV1_DELTA_RUN == 0)) len[i] = MSV1_DELTA_SKIP;
-        before = kept[i];
-    }
-
-    // exclusive scan of the contributions over the workgroup (low half: bytes, high half: codes); its first kept block
-    uint32_t mine = 0u;
-#pragma unroll
-    for (int i = 0; i < PA_LANE_BLOCKS; ++i) mine += len[i] == MSV1_DELTA_SKIP ? 2u : len[i] != 0u ? (1u << 16) | len[i] : 0u;
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) first = min(first, (uint32_t)__shfl_xor((int)first, k));
-    if (lane == 0) s_first[wave] = first;
-    uint32_t total;
-    uint32_t off = index_wg_scan(mine, s_wave, total) & 0xFFFFu;   // (its barrier also publishes s_first)
-    uint32_t* records = d.records + 2 * (size_t)pair * (size_t)r.nb;
-#pragma unroll
-    for (int i = 0; i < PA_LANE_BLOCKS; ++i) {
-        const int j = j0 + i;
-        if (j < r.nb) {
-            *(gu32*)(records + 2 * (size_t)j) = frame[i];
-            *(gu32*)(records + 2 * (size_t)j + 1) = (off << 8) | len[i];
-        }
-        off += len[i] == MSV1_DELTA_SKIP ? 2u : len[i];
-    }
-    if (threadIdx.x == 0) {
-        uint32_t f0 = s_first[0];
-#pragma unroll
-        for (int v = 1; v < WG / 64; ++v) f0 = min(f0, s_first[v]);
-        *(gu32*)(d.totals + (size_t)pair * nwg + blockIdx.x) = total & 0xFFFFu;
-        *(gu32*)(d.counts + (size_t)pair * nwg + blockIdx.x) = total >> 16;
-        *(gu32*)(d.first_written + (size_t)pair * nwg + blockIdx.x) = f0;
-    }
+__global__ __launch_bounds__(INDEX_CODES_WG) void msv1_index_path_sizes_kernel(const Msv1IndexSrc s, const Msv1CropRect r, Msv1ClipScratch d) {
+    const int a = d.pairs[2 * blockIdx.y], b = d.pairs[2 * blockIdx.y + 1];
+    clip_sizes_body<BITS, TIGHT>(s, clip_rect_src(s, r), PathRule<BITS, TIGHT>{a, b, a == MSV1_CROP_KEY}, d);
 }
 
 }  // namespace
 
-void msv1_launch_index_path_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, bool tight,
+void msv1_launch_index_path_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1ClipScratch& d, bool tight,
                                   hipStream_t stream) {
-    if (r.nb <= 0 || npairs <= 0) return;
-    const dim3 grid((unsigned)msv1_keyframe_workgroups(r.nb), (unsigned)npairs);
-    if (tight) {
-        if (src.bits == 16) hipLaunchKernelGGL((msv1_index_path_sizes_kernel<16, true>), grid, dim3(WG), 0, stream, src, r, d);
-        else hipLaunchKernelGGL((msv1_index_path_sizes_kernel<8, true>), grid, dim3(WG), 0, stream, src, r, d);
-    } else if (src.bits == 16) {
-        hipLaunchKernelGGL((msv1_index_path_sizes_kernel<16, false>), grid, dim3(WG), 0, stream, src, r, d);
-    } else {
-        hipLaunchKernelGGL((msv1_index_path_sizes_kernel<8, false>), grid, dim3(WG), 0, stream, src, r, d);
-    }
+    clip_launch(r.nb, npairs, src.bits, tight, [&](dim3 grid, dim3 wg, auto bits, auto tight_) {
+        hipLaunchKernelGGL((msv1_index_path_sizes_kernel<decltype(bits)::value, decltype(tight_)::value>), grid, wg, 0, stream, src, r, d);
+    });
 }
 
 }  // namespace jsp

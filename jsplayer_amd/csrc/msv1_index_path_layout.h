@@ -1,5 +1,5 @@
 // Host arithmetic of jsp_index_path_frames (msv1_seek.cpp) that needs neither HIP nor the codec: the kind of a pair and its check
-// against the index.  The rectangle and the scratch are crop's (msv1_index_crop_layout.h).  Plain C++, so that a program of its own
+// against the index.  The rectangle is crop's (msv1_index_crop_layout.h).  Plain C++, so that a program of its own
 // can run it under a sanitizer.
 #pragma once
 #include "msv1_index_crop_layout.h"

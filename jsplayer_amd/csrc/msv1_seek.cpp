@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "codec.h"
+#include "msv1_index_clip_layout.h"
 #include "msv1_index_crop_layout.h"
 #include "msv1_index_pan_layout.h"
 #include "msv1_index_path_layout.h"
@@ -40,9 +41,9 @@ struct jsp_index {
     PinnedBuffer h_key_frame;              // ... and where the status, the length and a refused block's record arrive (both: first call)
     DeviceBuffer d_delta;                  // jsp_index_delta_frames: one slice of pairs — their list, statuses, totals, records, frames ...
     PinnedBuffer h_delta;                  // ... and the host's side of the list, the statuses and the totals (both: first call)
-    DeviceBuffer d_crop;                   // jsp_index_crop_frames, jsp_index_path_frames: the same for a slice of pairs of a rectangle (CropLayout) ...
+    DeviceBuffer d_crop;                   // jsp_index_crop_frames, jsp_index_path_frames: the same for a slice of pairs of a rectangle ...
     PinnedBuffer h_crop;                   // ... and the host's side of it (both: first call)
-    DeviceBuffer d_pan;                    // jsp_index_pan_frames: the same with the pairs' origins in front (PanLayout) ...
+    DeviceBuffer d_pan;                    // jsp_index_pan_frames: the same with the pairs' origins in front (clip_layout) ...
     PinnedBuffer h_pan;                    // ... and the host's side of it (both: first call)
     uint64_t device_bytes() const {
         uint64_t n = d_chunks.cap + d_frame_chunk.cap + d_bitmap.cap + d_palette.cap + d_before.cap + d_frame_list.cap + d_play_dsts.cap +
@@ -871,33 +872,158 @@ extern "C" int jsp_index_key_frame(jsp_codec* c, jsp_index* idx, int t, uint8_t*
     }
 }
 
-// ---- inter frames that span a gap: a clip thinned to every s-th frame, or without its idle frames, needs frames that exist in no
-// file.  The inter frame from the picture of frame a to the picture of frame b is, block by block, the code of the block's last
-// writer in (a, b] or a skip (the rule: msv1_index_delta_kernels.hip).  n pairs a call, in slices of pairs so that the scratch stays
-// bounded: a sizes launch per slice first — statuses and lengths of ALL pairs are known before a byte reaches `out` — then a sizes
-// and a gather launch per slice (one slice: its records are still there, the gather alone).  Into HOST memory; the codec is only lent.
+// ---- the clip calls: stream bytes of frames that exist in no file, gathered from codes the index holds by a block rule — frames that
+// span a gap (delta, tight), frames of a block rectangle (crop), along any path (path), of a rectangle that moves (pan).  n pairs a call,
+// in slices of pairs so that the scratch stays bounded: a sizes launch per slice first — statuses and lengths of ALL pairs are known
+// before a byte reaches `out` — then a sizes and a gather launch per slice (one slice: its records are still there, the gather alone).
+// Into HOST memory; the codec is only lent.  The entry points check their arguments and pairs; clip_frames does the rest, once.
 namespace {
 constexpr uint64_t kDeltaSliceBudget = 64ull << 20;   // option "msv1_index_delta_slice" = "auto": the pairs whose scratch this holds
 
-// The parts of d_delta for slices of S pairs, each 16-byte aligned; h_delta has the first four at the same offsets.
-struct DeltaLayout {
-    size_t pairs_at, bases_at, status_at, totals_at, first_at, records_at, out_at, bytes;
+// Where a clip call's results go (keys: null for a call that reports none).  zero(): what a refusal leaves, and every call starts from.
+struct ClipOut {
+    int n;
+    uint8_t* out;
+    size_t cap;
+    size_t* lens;
+    int* keys;
+    size_t* total;
+    void zero() const {
+        const bool n_ok = n >= 1 && n <= 4096;
+        if (total) *total = 0;
+        if (lens && n_ok) std::fill(lens, lens + n, (size_t)0);
+        if (keys && n_ok) std::fill(keys, keys + n, 0);
+    }
 };
-DeltaLayout delta_layout(size_t S, size_t nblocks, size_t nwg, size_t bound) {
-    const auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
-    DeltaLayout l{};
-    l.pairs_at = 0;
-    l.bases_at = l.pairs_at + up16(2 * sizeof(int32_t) * S);
-    l.status_at = l.bases_at + up16(sizeof(uint64_t) * S);
-    l.totals_at = l.status_at + up16(sizeof(uint32_t) * S);
-    l.first_at = l.totals_at + up16(sizeof(uint32_t) * S * nwg);
-    l.records_at = l.first_at + up16(sizeof(uint32_t) * S * nwg);
-    l.out_at = l.records_at + up16(2 * sizeof(uint32_t) * S * nblocks);
-    l.bytes = l.out_at + S * bound;
-    return l;
+
+// Which of the index's scratch pairs a clip call uses, and in which layout.
+struct ClipBuffers {
+    ClipForm form;
+    DeviceBuffer& d;
+    PinnedBuffer& h;
+};
+
+// The words for block j of a rectangle at (bx, by), bw blocks wide, in a refusal.
+void rect_block_words(char (&block)[96], int nbx, int bx, int by, int bw, uint32_t j) {
+    snprintf(block, sizeof(block), "block %u of the rectangle (block %lld of the picture)", j, (long long)crop_src_block(nbx, bx, by, bw, (int64_t)j));
+}
+
+// The checked call `who` over frames of nb blocks, with the scratch pair `buf` of the index.  The call
+// supplies what is its own:
+//   put(p, pair, origin)        the two pair words of pair p for the device, and (CLIP_PAN; else origin is null) its four origin words;
+//   sizes(m, k), gather(m, k)   its two launches over the m pairs of a slice;
+//   name(p, j, pair, block)     the words that name pair p and block j of its frame in a refusal; returns the pair's `to`.
+template <class Put, class Sizes, class Gather, class Name>
+int clip_frames(const char* who, jsp_codec* c, const Msv1IndexSrc& src, const ClipBuffers& buf, size_t nb, const ClipOut& o, Put&& put,
+                Sizes&& sizes, Gather&& gather, Name&& name) {
+    const size_t n = (size_t)o.n;
+    const ClipForm form = buf.form;
+    try {
+        c->activate();
+        const size_t nwg = (size_t)msv1_keyframe_workgroups((int)nb);
+        const size_t bound = nb * (src.bits == 16 ? 18u : 10u);
+        size_t S = (size_t)c->index_delta_slice;
+        if (S == 0) S = std::clamp<uint64_t>(kDeltaSliceBudget / clip_layout(form, 1, nb, nwg, bound).bytes, 1, 4096);
+        S = std::min(S, n);
+        const ClipLayout l = clip_layout(form, S, nb, nwg, bound);
+        buf.d.reserve(l.bytes);
+        buf.h.reserve(l.host_bytes);
+        uint8_t* d = buf.d.as<uint8_t>();
+        uint8_t* h = buf.h.as<uint8_t>();
+        const auto words = [&](size_t at) { return reinterpret_cast<uint32_t*>(d + at); };
+        const Msv1ClipScratch k{form == CLIP_PAN ? reinterpret_cast<const int32_t*>(d + l.origins_at) : nullptr,
+                                reinterpret_cast<const int32_t*>(d + l.pairs_at),
+                                reinterpret_cast<const uint64_t*>(d + l.bases_at),
+                                words(l.status_at),
+                                words(l.totals_at),
+                                words(l.first_at),
+                                form == CLIP_GRID ? nullptr : words(l.counts_at),
+                                words(l.records_at),
+                                d + l.out_at};
+        std::vector<size_t> length(n, 0);
+        std::vector<uint8_t> all_coded(n, 0);
+        // pairs [j0, j0 + m) and where their frames start go to the device, then the sizes launch (not when the records are there)
+        const auto upload = [&](size_t j0, size_t m, bool launch) {
+            int32_t* ho = reinterpret_cast<int32_t*>(h + l.origins_at);
+            int32_t* hp = reinterpret_cast<int32_t*>(h + l.pairs_at);
+            uint64_t* hb = reinterpret_cast<uint64_t*>(h + l.bases_at);
+            uint64_t at = 0;
+            for (size_t i = 0; i < m; ++i) {
+                put(j0 + i, hp + 2 * i, k.origins ? ho + 4 * i : nullptr);
+                hb[i] = at;
+                at += length[j0 + i];
+            }
+            JSP_HIP(hipMemcpyAsync(d, h, l.status_at, hipMemcpyHostToDevice, c->stream));
+            if (!launch) return;
+            JSP_HIP(hipMemsetAsync(k.status, 0xFF, sizeof(uint32_t) * m, c->stream));
+            sizes((int)m, k);
+            JSP_HIP(hipGetLastError());
+        };
+        for (size_t j0 = 0; j0 < n; j0 += S) {
+            const size_t m = std::min(S, n - j0);
+            upload(j0, m, true);
+            JSP_HIP(hipMemcpyAsync(h + l.status_at, d + l.status_at, l.first_at - l.status_at, hipMemcpyDeviceToHost, c->stream));
+            JSP_HIP(hipStreamSynchronize(c->stream));
+            const uint32_t* status = reinterpret_cast<const uint32_t*>(h + l.status_at);
+            const uint32_t* totals = reinterpret_cast<const uint32_t*>(h + l.totals_at);
+            const uint32_t* counts = reinterpret_cast<const uint32_t*>(h + l.counts_at);
+            for (size_t i = 0; i < m; ++i) {
+                const size_t p = j0 + i;
+                if (status[i] != 0xFFFFFFFFu) {   // refused: the first pair, and its first block, that says so
+                    const uint32_t j = status[i] >> 1;
+                    char pair[64], block[96];
+                    const int to = name(p, j, pair, block);
+                    if ((status[i] & 1u) == MSV1_KEYFRAME_NO_WRITER) {
+                        set_error("%s: pair %d %s: %s has no writer up to frame %d in the index", who, (int)p, pair, block, to);
+                    } else {
+                        uint32_t* writer = reinterpret_cast<uint32_t*>(h + l.host_bytes - 16);
+                        JSP_HIP(hipMemcpyAsync(writer, k.records + 2 * (i * nb + j), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                        JSP_HIP(hipStreamSynchronize(c->stream));
+                        set_error("%s: pair %d %s: the code of %s in frame %u, its last writer, is cut off by the end of the frame's data", who,
+                                  (int)p, pair, block, *writer);
+                    }
+                    return JSP_ERROR_OCCURED;
+                }
+                size_t coded = 0;
+                for (size_t g = 0; g < nwg; ++g) {
+                    length[p] += totals[i * nwg + g];
+                    if (k.counts) coded += counts[i * nwg + g];
+                }
+                all_coded[p] = coded == nb;
+                if (length[p] > bound) throw std::runtime_error(std::string(who) + ": a frame is longer than its bound");
+            }
+        }
+        size_t sum = 0;
+        for (size_t j = 0; j < n; ++j) {
+            sum += (o.lens[j] = length[j]);
+            if (o.keys) o.keys[j] = all_coded[j];
+        }
+        *o.total = sum;
+        if (o.cap < sum) return fail("%s: cap is smaller than the frames (*total has their length, lens[] each frame's)", who);
+        size_t at = 0;
+        for (size_t j0 = 0; j0 < n; j0 += S) {
+            const size_t m = std::min(S, n - j0);
+            upload(j0, m, S < n);
+            gather((int)m, k);
+            JSP_HIP(hipGetLastError());
+            size_t bytes = 0;
+            for (size_t i = 0; i < m; ++i) bytes += length[j0 + i];
+            JSP_HIP(hipMemcpyAsync(o.out + at, k.out, bytes, hipMemcpyDeviceToHost, c->stream));
+            JSP_HIP(hipStreamSynchronize(c->stream));
+            at += bytes;
+        }
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        o.zero();
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
 }
 }  // namespace
 
+// ---- inter frames that span a gap: a clip thinned to every s-th frame, or without its idle frames.  The inter frame from the picture
+// of frame a to the picture of frame b is, block by block, the code of the block's last writer in (a, b] or a skip (the rule:
+// msv1_index_delta_kernels.hip).
 extern "C" int jsp_index_delta_bound(const jsp_index* idx, size_t* bytes) {
     if (!idx || !bytes) return fail("index_delta: null argument");
     *bytes = (size_t)std::max(idx->geo.nblocks, 0) * (idx->geo.bits == 16 ? 18u : 10u);
@@ -905,12 +1031,11 @@ extern "C" int jsp_index_delta_bound(const jsp_index* idx, size_t* bytes) {
 }
 
 namespace {
-// jsp_index_delta_frames (who = "index_delta") and jsp_index_tight_frames ("index_tight", tight): one routine, the rule of the sizes
-// launch apart.
+// jsp_index_delta_frames (who = "index_delta") and jsp_index_tight_frames ("index_tight", tight): the rule of the sizes launch apart.
 int index_gap_frames(const char* who, bool tight, jsp_codec* c, jsp_index* idx, int n, const int* from, const int* to, uint8_t* out, size_t cap,
                      size_t* lens, size_t* total) {
-    if (total) *total = 0;
-    if (lens && n >= 1 && n <= 4096) std::fill(lens, lens + n, (size_t)0);
+    const ClipOut o{n, out, cap, lens, nullptr, total};
+    o.zero();
     if (!c || !idx || !from || !to || !lens || !total || (!out && cap)) return fail("%s: null argument", who);
     if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
     if (idx->codec_serial != c->serial) return fail("%s: the index was built by another codec", who);
@@ -923,83 +1048,19 @@ int index_gap_frames(const char* who, bool tight, jsp_codec* c, jsp_index* idx, 
     const Msv1IndexSrc& src = idx->src;
     if (src.nblocks < 1) return fail("%s: the picture has no 4x4 block", who);
     if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
-    try {
-        c->activate();
-        const size_t nblocks = (size_t)src.nblocks, nwg = (size_t)msv1_keyframe_workgroups(src.nblocks);
-        const size_t bound = nblocks * (src.bits == 16 ? 18u : 10u);
-        size_t S = (size_t)c->index_delta_slice;
-        if (S == 0) S = std::clamp<uint64_t>(kDeltaSliceBudget / delta_layout(1, nblocks, nwg, bound).bytes, 1, 4096);
-        S = std::min(S, (size_t)n);
-        const DeltaLayout l = delta_layout(S, nblocks, nwg, bound);
-        idx->d_delta.reserve(l.bytes);
-        idx->h_delta.reserve(l.first_at + 16);
-        uint8_t* d = idx->d_delta.as<uint8_t>();
-        uint8_t* h = idx->h_delta.as<uint8_t>();
-        const Msv1DeltaScratch k{reinterpret_cast<const int32_t*>(d + l.pairs_at), reinterpret_cast<const uint64_t*>(d + l.bases_at),
-                                 reinterpret_cast<uint32_t*>(d + l.status_at),     reinterpret_cast<uint32_t*>(d + l.totals_at),
-                                 reinterpret_cast<uint32_t*>(d + l.first_at),      reinterpret_cast<uint32_t*>(d + l.records_at),
-                                 d + l.out_at};
-        std::vector<size_t> length((size_t)n, 0);
-        // pairs [j0, j0 + m) and where their frames start go to the device, then the sizes launch (not when the records are there)
-        const auto sizes = [&](size_t j0, size_t m, bool launch) {
-            int32_t* hp = reinterpret_cast<int32_t*>(h + l.pairs_at);
-            uint64_t* hb = reinterpret_cast<uint64_t*>(h + l.bases_at);
-            uint64_t at = 0;
-            for (size_t i = 0; i < m; ++i) {
-                hp[2 * i] = from[j0 + i];
-                hp[2 * i + 1] = to[j0 + i];
-                hb[i] = at;
-                at += length[j0 + i];
-            }
-            JSP_HIP(hipMemcpyAsync(d, h, l.status_at, hipMemcpyHostToDevice, c->stream));
-            if (!launch) return;
-            JSP_HIP(hipMemsetAsync(k.status, 0xFF, sizeof(uint32_t) * m, c->stream));
-            msv1_launch_index_delta_sizes(src, (int)m, k, tight, c->stream);
-            JSP_HIP(hipGetLastError());
-        };
-        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
-            const size_t m = std::min(S, (size_t)n - j0);
-            sizes(j0, m, true);
-            JSP_HIP(hipMemcpyAsync(h + l.status_at, d + l.status_at, l.first_at - l.status_at, hipMemcpyDeviceToHost, c->stream));
-            JSP_HIP(hipStreamSynchronize(c->stream));
-            const uint32_t* status = reinterpret_cast<const uint32_t*>(h + l.status_at);
-            const uint32_t* totals = reinterpret_cast<const uint32_t*>(h + l.totals_at);
-            for (size_t i = 0; i < m; ++i) {
-                if (status[i] != 0xFFFFFFFFu) {   // not cuttable: the first pair, and its first block, that says so, and the block's writer
-                    uint32_t* writer = reinterpret_cast<uint32_t*>(h + l.first_at);
-                    JSP_HIP(hipMemcpyAsync(writer, k.records + 2 * (i * nblocks + status[i]), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-                    JSP_HIP(hipStreamSynchronize(c->stream));
-                    set_error("%s: pair %d (%d, %d]: the code of block %u in frame %u, its last writer, is cut off by the end of the frame's data",
-                              who, (int)(j0 + i), from[j0 + i], to[j0 + i], status[i], *writer);
-                    return JSP_ERROR_OCCURED;
-                }
-                for (size_t g = 0; g < nwg; ++g) length[j0 + i] += totals[i * nwg + g];
-                if (length[j0 + i] > bound) throw std::runtime_error(std::string(who) + ": a frame is longer than its bound");
-            }
-        }
-        size_t sum = 0;
-        for (int j = 0; j < n; ++j) sum += (lens[j] = length[(size_t)j]);
-        *total = sum;
-        if (cap < sum) return fail("%s: cap is smaller than the frames (*total has their length, lens[] each frame's)", who);
-        size_t at = 0;
-        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
-            const size_t m = std::min(S, (size_t)n - j0);
-            sizes(j0, m, S < (size_t)n);
-            msv1_launch_index_delta_gather(src, (int)m, k, c->stream);
-            JSP_HIP(hipGetLastError());
-            size_t bytes = 0;
-            for (size_t i = 0; i < m; ++i) bytes += length[j0 + i];
-            JSP_HIP(hipMemcpyAsync(out + at, k.out, bytes, hipMemcpyDeviceToHost, c->stream));
-            JSP_HIP(hipStreamSynchronize(c->stream));
-            at += bytes;
-        }
-        return JSP_ZERO_STATE;
-    } catch (const std::exception& e) {
-        std::fill(lens, lens + n, (size_t)0);
-        *total = 0;
-        set_error("%s", e.what());
-        return JSP_ERROR_OCCURED;
-    }
+    return clip_frames(
+        who, c, src, ClipBuffers{CLIP_GRID, idx->d_delta, idx->h_delta}, (size_t)src.nblocks, o,
+        [&](size_t p, int32_t* pair, int32_t*) {
+            pair[0] = from[p];
+            pair[1] = to[p];
+        },
+        [&](int m, const Msv1ClipScratch& k) { msv1_launch_index_delta_sizes(src, m, k, tight, c->stream); },
+        [&](int m, const Msv1ClipScratch& k) { msv1_launch_index_delta_gather(src, m, k, c->stream); },
+        [&](size_t p, uint32_t j, char(&pair)[64], char(&block)[96]) {
+            snprintf(pair, sizeof(pair), "(%d, %d]", from[p], to[p]);
+            snprintf(block, sizeof(block), "block %u", j);
+            return to[p];
+        });
 }
 }  // namespace
 
@@ -1017,8 +1078,7 @@ extern "C" int jsp_index_tight_frames(jsp_codec* c, jsp_index* idx, int n, const
 // ---- a clip of a part of the picture: the frames of a block rectangle (bx, by, bw, bh) of the index — per pair a key frame of the
 // rectangle (from == JSP_CROP_KEY) or the inter frame over a gap, Delta or with JSP_CROP_TIGHT Tight, of the virtual index whose
 // block j is the rectangle's block j (the rule: msv1_index_crop_kernels.hip).  A code carries no position, so again only codes the
-// index holds are gathered.  Slices, launches and the contract are jsp_index_delta_frames'; keys[j] says that frame j codes every
-// block of the rectangle.  Into HOST memory; the codec is only lent.
+// index holds are gathered.  keys[j] says that frame j codes every block of the rectangle.
 extern "C" int jsp_index_crop_bound(const jsp_index* idx, int bw, int bh, size_t* bytes) {
     if (bytes) *bytes = 0;
     if (!idx || !bytes) return fail("index_crop: null argument");
@@ -1027,19 +1087,13 @@ extern "C" int jsp_index_crop_bound(const jsp_index* idx, int bw, int bh, size_t
     return JSP_ZERO_STATE;
 }
 
-// jsp_index_crop_frames (who = "index_crop") and jsp_index_path_frames ("index_path", path): one routine, the check of a pair, the sizes
-// launch and the words that name a pair in a refusal apart.  Both use the index's crop scratch.
-// (jsp_index_pan_frames below repeats this function's slices, refusals and gather loop with an origin per pair; the crop call is pinned
-// and is not routed through it, so a fix to the slice, refusal or gather logic here belongs there too.)
+// jsp_index_crop_frames (who = "index_crop") and jsp_index_path_frames ("index_path", path): the check of a pair, the sizes launch and
+// the words that name a pair in a refusal apart.  Both use the index's crop scratch.
 namespace {
 int index_rect_frames(const char* who, bool path, jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from,
                       const int* to, int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
-    const auto zero = [&]() {
-        if (total) *total = 0;
-        if (lens && n >= 1 && n <= 4096) std::fill(lens, lens + n, (size_t)0);
-        if (keys && n >= 1 && n <= 4096) std::fill(keys, keys + n, 0);
-    };
-    zero();
+    const ClipOut o{n, out, cap, lens, keys, total};
+    o.zero();
     if (!c || !idx || !from || !to || !lens || !total || (!out && cap)) return fail("%s: null argument", who);
     if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
     if (idx->codec_serial != c->serial) return fail("%s: the index was built by another codec", who);
@@ -1068,107 +1122,25 @@ int index_rect_frames(const char* who, bool path, jsp_codec* c, jsp_index* idx, 
     }
     if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
     const bool tight = (flags & JSP_CROP_TIGHT) != 0;
-    try {
-        c->activate();
-        const Msv1CropRect r{bx, by, bw, bh, bw * bh};
-        const size_t nb = (size_t)r.nb, nwg = (size_t)msv1_keyframe_workgroups(r.nb);
-        const size_t bound = nb * (src.bits == 16 ? 18u : 10u);
-        size_t S = (size_t)c->index_delta_slice;
-        if (S == 0) S = std::clamp<uint64_t>(kDeltaSliceBudget / crop_layout(1, nb, nwg, bound).bytes, 1, 4096);
-        S = std::min(S, (size_t)n);
-        const CropLayout l = crop_layout(S, nb, nwg, bound);
-        idx->d_crop.reserve(l.bytes);
-        idx->h_crop.reserve(l.records_at + 16);
-        uint8_t* d = idx->d_crop.as<uint8_t>();
-        uint8_t* h = idx->h_crop.as<uint8_t>();
-        const Msv1CropScratch k{reinterpret_cast<const int32_t*>(d + l.pairs_at), reinterpret_cast<const uint64_t*>(d + l.bases_at),
-                                reinterpret_cast<uint32_t*>(d + l.status_at),     reinterpret_cast<uint32_t*>(d + l.totals_at),
-                                reinterpret_cast<uint32_t*>(d + l.first_at),      reinterpret_cast<uint32_t*>(d + l.counts_at),
-                                reinterpret_cast<uint32_t*>(d + l.records_at),    d + l.out_at};
-        std::vector<size_t> length((size_t)n, 0);
-        std::vector<uint8_t> all_coded((size_t)n, 0);
-        // pairs [j0, j0 + m) and where their frames start go to the device, then the sizes launch (not when the records are there)
-        const auto sizes = [&](size_t j0, size_t m, bool launch) {
-            int32_t* hp = reinterpret_cast<int32_t*>(h + l.pairs_at);
-            uint64_t* hb = reinterpret_cast<uint64_t*>(h + l.bases_at);
-            uint64_t at = 0;
-            for (size_t i = 0; i < m; ++i) {
-                hp[2 * i] = from[j0 + i];
-                hp[2 * i + 1] = to[j0 + i];
-                hb[i] = at;
-                at += length[j0 + i];
-            }
-            JSP_HIP(hipMemcpyAsync(d, h, l.status_at, hipMemcpyHostToDevice, c->stream));
-            if (!launch) return;
-            JSP_HIP(hipMemsetAsync(k.status, 0xFF, sizeof(uint32_t) * m, c->stream));
-            if (path) msv1_launch_index_path_sizes(src, r, (int)m, k, tight, c->stream);
-            else msv1_launch_index_crop_sizes(src, r, (int)m, k, tight, c->stream);
-            JSP_HIP(hipGetLastError());
-        };
-        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
-            const size_t m = std::min(S, (size_t)n - j0);
-            sizes(j0, m, true);
-            JSP_HIP(hipMemcpyAsync(h + l.status_at, d + l.status_at, l.first_at - l.status_at, hipMemcpyDeviceToHost, c->stream));
-            JSP_HIP(hipStreamSynchronize(c->stream));
-            const uint32_t* status = reinterpret_cast<const uint32_t*>(h + l.status_at);
-            const uint32_t* totals = reinterpret_cast<const uint32_t*>(h + l.totals_at);
-            const uint32_t* counts = reinterpret_cast<const uint32_t*>(h + l.counts_at);
-            for (size_t i = 0; i < m; ++i) {
-                if (status[i] != 0xFFFFFFFFu) {   // refused: the first pair, and its first block of the rectangle, that says so
-                    const size_t p = j0 + i;
-                    const uint32_t j = status[i] >> 1;
-                    const long long blk = (long long)crop_src_block(src.nbx, bx, by, bw, (int64_t)j);
-                    char what[64];
-                    if (from[p] == JSP_CROP_KEY) snprintf(what, sizeof(what), "(key, %d)", to[p]);
-                    else if (from[p] > to[p]) snprintf(what, sizeof(what), "(%d -> %d, back)", from[p], to[p]);   // (path only)
-                    else snprintf(what, sizeof(what), "(%d, %d]", from[p], to[p]);
-                    if ((status[i] & 1u) == MSV1_KEYFRAME_NO_WRITER) {
-                        set_error("%s: pair %d %s: block %u of the rectangle (block %lld of the picture) has no writer up to frame %d in the index",
-                                  who, (int)p, what, j, blk, to[p]);
-                    } else {
-                        uint32_t* writer = reinterpret_cast<uint32_t*>(h + l.records_at);
-                        JSP_HIP(hipMemcpyAsync(writer, k.records + 2 * (i * nb + j), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-                        JSP_HIP(hipStreamSynchronize(c->stream));
-                        set_error("%s: pair %d %s: the code of block %u of the rectangle (block %lld of the picture) in frame %u, its last "
-                                  "writer, is cut off by the end of the frame's data",
-                                  who, (int)p, what, j, blk, *writer);
-                    }
-                    return JSP_ERROR_OCCURED;
-                }
-                size_t coded = 0;
-                for (size_t g = 0; g < nwg; ++g) {
-                    length[j0 + i] += totals[i * nwg + g];
-                    coded += counts[i * nwg + g];
-                }
-                all_coded[j0 + i] = coded == nb;
-                if (length[j0 + i] > bound) throw std::runtime_error(std::string(who) + ": a frame is longer than its bound");
-            }
-        }
-        size_t sum = 0;
-        for (int j = 0; j < n; ++j) {
-            sum += (lens[j] = length[(size_t)j]);
-            if (keys) keys[j] = all_coded[(size_t)j];
-        }
-        *total = sum;
-        if (cap < sum) return fail("%s: cap is smaller than the frames (*total has their length, lens[] each frame's)", who);
-        size_t at = 0;
-        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
-            const size_t m = std::min(S, (size_t)n - j0);
-            sizes(j0, m, S < (size_t)n);
-            msv1_launch_index_crop_gather(src, r, (int)m, k, c->stream);
-            JSP_HIP(hipGetLastError());
-            size_t bytes = 0;
-            for (size_t i = 0; i < m; ++i) bytes += length[j0 + i];
-            JSP_HIP(hipMemcpyAsync(out + at, k.out, bytes, hipMemcpyDeviceToHost, c->stream));
-            JSP_HIP(hipStreamSynchronize(c->stream));
-            at += bytes;
-        }
-        return JSP_ZERO_STATE;
-    } catch (const std::exception& e) {
-        zero();
-        set_error("%s", e.what());
-        return JSP_ERROR_OCCURED;
-    }
+    const Msv1CropRect r{bx, by, bw, bh, bw * bh};
+    return clip_frames(
+        who, c, src, ClipBuffers{CLIP_RECT, idx->d_crop, idx->h_crop}, (size_t)r.nb, o,
+        [&](size_t p, int32_t* pair, int32_t*) {
+            pair[0] = from[p];
+            pair[1] = to[p];
+        },
+        [&](int m, const Msv1ClipScratch& k) {
+            if (path) msv1_launch_index_path_sizes(src, r, m, k, tight, c->stream);
+            else msv1_launch_index_crop_sizes(src, r, m, k, tight, c->stream);
+        },
+        [&](int m, const Msv1ClipScratch& k) { msv1_launch_index_crop_gather(src, r, m, k, c->stream); },
+        [&](size_t p, uint32_t j, char(&pair)[64], char(&block)[96]) {
+            if (from[p] == JSP_CROP_KEY) snprintf(pair, sizeof(pair), "(key, %d)", to[p]);
+            else if (from[p] > to[p]) snprintf(pair, sizeof(pair), "(%d -> %d, back)", from[p], to[p]);   // (path only)
+            else snprintf(pair, sizeof(pair), "(%d, %d]", from[p], to[p]);
+            rect_block_words(block, src.nbx, bx, by, bw, j);
+            return to[p];
+        });
 }
 }  // namespace
 
@@ -1179,8 +1151,8 @@ extern "C" int jsp_index_crop_frames(jsp_codec* c, jsp_index* idx, int bx, int b
 
 // ---- a clip along any path through the index: jsp_index_crop_frames with pairs in either direction — a step back (from > to), a hold
 // (from == to), and crop's key and gap pairs unchanged (the rule: msv1_index_path_kernels.hip).  A step back gathers, for the blocks
-// the frames of (to, from] coded, the code of the last writer <= to: again only codes the index holds.  Slices, scratch, gather launch
-// and the contract are jsp_index_crop_frames'.  Into HOST memory; the codec is only lent.
+// the frames of (to, from] coded, the code of the last writer <= to: again only codes the index holds.  Scratch and gather launch are
+// jsp_index_crop_frames'.
 extern "C" int jsp_index_path_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to,
                                      int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
     return index_rect_frames("index_path", true, c, idx, bx, by, bw, bh, n, from, to, flags, out, cap, lens, keys, total);
@@ -1188,18 +1160,13 @@ extern "C" int jsp_index_path_frames(jsp_codec* c, jsp_index* idx, int bx, int b
 
 // ---- a clip that pans across the picture: jsp_index_crop_frames with an origin per pair and end of a pair (the rule:
 // msv1_index_pan_kernels.hip).  A moved pair of a call without JSP_CROP_TIGHT goes to the device as the key pair of its rectangle at
-// `to`.  Slices, launches and the contract are jsp_index_crop_frames' — the body is that function's, copied, with the origins added:
-// a fix to the slice, refusal or gather logic belongs in both.  Into HOST memory; the codec is only lent.
+// `to`.
 extern "C" int jsp_index_pan_frames(jsp_codec* c, jsp_index* idx, int bw, int bh, int n, const int* from, const int* to, const int* from_xy,
                                     const int* to_xy, int flags, uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total) {
     const char* who = "index_pan";
     const bool n_ok = n >= 1 && n <= 4096;
-    const auto zero = [&]() {
-        if (total) *total = 0;
-        if (lens && n_ok) std::fill(lens, lens + n, (size_t)0);
-        if (keys && n_ok) std::fill(keys, keys + n, 0);
-    };
-    zero();
+    const ClipOut o{n, out, cap, lens, keys, total};
+    o.zero();
     if (!c || !idx || !from || !to || !to_xy || !lens || !total || (!out && cap)) return fail("%s: null argument", who);
     if (!from_xy && n_ok && std::any_of(from, from + n, [](int f) { return f != JSP_CROP_KEY; })) return fail("%s: null argument", who);
     if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
@@ -1236,117 +1203,29 @@ extern "C" int jsp_index_pan_frames(jsp_codec* c, jsp_index* idx, int bw, int bh
     if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
     const bool tight = (flags & JSP_CROP_TIGHT) != 0;
     const auto kind_of = [&](size_t p) { return pan_kind(from[p], JSP_CROP_KEY, from_xy ? from_xy + 2 * p : to_xy + 2 * p, to_xy + 2 * p); };
-    try {
-        c->activate();
-        const size_t nb = (size_t)bw * (size_t)bh, nwg = (size_t)msv1_keyframe_workgroups((int)nb);
-        const size_t bound = nb * (src.bits == 16 ? 18u : 10u);
-        size_t S = (size_t)c->index_delta_slice;
-        if (S == 0) S = std::clamp<uint64_t>(kDeltaSliceBudget / pan_layout(1, nb, nwg, bound).bytes, 1, 4096);
-        S = std::min(S, (size_t)n);
-        const PanLayout pl = pan_layout(S, nb, nwg, bound);
-        const CropLayout& l = pl.c;
-        idx->d_pan.reserve(pl.bytes);
-        idx->h_pan.reserve(l.records_at + 16);
-        uint8_t* d = idx->d_pan.as<uint8_t>();
-        uint8_t* h = idx->h_pan.as<uint8_t>();
-        const Msv1PanScratch k{reinterpret_cast<const int32_t*>(d + pl.origins_at),
-                               {reinterpret_cast<const int32_t*>(d + l.pairs_at), reinterpret_cast<const uint64_t*>(d + l.bases_at),
-                                reinterpret_cast<uint32_t*>(d + l.status_at), reinterpret_cast<uint32_t*>(d + l.totals_at),
-                                reinterpret_cast<uint32_t*>(d + l.first_at), reinterpret_cast<uint32_t*>(d + l.counts_at),
-                                reinterpret_cast<uint32_t*>(d + l.records_at), d + l.out_at}};
-        std::vector<size_t> length((size_t)n, 0);
-        std::vector<uint8_t> all_coded((size_t)n, 0);
-        // pairs [j0, j0 + m), their origins and where their frames start go to the device, then the sizes launch (not when the records are there)
-        const auto sizes = [&](size_t j0, size_t m, bool launch) {
-            int32_t* ho = reinterpret_cast<int32_t*>(h + pl.origins_at);
-            int32_t* hp = reinterpret_cast<int32_t*>(h + l.pairs_at);
-            uint64_t* hb = reinterpret_cast<uint64_t*>(h + l.bases_at);
-            uint64_t at = 0;
-            for (size_t i = 0; i < m; ++i) {
-                const size_t p = j0 + i;
-                const PanKind kind = kind_of(p);
-                const int* b = to_xy + 2 * p;
-                const int* a = kind == PAN_KEY ? b : from_xy + 2 * p;
-                ho[4 * i] = a[0];
-                ho[4 * i + 1] = a[1];
-                ho[4 * i + 2] = b[0];
-                ho[4 * i + 3] = b[1];
-                hp[2 * i] = kind == PAN_MOVED && !tight ? JSP_CROP_KEY : from[p];
-                hp[2 * i + 1] = to[p];
-                hb[i] = at;
-                at += length[p];
-            }
-            JSP_HIP(hipMemcpyAsync(d, h, l.status_at, hipMemcpyHostToDevice, c->stream));
-            if (!launch) return;
-            JSP_HIP(hipMemsetAsync(k.c.status, 0xFF, sizeof(uint32_t) * m, c->stream));
-            msv1_launch_index_pan_sizes(src, bw, bh, (int)m, k, tight, c->stream);
-            JSP_HIP(hipGetLastError());
-        };
-        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
-            const size_t m = std::min(S, (size_t)n - j0);
-            sizes(j0, m, true);
-            JSP_HIP(hipMemcpyAsync(h + l.status_at, d + l.status_at, l.first_at - l.status_at, hipMemcpyDeviceToHost, c->stream));
-            JSP_HIP(hipStreamSynchronize(c->stream));
-            const uint32_t* status = reinterpret_cast<const uint32_t*>(h + l.status_at);
-            const uint32_t* totals = reinterpret_cast<const uint32_t*>(h + l.totals_at);
-            const uint32_t* counts = reinterpret_cast<const uint32_t*>(h + l.counts_at);
-            for (size_t i = 0; i < m; ++i) {
-                if (status[i] != 0xFFFFFFFFu) {   // refused: the first pair, and its first block of the rectangle, that says so
-                    const size_t p = j0 + i;
-                    const uint32_t j = status[i] >> 1;
-                    const long long blk = (long long)crop_src_block(src.nbx, to_xy[2 * p], to_xy[2 * p + 1], bw, (int64_t)j);
-                    char what[64];
-                    const PanKind kind = kind_of(p);
-                    if (kind == PAN_KEY) snprintf(what, sizeof(what), "(key, %d)", to[p]);
-                    else if (kind == PAN_STILL) snprintf(what, sizeof(what), "(%d, %d]", from[p], to[p]);
-                    else snprintf(what, sizeof(what), "(%d -> %d, moved)", from[p], to[p]);
-                    if ((status[i] & 1u) == MSV1_KEYFRAME_NO_WRITER) {
-                        set_error("%s: pair %d %s: block %u of the rectangle (block %lld of the picture) has no writer up to frame %d in the index",
-                                  who, (int)p, what, j, blk, to[p]);
-                    } else {
-                        uint32_t* writer = reinterpret_cast<uint32_t*>(h + l.records_at);
-                        JSP_HIP(hipMemcpyAsync(writer, k.c.records + 2 * (i * nb + j), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-                        JSP_HIP(hipStreamSynchronize(c->stream));
-                        set_error("%s: pair %d %s: the code of block %u of the rectangle (block %lld of the picture) in frame %u, its last "
-                                  "writer, is cut off by the end of the frame's data",
-                                  who, (int)p, what, j, blk, *writer);
-                    }
-                    return JSP_ERROR_OCCURED;
-                }
-                size_t coded = 0;
-                for (size_t g = 0; g < nwg; ++g) {
-                    length[j0 + i] += totals[i * nwg + g];
-                    coded += counts[i * nwg + g];
-                }
-                all_coded[j0 + i] = coded == nb;
-                if (length[j0 + i] > bound) throw std::runtime_error(std::string(who) + ": a frame is longer than its bound");
-            }
-        }
-        size_t sum = 0;
-        for (int j = 0; j < n; ++j) {
-            sum += (lens[j] = length[(size_t)j]);
-            if (keys) keys[j] = all_coded[(size_t)j];
-        }
-        *total = sum;
-        if (cap < sum) return fail("%s: cap is smaller than the frames (*total has their length, lens[] each frame's)", who);
-        size_t at = 0;
-        for (size_t j0 = 0; j0 < (size_t)n; j0 += S) {
-            const size_t m = std::min(S, (size_t)n - j0);
-            sizes(j0, m, S < (size_t)n);
-            msv1_launch_index_pan_gather(src, bw, bh, (int)m, k, c->stream);
-            JSP_HIP(hipGetLastError());
-            size_t bytes = 0;
-            for (size_t i = 0; i < m; ++i) bytes += length[j0 + i];
-            JSP_HIP(hipMemcpyAsync(out + at, k.c.out, bytes, hipMemcpyDeviceToHost, c->stream));
-            JSP_HIP(hipStreamSynchronize(c->stream));
-            at += bytes;
-        }
-        return JSP_ZERO_STATE;
-    } catch (const std::exception& e) {
-        zero();
-        set_error("%s", e.what());
-        return JSP_ERROR_OCCURED;
-    }
+    return clip_frames(
+        who, c, src, ClipBuffers{CLIP_PAN, idx->d_pan, idx->h_pan}, (size_t)bw * (size_t)bh, o,
+        [&](size_t p, int32_t* pair, int32_t* origin) {
+            const PanKind kind = kind_of(p);
+            const int* b = to_xy + 2 * p;
+            const int* a = kind == PAN_KEY ? b : from_xy + 2 * p;
+            origin[0] = a[0];
+            origin[1] = a[1];
+            origin[2] = b[0];
+            origin[3] = b[1];
+            pair[0] = kind == PAN_MOVED && !tight ? JSP_CROP_KEY : from[p];
+            pair[1] = to[p];
+        },
+        [&](int m, const Msv1ClipScratch& k) { msv1_launch_index_pan_sizes(src, bw, bh, m, k, tight, c->stream); },
+        [&](int m, const Msv1ClipScratch& k) { msv1_launch_index_pan_gather(src, bw, bh, m, k, c->stream); },
+        [&](size_t p, uint32_t j, char(&pair)[64], char(&block)[96]) {
+            const PanKind kind = kind_of(p);
+            if (kind == PAN_KEY) snprintf(pair, sizeof(pair), "(key, %d)", to[p]);
+            else if (kind == PAN_STILL) snprintf(pair, sizeof(pair), "(%d, %d]", from[p], to[p]);
+            else snprintf(pair, sizeof(pair), "(%d -> %d, moved)", from[p], to[p]);
+            rect_block_words(block, src.nbx, to_xy[2 * p], to_xy[2 * p + 1], bw, j);
+            return to[p];
+        });
 }
 
 extern "C" int jsp_index_significance(const jsp_index* idx, int* out) {

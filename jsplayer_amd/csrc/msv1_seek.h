@@ -130,70 +130,53 @@ inline int msv1_keyframe_workgroups(int nblocks) { return (nblocks + MSV1_KEYFRA
 // then not a key frame.  Nothing for an index without a block.
 void msv1_launch_index_keyframe(const Msv1IndexSrc& src, int t, const Msv1KeyFrameScratch& k, hipStream_t stream);
 
-// The device scratch of jsp_index_delta_frames for one slice of pairs (the index owns it; every part 16-byte aligned).  nwg =
-// msv1_keyframe_workgroups(nblocks): the two kernels keep the key frame's shape, a workgroup owns MSV1_KEYFRAME_WG_BLOCKS blocks.
-struct Msv1DeltaScratch {
-    const int32_t* pairs;            // per pair: from (-1: before the range), to
+// The device scratch of the clip calls — jsp_index_delta_frames / _tight_frames / _crop_frames / _path_frames / _pan_frames — for one
+// slice of pairs (the index owns it; every part 16-byte aligned: clip_layout, msv1_index_clip_layout.h).  A frame has nb blocks in
+// j-numbering — the whole grid, or a rectangle — and nwg = msv1_keyframe_workgroups(nb) workgroups of MSV1_KEYFRAME_WG_BLOCKS blocks.
+// The bodies of the kernels that write and read it stand once, in msv1_index_clip_device.h.
+struct Msv1ClipScratch {
+    const int32_t* origins;          // pan only, else null.  Per pair: x, y of the rectangle at `from` (a key pair: not read), x, y at `to`
+    const int32_t* pairs;            // per pair: from (-1: before the range; MSV1_CROP_KEY: a key pair), to.  Pan: a moved pair of a
+                                     // call without the tight flag stands there as the key pair (to)
     const uint64_t* bases;           // per pair: where its frame starts in `out` (even; read by the gather only)
-    uint32_t* status;                // per pair: all ones, else the first written block whose last writer's code is cut off
+    uint32_t* status;                // per pair: all ones, else the first block of the frame that refuses (j << 1 | kind,
+                                     // MSV1_KEYFRAME_NO_WRITER or MSV1_KEYFRAME_CUT)
     uint32_t* totals;                // per pair and workgroup (pair * nwg + g): the bytes of its codes and skip words
-    uint32_t* first_written;         // per pair and workgroup: its first written block, MSV1_DELTA_NONE when it has none
-    uint32_t* records;               // per pair and block ((pair * nblocks + blk) * 2): writer frame, (offset within its workgroup's
-                                     // bytes << 8 | L); L = code length, MSV1_DELTA_SKIP for a run head, 0 for nothing (or a status)
+    uint32_t* first_written;         // per pair and workgroup: its first coded block j, MSV1_DELTA_NONE when it has none
+    uint32_t* counts;                // per pair and workgroup: the blocks that got a code.  Delta and tight: null, nobody asks
+    uint32_t* records;               // per pair and block ((pair * nb + j) * 2): writer frame, (offset within its workgroup's bytes
+                                     // << 8 | L); L = code length, MSV1_DELTA_SKIP for a run head, 0 for nothing (or a status)
     uint8_t* out;                    // the slice's frames back to back, room for npairs * the bound
 };
 constexpr uint32_t MSV1_DELTA_NONE = 0xFFFFFFFFu;
 constexpr uint32_t MSV1_DELTA_SKIP = 1u;           // (odd: no code has this length)
 constexpr int MSV1_DELTA_RUN = 1023;               // a skip word's count is 10 bits: no skip word crosses a multiple of this
-// ONE launch each (msv1_index_delta_kernels.hip, which states the rule), grid.y = the pair.  Sizes: status (all ones from the
-// caller), totals, first_written and records of npairs pairs.  Gather, after a sizes launch over the same pairs with no status
-// raised and with bases[] = the running sums of the pairs' lengths: the frames into d.out.  Nothing for an index without a block.
-// tight (jsp_index_tight_frames): the sizes launch decodes both ends of the gap of every written block and keeps the block only
-// where a pixel changed; "written" in the scratch then reads "kept", and the gather launch is the same.
-void msv1_launch_index_delta_sizes(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, bool tight, hipStream_t stream);
-void msv1_launch_index_delta_gather(const Msv1IndexSrc& src, int npairs, const Msv1DeltaScratch& d, hipStream_t stream);
-
+constexpr int MSV1_CROP_KEY = -2;                  // a pair's `from` that says "key pair" (JSP_CROP_KEY)
 // A block rectangle of the picture, in table order (block row 0 = stored rows 0 .. 3), checked against the block grid by the host
 // (crop_rect_ok, msv1_index_crop_layout.h): bw, bh >= 1, bx + bw <= nbx, by + bh <= nby; nb = bw * bh.  Block j < nb of the
 // rectangle is source block (by + j / bw) * nbx + bx + j % bw.
 struct Msv1CropRect {
     int bx, by, bw, bh, nb;
 };
-constexpr int MSV1_CROP_KEY = -2;                  // a pair's `from` that says "key pair" (JSP_CROP_KEY)
-// The device scratch of jsp_index_crop_frames for one slice of pairs (the index owns it; every part 16-byte aligned): the delta
-// call's with everything in the rectangle's numbering — nwg = msv1_keyframe_workgroups(nb), records of nb blocks a pair — and
-// the workgroups' code counts.
-struct Msv1CropScratch {
-    const int32_t* pairs;            // per pair: from (-1: before the range; MSV1_CROP_KEY: a key pair), to
-    const uint64_t* bases;           // per pair: where its frame starts in `out` (even; read by the gather only)
-    uint32_t* status;                // per pair: all ones, else the first block of the rectangle that refuses (j << 1 | kind,
-                                     // MSV1_KEYFRAME_NO_WRITER — key pairs only — or MSV1_KEYFRAME_CUT)
-    uint32_t* totals;                // per pair and workgroup (pair * nwg + g): the bytes of its codes and skip words
-    uint32_t* first_written;         // per pair and workgroup: its first written block j, MSV1_DELTA_NONE when it has none
-    uint32_t* counts;                // per pair and workgroup: the blocks that got a code
-    uint32_t* records;               // per pair and block ((pair * nb + j) * 2): as Msv1DeltaScratch's
-    uint8_t* out;                    // the slice's frames back to back, room for npairs * the bound
-};
-// ONE launch each (msv1_index_crop_kernels.hip, which states the rule), grid.y = the pair, in the shape of the two delta launches.
-// tight: THE TIGHT RULE for the gap pairs; key pairs are not touched by it.  Nothing for a rectangle without a block.
-void msv1_launch_index_crop_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, bool tight,
+// ONE launch each, grid.y = the pair; the .hip file of a call states its rule.  Sizes: status (all ones from the caller), totals,
+// first_written, records and (not delta) counts of npairs pairs.  Gather, after a sizes launch over the same pairs with no status
+// raised and with bases[] = the running sums of the pairs' lengths: the frames into d.out.  Nothing for a frame without a block.
+// Delta (msv1_index_delta_kernels.hip): the whole grid, gap pairs only.  tight (jsp_index_tight_frames): the sizes launch decodes both
+// ends of the gap of every written block and keeps the block only where a pixel changed.
+void msv1_launch_index_delta_sizes(const Msv1IndexSrc& src, int npairs, const Msv1ClipScratch& d, bool tight, hipStream_t stream);
+void msv1_launch_index_delta_gather(const Msv1IndexSrc& src, int npairs, const Msv1ClipScratch& d, hipStream_t stream);
+// Crop (msv1_index_crop_kernels.hip): the rectangle r, key and gap pairs.  tight: THE TIGHT RULE for the gap pairs.
+void msv1_launch_index_crop_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1ClipScratch& d, bool tight,
                                   hipStream_t stream);
-void msv1_launch_index_crop_gather(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, hipStream_t stream);
-// The sizes launch of jsp_index_path_frames (msv1_index_path_kernels.hip, which states the rule): crop's with pairs in either direction
-// — d.pairs may hold from > to (a step back) and from == to (a hold), checked by the host (path_pair_ok, msv1_index_path_layout.h).
-// It leaves what msv1_launch_index_crop_gather reads; that launch gathers.
-void msv1_launch_index_path_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1CropScratch& d, bool tight,
+void msv1_launch_index_crop_gather(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1ClipScratch& d, hipStream_t stream);
+// Path (msv1_index_path_kernels.hip): crop's with pairs in either direction — d.pairs may hold from > to (a step back) and from == to
+// (a hold), checked by the host (path_pair_ok, msv1_index_path_layout.h).  msv1_launch_index_crop_gather gathers.
+void msv1_launch_index_path_sizes(const Msv1IndexSrc& src, const Msv1CropRect& r, int npairs, const Msv1ClipScratch& d, bool tight,
                                   hipStream_t stream);
-
-// The device scratch of jsp_index_pan_frames for one slice of pairs: crop's, and beside the pair words the pairs' origins, checked
-// against the block grid by the host (pan_pair_check, msv1_index_pan_layout.h).
-struct Msv1PanScratch {
-    const int32_t* origins;          // per pair: x, y of the rectangle at `from` (a key pair: not read), x, y at `to`, in blocks
-    Msv1CropScratch c;               // c.pairs: a moved pair of a call without the tight flag stands there as the key pair (to)
-};
-// ONE launch each (msv1_index_pan_kernels.hip, which states the rule), grid.y = the pair, in the shape of the two crop launches; the
-// rectangle is bw x bh blocks for every pair.  tight: THE TIGHT RULE for still gap pairs, the two-block compare for moved ones.
-void msv1_launch_index_pan_sizes(const Msv1IndexSrc& src, int bw, int bh, int npairs, const Msv1PanScratch& d, bool tight, hipStream_t stream);
-void msv1_launch_index_pan_gather(const Msv1IndexSrc& src, int bw, int bh, int npairs, const Msv1PanScratch& d, hipStream_t stream);
+// Pan (msv1_index_pan_kernels.hip): a rectangle of bw x bh blocks whose origins stand per pair in d.origins, checked against the block
+// grid by the host (pan_pair_check, msv1_index_pan_layout.h).  tight: THE TIGHT RULE for still gap pairs, the two-block compare for
+// moved ones.
+void msv1_launch_index_pan_sizes(const Msv1IndexSrc& src, int bw, int bh, int npairs, const Msv1ClipScratch& d, bool tight, hipStream_t stream);
+void msv1_launch_index_pan_gather(const Msv1IndexSrc& src, int bw, int bh, int npairs, const Msv1ClipScratch& d, hipStream_t stream);
 
 }  // namespace jsp

@@ -24,7 +24,10 @@ SIZES = 33x31 (1023 blocks, one run), 32x32 (1024, one workgroup), 41x25 (1025),
                             other origin in the picture before the range.
 
 A clip is kc.Clip with .size, .pal, .pairs = [(a, b, A, B)] in index frames (a chain behind a KEY pair comes first: .chain of them),
-.named = {pair: "all dropped" | "all kept" | ("none", j) | ("cut", j)} for the moved tight pairs that are not a mix."""
+.named = {pair: "all dropped" | "all kept" | ("none", j) | ("cut", j)} for the moved tight pairs that are not a mix.
+
+  spliced(bits)             frames of `bounds` and then of `cuts` in one clip, for calls of different kinds on one index
+                            (tests/test_index_clip_interleave_gpu.py); no pairs of its own."""
 import numpy as np
 
 import msv1_delta_clips as dc
@@ -294,6 +297,21 @@ def wander(bits, n=10):
             pics.append(pic)
         frames = [p.key(pics[0])] + [p.frame(pics[t - 1], pics[t], t) for t in range(1, n)]
         _cache[k] = _clip("pan_wander", p, None, frames)
+    return _cache[k]
+
+
+SPLICE_HEAD = 6             # frames of bounds(bits, (32, 32)) in front of a spliced clip
+
+
+def spliced(bits):
+    """One index for every clip call at once: the first SPLICE_HEAD frames of bounds(bits, (32, 32)) — the key frame and the patterns
+    nothing, every, from_4, to_4, to_256 — then the cut frame of cuts(bits) (index frame SPLICE_HEAD: its data ends one byte short of
+    the code of block CUT_AT) and that clip's empty frame.  A code carries no position and no reference, so the frames of two clips of
+    one picture size and palette in a row are a clip.  kc.Clip without a size and without pairs."""
+    k = ("spliced", bits)
+    if k not in _cache:
+        frames = list(bounds(bits, (32, 32)).frames[:SPLICE_HEAD]) + list(cuts(bits).frames[1:3])
+        _cache[k] = _clip("pan_spliced", Paint(bits, 211), None, frames)
     return _cache[k]
 
 
