@@ -37,6 +37,11 @@
 //                                FIRST .. FIRST + COUNT - 1 (default: the whole clip), ONE jsp_index_activity / jsp_sp_index_activity call
 //                                per 4096 frames: prints "<frame> <changed pixels> <x,y,w,h of its non-zero 16x16 cells, display
 //                                coordinates, or ->" per frame and "map <cols>x<rows>x<frames> <crc32 of the map's uint16 words>"
+//   jsp_play clip.avi --distance REF[:FIRST[:COUNT]]
+//                                the same index, then its distance map against the picture of frame REF (-1: the picture before frame
+//                                0) for frames FIRST .. FIRST + COUNT - 1 (default: the whole clip), ONE jsp_index_distance /
+//                                jsp_sp_index_distance call per 4096 frames: prints "<frame> <pixels that differ from REF's picture>" per
+//                                frame, "zero <the frames at distance 0 ...>" and "map <cols>x<rows>x<frames> <crc32>".  Goes alone.
 //   jsp_play clip.avi --cut FIRST[:COUNT] OUT.avi
 //                                MSVideo1: the clip from frame FIRST on (COUNT frames; default: to the end) as an AVI file of its own.
 //                                ONE seek index from the nearest key frame <= FIRST up to FIRST, ONE jsp_index_key_frame call (a key frame
@@ -574,6 +579,8 @@ int main(int argc, char** argv) {
     bool skip_stills = false;                                 // --skip-stills: from frame 0, skip to each significant change (jsp_find_change)
     bool step_back = false;                                   // --step-back: a seek index over the clip, shown from the last frame down to 0
     long act_first = -1, act_count = -1;                      // --activity [FIRST[:COUNT]]: the activity map of a seek index over the clip
+    bool dist = false;                                        // --distance REF[:FIRST[:COUNT]]: the distance map instead, against frame REF's picture
+    long dist_ref = 0;
     long cut_first = -1, cut_count = -1;                      // --cut FIRST[:COUNT] OUT.avi: the clip from frame FIRST on as a file of its own
     std::string cut_path;
     bool thin_tight = false;   // --thin-tight: --thin with jsp_index_tight_frames
@@ -609,6 +616,7 @@ int main(int argc, char** argv) {
         else if (o == "--skip-stills") skip_stills = true;
         else if (o == "--step-back") step_back = true;
         else if (o == "--activity") {
+            if (dist) { std::fprintf(stderr, "--distance and --activity each go alone\n"); return 2; }
             act_first = 0;
             if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') {
                 const std::string v = argv[++a];
@@ -616,6 +624,19 @@ int main(int argc, char** argv) {
                 act_first = std::atol(v.substr(0, colon).c_str());
                 if (colon != std::string::npos) act_count = std::atol(v.substr(colon + 1).c_str());
             }
+        }
+        else if (o == "--distance" && a + 1 < argc) {
+            const std::string v = argv[++a];
+            const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            const bool numbers = !v.empty() && v.find_first_not_of("0123456789:-") == std::string::npos && v.find('-', 1) == std::string::npos &&
+                                 v[0] != ':' && v.back() != ':' && v.find("::") == std::string::npos && v != "-";
+            if (!numbers) { std::fprintf(stderr, "--distance REF[:FIRST[:COUNT]]: REF, FIRST and COUNT are numbers, REF >= -1 (got %s)\n", v.c_str()); return 2; }
+            if (act_first >= 0) { std::fprintf(stderr, "--distance and --activity each go alone\n"); return 2; }
+            dist = true;
+            dist_ref = std::atol(v.substr(0, c1).c_str());
+            act_first = c1 == std::string::npos ? 0 : std::atol(v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1).c_str());
+            if (c2 != std::string::npos) act_count = std::atol(v.substr(c2 + 1).c_str());
+            if (act_first < 0 || (c2 != std::string::npos && act_count < 1)) { std::fprintf(stderr, "--distance REF[:FIRST[:COUNT]]: FIRST >= 0, COUNT >= 1\n"); return 2; }
         }
         else if (o == "--cut" && a + 2 < argc) {
             const std::string v = argv[++a];
@@ -749,7 +770,7 @@ int main(int argc, char** argv) {
     if (seek_to >= 0 && (pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--seek goes with the plain per-frame run\n"); return 2; }
     if (skip_stills && (seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--skip-stills goes alone\n"); return 2; }
     if (step_back && (skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--step-back goes alone\n"); return 2; }
-    if (act_first >= 0 && (run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--activity goes alone\n"); return 2; }
+    if (act_first >= 0 && (run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "%s goes alone\n", dist ? "--distance" : "--activity"); return 2; }
     if (cut_first >= 0 && (act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--cut goes alone\n"); return 2; }
     if (cut_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--cut: MSVideo1 only (a ScreenPressor key frame needs the entropy encoder)\n"); return 2; }
     if (thin_first >= 0 && (cut_first >= 0 || act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--thin goes alone\n"); return 2; }
@@ -1062,14 +1083,15 @@ int main(int argc, char** argv) {
         jsp_index* idx = n && !sp ? jsp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
         jsp_sp_index* sidx = n && sp ? jsp_sp_index_build(dec, (int)n, srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
         if (!idx && !sidx) { std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_build" : "jsp_index_build", n ? jsp_last_error() : "no frames"); rc = 1; }
-        const char* const call = sp ? "jsp_sp_index_activity" : "jsp_index_activity";
+        const char* const call = dist ? (sp ? "jsp_sp_index_distance" : "jsp_index_distance") : sp ? "jsp_sp_index_activity" : "jsp_index_activity";
         int cols = 0, rows = 0;
         if (rc == 0 && (sp ? jsp_sp_index_activity_size(sidx, &cols, &rows) : jsp_index_activity_size(idx, &cols, &rows)) != JSP_ZERO_STATE) {
             std::fprintf(stderr, "%s_size: %s\n", call, jsp_last_error());
             rc = 1;
         }
         const long count = act_count >= 0 ? act_count : (long)n - act_first;
-        if (rc == 0 && (count < 1 || act_first + count > (long)n)) { std::fprintf(stderr, "--activity: frames %ld .. %ld are not all in the clip (%zu frames)\n", act_first, act_first + count - 1, n); rc = 1; }
+        if (rc == 0 && (count < 1 || act_first + count > (long)n)) { std::fprintf(stderr, "%s: frames %ld .. %ld are not all in the clip (%zu frames)\n", dist ? "--distance" : "--activity", act_first, act_first + count - 1, n); rc = 1; }
+        if (rc == 0 && dist && (dist_ref < -1 || dist_ref >= (long)n)) { std::fprintf(stderr, "--distance: frame %ld is neither in the clip (%zu frames) nor -1\n", dist_ref, n); rc = 1; }
         const size_t cell = (size_t)cols * (size_t)rows;
         jsp_pool* sheet = nullptr;   // one "frame" that holds the map: cell ints a row, a row per two frames of the run
         if (rc == 0 && !(sheet = jsp_pool_create(0, (int)cell, (int)((count + 1) / 2), 1))) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
@@ -1078,15 +1100,31 @@ int main(int argc, char** argv) {
             uint16_t* out = reinterpret_cast<uint16_t*>(jsp_pool_buffer(sheet, 0));
             for (long k = 0; rc == 0 && k < count; k += 4096) {
                 const int m = (int)std::min<long>(4096, count - k);
-                if ((sp ? jsp_sp_index_activity(dec, sidx, (int)(act_first + k), m, out + (size_t)k * cell, (size_t)(count - k) * cell)
-                        : jsp_index_activity(dec, idx, (int)(act_first + k), m, out + (size_t)k * cell, (size_t)(count - k) * cell)) != JSP_ZERO_STATE) {
+                uint16_t* const at = out + (size_t)k * cell;
+                const size_t room = (size_t)(count - k) * cell;
+                const int f = (int)(act_first + k);
+                const int got = dist ? (sp ? jsp_sp_index_distance(dec, sidx, (int)dist_ref, nullptr, f, m, at, room) : jsp_index_distance(dec, idx, (int)dist_ref, nullptr, f, m, at, room))
+                                     : (sp ? jsp_sp_index_activity(dec, sidx, f, m, at, room) : jsp_index_activity(dec, idx, f, m, at, room));
+                if (got != JSP_ZERO_STATE) {
                     std::fprintf(stderr, "%s: %s\n", call, jsp_last_error());
                     rc = 1;
                 }
             }
             if (rc == 0 && jsp_download(jsp_pool_buffer(sheet, 0), words.data(), words.size()) != 0) { std::fprintf(stderr, "jsp_download: %s\n", jsp_last_error()); rc = 1; }
             const uint16_t* map = reinterpret_cast<const uint16_t*>(words.data());
-            for (long k = 0; rc == 0 && k < count; ++k) {   // per frame: changed pixels and the box of its non-zero cells, display coordinates (top row first)
+            if (rc == 0 && dist) {   // per frame: the pixels that differ from the reference picture; then the frames that show it
+                std::vector<long> same;
+                for (long k = 0; k < count; ++k) {
+                    long total = 0;
+                    for (size_t e = 0; e < cell; ++e) total += map[(size_t)k * cell + e];
+                    std::printf("%ld %ld\n", act_first + k, total);
+                    if (total == 0) same.push_back(act_first + k);
+                }
+                std::printf("zero");
+                for (long t : same) std::printf(" %ld", t);
+                std::printf("\n");
+            }
+            for (long k = 0; rc == 0 && !dist && k < count; ++k) {   // per frame: changed pixels and the box of its non-zero cells, display coordinates (top row first)
                 long total = 0;
                 int q0 = cols, q1 = -1, r0 = rows, r1 = -1;
                 for (int r = 0; r < rows; ++r)

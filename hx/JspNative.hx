@@ -69,6 +69,10 @@ extern class JspNative {
     @:native("jsp_index_activity_size") static function indexActivitySize(idx:RawPointer<JspIndex>, cols:RawPointer<Int>, rows:RawPointer<Int>):Int;
     @:native("jsp_index_activity")     static function indexActivity(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, first:Int, n:Int,
                                                                      out:RawPointer<cpp.UInt16>, outElems:SizeT):Int;
+    // refFrame -1 .. nframes-1 with refPicture null, or JSP_REF_PICTURE (-2) with a device picture of X * Y words
+    @:native("jsp_index_distance")     static function indexDistance(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, refFrame:Int,
+                                                                     refPicture:RawConstPointer<cpp.Int32>, first:Int, n:Int,
+                                                                     out:RawPointer<cpp.UInt16>, outElems:SizeT):Int;
     @:native("jsp_index_key_frame_bound") static function indexKeyFrameBound(idx:RawPointer<JspIndex>, bytes:RawPointer<SizeT>):Int;
     @:native("jsp_index_key_frame")    static function indexKeyFrame(c:RawPointer<JspCodec>, idx:RawPointer<JspIndex>, t:Int, out:RawPointer<UInt8>,
                                                                      cap:SizeT, len:RawPointer<SizeT>):Int;
@@ -118,6 +122,9 @@ extern class JspNative {
                                                                       dsts:RawPointer<RawPointer<cpp.Int32>>, significant:RawPointer<Int>):Int;
     @:native("jsp_sp_index_activity_size") static function spIndexActivitySize(idx:RawPointer<JspSpIndex>, cols:RawPointer<Int>, rows:RawPointer<Int>):Int;
     @:native("jsp_sp_index_activity")     static function spIndexActivity(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, first:Int, n:Int,
+                                                                          out:RawPointer<cpp.UInt16>, outElems:SizeT):Int;
+    @:native("jsp_sp_index_distance")     static function spIndexDistance(c:RawPointer<JspCodec>, idx:RawPointer<JspSpIndex>, refFrame:Int,
+                                                                          refPicture:RawConstPointer<cpp.Int32>, first:Int, n:Int,
                                                                           out:RawPointer<cpp.UInt16>, outElems:SizeT):Int;
     @:native("jsp_sp_index_significance") static function spIndexSignificance(idx:RawPointer<JspSpIndex>, out:RawPointer<Int>):Int;
     @:native("jsp_sp_index_info")         static function spIndexInfo(idx:RawPointer<JspSpIndex>, nframes:RawPointer<Int>, deviceBytes:RawPointer<cpp.UInt64>,

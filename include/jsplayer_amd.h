@@ -684,6 +684,42 @@ int jsp_index_activity(jsp_codec* c, jsp_index* idx, int first, int n, uint16_t*
 int jsp_sp_index_activity_size(const jsp_sp_index* idx, int* cols, int* rows);
 int jsp_sp_index_activity(jsp_codec* c, jsp_sp_index* idx, int first, int n, uint16_t* out, size_t out_elems);
 
+/* ---- distance map of an index, either codec: how far each frame is from ONE picture — where else the recording shows this picture (a
+ * dialog that comes back, a loop, A -> B -> A), which frame looks like this screenshot, which frames differ enough from the last kept one
+ * to be worth keeping, where a loop can close without a jump — as differing pixels per frame and 16x16 cell.  The activity map cannot
+ * say it: the sum of changes along a path is the path's length, not the distance between its ends ---------------------------------------
+ * Distance: THE PICTURE P(t), P(-1) and THE GRID are the activity map's, above (jsp_index_activity_size / jsp_sp_index_activity_size
+ *       give cols and rows): not restated.
+ *   THE REFERENCE R, two forms:
+ *       ref_picture == NULL: R = P(ref_frame), ref_frame -1 .. nframes-1.  The kernel composes R's blocks itself; no picture is written
+ *           and no Show is needed first.
+ *       ref_picture != NULL: ref_frame must be JSP_REF_PICTURE.  R is a device buffer of X * Y words in frame-buffer layout.  It is
+ *           only read; it may be any frame buffer, the codec's previous frame included.  It must be aligned to 4 bytes: rows are read
+ *           16 bytes at a time where the pointer is 16-byte aligned and X % 4 == 0, word by word otherwise.
+ *   EQUIVALENCE  out[(k * rows + r) * cols + q] = the number of pixels of cell (r, q) whose whole 32-bit word differs between
+ *       P(first + k) and R, for k = 0 .. n-1: 0 .. 256.  ScreenPressor: every pixel of the cell inside the picture is compared.
+ *       MSVideo1: the pixels inside whole 4 x 4 blocks are compared; THE X % 4 / Y % 4 REMAINDER PIXELS ARE NEVER READ AND NEVER
+ *       COUNTED.  They are the same in every P(t), so with a frame as reference they would contribute 0 anyway; with a device picture as
+ *       reference they are the caller's to compare.  Exactly n * rows * cols elements are written, every one of them, by the launch
+ *       itself: nothing else is written and no memset goes in front (most elements are non-zero, unlike Activity's).
+ *   ONE kernel launch whatever n (msv1_index_distance_kernel / sp_index_distance_kernel): the walk of Play and Activity with a third
+ *       last step, a count against R; where a cell has no event its value is stored again.  Option "msv1_index_activity_segments" splits
+ *       an MSVideo1 run along the grid here too — it is ONE knob for both walks, Activity's and Distance's — and the result does not
+ *       depend on it.  Runs on the codec's stream and returns synchronised.  THE CODEC IS ONLY LENT, as for Activity; no full-size
+ *       picture is written anywhere, and the index grows as for Activity.
+ *   BOUNDS  Activity's: n 1..4096; first >= 0; first + n <= nframes (computed in 64 bits); out_elems >= n * rows * cols; `out` is a
+ *       device pointer aligned to 2 bytes.
+ *   ERRORS, each before anything is queued, with nothing changed and nothing written (jsp_last_error() starts with "index_distance:",
+ *       but for the wrong codec kind's "index: MSVideo1 only" / "sp_index: ScreenPressor only"): Activity's — a null c, idx or out, n or
+ *       first outside their bounds, out_elems too small, a misaligned or host-pointer `out`, an index built by another codec, the wrong
+ *       codec kind, an asynchronous frame in flight — and three more: a ref_frame outside -1 .. nframes-1; ref_frame and ref_picture that
+ *       disagree (a picture without JSP_REF_PICTURE, JSP_REF_PICTURE without a picture); a ref_picture that is a host pointer or not
+ *       aligned to 4 bytes. */
+#define JSP_REF_PICTURE (-2)
+int jsp_index_distance(jsp_codec* c, jsp_index* idx, int ref_frame, const int32_t* ref_picture, int first, int n, uint16_t* out, size_t out_elems);
+int jsp_sp_index_distance(jsp_codec* c, jsp_sp_index* idx, int ref_frame, const int32_t* ref_picture, int first, int n, uint16_t* out,
+                          size_t out_elems);
+
 /* ---- a key frame for any frame of an MSVideo1 index: cut a clip at frame t.  A clip has to start on a key frame, and t is almost never
  * one.  The picture of frame t is, block by block, what the last frame <= t that coded the block made of it, and that frame's code for
  * the block lies in the index's resident stream bytes: the key frame is those codes, concatenated in block order.  No pixel is

@@ -126,6 +126,8 @@ SIGNATURES = {
     "jsp_index_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "jsp_sp_index_activity_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "jsp_sp_index_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "jsp_index_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "jsp_sp_index_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "jsp_index_key_frame_bound": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "jsp_index_key_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "jsp_index_delta_bound": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),

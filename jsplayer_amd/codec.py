@@ -556,7 +556,8 @@ class _IndexTensor:
         return out.reshape(-1)[:count].reshape(shape)
 
 
-ACTIVITY_MAX_RUN = 4096   # frames one jsp_index_activity / jsp_sp_index_activity call takes
+ACTIVITY_MAX_RUN = 4096   # frames one jsp_index_activity / jsp_sp_index_activity call takes (jsp_index_distance / jsp_sp_index_distance too)
+REF_PICTURE = -2          # JSP_REF_PICTURE: the ref_frame that goes with a reference picture
 DELTA_ASK_TWICE = 64 << 20   # SeekIndex.DeltaFrames: above this many bytes of n frames at their bound, the lengths are asked for first
 
 
@@ -607,12 +608,55 @@ class _IndexActivity:
             self._info()   # (a ScreenPressor index that never played gets Play's per-frame table at the first call)
         return out
 
+    _DISTANCE_CALL = ""   # jsp_index_distance / jsp_sp_index_distance, without the "jsp_" in front: one contract, on Activity's grid
+
+    def Distance(self, ref, first: int = 0, n: Optional[int] = None, out=None):
+        """How many pixels of each 16 x 16 cell of each of the frames first .. first + n - 1 (n None: to the end of the index) differ
+        from ONE reference picture: element [k, r, q] counts the pixels of cell (r, q) that differ between the picture of frame
+        first + k and R — 0 .. 256, on Activity's grid.  `ref` is an int, -1 .. frames - 1 (R is that frame's picture, -1 the picture
+        before frame 0; nothing is written or shown for it), or a device frame buffer — a contiguous int32 device tensor of at least
+        X * Y elements, anything else raises CodecError before the native call —, which is only read
+        (MSVideo1: its X % 4 / Y % 4 remainder pixels are not compared).  ONE launch per 4096 frames, no picture written, the codec
+        not touched.  Returns an int16 device tensor of shape (n, rows, cols), `out` when it is given (that shape and dtype,
+        contiguous) or a new one."""
+        import torch
+        call = self._DISTANCE_CALL
+        codec = self._open(call)
+        first = int(first)
+        n = self.frames - first if n is None else int(n)
+        if hasattr(ref, "data_ptr") or isinstance(ref, np.ndarray):   # (the kernel reads X * Y words of it: checked before the call)
+            ref_frame, ref_ptr = REF_PICTURE, C.c_void_p(_device_frame_ptr(ref, codec.X * codec.Y, call))
+        elif isinstance(ref, bool) or not hasattr(ref, "__index__"):
+            raise CodecError(f"{call}: ref must be a frame number or a device frame buffer")
+        else:
+            ref_frame, ref_ptr = int(ref), None
+        cols, rows = self.ActivitySize()
+        shape = (max(n, 0), rows, cols)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int16, device=f"cuda:{codec._device}")
+        elif not hasattr(out, "data_ptr") or out.dtype != torch.int16 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise CodecError(f"{call}: out must be a contiguous int16 tensor of shape {shape}")
+        fn = getattr(self._lib, "jsp_" + call)
+        cell = rows * cols
+        k = 0
+        while True:   # (a run the C call refuses — empty, outside the index — goes to it once, for its message)
+            m = min(n - k, ACTIVITY_MAX_RUN)
+            if fn(codec._h, self._h, ref_frame, ref_ptr, first + k, m, C.c_void_p(out.data_ptr() + 2 * k * cell), (out.numel() - k * cell)) != 0:
+                raise CodecError(N.last_error())
+            k += m
+            if k >= n:
+                break
+        if hasattr(self, "_info"):
+            self._info()
+        return out
+
 
 class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     """A range resident in HBM (jsp_index_build, via BuildIndex): Show(t) is one launch, Play(first, dsts, stride) one launch for
     a run of frames, each into a buffer of its own (jsp_index_play), Present(frames, ...) one launch for the windows of any
     frames (jsp_index_present), Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_index_tensor),
     Activity(first, n) one launch for the changed pixels per frame and 16x16 cell of a run (jsp_index_activity; _IndexActivity),
+    Distance(ref, first, n) one launch for the pixels per frame and cell that differ from ONE reference picture (jsp_index_distance),
     KeyFrame(t) two launches for a key frame that decodes to frame t's picture, made of the codes the range holds (jsp_index_key_frame),
     DeltaFrames(pairs) inter frames that each span a gap (a, b] of the range, made of the same codes and skips (jsp_index_delta_frames);
     with tight=True without the blocks whose pixels the gap did not change (jsp_index_tight_frames).  CropFrames / PanFrames the same
@@ -625,6 +669,7 @@ class SeekIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     _PRESENT_CALL = "index_present"
     _TENSOR_CALL = "index_tensor"
     _ACTIVITY_CALLS = ("index_activity_size", "index_activity")
+    _DISTANCE_CALL = "index_distance"
 
     def __init__(self, codec: _NativeCodec, handle: int, prev_at_build):
         self._codec, self._h = codec, handle
@@ -926,7 +971,8 @@ class SpScrubIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     Thumbs(frames) one launch for any number of downscaled frames (jsp_sp_index_thumbs; _IndexThumbs has the two methods),
     Present(frames, ...) one launch for their windows of any size (jsp_sp_index_present; _IndexPresent),
     Tensor(frames, ...) one launch for the same windows as a model's input batch (jsp_sp_index_tensor; _IndexTensor),
-    Activity(first, n) one launch for the changed pixels per frame and 16x16 block of a run (jsp_sp_index_activity; _IndexActivity).
+    Activity(first, n) one launch for the changed pixels per frame and 16x16 block of a run (jsp_sp_index_activity; _IndexActivity),
+    Distance(ref, first, n) one launch for the pixels per frame and block that differ from ONE reference picture (jsp_sp_index_distance).
     `significance` = the verdict the sequential run records for every frame, `frames`, `device_bytes`, `host_bytes`.  close() (or
     the context manager) frees it; safe after the codec is gone."""
 
@@ -935,6 +981,7 @@ class SpScrubIndex(_IndexThumbs, _IndexPresent, _IndexTensor, _IndexActivity):
     _PRESENT_CALL = "sp_index_present"
     _TENSOR_CALL = "sp_index_tensor"
     _ACTIVITY_CALLS = ("sp_index_activity_size", "sp_index_activity")
+    _DISTANCE_CALL = "sp_index_distance"
 
     def _present_mode(self) -> int:   # 16-bpp frames hold 5-bit components (Manager.hx:121), as Manager.present chooses it
         return 1 if getattr(self._codec, "bpp", 0) == 16 else 0   # DISPLAY_CANVAS_RGB15 / DISPLAY_CANVAS

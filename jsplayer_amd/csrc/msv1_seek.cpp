@@ -810,6 +810,39 @@ extern "C" int jsp_index_activity(jsp_codec* c, jsp_index* idx, int first, int n
     }
 }
 
+// ---- distance: how many pixels of every 16x16 cell each frame of a run differs from ONE reference picture — a frame of the index or a
+// device picture — in ONE launch of msv1_index_distance_kernel: Activity's walk with another last step.  The launch writes every
+// element, so no memset goes in front; the codec is only lent and no picture is written.
+extern "C" int jsp_index_distance(jsp_codec* c, jsp_index* idx, int ref_frame, const int32_t* ref_picture, int first, int n, uint16_t* out,
+                                  size_t out_elems) {
+    const char* who = "index_distance";
+    if (!c || !idx || !out) return fail("index_distance: null argument");
+    if (!is_msv1(c, "index")) return JSP_ERROR_OCCURED;
+    if (idx->codec_serial != c->serial) return fail("index_distance: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("index_distance: n is outside 1..4096");
+    if (first < 0 || (int64_t)first + (int64_t)n > (int64_t)idx->nframes) return fail("index_distance: the run is outside the index");
+    if ((ref_picture != nullptr) != (ref_frame == JSP_REF_PICTURE)) return fail("index_distance: ref_frame and ref_picture disagree (JSP_REF_PICTURE goes with a picture, a frame with none)");
+    if (!ref_picture && (ref_frame < -1 || ref_frame >= idx->nframes)) return fail("index_distance: ref_frame is outside -1..nframes-1");
+    if (reinterpret_cast<uintptr_t>(ref_picture) & 3) return fail("index_distance: ref_picture is not aligned to 4 bytes");
+    const int cols = (std::max(idx->geo.X, 0) + 15) / 16, rows = (std::max(idx->geo.Y, 0) + 15) / 16;
+    const uint64_t elems = (uint64_t)n * (uint64_t)rows * (uint64_t)cols;
+    if ((uint64_t)out_elems < elems) return fail("index_distance: out_elems is smaller than the map");
+    if (reinterpret_cast<uintptr_t>(out) & 1) return fail("index_distance: out is not aligned to 2 bytes");
+    if (!nothing_in_flight(c, who)) return JSP_ERROR_OCCURED;
+    try {
+        c->activate();
+        if (!on_device(out, who, "out must be a device buffer")) return JSP_ERROR_OCCURED;
+        if (ref_picture && !on_device(ref_picture, who, "ref_picture must be a device frame buffer")) return JSP_ERROR_OCCURED;
+        if (elems == 0) return JSP_ZERO_STATE;   // (an index without a picture)
+        const int segs = c->index_activity_segments > 0 ? c->index_activity_segments : msv1_index_play_auto_segments(idx->src, n);
+        msv1_launch_index_distance(idx->src, ref_frame, ref_picture, first, n, segs, out, cols, rows, c->stream);
+        return launched(c);
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
 // ---- a key frame for any frame: the clip from frame t on has to start on a key frame, and t is almost never one.  The picture of
 // frame t is, block by block, what the last frame <= t that coded the block made of it, and that frame's code lies in the resident
 // stream bytes: the key frame is those codes in block order — file bytes the file already contained, no pixel decoded (the rule:

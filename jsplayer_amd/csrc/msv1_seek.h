@@ -113,6 +113,13 @@ void msv1_launch_index_tensor(const Msv1IndexSrc& src, const int32_t* d_frames, 
 // `out` first.  The run is split into `segs` (clamped to 1..n) contiguous segments along grid.y, each composing the picture before its
 // own first frame; the counts do not depend on the split.
 void msv1_launch_index_activity(const Msv1IndexSrc& src, int first, int n, int segs, uint16_t* out, int cols, int rows, hipStream_t stream);
+// ONE launch of msv1_index_distance_kernel (msv1_index_distance_kernels.hip): out[(k * rows + r) * cols + q], k < n, = the pixels of
+// the 16x16 cell (r, q), inside whole 4x4 blocks, that differ between the picture of index frame first + k and the reference R — the
+// picture of index frame ref_frame (-1: `before`, else zeros) when ref_picture is null, else the device picture ref_picture of X * Y
+// words (4-byte aligned, only read; ref_frame is not looked at).  EVERY element is stored: the caller zeroes nothing.  Segments as for
+// msv1_launch_index_activity; the counts do not depend on the split.
+void msv1_launch_index_distance(const Msv1IndexSrc& src, int ref_frame, const int32_t* ref_picture, int first, int n, int segs, uint16_t* out,
+                                int cols, int rows, hipStream_t stream);
 // The device scratch of jsp_index_key_frame (the index owns it; every part 16-byte aligned).
 struct Msv1KeyFrameScratch {
     uint32_t* status;                // [0]: all ones, else the first block that cannot be cut (block << 1 | kind); [1]: the frame's length

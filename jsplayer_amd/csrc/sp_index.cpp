@@ -598,6 +598,43 @@ extern "C" int jsp_sp_index_activity(jsp_codec* c, jsp_sp_index* idx, int first,
     }
 }
 
+// ---- distance: how many pixels of every 16x16 block each frame of a run differs from ONE reference picture (jsp_index_distance's
+// contract), in ONE launch of sp_index_distance_kernel: Activity's walk with another last step.  The launch writes every element, so no
+// memset goes in front; the codec is lent its stream and nothing else, and the per-frame table is Play's.
+extern "C" int jsp_sp_index_distance(jsp_codec* c, jsp_sp_index* idx, int ref_frame, const int32_t* ref_picture, int first, int n, uint16_t* out,
+                                     size_t out_elems) {
+    if (!c || !idx || !out) return fail("index_distance: null argument");
+    if (c->kind != JSP_CODEC_SCREENPRESSOR || !dynamic_cast<IndexLender*>(c)) return fail("sp_index: ScreenPressor only");
+    if (idx->codec_serial != c->serial) return fail("index_distance: the index was built by another codec");
+    if (n < 1 || n > 4096) return fail("index_distance: n is outside 1..4096");
+    if (first < 0 || (int64_t)first + (int64_t)n > (int64_t)idx->nframes) return fail("index_distance: the run is outside the index");
+    if ((ref_picture != nullptr) != (ref_frame == JSP_REF_PICTURE)) return fail("index_distance: ref_frame and ref_picture disagree (JSP_REF_PICTURE goes with a picture, a frame with none)");
+    if (!ref_picture && (ref_frame < -1 || ref_frame >= idx->nframes)) return fail("index_distance: ref_frame is outside -1..nframes-1");
+    if (reinterpret_cast<uintptr_t>(ref_picture) & 3) return fail("index_distance: ref_picture is not aligned to 4 bytes");
+    const uint64_t elems = (uint64_t)n * (uint64_t)idx->geo.nby * (uint64_t)idx->geo.nbx;
+    if ((uint64_t)out_elems < elems) return fail("index_distance: out_elems is smaller than the map");
+    if (reinterpret_cast<uintptr_t>(out) & 1) return fail("index_distance: out is not aligned to 2 bytes");
+    if (c->next_ticket != c->oldest_ticket) return fail("index_distance: an asynchronous frame is in flight (jsp_wait for it first)");
+    try {
+        c->activate();
+        if (!on_device(out)) return fail("index_distance: out must be a device buffer");
+        if (ref_picture && !on_device(ref_picture)) return fail("index_distance: ref_picture must be a device frame buffer");
+        hipStream_t stream = c->stream;
+        play_frames(idx, stream);
+        launch_index_distance(idx->geo, out, ref_frame, ref_picture, first, n, static_cast<const int32_t*>(idx->d_keys.p), idx->pic_stride,
+                              static_cast<const IndexPlayFrame*>(idx->d_play_frames.p),
+                              reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(idx->d_play_frames.p) + idx->play_mask_offset()),
+                              static_cast<const PBlock*>(idx->d_blocks.p), static_cast<const uint32_t*>(idx->d_payload.p),
+                              static_cast<const uint32_t*>(idx->d_bitmap.p), stream);
+        JSP_HIP(hipGetLastError());
+        JSP_HIP(hipStreamSynchronize(stream));
+        return JSP_ZERO_STATE;
+    } catch (const std::exception& e) {
+        set_error("%s", e.what());
+        return JSP_ERROR_OCCURED;
+    }
+}
+
 extern "C" int jsp_sp_index_significance(const jsp_sp_index* idx, int* out) {
     if (!idx || !out) return fail("sp_index_significance: null argument");
     std::copy(idx->significance.begin(), idx->significance.end(), out);

@@ -18,6 +18,8 @@ shown — ScreenPressor's, `ADOPTS` false — serves the frame and leaves the de
 index, one `Play` launch per batch of free buffers; `preview` / `filmstrip` are the seek bar's small pictures, one
 `Thumbs` launch of the attached index of either codec (SeekIndex or SpScrubIndex); `activity` / `change_totals` / `change_box` /
 `next_change` say where and when the picture changes, from the index's `Activity` map (changed pixels per frame and 16x16 cell);
+`distance` / `distance_totals` / `find_picture` / `repeats_of` / `distinct_frames` say how far each frame is from ONE picture, from
+the index's `Distance` map (pixels per frame and cell that differ from a reference frame or device picture);
 `cut` / `write_cut` give the clip from any frame on as frames and flags / as an AVI file, its first frame the index's `KeyFrame`;
 `thin` / `write_thin` the clip made of any ascending list of frames, the gaps spanned by the index's `DeltaFrames`.  `crop_rect` / `crop` / `write_crop`
 the same list of frames for a part of the picture, from the index's `CropFrames`; `follow` / `pan` / `write_pan` for a part that follows what
@@ -198,8 +200,10 @@ class Manager:
         touched, and decoding continues later from where the decoder really stands."""
         self.index, self.index_first = index, int(first)
         self._activity = None   # (the map belongs to the index it was computed from)
+        self._distance = None   # (the distance maps too: per reference frame of the index)
 
     _activity = None
+    _distance = None
 
     # -- where and when the picture changes: the attached index's activity map (jsp_index_activity / jsp_sp_index_activity) ----------
     def activity(self):
@@ -264,6 +268,94 @@ class Manager:
         if hits.size == 0:
             return None
         return self.seek(frames, self.index_first + k0 + int(hits[0]), key_flags)
+
+    # -- how far each frame is from ONE picture: the attached index's distance map (jsp_index_distance / jsp_sp_index_distance) ---------
+    def _need_distance(self) -> None:
+        if self.index is None:
+            raise ValueError("no seek index attached")
+        if not hasattr(self.index, "Distance"):
+            raise ValueError("the attached seek index has no distance map")
+
+    def _ref_of(self, ref):
+        """`ref` as the index's Distance takes it: a clip frame number index_first - 1 .. index_first + frames - 1 becomes a frame of
+        the index (-1: the picture before it); a device tensor / frame buffer passes through."""
+        self._need_distance()
+        if hasattr(ref, "data_ptr"):
+            return ref
+        t = int(ref) - self.index_first
+        if not -1 <= t < self.index.frames:
+            raise ValueError(f"frame {int(ref)} is neither in the attached seek index nor the frame before it")
+        return t
+
+    def distance(self, ref):
+        """The distance map of the whole attached index against ONE reference picture: [frame of the index, grid row, grid column]
+        -> pixels of that 16 x 16 cell that differ from the reference, on Activity's grid (the index's `Distance`: one launch per
+        4096 frames, no picture written, the decoder not touched).  `ref` is a clip frame number, index_first - 1 (the picture before
+        the index) .. the index's last frame, or a device tensor / frame buffer.  The map of a frame number is computed once and
+        kept where the index puts it; attach_index drops them all (a tensor's map is computed at every call: its pixels may have
+        changed).  No index attached, an index object without `Distance`, a frame outside the range: ValueError."""
+        r = self._ref_of(ref)
+        if not isinstance(r, int):
+            return self.index.Distance(r)
+        if self._distance is None:
+            self._distance = {}
+        if r not in self._distance:
+            self._distance[r] = self.index.Distance(r)
+        return self._distance[r]
+
+    def _rect_cells(self, rect):
+        """(row slice, column slice) of the cells the display rectangle `rect` intersects (next_change's rule: top row first, every
+        cell it touches counts in full); None when nothing of it lies inside the picture.  rect None: the whole grid."""
+        W, H = self.vi.X, self.vi.Y
+        if rect is None:
+            return slice(None), slice(None)
+        x, y, w, h = (int(v) for v in rect)
+        x0, x1 = max(x, 0), min(x + w, W)
+        s0, s1 = max(H - (y + h), 0), min(H - y, H)          # stored rows s0 .. s1 - 1
+        if x0 >= x1 or s0 >= s1:
+            return None
+        return slice(s0 // 16, (s1 + 15) // 16), slice(x0 // 16, (x1 + 15) // 16)
+
+    def distance_totals(self, ref, rect=None) -> List[int]:
+        """Pixels per frame of the attached index (entry k: clip frame index_first + k) that differ from the reference `ref`
+        (see distance).  rect = (x, y, w, h) in display coordinates: summed over the 16 x 16 cells it intersects, each in full, as
+        next_change does (a rectangle outside the picture: all zeros)."""
+        cells = self.distance(ref)
+        at = self._rect_cells(rect)
+        if at is None:
+            return [0] * self.index.frames
+        return [int(v) for v in self._frame_sums(cells[:, at[0], at[1]])]
+
+    def find_picture(self, ref, max_pixels: int = 0, rect=None) -> List[int]:
+        """The clip frames of the attached index, ascending, that differ from the reference `ref` (see distance) by at most
+        `max_pixels` pixels — of `rect` when one is given (distance_totals): where else the recording shows this picture, which
+        frame looks like this screenshot.  A frame of the index as `ref` is in the list itself."""
+        totals = self.distance_totals(ref, rect)
+        return [self.index_first + k for k, v in enumerate(totals) if v <= int(max_pixels)]
+
+    def repeats_of(self, i: int) -> List[int]:
+        """The other frames of the attached index that show exactly the picture of clip frame `i`: find_picture(i) without i."""
+        return [k for k in self.find_picture(int(i)) if k != int(i)]
+
+    def distinct_frames(self, min_pixels: int, first: Optional[int] = None, count: Optional[int] = None) -> List[int]:
+        """A `keep` list for thin / crop / sequence: the frames of clip frames first .. first + count - 1 (None: from the index's
+        first frame / to its last) that are worth keeping.  The first frame is kept; then the next frame that differs from the LAST
+        KEPT frame by at least `min_pixels` pixels, and so on — one `Distance` call per kept frame, over the frames still ahead of
+        it; the last frame of the range is always kept.  Strictly ascending.  These calls cover a part of the index each and go to
+        the index directly: they neither use nor fill the maps `distance` keeps.  ValueError: no index attached, an index object
+        without `Distance`, an empty range or one outside the index."""
+        self._need_distance()
+        first = self.index_first if first is None else int(first)
+        end = self.index_first + self.index.frames if count is None else first + int(count)   # one past the range
+        if not (self._in_index(first) and first < end <= self.index_first + self.index.frames):
+            raise ValueError(f"distinct_frames: frames {first} .. {end - 1} are not a range of the attached seek index")
+        keep = [first]
+        while keep[-1] < end - 1:
+            at = keep[-1]
+            ahead = self.index.Distance(at - self.index_first, at + 1 - self.index_first, end - 1 - at)
+            hits = np.nonzero(self._frame_sums(ahead) >= int(min_pixels))[0]
+            keep.append(at + 1 + int(hits[0]) if hits.size else end - 1)
+        return keep
 
     # -- a clip that starts at any frame: the attached index's KeyFrame (jsp_index_key_frame) ------------------------------------------
     def cut(self, frames: Sequence[bytes], first: int, last: Optional[int] = None, key_flags: Optional[Sequence[bool]] = None):
