@@ -556,7 +556,7 @@ long play_batched(const Clip& clip, int batch, int repeat, bool quiet, int warmu
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]] | --present-area WxH[:zoom[:hpos:vpos]] | --index-present WxH[:zoom[:hpos:vpos]] N[:filter] | --index-tensor WxH N[:filter[:dtype[:layout]]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s clip.avi [--pipelined [--depth D] [--quiet [--streams T] [--repeat R] [--warmup W]]] | --batch B [--quiet [--repeat R]] | --seek N | --skip-stills | --step-back | --filmstrip N[:scale] | --play-index FIRST[:COUNT[:STRIDE]] | --index-run FIRST[:COUNT[:STRIDE]] | --present WxH[:zoom[:hpos:vpos]] | --present-area WxH[:zoom[:hpos:vpos]] | --index-present WxH[:zoom[:hpos:vpos]] N[:filter] | --index-tensor WxH N[:filter[:dtype[:layout]]] | --transcode FIRST[:COUNT[:STRIDE]] OUT.avi | --proxy WxH FIRST[:COUNT[:STRIDE]] OUT.avi\n", argv[0]); return 2; }
     // (throughput runs: several files, separated by commas — stream s plays file s modulo their number, so that the streams of a
     // multi-stream run are independent inputs)
     std::deque<Clip> clips;                                   // (a deque: elements never move)
@@ -599,6 +599,9 @@ int main(int argc, char** argv) {
     bool present_area = false;                                // --present-area: the window from jsp_display_present_area
     int ip_n = 0, ip_filter = JSP_PRESENT_BILINEAR;           // --index-present WxH[:zoom[:hpos:vpos]] N[:filter]: N windows out of a seek index, one sheet
     int it_dtype = -1, it_layout = JSP_TENSOR_NCHW;           // --index-tensor WxH N[:filter[:dtype[:layout]]]: the same N frames, Fit, as one dense tensor
+    long tc_first = -1, tc_count = -1, tc_stride = 1;         // --transcode FIRST[:COUNT[:STRIDE]] OUT.avi: the pictures of those frames, encoded as 16-bit MSVideo1
+    int proxy_w = 0, proxy_h = 0;                             // --proxy WxH FIRST[:COUNT[:STRIDE]] OUT.avi: the same of their windows, Fit into W x H
+    std::string tc_path;
     std::vector<int> devices;                                 // --devices: streams sharded one per GPU (stream s -> devices[s mod G])
     for (int a = 2; a < argc; ++a) {
         const std::string o = argv[a];
@@ -703,6 +706,25 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if ((o == "--transcode" && a + 2 < argc) || (o == "--proxy" && a + 3 < argc)) {
+            if (o == "--proxy") {
+                const std::string r = argv[++a];
+                char* end = nullptr;
+                proxy_w = (int)std::strtol(r.c_str(), &end, 10);
+                if (end != r.c_str() && *end == 'x' && end[1]) proxy_h = (int)std::strtol(end + 1, &end, 10);
+                if (proxy_w < 4 || proxy_h < 4 || proxy_w % 4 || proxy_h % 4 || *end) { std::fprintf(stderr, "--proxy WxH FIRST[:COUNT[:STRIDE]] OUT.avi: W and H positive multiples of 4\n"); return 2; }
+            }
+            const std::string v = argv[++a];
+            const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            tc_first = std::atol(v.substr(0, c1).c_str());
+            if (c1 != std::string::npos) tc_count = std::atol(v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1).c_str());
+            if (c2 != std::string::npos) tc_stride = std::atol(v.substr(c2 + 1).c_str());
+            tc_path = argv[++a];
+            if (tc_first < 0 || (c1 != std::string::npos && tc_count < 1) || tc_stride < 1) {
+                std::fprintf(stderr, "%s FIRST[:COUNT[:STRIDE]] OUT.avi: FIRST >= 0, COUNT >= 1, STRIDE >= 1\n", o.c_str());
+                return 2;
+            }
+        }
         else if (o == "--filmstrip" && a + 1 < argc) {
             const std::string v = argv[++a];
             const size_t colon = v.find(':');
@@ -786,6 +808,8 @@ int main(int argc, char** argv) {
     if (run_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR) { std::fprintf(stderr, "--index-run: MSVideo1 only (--play-index plays a ScreenPressor index)\n"); return 2; }
     if (ip_n > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "%s goes alone\n", it_dtype >= 0 ? "--index-tensor" : "--index-present"); return 2; }
     if (ip_n == 0 && present_w > 0 && (run_first >= 0 || play_first >= 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "--present goes with the plain per-frame run\n"); return 2; }
+    if (tc_first >= 0 && (thin_first >= 0 || cut_first >= 0 || act_first >= 0 || run_first >= 0 || play_first >= 0 || ip_n > 0 || present_w > 0 || strip > 0 || step_back || skip_stills || seek_to >= 0 || pipelined || batch > 0 || !devices.empty())) { std::fprintf(stderr, "%s goes alone\n", proxy_w ? "--proxy" : "--transcode"); return 2; }
+    if (tc_first >= 0 && clip.kind == JSP_CODEC_SCREENPRESSOR && clip.bpp == 16) { std::fprintf(stderr, "%s: a 16-bpp ScreenPressor clip holds 5-bit components, not 0x00RRGGBB words\n", proxy_w ? "--proxy" : "--transcode"); return 2; }
     if (batch > 0) {
         batch = batch > 1024 ? 1024 : batch;
         if (!quiet) return play_batched(clip, batch, 1, false) < 0 ? 1 : 0;
@@ -904,6 +928,116 @@ int main(int argc, char** argv) {
     bool last_was_key = false;
     int rc = 0;
     size_t begin = 0;
+    if (tc_first >= 0) {   // pictures that exist only as pixels, as a 16-bit MSVideo1 clip: one index build over the clip, the frames shown (--proxy: presented, Fit) a run at a time, jsp_msv1_encode_frames per run, the file, its playback
+        const char* const opt = proxy_w ? "--proxy" : "--transcode";
+        const size_t n = clip.frames.size();
+        std::vector<int> keep;
+        for (long i = tc_first; i < (long)n && (tc_count < 0 || (long)keep.size() < tc_count); i += tc_stride) keep.push_back((int)i);
+        if (keep.empty() || (tc_count >= 0 && (long)keep.size() < tc_count)) {
+            std::fprintf(stderr, "%s: frames %ld, %ld, ... (%ld of them) are not all in the clip (%zu frames)\n", opt, tc_first, tc_first + tc_stride, tc_count, n);
+            rc = 1;
+        }
+        std::vector<const uint8_t*> srcs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> keys;
+        for (size_t i = 0; rc == 0 && i <= (size_t)keep.back(); ++i) {
+            srcs.push_back(clip.bytes.data() + clip.frames[i].first);
+            lens.push_back(clip.frames[i].second);
+            keys.push_back(i == 0 || frame_is_key(clip, dec, i) ? 1 : 0);
+        }
+        const bool sp = clip.kind == JSP_CODEC_SCREENPRESSOR;
+        jsp_index* idx = rc == 0 && !sp ? jsp_index_build(dec, (int)srcs.size(), srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        jsp_sp_index* sidx = rc == 0 && sp ? jsp_sp_index_build(dec, (int)srcs.size(), srcs.data(), lens.data(), keys.data(), kInsignificantLines) : nullptr;
+        if (rc == 0 && !idx && !sidx) { std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_build" : "jsp_index_build", jsp_last_error()); rc = 1; }
+        const int W = proxy_w ? proxy_w : clip.X, H = proxy_w ? proxy_h : clip.Y;
+        const int run = nbuf - 1;                                   // one buffer of the pool keeps the last picture of the run before
+        const ptrdiff_t sheet_pitch = (ptrdiff_t)run * W;            // --proxy: a sheet of `run` cells in one row, two sheets in turn
+        jsp_pool* sheets = rc == 0 && proxy_w ? jsp_pool_create(0, (int)sheet_pitch, H, 2) : nullptr;
+        if (rc == 0 && proxy_w && !sheets) { std::fprintf(stderr, "jsp_pool_create: %s\n", jsp_last_error()); rc = 1; }
+        jsp_encoder* enc = rc == 0 ? jsp_msv1_encoder_create(0, W, H) : nullptr;
+        if (rc == 0 && !enc) { std::fprintf(stderr, "jsp_msv1_encoder_create: %s\n", jsp_last_error()); rc = 1; }
+        size_t bound = 0;
+        if (rc == 0) jsp_msv1_encode_bound(enc, &bound);
+        double k = 1, dx = 0, dy = 0;
+        if (rc == 0 && proxy_w && jsp_view_matrix(clip.X, clip.Y, W, H, 0.0, 0.5, 0.5, &k, &dx, &dy) != 0) { std::fprintf(stderr, "jsp_view_matrix: %s\n", jsp_last_error()); rc = 1; }
+        std::vector<uint8_t> bytes;
+        std::vector<size_t> out_lens;
+        const int32_t* last_pic = nullptr;
+        int spare = 0;                                              // the pool buffer (the sheet) that holds last_pic
+        for (size_t k0 = 0, turn = 0; rc == 0 && k0 < keep.size(); k0 += (size_t)run, ++turn) {
+            const int m = (int)std::min<size_t>((size_t)run, keep.size() - k0);
+            std::vector<const int32_t*> pics, prevs;
+            if (proxy_w) {
+                int32_t* sheet = jsp_pool_buffer(sheets, (int)(turn & 1));
+                const size_t ints = (size_t)sheet_pitch * H;
+                const int prc = sp ? jsp_sp_index_present(dec, sidx, m, keep.data() + k0, sheet, ints, W, H, (size_t)sheet_pitch, run, k, dx, dy, JSP_DISPLAY_SETPIXELS, JSP_PRESENT_AREA, 0xFF000000u)
+                                   : jsp_index_present(dec, idx, m, keep.data() + k0, sheet, ints, W, H, (size_t)sheet_pitch, run, k, dx, dy, JSP_DISPLAY_SETPIXELS, JSP_PRESENT_AREA, 0xFF000000u);
+                if (prc != 0) { std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_present" : "jsp_index_present", jsp_last_error()); rc = 1; break; }
+                for (int i = 0; i < m; ++i) pics.push_back(sheet + (ptrdiff_t)(H - 1) * sheet_pitch + (ptrdiff_t)i * W);   // a cell by its last row
+            } else {
+                for (int i = 0, b = 0; i < m; ++i, ++b) {
+                    if (last_pic && b == spare) ++b;
+                    int32_t* dst = jsp_pool_buffer(pool, b);
+                    int32_t* shown = nullptr;
+                    int signif = 0;
+                    const int src_rc = sp ? jsp_sp_index_show(dec, sidx, keep[k0 + i], dst, &signif) : jsp_index_show(dec, idx, keep[k0 + i], dst, 0, &shown, &signif);
+                    if (src_rc != 0) { std::fprintf(stderr, "%s: %s\n", sp ? "jsp_sp_index_show" : "jsp_index_show", jsp_last_error()); rc = 1; break; }
+                    pics.push_back(dst);
+                    if (i == m - 1) spare = b;
+                }
+                if (rc != 0) break;
+            }
+            for (int i = 0; i < m; ++i) prevs.push_back(i == 0 ? last_pic : pics[i - 1]);
+            std::vector<size_t> ls(m);
+            size_t total = 0;
+            const size_t at = bytes.size();
+            bytes.resize(at + (size_t)m * bound);
+            if (jsp_msv1_encode_frames(enc, m, pics.data(), prevs.data(), proxy_w ? -sheet_pitch : (ptrdiff_t)W, bytes.data() + at, (size_t)m * bound, ls.data(), &total, nullptr) != JSP_ZERO_STATE) {
+                std::fprintf(stderr, "jsp_msv1_encode_frames: %s\n", jsp_last_error());
+                rc = 1;
+                break;
+            }
+            bytes.resize(at + total);
+            out_lens.insert(out_lens.end(), ls.begin(), ls.end());
+            last_pic = pics.back();
+        }
+        if (enc) jsp_msv1_encoder_destroy(enc);
+        if (sheets) jsp_pool_destroy(sheets);
+        if (idx) jsp_index_destroy(idx);
+        if (sidx) jsp_sp_index_destroy(sidx);
+        jsp_pool_destroy(pool);
+        jsp_codec_destroy(dec);
+        if (rc != 0) return rc;
+        std::vector<std::pair<const uint8_t*, size_t>> out_frames;
+        std::vector<uint8_t> out_keys;
+        size_t at = 0;
+        for (size_t j = 0; j < out_lens.size(); ++j) {
+            out_frames.emplace_back(bytes.data() + at, out_lens[j]);
+            out_keys.push_back(j == 0 ? 1 : 0);
+            at += out_lens[j];
+        }
+        Clip head;                                                  // the stream the file describes: W x H, 16 bpp, the clip's frame time
+        head.X = W; head.Y = H; head.bpp = 16; head.kind = JSP_CODEC_MSVIDEO1_16; head.usec = clip.usec;
+        const std::vector<uint8_t> file = avi_file(head, out_frames, out_keys);
+        FILE* f = std::fopen(tc_path.c_str(), "wb");
+        if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size()) { std::fprintf(stderr, "cannot write %s\n", tc_path.c_str()); if (f) std::fclose(f); return 1; }
+        std::fclose(f);
+        // OUT.avi played back through the ordinary decode loop: frame, bytes, the CRC of its picture — and, where the encoder is exact
+        // (--transcode of a 16-bit MSVideo1 clip), the CRC of the clip's own picture of that frame beside it
+        Clip made;
+        if (!load(tc_path.c_str(), made) || made.frames.size() != keep.size()) { std::fprintf(stderr, "cannot read %s back\n", tc_path.c_str()); return 1; }
+        std::vector<uint32_t> got, want;
+        if (!covered_crcs(made, made.frames.size(), got)) return 1;
+        const bool exact = !proxy_w && clip.kind == JSP_CODEC_MSVIDEO1_16;
+        if (exact && !covered_crcs(clip, (size_t)keep.back() + 1, want)) return 1;
+        for (size_t j = 0; j < keep.size(); ++j) {
+            if (exact) {
+                std::printf("%d %zu %08x %08x\n", keep[j], out_lens[j], got[j], want[(size_t)keep[j]]);
+                if (got[j] != want[(size_t)keep[j]]) rc = 1;
+            } else std::printf("%d %zu %08x\n", keep[j], out_lens[j], got[j]);
+        }
+        return rc;
+    }
     if (skip_stills) {   // Manager.SkipStills + SeekTo (Manager.hx:289-317), again and again: frame 0, then ONE jsp_find_change per skip
         const size_t n = clip.frames.size();
         std::vector<const uint8_t*> srcs;

@@ -153,6 +153,14 @@ extern class JspNative {
     @:native("jsp_display_present_area") static function displayPresentArea(frame:RawConstPointer<cpp.Int32>, frameW:Int, frameH:Int, out:RawPointer<cpp.Int32>, winW:Int, winH:Int,
                                                                       outPitch:SizeT, k:Float, dx:Float, dy:Float, mode:Int, background:cpp.UInt32,
                                                                       stream:RawPointer<cpp.Void>):Int;
+    // the MSVideo1 16-bit encoder: frames from any pictures in device memory, two launches per slice of pictures (no codec involved)
+    @:native("jsp_msv1_encoder_create")  static function msv1EncoderCreate(device:Int, w:Int, h:Int):RawPointer<JspEncoder>;
+    @:native("jsp_msv1_encoder_destroy") static function msv1EncoderDestroy(e:RawPointer<JspEncoder>):Void;
+    @:native("jsp_msv1_encode_bound")    static function msv1EncodeBound(e:RawPointer<JspEncoder>, bytes:RawPointer<SizeT>):Int;
+    @:native("jsp_msv1_encode_frames")   static function msv1EncodeFrames(e:RawPointer<JspEncoder>, n:Int, pictures:RawConstPointer<RawConstPointer<cpp.Int32>>,
+                                                                       previous:RawConstPointer<RawConstPointer<cpp.Int32>>, pitch:cpp.Int64,
+                                                                       out:RawPointer<UInt8>, cap:SizeT, lens:RawPointer<SizeT>, total:RawPointer<SizeT>,
+                                                                       stream:RawPointer<cpp.Void>):Int;
     @:native("jsp_frames_differ")      static function framesDiffer(a:RawConstPointer<cpp.Int32>, b:RawConstPointer<cpp.Int32>, firstPixel:SizeT, npixels:SizeT, differ:RawPointer<Int>, stream:RawPointer<cpp.Void>):Int;
 }
 
@@ -160,4 +168,5 @@ extern class JspNative {
 @:include("jsplayer_amd.h") @:native("jsp_index") @:structAccess extern class JspIndex {}
 @:include("jsplayer_amd.h") @:native("jsp_sp_index") @:structAccess extern class JspSpIndex {}
 @:include("jsplayer_amd.h") @:native("jsp_pool") @:structAccess extern class JspPool {}
+@:include("jsplayer_amd.h") @:native("jsp_encoder") @:structAccess extern class JspEncoder {}
 #end

@@ -927,6 +927,65 @@ int jsp_index_pan_frames(jsp_codec* c, jsp_index* idx, int bw, int bh, int n, co
 int jsp_index_path_frames(jsp_codec* c, jsp_index* idx, int bx, int by, int bw, int bh, int n, const int* from, const int* to, int flags,
                           uint8_t* out, size_t cap, size_t* lens, int* keys, size_t* total);
 
+/* ---- ENCODE PICTURES AS MSVIDEO1: frames from any picture in device memory.  Every clip call above gathers codes that an MSVideo1
+ * index already holds — exact and fast, and no help for what exists only as pixels: the pictures of a ScreenPressor index (its stream
+ * is entropy coded), a window of jsp_index_present, a block that no frame of an index codes (KeyFrame refuses it), any picture the
+ * caller holds.  This is the encoder for those, 16-bit MSVideo1 only: a pure function of pictures in HBM ---------------------------------
+ * Encode (the decoder it inverts: MSVideo1.hx:119-181):
+ *   GEOMETRY  A picture is width x height 32-bit words; row y starts at base + y * pitch ints; pitch is signed and |pitch| >= width.  A
+ *       frame buffer as the codecs leave it has pitch = width; a top-row-first window is given as a pointer to its LAST row with a
+ *       negative pitch; a cell of a sheet by the sheet's pitch.  nbx = width >> 2, nby = height >> 2, blocks in table order (block row 0
+ *       is rows 0..3); pixel k = 4 y + x of a block is flag bit k.  The width % 4 / height % 4 remainder pixels are never read.
+ *   QUANTISATION  q(p) = ((p >> 3) & 0x1F) | ((p >> 6) & 0x3E0) | ((p >> 9) & 0x7C00), the inverse of fromRGB15 on the layout
+ *       0x00RRGGBB that MSVideo1 and 24-bpp ScreenPressor frame buffers share.  No other bit of a word is read: the top byte may hold
+ *       anything, for example the 0xFF of JSP_DISPLAY_SETPIXELS.  v[k] = q(p[k]).
+ *   QUADRANTS  Quadrant i of 0..3 holds pixels {0,1,4,5}, {2,3,6,7}, {8,9,12,13}, {10,11,14,15}; its last pixel is 5, 7, 13, 15; its
+ *       colour pair is stream colours 2i (taken where the code word's bit is SET) and 2i + 1 (where it is CLEAR).
+ *   THE CODE OF A BLOCK, decided on v alone:
+ *       1. all 16 values equal c: the two bytes of 0x8000 | c when (c & 0x7C00) != 0x0400; otherwise the word's high byte would be
+ *          0x84..0x87, a skip: then the six bytes 00 00, c, c — a two-colour code of one colour;
+ *       2. exactly two distinct values: B = v[15], A the other; the word has bit k set where v[k] == A (bit 15 is clear by
+ *          construction); then A, B.  Six bytes; A carries bit 15 clear;
+ *       3. otherwise 18 bytes: the word, then F0 | 0x8000, S0, F1, S1, F2, S2, F3, S3 (bit 15 clear in all colours but the first).  Per
+ *          quadrant — at most two distinct values: S is the value of the quadrant's last pixel, F the other (F = S when there is one),
+ *          bits are set where v[k] != S; three or four distinct values (THE ONLY LOSSY STEP): Y = R + 2 G + B of the 5-bit fields, T the
+ *          sum of the four Y, a pixel is high when 4 Y > T, the last pixel's group is the pixels on its side of that test; S is the
+ *          per-channel floor((sum + n / 2) / n) over that group (n / 2 in integers), F the same over the other group (F = S when it
+ *          is empty); bits are set for the other group.
+ *   FRAMES  Key(P) = the codes of blocks 0 .. nblocks-1; no skip word, no end marker.  Inter(Q, P): block i is CODED when v of P differs
+ *       from v of Q in at least one of its 16 pixels (quantised values are compared, not words); the frame is Delta's rule above with
+ *       "written" read as "coded": the run-head test, the count, never crossing a multiple of 1023, ceil(nblocks / 1023) skip words
+ *       when nothing changed.
+ *   PROMISED, D(P) being the decode of Key(P): jsp_is_key_frame(Key(P)) says yes; D(P) == P on every covered pixel when every word of P
+ *       is fromRGB15 of something and every quadrant has at most two colours — every picture an MSVideo1 16-bit decoder produced;
+ *       D(D(P)) == D(P) always; Key(P0), Inter(P0, P1), Inter(P1, P2), ... decoded in sequence give exactly D(Pt) at every t (equal
+ *       quantised blocks encode alike, so a skip loses nothing); len(Inter) <= len(Key); Inter(Q, P) == Key(P) when every block is
+ *       coded; the bytes do not depend on pitch sign, alignment, slice size, or which pictures share a call.  NOT promised: that the
+ *       bytes equal what any other encoder, or the original stream, holds.
+ *   jsp_msv1_encoder_create: an encoder for pictures of width x height on a device; it owns its scratch (per picture of a slice 24 bytes
+ *       per block, 8 per workgroup, the frame at its bound; allocated by the first call).  NULL and jsp_last_error() for a width or
+ *       height below 4 or above 16384, or a device that is not there.  jsp_msv1_encode_bound: nblocks * 18, the most bytes of a frame.
+ *   jsp_msv1_encode_frames: n pictures, n in 1 .. 4096; pictures[j] and previous[j] are DEVICE pointers (the two arrays themselves are
+ *       host memory), all of one pitch; `previous` may be null, or hold null entries: a null entry means a key frame, else frame j =
+ *       Inter(previous[j], pictures[j]).  The frames lie back to back in `out`, HOST memory.  lens[j] and *total are set also when
+ *       `cap` is smaller than *total — that is then an error with nothing written, as Delta (`out` may be null when cap is 0); they
+ *       are zeros after every other error.  The pictures are only read.
+ *   TWO kernel launches for a slice of pictures, grid.y = the picture, in the shape of KeyFrame's (msv1_encode_sizes_kernel: a block's
+ *       words 16 bytes a row when every base is 16-byte aligned and pitch % 4 == 0, else word by word; the classification, the code
+ *       kept in scratch, the run-head test, a scan inside each workgroup of 1024 blocks; msv1_encode_gather_kernel: the totals before
+ *       its own summed, the codes and skip words through an LDS image, out in 16-byte pieces) — no workgroup waits for another and
+ *       nothing is atomic on global memory.  A call runs in slices of at most 16 pictures (fewer for large pictures) so that the
+ *       scratch stays bounded: a sizes launch per slice first, then sizes and gather per slice (a single slice: the gather alone).
+ *       Runs on `hip_stream` and returns synchronised.  No codec is involved and no frame buffer is written.
+ *   ERRORS, each before anything is queued (jsp_last_error() starts with "msv1_encode:"): a null argument, |pitch| < width, n outside
+ *       1 .. 4096, a null entry of pictures[]. */
+typedef struct jsp_encoder jsp_encoder;
+jsp_encoder* jsp_msv1_encoder_create(int device_id, int width, int height);
+void jsp_msv1_encoder_destroy(jsp_encoder* e);
+int jsp_msv1_encode_bound(const jsp_encoder* e, size_t* bytes);
+int jsp_msv1_encode_frames(jsp_encoder* e, int n, const int32_t* const* pictures, const int32_t* const* previous, ptrdiff_t pitch,
+                           uint8_t* out, size_t cap, size_t* lens, size_t* total, void* hip_stream);
+
 /* ---- what sits right after the codec in the reference's Manager, on the GPU --------------- */
 
 /* Manager.fill_bitmap_data (Manager.hx:325-390): RGB32 frame -> canvas pixels.  Modes: */

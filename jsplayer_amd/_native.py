@@ -145,6 +145,11 @@ SIGNATURES = {
     "jsp_index_path_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                         C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                         C.POINTER(C.c_size_t)]),
+    "jsp_msv1_encoder_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int]),
+    "jsp_msv1_encoder_destroy": (None, [C.c_void_p]),
+    "jsp_msv1_encode_bound": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "jsp_msv1_encode_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_ssize_t, C.c_void_p,
+                                         C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
     "jsp_display_convert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "jsp_view_matrix": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -1125,6 +1125,86 @@ class HostBuffer:
             pass
 
 
+class Msv1Encoder:
+    """An MSVideo1 16-bit encoder for pictures of width x height in device memory (jsp_msv1_encoder_create; the rule:
+    include/jsplayer_amd.h, "Encode").  No codec is involved; the pictures are only read."""
+
+    def __init__(self, width: int, height: int, device: int = 0):
+        self._lib = N.lib()
+        self.width, self.height, self.device = int(width), int(height), int(device)
+        self._h = self._lib.jsp_msv1_encoder_create(self.device, self.width, self.height)
+        if not self._h:
+            raise CodecError(N.last_error())
+
+    def Bound(self) -> int:
+        """The most bytes one frame has: 18 per 4x4 block."""
+        if not self._h:
+            raise CodecError("msv1_encode: the encoder is closed")
+        n = C.c_size_t(0)
+        if self._lib.jsp_msv1_encode_bound(self._h, C.byref(n)) != 0:
+            raise CodecError(N.last_error())
+        return n.value
+
+    def _picture_ptr(self, buf, pitch: int):
+        """The base of a picture: a device int32 tensor that starts at row 0 (pitch < 0: at the LAST row of a top-row-first window, the
+        rows before it in memory being the caller's word), or a device address as an int."""
+        if buf is None:
+            return None
+        if isinstance(buf, int):
+            return buf
+        need = (self.height - 1) * pitch + self.width if pitch > 0 else self.width
+        return _device_frame_ptr(buf, max(need, 1), "msv1_encode")
+
+    def EncodeFrames(self, pictures, previous=None, pitch: Optional[int] = None, stream: int = 0) -> list:
+        """One frame per picture: a key frame where previous is None or previous[j] is None, else the inter frame that takes the
+        decode of previous[j] to the decode of pictures[j] (blocks whose quantised pixels are equal are skipped).  `pitch`: ints
+        from a row to the next, default the width; negative for a top-row-first window handed over by its last row.  Two launches
+        per slice of pictures; returns synchronised.  Exact on every picture an MSVideo1 16-bit decoder produced."""
+        if not self._h:
+            raise CodecError("msv1_encode: the encoder is closed")
+        pitch = self.width if pitch is None else int(pitch)
+        pictures = list(pictures)
+        n = len(pictures)
+        if previous is not None and len(previous) != n:
+            raise CodecError("msv1_encode: previous must have an entry per picture")
+        pics = (C.c_void_p * max(n, 1))(*[self._picture_ptr(p, pitch) for p in pictures])
+        prevs = (C.c_void_p * max(n, 1))(*[self._picture_ptr(p, pitch) for p in previous]) if previous is not None else None
+        lens = (C.c_size_t * max(n, 1))()
+        total = C.c_size_t(0)
+        call = lambda out, room: self._lib.jsp_msv1_encode_frames(self._h, n, pics, prevs, pitch, out, room, lens, C.byref(total),
+                                                                  C.c_void_p(stream) if stream else None)
+        cap = max(n, 1) * self.Bound()
+        if cap > DELTA_ASK_TWICE:   # many large frames: the lengths first (cap 0 is the refusal that still sets them), then the bytes
+            if call(None, 0) == 0 or total.value == 0:
+                raise CodecError(N.last_error())
+            cap = total.value
+        buf = (C.c_uint8 * max(cap, 1))()
+        if call(buf, len(buf)) != 0:
+            raise CodecError(N.last_error())
+        view, out, at = memoryview(buf), [], 0
+        for j in range(n):
+            out.append(bytes(view[at:at + lens[j]]))
+            at += lens[j]
+        return out
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.jsp_msv1_encoder_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- the two Manager passes that follow the codec (Manager.hx:325-390, 413-419), on the GPU --------
 DISPLAY_CANVAS, DISPLAY_CANVAS_RGB15, DISPLAY_SETPIXELS, DISPLAY_SETPIXELS_RGB15 = 0, 1, 2, 3
 

@@ -23,7 +23,8 @@ the index's `Distance` map (pixels per frame and cell that differ from a referen
 `cut` / `write_cut` give the clip from any frame on as frames and flags / as an AVI file, its first frame the index's `KeyFrame`;
 `thin` / `write_thin` the clip made of any ascending list of frames, the gaps spanned by the index's `DeltaFrames`.  `crop_rect` / `crop` / `write_crop`
 the same list of frames for a part of the picture, from the index's `CropFrames`; `follow` / `pan` / `write_pan` for a part that follows what
-changes, from `activity` and the index's `PanFrames`.  `View` is the zoom / scroll / fit state of Main
+changes, from `activity` and the index's `PanFrames`; `transcode` / `write_transcode` the pictures of any frames of an index of either codec as a 16-bit MSVideo1
+clip, made by the encoder (`Msv1Encoder`), `proxy` / `write_proxy` the same of their windows.  `View` is the zoom / scroll / fit state of Main
 (Main.hx:288-319, 1186-1278) and `Manager.present` draws the window it shows of a frame buffer, one launch.  Timers, bitmaps and audio
 of the reference's Manager are not rebuilt.
 """
@@ -38,6 +39,7 @@ from .avi import CODEC_MSVC16, CODEC_MSVC8, CODEC_SCREENPRESSOR, VideoInfo
 
 INSIGNIFICANT_LINES = 36  # Manager.hx:61
 NUM_BUFFERS = 8           # Main.hx:148 (the pool holds NUM_BUFFERS + 1 frames, Manager.hx:114-118)
+PRESENT_AREA = 2          # codec.PRESENT_AREA (JSP_PRESENT_AREA): the default filter of Manager.proxy
 
 
 @dataclass
@@ -455,6 +457,95 @@ class Manager:
         out, flags = self.thin(frames, keep, key_flags, tight=tight)
         fourcc = b"SCPR" if self.vi.codec == CODEC_SCREENPRESSOR else b"CRAM"
         return write_avi(self.vi.X, self.vi.Y, out, fourcc=fourcc, bpp=self.vi.bpp, fps=fps, palette=self.vi.palette, key_flags=flags)
+
+    # -- a clip of pictures that exist only as pixels: the MSVideo1 encoder (jsp_msv1_encode_frames) ----------------------------------------
+    def _transcode_frames(self, who: str, keep: Sequence[int]) -> List[int]:
+        """`keep` as frame numbers of the attached index, checked: what transcode and proxy refuse alike."""
+        keep = [int(k) for k in keep]
+        if not keep:
+            raise ValueError(f"{who}: keep is empty")
+        if self.index is None:
+            raise ValueError(f"{who}: no seek index is attached")
+        if self.vi.codec == CODEC_SCREENPRESSOR and self.vi.bpp == 16:
+            raise ValueError(f"{who}: a 16-bpp ScreenPressor index holds 5-bit components, not 0x00RRGGBB words")
+        for k in keep:
+            if not self._in_index(k):
+                raise ValueError(f"{who}: frame {k} is not in the attached seek index")
+        return [k - self.index_first for k in keep]
+
+    def transcode(self, keep: Sequence[int]):
+        """The pictures of clip frames `keep` (any order, repeats allowed) of the attached index — MSVideo1's or ScreenPressor's
+        alike — as a 16-bit MSVideo1 clip of its own: (list of frame bytes, key flags).  The pictures are shown into device buffers
+        of this call's own, as many as the Manager's pool has, a run at a time (index.Show, the decoder not touched), and each is
+        encoded against the one before it (Msv1Encoder: two launches per slice of a run); the first is a key frame and the only one
+        flagged.  Exact for an MSVideo1 16-bit index; for any other the pinned rule of the encoder (include/jsplayer_amd.h,
+        "Encode").  Neither decoder nor the Manager's buffers change.  ValueError: `keep` empty, no index attached, a frame outside
+        it, a 16-bpp ScreenPressor index (its frame words are not 0x00RRGGBB)."""
+        import torch
+        from .codec import Msv1Encoder
+        frames = self._transcode_frames("transcode", keep)
+        device = getattr(self.index._codec, "_device", 0)
+        run = max(len(self.buffers), 1)
+        bufs = [torch.zeros(self.vi.X * self.vi.Y, dtype=torch.int32, device=f"cuda:{device}") for _ in range(run + 1)]
+        out: List[bytes] = []
+        last = None
+        with Msv1Encoder(self.vi.X, self.vi.Y, device) as enc:
+            for k0 in range(0, len(frames), run):
+                batch = frames[k0:k0 + run]
+                free = [b for b in bufs if b is not last]
+                pics = []
+                for t, dst in zip(batch, free):
+                    self.index.Show(t, dst, adopt=False)   # (the pixels are in dst whatever the call says of data_pnt)
+                    pics.append(dst)
+                out += enc.EncodeFrames(pics, [last] + pics[:-1])
+                last = pics[-1]
+        return out, [True] + [False] * (len(out) - 1)
+
+    def write_transcode(self, keep: Sequence[int], fps: float = 15.0) -> bytes:
+        """`transcode` as an AVI file (avi.write_avi): fourcc CRAM, 16 bpp, this Manager's width and height."""
+        from .avi import write_avi
+        out, flags = self.transcode(keep)
+        return write_avi(self.vi.X, self.vi.Y, out, fourcc=b"CRAM", bpp=16, fps=fps, key_flags=flags)
+
+    def proxy(self, keep: Sequence[int], win_w: int, win_h: int, filter: int = PRESENT_AREA):
+        """Clip frames `keep` of the attached index, each Fit into a window of win_w x win_h (multiples of 4) as `contact_sheet` fits
+        them, as a 16-bit MSVideo1 clip of that size: (list of frame bytes, key flags) — a 640x360 proxy of a 1080p recording.  The
+        windows come from index.Present on a sheet (mode JSP_DISPLAY_SETPIXELS), a run of as many cells as
+        the Manager's pool has buffers at a time; each cell goes to the encoder by the sheet's pitch, negated from its last row, so
+        that the decoded frame buffer is bottom-up as every frame buffer is and the proxy plays upright.  No full-size picture is
+        written.  ValueError as `transcode`, and for a window size that is not a positive multiple of 4."""
+        import torch
+        from .codec import DISPLAY_SETPIXELS, Msv1Encoder, view_matrix
+        win_w, win_h = int(win_w), int(win_h)
+        if win_w < 4 or win_h < 4 or win_w % 4 or win_h % 4:
+            raise ValueError(f"proxy: the window size must be a positive multiple of 4 (got {win_w} x {win_h})")
+        frames = self._transcode_frames("proxy", keep)
+        if not hasattr(self.index, "Present"):
+            raise ValueError("proxy: the attached seek index cannot present")
+        device = getattr(self.index._codec, "_device", 0)
+        cols = max(len(self.buffers), 1)
+        pitch = cols * win_w
+        sheets = [torch.zeros(win_h * pitch, dtype=torch.int32, device=f"cuda:{device}") for _ in range(2)]
+        k, dx, dy = view_matrix(self.vi.X, self.vi.Y, win_w, win_h, 0.0)
+        cell = lambda sheet, i: sheet.data_ptr() + 4 * ((win_h - 1) * pitch + i * win_w)   # the last row of cell i
+        out: List[bytes] = []
+        last = None
+        with Msv1Encoder(win_w, win_h, device) as enc:
+            for n, k0 in enumerate(range(0, len(frames), cols)):
+                batch = frames[k0:k0 + cols]
+                sheet = sheets[n & 1]
+                self.index.Present(batch, win_w, win_h, k, dx, dy, mode=DISPLAY_SETPIXELS,
+                                   filter=int(filter), cols=cols, out=sheet)
+                pics = [cell(sheet, i) for i in range(len(batch))]
+                out += enc.EncodeFrames(pics, [last] + pics[:-1], pitch=-pitch)
+                last = pics[-1]
+        return out, [True] + [False] * (len(out) - 1)
+
+    def write_proxy(self, keep: Sequence[int], win_w: int, win_h: int, filter: int = PRESENT_AREA, fps: float = 15.0) -> bytes:
+        """`proxy` as an AVI file (avi.write_avi): fourcc CRAM, 16 bpp, win_w x win_h."""
+        from .avi import write_avi
+        out, flags = self.proxy(keep, win_w, win_h, filter)
+        return write_avi(int(win_w), int(win_h), out, fourcc=b"CRAM", bpp=16, fps=fps, key_flags=flags)
 
     # -- a clip of a part of the picture: the attached index's CropFrames (jsp_index_crop_frames) ------------------------------------------
     def crop_rect(self, rect):
